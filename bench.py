@@ -22,9 +22,16 @@ Steps are PIPELINED by default (--no-pipeline for strictly sequential steps): th
 neighbour search, KDE -- they depend on the points only) are launched on a side stream while the convolution kernels of
 the previous batch run (ConvolutionBuilder.prefetch_geometry). Every step still executes every op: inside the timed
 region K geometry passes and K convolution passes run. Before timing, three pipelined steps are checked to reproduce a
-sequential step's forward output bit for bit; config.sequential_ms_per_step reports the same K steps unpipelined.
+sequential step's forward output bit for bit; with --full, config.sequential_ms_per_step reports the same K steps unpipelined.
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the field contract), including
+A plain run measures the headline only: set-up, W warm-up steps (on one rank: at least half a second of them), K timed
+steps in the default (pipelined) form, the outputs if --dump-outputs DIR is given, and the result line. --full adds everything below, as well as the same K steps
+timed strictly sequentially (the faster form is then the headline).
+    --dump-outputs DIR   after the timed steps, what the last timed step handed its caller -- the convolution output, the
+                         input-feature gradient and the kernel-MLP parameter gradients -- as DIR/<name>.npy (float32; a
+                         fixed, seeded sample of rows when they exceed 64 MB in all). Same arguments, same inputs.
+
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the field contract); with --full it also holds
   roofline     -- the dominant kernel's algorithmic flops (or bytes) / its HIP-event duration
   layers       -- the same measurement for all three layer shapes of SURVEY 8d (1to64, 3to8, dw256), so that the
                   headline shape cannot hide the depth-wise regime
@@ -204,11 +211,18 @@ class Workload:
             self.bucket.allreduce(async_op=True)
         return out
 
-    def timed(self, steps, warmup):
+    def timed(self, steps, warmup, min_warmup_s=0.0):
         """K timed steps after W warm-up steps; barrier + synchronize on both sides; max over ranks. self.rank_stats holds
-        every rank's own loop time and how long it then waited for the last gradient all-reduce (a slow rank shows)."""
+        every rank's own loop time and how long it then waited for the last gradient all-reduce (a slow rank shows).
+        min_warmup_s (one rank only: the step count may differ from run to run): further warm-up steps until the device has
+        run them for that long."""
         for _ in range(max(warmup, 0)):
             self.step()
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < min_warmup_s:
+            for _ in range(8):
+                self.step()
+            torch.cuda.current_stream().synchronize()
         if self.bucket is not None:
             self.bucket.wait()
         torch.cuda.synchronize()
@@ -219,10 +233,13 @@ class Workload:
         trace = [] if os.environ.get("MCCNN_BENCH_TRACE") else None  # diagnostic: per-step times of the region to stderr
         hlag = int(os.environ.get("MCCNN_BENCH_LAG_HEADLINE", "0"))  # A/B: the host at most `hlag` steps ahead of the GPU
         hevs = []
-        for _ in range(steps):
+        out = None
+        for i in range(steps):
             if hlag and len(hevs) >= hlag:
                 hevs[-hlag].synchronize()
-            self.step()
+            out = self.step()
+            if i + 1 < steps:   # only the last step's output outlives its step (outputs())
+                out = None
             if hlag:
                 e_ = torch.cuda.Event()
                 e_.record()
@@ -233,6 +250,7 @@ class Workload:
                 trace.append((ev, time.perf_counter() - t0))
         torch.cuda.current_stream().synchronize()  # this rank's own kernels
         t_own = time.perf_counter() - t0
+        self.last_out = out
         if trace:
             log("per-step GPU ms: " + " ".join("%.3f" % trace[i][0].elapsed_time(trace[i + 1][0]) for i in range(len(trace) - 1))
                 + " | host issue ms: " + " ".join("%.3f" % ((trace[i + 1][1] - trace[i][1]) * 1e3) for i in range(len(trace) - 1)))
@@ -262,6 +280,15 @@ class Workload:
         else:
             m_total = float(m_local)
         return elapsed / steps * 1e3, m_total * steps / elapsed, m_total
+
+    def outputs(self):
+        """What the last step of timed() handed its caller, as float32 host arrays: the convolution output, the gradient
+        of the input features and the gradients of the kernel-MLP parameters (under the builder's variable names)."""
+        torch.cuda.synchronize()
+        arrs = {"conv_out": self.last_out, "features_grad": self.F.grad}
+        for name, p in self.builder.named_parameters():
+            arrs[name + "_grad"] = p.grad
+        return {k: v.detach().float().cpu().numpy() for k, v in arrs.items() if v is not None}
 
     def find_neighbors_roofline(self):
         """find_neighbors alone on THIS workload's batch (the north star's gather-bound pass): HIP-event time of the op
@@ -986,6 +1013,26 @@ def cpu_baseline(wl, out_gpu):
     return cpu
 
 
+DUMP_LIMIT = 60 * 2 ** 20  # bytes of --dump-outputs arrays in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """arrays -> path/<name>.npy as float32. Above `limit` bytes in all, every array of more than 1 MiB keeps the same
+    fraction of its rows: a seeded sample in their original order, the same rows for the same names and shapes from run to
+    run. The small ones (parameter gradients) are written whole."""
+    os.makedirs(path, exist_ok=True)
+    small = 2 ** 20
+    total = sum(a.size * 4 for a in arrays.values())
+    big = sum(a.size * 4 for a in arrays.values() if a.size * 4 > small)
+    room = limit - (total - big)
+    for i, name in enumerate(sorted(arrays)):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float32)
+        if total > limit and a.nbytes > small:
+            k = max(1, a.shape[0] * room // big)
+            a = a[np.sort(np.random.default_rng(i).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 LINE_LIMIT = 4096  # bytes of the final stdout line: the driver's parser gave up on the 32 KB line of round 3
 
 
@@ -1138,6 +1185,13 @@ def main():
                     help="strictly sequential steps. Default: the geometry (grid build, search, KDE) of batch k+1 runs on a "
                          "side stream under the convolutions of batch k (ConvolutionBuilder.prefetch_geometry); every step "
                          "still executes all of it, and the sequential time is reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the same steps timed sequentially, the other layer shapes, per-op breakdowns "
+                         "and rooflines, strong scaling, the BASELINE.json configurations and the CPU baselines (the --no-* "
+                         "options and --config select among them). Default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (output, feature and parameter gradients) as "
+                         "DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1221,17 +1275,19 @@ def main():
     # (rank 0; they drain the queue around every op), and the 8-room batch of the strong-scaling point last. (The headline
     # region used to follow the 8-room loop: after its 5 ms steps the 0.6 ms steps of the headline started at 0.70 ms and
     # took more than 20 steps to settle -- 0.67 instead of 0.61 ms per step in a `--steps 20 --warmup 5` run.)
+    # (a plain run: the headline region alone; everything else is measured with --full)
     others = {}
-    if not args.no_layers:
+    if args.full and not args.no_layers:
         for name in sorted(LAYERS, reverse=True):  # the long one first: it carries the load through the ramp
             if name != args.layer:
                 others[name] = Workload(args, name, seeds, rank, world, device)
     wl_strong = None
-    if args.scaling == "both" and args.strong_rooms >= world:
+    strong_on = args.full and args.scaling == "both" and args.strong_rooms >= world
+    if strong_on:
         sseeds = strong_seeds()
         if sseeds != seeds:  # (one rank of an 8-rank run with 8 rooms owns exactly its weak-scaling room)
             wl_strong = Workload(args, args.layer, sseeds, rank, world, device)
-    layers = None if args.no_layers else {}
+    layers = None if (args.no_layers or not args.full) else {}
     for name, w2 in others.items():
         ms, val, _ = w2.timed(max(args.steps // 2, 3), 2)
         layers[name] = {"ms_per_step": round(ms, 4), "value": round(val, 1), "unit": "points/s", "edges_per_gpu": w2.e_local,
@@ -1245,15 +1301,21 @@ def main():
                 layers[name].update(ms_per_step=round(ms_s, 4), value=round(val_s, 1), mode="sequential")
 
     # ------------------------------------------------------------------ the headline region
-    ms_per_step, value, m_total = wl.timed(args.steps, max(args.warmup - 1, 0))
+    # A plain run has no other step loops in front of the region to carry the GPU through its clock ramp (see above): its
+    # warm-up runs the headline's own steps for at least half a second, about as long as --full's loops before the region.
+    ramp_s = 0.5 if (not args.full and world == 1) else 0.0
+    ms_per_step, value, m_total = wl.timed(args.steps, max(args.warmup - 1, 0), min_warmup_s=ramp_s)
     rank_stats = wl.rank_stats
+    # (to the host at once: the regions below run the same steps again; the files are written before the result line)
+    outputs = wl.outputs() if (args.dump_outputs and rank == 0) else None
     ms_sequential = ms_pipelined = None
     headline_mode = "sequential"
-    if wl.pipeline:  # the same K steps strictly one after the other (nothing prefetched)
+    if wl.pipeline:
+        ms_pipelined, headline_mode = ms_per_step, "pipelined"
+    if wl.pipeline and args.full:  # the same K steps strictly one after the other (nothing prefetched)
         wl.pipeline = False
         ms_sequential, value_seq, _ = wl.timed(args.steps, 2)
         wl.pipeline = True
-        ms_pipelined, headline_mode = ms_per_step, "pipelined"
         if ms_sequential < ms_per_step:
             # e.g. a slow host, or ranks sharing one GPU: the pipelined form is the host-heavier one. Both regions are
             # K timed steps of the same work; the faster one is the headline, the other is reported beside it.
@@ -1267,7 +1329,7 @@ def main():
 
     # ------------------------------------------------------------------ per-op breakdowns and rooflines (rank 0)
     roofline = breakdown = None
-    if rank == 0 and not args.no_breakdown:
+    if rank == 0 and args.full and not args.no_breakdown:
         roofline, breakdown = wl.breakdown()
         for name, w2 in list(others.items()) + ([(args.layer, wl)] if layers is not None else []):
             rl, bd = (roofline, breakdown) if w2 is wl else w2.breakdown()
@@ -1282,7 +1344,7 @@ def main():
                 ent["bf16_rows"] = bd["spatial_conv_bf16_rows"]
     # ------------------------------------------------------------------ strong scaling: the fixed batch split over the ranks
     strong = None
-    if args.scaling == "both" and args.strong_rooms >= world:
+    if strong_on:
         sw = wl_strong if wl_strong is not None else wl
         s_ms, s_val, s_total = sw.timed(max(args.steps // 4, 5) if wl_strong is not None else args.steps, 3)
         strong = {"rooms": args.strong_rooms, "rooms_on_rank0": len(strong_seeds()), "points_total": int(s_total),
@@ -1306,7 +1368,7 @@ def main():
 
     # ------------------------------------------------------------------ BASELINE.json configurations (rank 0, N == 1)
     configs = None
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         configs = {}
         # GPU steps of all configurations first: the CPU legs keep 128 OpenMP threads busy for seconds, and the steps of the
         # small configurations are bound by the host thread that issues them (cfg4 right after cfg3's CPU leg: +15 %)
@@ -1328,7 +1390,7 @@ def main():
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N == 1)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(wl, wl.out)
         except Exception as ex:  # the baseline is informative; never fail the bench on it
@@ -1348,10 +1410,12 @@ def main():
             "scaling": "strong" if args.scaling == "strong" else "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             # the same K steps strictly one after the other, nothing carried over or run ahead: SURVEY 8(d)'s literal
-            # definition of the metric, beside the pipelined `value` (every pipelined step still executes all of it)
+            # definition of the metric, beside the pipelined `value` (every pipelined step still executes all of it); a
+            # plain run with a pipelined headline has not timed it (null)
             "sequential": ({"ms_per_step": round(ms_sequential, 4), "value": round(m_total / (ms_sequential * 1e-3), 1),
                             "unit": "points/s"} if ms_sequential is not None else
-                           {"ms_per_step": round(ms_per_step, 4), "value": round(value, 1), "unit": "points/s"}),
+                           {"ms_per_step": round(ms_per_step, 4), "value": round(value, 1), "unit": "points/s"}
+                           if headline_mode == "sequential" else None),
             "config": {"workload": "ScanNet-like non-uniform room, %d pts/room, %d room(s) on rank 0, absolute radius %g, "
                                    "KDE window %g, same-level conv %s (Fin=%d, Fout=%d, %s), avg on"
                                    % (args.points, B, args.radius, args.window, args.layer, fin, fout,
@@ -1375,6 +1439,8 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         emit_record(rec, args.details)
     if dist_on:
         dist.destroy_process_group()

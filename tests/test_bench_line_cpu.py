@@ -134,3 +134,28 @@ def test_last_committed_full_record_compacts():
     rec = json.load(open(p))
     line = _bench().compact_record(rec, None)
     assert len(line) < 4096 and json.loads(line)["roofline"]["frac"] == rec["roofline"]["frac"]
+
+
+def test_dump_outputs_samples_large_arrays_the_same_way_every_time(tmp_path):
+    """--dump-outputs: float32 .npy files; above the byte limit the large arrays keep a seeded sample of their rows (the same
+    rows in every run), the small ones are written whole."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(0)
+    arrs = {"conv_out": rng.random((100000, 8)), "features_grad": rng.random((100000, 1)).astype(np.float32),
+            "Conv_weights_grad": rng.random((3, 64)).astype(np.float32)}
+    limit = 2 ** 21
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), arrs, limit=limit)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["Conv_weights_grad.npy", "conv_out.npy", "features_grad.npy"]
+    loaded = {f: np.load(str(tmp_path / "a" / f)) for f in files}
+    assert all(a.dtype == np.float32 for a in loaded.values())
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= limit + 1024
+    assert np.array_equal(loaded["Conv_weights_grad.npy"], arrs["Conv_weights_grad"])
+    assert 0 < loaded["conv_out.npy"].shape[0] < 100000 and loaded["conv_out.npy"].shape[1] == 8
+    for f in files:
+        assert np.array_equal(loaded[f], np.load(str(tmp_path / "b" / f))), f
+    # below the limit everything is written whole
+    b.dump_outputs(str(tmp_path / "c"), arrs)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "conv_out.npy")), arrs["conv_out"].astype(np.float32))

@@ -141,7 +141,7 @@ def test_bench_through_rccl_with_one_rank(mc):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-layers",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-layers",
                         "--no-breakdown", "--no-cpu-baseline", "--no-configs", "--strong-rooms", "2"], env=env, cwd=root,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -179,7 +179,7 @@ def _torchrun_bench(nproc, extra, timeout=900):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCCNN_BENCH_FORCE_PG"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "4",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", str(nproc), "--steps", "4",
            "--warmup", "2", "--points", "20000", "--no-layers", "--no-breakdown", "--no-cpu-baseline", "--no-configs"] + extra
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -236,7 +236,7 @@ def test_bare_bench_with_gpus_2_launches_its_own_ranks(mc):
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCCNN_BENCH_FORCE_PG",
                         "MCCNN_BENCH_BACKEND")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                         "--points", "20000", "--no-layers", "--no-breakdown", "--strong-rooms", "4"], env=env, cwd=root,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -1,5 +1,5 @@
-import sys, torch, numpy as np
-sys.path.insert(0,'/root/repo')
+import os, sys, torch, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench, argparse
 from mccnn_amd import MCConvModule as M
 ap = argparse.Namespace(points=100000, radius=0.1, window=0.2, layer='1to64', rooms_per_gpu=1, steps=20, warmup=5, scaling='weak', strong_rooms=8, gpus=1, no_cpu_baseline=True, no_breakdown=True, no_layers=True, no_pipeline=True)

@@ -1,7 +1,7 @@
-"""Pipelined vs sequential steps in ONE rocprofv3 kernel trace of `python bench.py --no-layers --no-breakdown
+"""Pipelined vs sequential steps in ONE rocprofv3 kernel trace of `python bench.py --full --no-layers --no-breakdown
 --no-cpu-baseline`: per-kernel mean duration in the two regions, the step period, and the timeline of one pipelined
 step (main queue, with the side queue's kernels beside it).
-    cd /tmp && rocprofv3 --kernel-trace -d /tmp/kt -o t --output-format csv -- python $REPO/bench.py --steps 40 ...
+    cd /tmp && rocprofv3 --kernel-trace -d /tmp/kt -o t --output-format csv -- python $REPO/bench.py --full --steps 40 ...
     python tools/pipe_overlap.py /tmp/kt/t_kernel_trace.csv"""
 import sys
 

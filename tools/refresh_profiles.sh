@@ -4,7 +4,7 @@
 # 1. tools/prof.sh for the three benchmark layers, the 8-rooms-per-GPU size, the hierarchy build and the five
 #    BASELINE.json configurations (tools/config_time.py)
 #    (kernel-trace stats + separate PMC passes), copied to profiles/<round>_{rocprofv3_summary,kernels,pmc_traffic,command}_<tag>.*
-# 2. the default `python bench.py` line (reads the traffic files of step 1) -> profiles/<round>_bench.json
+# 2. the `python bench.py --full` line (reads the traffic files of step 1) -> profiles/<round>_bench.json
 # The copies land in gpurun_out/profiles_<round>/ as well, so that a `gpurun` call brings them home.
 set -u
 ROUND=${1:-r03}
@@ -38,6 +38,6 @@ for cfg in cfg0 cfg1 cfg2 cfg3 cfg4; do
 done
 
 # the full record (bench_details.json) and the compact line the driver parses (the LAST stdout line)
-python bench.py --details $DST/${ROUND}_bench.json 2> gpurun_out/profiles_$ROUND/bench.err | tail -n 1 > $DST/${ROUND}_bench_line.json
+python bench.py --full --details $DST/${ROUND}_bench.json | tail -n 1 > $DST/${ROUND}_bench_line.json
 cp $DST/${ROUND}_* gpurun_out/profiles_$ROUND/
 tail -c 600 $DST/${ROUND}_bench_line.json
