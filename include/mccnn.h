@@ -285,6 +285,45 @@ size_t mccnn_transpose_neighbors_workspace_bytes(int n, int e);
 int mccnn_transpose_neighbors(const int* packed, int e, int n, int* start_t, int* perm_t, void* ws,
                               size_t ws_bytes, mccnn_stream_t stream);
 
+/* GRADIENTS WITH RESPECT TO POSITIONS (extension, no TF counterpart: the reference differentiates spatial_conv w.r.t.
+ * the features and the six kernel-MLP tensors only). Every discrete decision of the forward pass -- cells, sort order,
+ * neighbour sets, the K of `avg`, the longest box axis -- is held fixed; the results are the exact f32 derivatives of
+ * the forward arithmetic. No float atomics: two calls give bit-identical results.
+ *
+ * mccnn_spatial_conv_bwd_points: the derivative of spatial_conv through delta = (p_j - c_i) / R_b and the 1 / (pdf K)
+ * factor, for out_grad [m, out_feats] (f32 even when the feature rows are bf16 storage, feats_bf16 = 1). Outputs:
+ *   dpts_edge [e, 3]  per-edge gradient of the neighbour point (sum it per point with mccnn_edge_grad_reduce);
+ *   dsamples  [m, 3]  gradient of the centres;
+ *   dpdfs     [e]     gradient of the PDFs (optional: NULL skips it);
+ *   dradius   [B]     gradient of R_b (optional, scale_inv only; its chain to the box is R_b = radius * maxExtent_b).
+ * Every layer shape of mccnn_spatial_conv_bwd (combin and depth-wise, any Fin, avg on / off). Workspace (only with
+ * dradius): mccnn_spatial_conv_bwd_points_workspace_bytes(m, batch_size).
+ *
+ * mccnn_compute_pdf_bwd_points: the derivative of compute_pdf (any mode: the analytic f32 derivative of the KDE sum)
+ * for pdf_grad [e]: every pair of a centre's row contributes to both of its points. Writes (accumulate = 0) or adds
+ * to (accumulate = 1) dpts_edge [e, 3]; dradius [B] as above (optional, scale_inv only; workspace then
+ * mccnn_compute_pdf_bwd_points_workspace_bytes(m, batch_size)).
+ *
+ * mccnn_edge_grad_reduce: dpts[j] = sum of dpts_edge[t] over the edges t whose neighbour is j, in the order of the
+ * transposed list of mccnn_transpose_neighbors (start_t [n + 1], perm_t [e]). Every row of dpts is written. */
+size_t mccnn_spatial_conv_bwd_points_workspace_bytes(int m, int batch_size);
+int mccnn_spatial_conv_bwd_points(const float* sorted_pts, const void* sorted_feats, int feats_bf16,
+                                  const int* sorted_batch_ids, const float* pdfs, const float* samples,
+                                  const int* start_idx, const int* packed, const float* aabb_min,
+                                  const float* aabb_max, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* w3, const float* b3, const float* out_grad, int n,
+                                  int m, int e, int num_in_feats, int num_out_feats, int combin, int batch_size,
+                                  float radius, int scale_inv, int avg, float* dpts_edge, float* dsamples,
+                                  float* dpdfs, float* dradius, void* ws, size_t ws_bytes, mccnn_stream_t stream);
+size_t mccnn_compute_pdf_bwd_points_workspace_bytes(int m, int batch_size);
+int mccnn_compute_pdf_bwd_points(const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m,
+                                 const int* packed, int e, const float* aabb_min, const float* aabb_max,
+                                 int batch_size, float window, float radius, int scale_inv, const float* pdf_grad,
+                                 int accumulate, float* dpts_edge, float* dradius, void* ws, size_t ws_bytes,
+                                 mccnn_stream_t stream);
+int mccnn_edge_grad_reduce(const float* dpts_edge, const int* start_t, const int* perm_t, int n, int e, float* dpts,
+                           mccnn_stream_t stream);
+
 /* DEVICE-SIDE POINT COUNTS (hierarchy construction without per-level host read-backs).
  * PointHierarchy (MCConvBuilder.py:101-128) chains sort -> Poisson sampling -> transform_indexs level
  * after level, and the reference reads the number of samples back to the host at every level

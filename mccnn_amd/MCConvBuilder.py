@@ -223,7 +223,9 @@ class PointHierarchy(_PlainState, torch.nn.Module):
 
         if prefetched is not None:
             prefetched.check(inPoints, inBatchIds, radiusList, batchSize, relativeRadius)
-            if aabbReduceGroup is None and ops._ops is None and self.__adopt_prefetched__(prefetched, inFeatures, ops):
+            # (points that require a gradient: the prefetched levels are detached from them -- built directly instead)
+            if aabbReduceGroup is None and ops._ops is None and not getattr(inPoints, "requires_grad", False) \
+                    and self.__adopt_prefetched__(prefetched, inFeatures, ops):
                 return
         aabbMin, aabbMax = ops.compute_aabb(inPoints, inBatchIds, batchSize, self.relativeRadius_)
         if aabbReduceGroup is not None and not self.relativeRadius_:
@@ -240,10 +242,14 @@ class PointHierarchy(_PlainState, torch.nn.Module):
                                               self.relativeRadius_)
             if fused is not None:
                 currFeatures = inFeatures
+                currPts = inPoints
                 for (sampledPts, sampledBatchsIds, _sortedIdx, transformedIndexs), currRadius in zip(fused, radiusList):
                     # the level's feature rows: sortFeatures[sampledIndexs] == features[transformedIndexs]
                     # (MCConvBuilder.py:112-116), one differentiable gather now that the sizes are known
                     currFeatures = ops.get_sampled_features(transformedIndexs, currFeatures)
+                    if getattr(inPoints, "requires_grad", False):
+                        # points that require a gradient: the same rows as a differentiable gather of the previous level
+                        sampledPts = currPts = ops.get_sampled_features(transformedIndexs, currPts)
                     self.points_.append(sampledPts)
                     self.batchIds_.append(sampledBatchsIds)
                     self.features_.append(currFeatures)

@@ -538,7 +538,15 @@ _AABB_EXT = _env.debug("aabb_ext", True)   # A/B: 0 = the ctypes op
 
 
 def compute_aabb(inPts, inBatchIds, batchSize, scaleInv=True):
-    """ComputeAabb (MCConvModuleSrc:20, aabb_gpu.cc:22-86). Non differentiable."""
+    """ComputeAabb (MCConvModuleSrc:20, aabb_gpu.cc:22-86). Extension: with scaleInv and points that require a gradient the
+    box is differentiable -- each extreme passes its gradient to the point(s) attaining it, split equally among ties (as
+    torch.amin / torch.amax do). Otherwise non differentiable (without scaleInv no op reads the box's gradient)."""
+    if scaleInv and getattr(inPts, "requires_grad", False) and torch.is_grad_enabled():
+        return _ComputeAabb.apply(inPts, inBatchIds, batchSize)
+    return _compute_aabb(inPts, inBatchIds, batchSize, scaleInv)
+
+
+def _compute_aabb(inPts, inBatchIds, batchSize, scaleInv):
     op = "ComputeAabbOp"
     _req(batchSize > 0, op + " expects a positive batch size")
     pts, bids = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
@@ -557,6 +565,28 @@ def compute_aabb(inPts, inBatchIds, batchSize, scaleInv=True):
     check(lib.mccnn_compute_aabb(ptr(pts), ptr(bids), pts.shape[0], batchSize, int(bool(scaleInv)), ptr(mn), ptr(mx),
                                  ptr(ws), ws.numel(), stream_handle()), "compute_aabb")
     return mn, mx
+
+
+class _ComputeAabb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inPts, inBatchIds, batchSize):
+        mn, mx = _compute_aabb(inPts, inBatchIds, batchSize, True)
+        ctx.save_for_backward(inPts.detach(), inBatchIds, mn, mx)
+        return mn, mx
+
+    @staticmethod
+    def backward(ctx, gMin, gMax):
+        pts, bids, mn, mx = ctx.saved_tensors
+        b = bids.reshape(-1).long().clamp(0, mn.shape[0] - 1)
+        dp = torch.zeros_like(pts)
+        for box, g in ((mn, gMin), (mx, gMax)):
+            if g is None:
+                continue
+            hit = (pts == box[b]).to(pts.dtype)
+            # tie counts: integer sums, exact in any order
+            cnt = torch.zeros_like(box).index_put_((b,), hit, accumulate=True)
+            dp = dp + hit * (g / cnt.clamp(min=1.0))[b]
+        return dp, None, None
 
 
 def sort_points_step1(inPts, inBatchIds, aabbMin, aabbMax, batchSize, cellSize, scaleInv):
@@ -831,7 +861,19 @@ POISSON_FALLBACKS = 0  # number of calls that had to repeat with the phased form
 
 def compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize, scaleInv,
                 mode=None):
-    """ComputePDF (MCConvModuleSrc:55, compute_pdf.cc:57-142) -> pdfs [E,1]. Non differentiable."""
+    """ComputePDF (MCConvModuleSrc:55, compute_pdf.cc:57-142) -> pdfs [E,1]. Extension: differentiable with respect to the
+    points (and, with scaleInv, the box) when they require a gradient -- the analytic f32 derivative of the KDE sum, every
+    pair of a centre's row contributing to both of its points, whatever `mode` the forward ran in. Otherwise non
+    differentiable."""
+    if torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in (inPts, aabbMin, aabbMax)):
+        return _ComputePDF.apply(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize,
+                                 scaleInv, mode)
+    return _compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize, scaleInv,
+                        mode)
+
+
+def _compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize, scaleInv,
+                 mode=None):
     op = "ComputePDFOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(window > 0.0, op + " expects a positive window")
@@ -853,6 +895,60 @@ def compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, win
                                 float(window), float(radius), int(bool(scaleInv)), md, ptr(pdfs), ptr(ws), ws.numel(),
                                 stream_handle()), "compute_pdf")
     return pdfs
+
+
+def _edge_grads_to_points(dp_edge, packed_obj, n):
+    """Per-point sums of per-edge position gradients [E,3] -> [n,3], gathered through the transposed neighbour list in a
+    fixed order (bit-reproducible, no float atomics)."""
+    start_t, perm_t, _ = _transposed_neighbors(packed_obj, n)
+    out = torch.empty((n, 3), dtype=torch.float32, device=dp_edge.device)
+    check(_lib.load().mccnn_edge_grad_reduce(ptr(dp_edge), ptr(start_t), ptr(perm_t), n, dp_edge.shape[0], ptr(out),
+                                             stream_handle()), "edge_grad_reduce")
+    return out
+
+
+def _box_grads(mn, mx, dR, radius):
+    """dL/dR_b -> (dL/daabbMin, dL/daabbMax) through R_b = radius * max(max(ex, ey), ez): the longest axis takes it (the
+    lowest axis on a tie, like the forward's expression)."""
+    axis = (mx - mn).argmax(dim=1)
+    g = torch.nn.functional.one_hot(axis, 3).to(dR.dtype) * (dR * float(radius)).unsqueeze(1)
+    return -g, g
+
+
+class _ComputePDF(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize, scaleInv, mode):
+        pdfs = _compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, window, radius, batchSize,
+                            scaleInv, mode)
+        ctx.save_for_backward(_f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids"), _f32(aabbMin.detach(), "aabb_min"),
+                              _f32(aabbMax.detach(), "aabb_max"), _i32(startIndexs, "start_indexs"), _i32(neighbors, "neighbors"))
+        ctx.packed_ref = weakref.ref(neighbors)
+        ctx.attrs = (float(window), float(radius), int(batchSize), bool(scaleInv))
+        return pdfs
+
+    @staticmethod
+    def backward(ctx, gPdfs):
+        pts, bids, mn, mx, st, pk = ctx.saved_tensors
+        window, radius, batchSize, scaleInv = ctx.attrs
+        need = ctx.needs_input_grad
+        want_box = scaleInv and (need[2] or need[3])
+        lib = _lib.load()
+        n, m, e = pts.shape[0], st.shape[0], pk.shape[0]
+        g = _f32(gPdfs, "pdfs_grad")
+        dp = torch.empty((max(e, 1), 3), dtype=torch.float32, device=pts.device)
+        dR = torch.empty(batchSize, dtype=torch.float32, device=pts.device) if want_box else None
+        ws = _ws(lib.mccnn_compute_pdf_bwd_points_workspace_bytes(m, batchSize), pts.device)
+        check(lib.mccnn_compute_pdf_bwd_points(ptr(pts), ptr(bids), ptr(st), m, ptr(pk), e, ptr(mn), ptr(mx), batchSize,
+                                               window, radius, int(scaleInv), ptr(g), 0, ptr(dp), ptr(dR), ptr(ws), ws.numel(),
+                                               stream_handle()), "compute_pdf_grad(points)")
+        dPts = None
+        if need[0]:
+            packed_obj = ctx.packed_ref()
+            dPts = _edge_grads_to_points(dp[:e], pk if packed_obj is None else packed_obj, n)
+        dMin = dMax = None
+        if want_box:
+            dMin, dMax = _box_grads(mn, mx, dR, radius)
+        return (dPts, None, dMin if need[2] else None, dMax if need[3] else None, None, None, None, None, None, None, None)
 
 
 class DeferredNeighborsPDF:
@@ -960,7 +1056,8 @@ def find_neighbors_pdf_deferred(inPts, inBatchIds, sortedPts, sortedBatchIds, ce
 
 def poisson_sampling(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv):
     """PoissonSampling (MCConvModuleSrc:59, poisson_sampling.cc:109-211) -> (pts [S,3], batchIds [S,1], indexs [S]).
-    indexs point into the SORTED input list. Non differentiable."""
+    indexs point into the SORTED input list. Extension: when inPts require a gradient the sampled points are a
+    differentiable row gather of them; the batch ids and indexs are never differentiable."""
     op = "PoissonSamplingOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
@@ -994,6 +1091,10 @@ def poisson_sampling(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, radius, ba
     oI = torch.empty(s, dtype=torch.int32, device=p.device)
     check(lib.mccnn_poisson_sampling_fill(ptr(p), n, ptr(cells), batchSize, nc, s, ptr(oP), ptr(oB), ptr(oI), ptr(ws),
                                           ws.numel(), stream_handle()), "poisson_sampling(fill)")
+    if getattr(inPts, "requires_grad", False) and torch.is_grad_enabled():
+        # the samples are rows of the sorted input points: the same values as a differentiable gather (backward: scatter
+        # with zero fill)
+        oP = _GetSampledFeatures.apply(oI, inPts)
     return oP, oB, oI
 
 
@@ -1295,7 +1396,19 @@ class _SpatialConv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, outGrad):
-        # _spatial_conv_grad (MCConvModuleSrc:74-81): grads for features and the 6 MLP tensors only
+        res = _SpatialConv._feature_grads(ctx, outGrad)
+        # extension: gradients with respect to positions -- the neighbour points (0), the PDFs (3), the centres (4) and,
+        # with scaleInv, the box (7, 8) -- only for the inputs that ask for one; the seven above are computed as before
+        need = ctx.needs_input_grad
+        if need[0] or need[3] or need[4] or (ctx.attrs[4] and (need[7] or need[8])):
+            res = list(res)
+            res[0], res[3], res[4], res[7], res[8] = _conv_point_grads(ctx, outGrad)
+            res = tuple(res)
+        return res
+
+    @staticmethod
+    def _feature_grads(ctx, outGrad):
+        # _spatial_conv_grad (MCConvModuleSrc:74-81): grads for features and the 6 MLP tensors
         saved = ctx.saved_tensors
         pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3 = saved[:15]
         sort_index = saved[15] if len(saved) > 15 else None
@@ -1369,6 +1482,40 @@ class _SpatialConv(torch.autograd.Function):
               "spatial_conv_grad")
         return (None, _unsort_grad(sort_index, fg), None, None, None, None, None, None, None, dw1, db1, dw2.view(ws2), db2.view(bs2), dw3.view(ws3), db3.view(bs3),
                 None, None, None, None, None, None, None, None, None)
+
+
+def _conv_point_grads(ctx, outGrad):
+    """-> (dPts, dPDFs, dSamplePts, dAabbMin, dAabbMax) of a spatial_conv node, None for what is not asked for."""
+    saved = ctx.saved_tensors
+    pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3 = saved[:15]
+    numOutFeatures, combin, batchSize, radius, scaleInv, avg = ctx.attrs
+    need = ctx.needs_input_grad
+    if len(saved) > 16:  # ctx.unsorted: the saved rows are those of the unsorted points -- the kernel reads sorted rows
+        feats = _scatter_rows(feats, saved[15], feats.shape[0], False)
+    want_box = scaleInv and (need[7] or need[8])
+    lib = _lib.load()
+    n, fin = feats.shape
+    m, e = smp.shape[0], pk.shape[0]
+    og = outGrad.float().contiguous()
+    dev = pts.device
+    dp = torch.empty((max(e, 1), 3), dtype=torch.float32, device=dev)
+    dc = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    dpdf = torch.empty((e, 1), dtype=torch.float32, device=dev) if need[3] else None
+    dR = torch.empty(batchSize, dtype=torch.float32, device=dev) if want_box else None
+    ws = _ws(lib.mccnn_spatial_conv_bwd_points_workspace_bytes(m, batchSize), dev)
+    check(lib.mccnn_spatial_conv_bwd_points(ptr(pts), ptr(feats), int(feats.dtype == torch.bfloat16), ptr(bids), ptr(pdfs),
+                                            ptr(smp), ptr(st), ptr(pk), ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                            ptr(w3), ptr(b3), ptr(og), n, m, e, fin, numOutFeatures, int(combin), batchSize,
+                                            radius, int(scaleInv), int(avg), ptr(dp), ptr(dc), ptr(dpdf), ptr(dR), ptr(ws),
+                                            ws.numel(), stream_handle()), "spatial_conv_grad(points)")
+    dPts = None
+    if need[0]:
+        packed_obj = ctx.packed_ref()
+        dPts = _edge_grads_to_points(dp[:e], pk if packed_obj is None else packed_obj, n)
+    dMin = dMax = None
+    if want_box:
+        dMin, dMax = _box_grads(mn, mx, dR, radius)
+    return (dPts, dpdf, dc if need[4] else None, dMin if need[7] else None, dMax if need[8] else None)
 
 
 def _unsort_grad(idx, fg):

@@ -83,6 +83,14 @@ SIGNATURES = {
     "mccnn_spatial_conv_bwd_rows": (_i, [_vp] * 16 + [_i, _i, _i, _i, _i, _f, _i, _i, _i] + [_vp] * 7 + [_vp] * 8 + [_vp, _vp, _sz, _vp]),
     "mccnn_transpose_neighbors_workspace_bytes": (_sz, [_i, _i]),
     "mccnn_transpose_neighbors": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    # gradients with respect to positions (conv_points.hip)
+    "mccnn_spatial_conv_bwd_points_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_spatial_conv_bwd_points": (_i, [_vp, _vp, _i] + [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _i, _f, _i, _i]
+                                      + [_vp] * 5 + [_sz, _vp]),
+    "mccnn_compute_pdf_bwd_points_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_compute_pdf_bwd_points": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _f, _f, _i, _vp, _i, _vp, _vp, _vp, _sz,
+                                          _vp]),
+    "mccnn_edge_grad_reduce": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     # native step executor (exec.hip)
     "mccnn_geometry_create": (_vp, []),
     "mccnn_geometry_destroy": (None, [_vp]),
