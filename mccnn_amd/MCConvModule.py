@@ -172,16 +172,6 @@ def _remember_edges(gkey, e):
     if gkey[1] > 0:
         _EDGE_RATIO[(gkey[0], gkey[3], gkey[5])] = e / float(gkey[1])
 _TLS = threading.local()
-_MAILBOX_COPY = _env.debug("mailbox_copy", False)
-
-
-def _pinned_int():
-    """One pinned int32 per host thread: the copy into it and the wait for it happen back to back on the calling
-    thread, so concurrent callers (threads / streams) never share a slot."""
-    buf = getattr(_TLS, "pinned", None)
-    if buf is None:
-        buf = _TLS.pinned = torch.empty(1, dtype=torch.int32).pin_memory()
-    return buf
 
 
 def _host_mailbox():
@@ -196,9 +186,6 @@ def _host_mailbox():
     return box
 
 
-# find_neighbors: True = the count kernel stores the edge total into the pinned mailbox and the host polls it;
-# False = total in device memory + an asynchronous copy + an event wait
-COUNT_MAILBOX = _env.debug("count_mailbox", True)
 _MAILBOX_SPIN_S = 200e-6  # tight polling for this long (the producing kernel retires within tens of microseconds) ...
 _MAILBOX_YIELD_S = 0.25   # ... then polling that hands the GIL to other threads between reads, then a synchronisation
 
@@ -534,9 +521,6 @@ def _seed_num_cells(aabbMin, aabbMax, extent):
 
 
 # ---------------------------------------------------------------------------------------------
-_AABB_EXT = _env.debug("aabb_ext", True)   # A/B: 0 = the ctypes op
-
-
 def compute_aabb(inPts, inBatchIds, batchSize, scaleInv=True):
     """ComputeAabb (MCConvModuleSrc:20, aabb_gpu.cc:22-86). Extension: with scaleInv and points that require a gradient the
     box is differentiable -- each extreme passes its gradient to the point(s) attaining it, split equally among ties (as
@@ -556,7 +540,7 @@ def _compute_aabb(inPts, inBatchIds, batchSize, scaleInv):
     if CHECK_BATCH_IDS and check_batch_ids(bids, batchSize):
         check(-2, op)  # MCCNN_E_BATCHID
     ext = _torch_ext()
-    if ext is not None and _AABB_EXT and pts.is_cuda and bids.dim() in (1, 2):   # one C++ call (the op every hierarchy of a step starts with)
+    if ext is not None and pts.is_cuda and bids.dim() in (1, 2):   # one C++ call (the op every hierarchy of a step starts with)
         mn, mx = ext.compute_aabb(pts, bids.view(-1), int(batchSize), bool(scaleInv))
         return mn, mx
     mn = torch.empty((batchSize, 3), dtype=torch.float32, device=pts.device)
@@ -799,32 +783,15 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     n2 = p2.shape[0]
     ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
     order = _order_hint(inPts)
-    if order is not None and (order.shape[0] != m or _env.debug("nw_no_order", False)):
+    if order is not None and order.shape[0] != m:
         order = None
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
             int(bool(scaleInv)), ptr(order))
     # The size of the second output is only known on the device: the prefix sum stores the total straight into a
     # pinned host word (no copy is enqueued) and the host polls it.
-    total = None
-    if COUNT_MAILBOX:
-        boxv[0] = -1
-        total_ptr = box.data_ptr()
-    else:  # the total lands in device memory and is copied to the host (stream-ordered BEFORE the fill)
-        total = torch.empty(1, dtype=torch.int32, device=c.device)
-        total_ptr = ptr(total)
-    check(lib.mccnn_find_neighbors_count(*args, ptr(start), total_ptr, ptr(ws), ws.numel(), stream_handle()),
+    boxv[0] = -1
+    check(lib.mccnn_find_neighbors_count(*args, ptr(start), box.data_ptr(), ptr(ws), ws.numel(), stream_handle()),
           "find_neighbors(count)")
-    ev = None
-    if total is not None:
-        box.copy_(total, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-
-    def read_total():
-        if ev is None:
-            return _await_mailbox(boxv)
-        ev.synchronize()
-        return int(boxv[0])
     # Searches repeat with the same shapes step after step, so the fill is launched into a buffer sized from the last
     # total of this shape BEFORE the total is read: the host round trip hides behind the kernel. Too small a guess ->
     # exact rerun.
@@ -835,11 +802,11 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
         buf = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
         check(lib.mccnn_find_neighbors_fill(*args, ptr(start), guess, ptr(buf), ptr(ws), ws.numel(), stream_handle()),
               "find_neighbors(fill)")
-        e = read_total()
+        e = _await_mailbox(boxv)
         if e <= guess:
             packed = buf[:e]
     else:
-        e = read_total()
+        e = _await_mailbox(boxv)
     if packed is None:
         packed = torch.empty((e, 2), dtype=torch.int32, device=c.device)
         check(lib.mccnn_find_neighbors_fill(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle()),
@@ -1014,7 +981,7 @@ def find_neighbors_pdf_deferred(inPts, inBatchIds, sortedPts, sortedBatchIds, ce
     total_dev = torch.empty(1, dtype=torch.int32, device=c.device)
     ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
     order = _order_hint(inPts)
-    if order is not None and (order.shape[0] != m or _env.debug("nw_no_order", False)):
+    if order is not None and order.shape[0] != m:
         order = None
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
             int(bool(scaleInv)), ptr(order))
@@ -1027,13 +994,8 @@ def find_neighbors_pdf_deferred(inPts, inBatchIds, sortedPts, sortedBatchIds, ce
     slot[1][0] = -1
     # the prefix sum stores the total twice: in device memory for the KDE kernels and straight into the pinned host word
     # (no copy is enqueued); nobody waits for it here
-    if _MAILBOX_COPY:  # A/B switch: the total travels through an enqueued device-to-host copy instead
-        check(lib.mccnn_find_neighbors_count(*args, ptr(start), ptr(total_dev), ptr(ws), ws.numel(), stream_handle()),
-              "find_neighbors(count)")
-        slot[0].copy_(total_dev, non_blocking=True)
-    else:
-        check(lib.mccnn_find_neighbors_count2(*args, ptr(start), ptr(total_dev), slot[0].data_ptr(), ptr(ws), ws.numel(),
-                                              stream_handle()), "find_neighbors(count)")
+    check(lib.mccnn_find_neighbors_count2(*args, ptr(start), ptr(total_dev), slot[0].data_ptr(), ptr(ws), ws.numel(),
+                                          stream_handle()), "find_neighbors(count)")
     packed = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
     check(lib.mccnn_find_neighbors_fill(*args, ptr(start), guess, ptr(packed), ptr(ws), ws.numel(), stream_handle()),
           "find_neighbors(fill)")

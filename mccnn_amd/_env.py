@@ -13,23 +13,34 @@ the library (csrc/debug_opts.h names the library's keys):
     MCCNN_DEBUG="key=value,key,..."      (a bare key means key=1; read once per process)
 
 THE table of keys is KNOWN_KEYS below -- the same table as kDebugKeys of csrc/debug_opts.h (tests/test_capi_cpu.py checks
-that they are equal and that every key any source file queries is in it); a key of MCCNN_DEBUG that is not in it is
-reported once on stderr instead of being silently ignored. Python-side keys (default): fuse_sort (1), native_prefetch (1),
-plan_prefetch (1), plan_prefetch_max_e (1e12), geo_prefetch_min (5), mailbox_copy (0), count_mailbox (1), ecap_scale (1),
-hier_pmode (1), rows_min_degree (16), unsorted_max_points (32768), geo_trace (0), nw_no_order (0).
+that they are equal, that every key any source file queries is in it and that every key in it is queried); a key of
+MCCNN_DEBUG that is not in it is reported once on stderr instead of being silently ignored. Keys read on the Python side
+(default):
+
+    fuse_sort (1)                 0 = ConvolutionBuilder sorts the feature rows in an op of its own
+    native_prefetch (1)           0 = prefetch_geometry takes the op-by-op prefetch
+    plan_prefetch (1)             0 = prefetch_step builds no row plans / transposed lists ahead
+    plan_prefetch_max_e (1e12)    no pieces ahead for geometries with a larger edge capacity
+    geo_prefetch_min (5)          geometries a builder's step needs before it builds them ahead on side streams
+    ecap_scale (1)                debugging: scales the native executor's edge-capacity guesses
+    hier_pmode (1)                Poisson mode of the prefetched hierarchies (2 = dataflow form that gives up early)
+    geo_trace (0)                 1 = a stderr line wherever the native path hands a convolution to the op-by-op one
+    rows_min_degree (16)          (shared with the library, csrc/debug_opts.h)
+    unsorted_max_points (32768)   (shared with the library, csrc/debug_opts.h)
+
 (MCCNN_LIB_NAME / MCCNN_EXTRA_FLAGS belong to mccnn_amd.build: A/B builds of the library.)"""
 import os
 import sys
 
 KNOWN_KEYS = (
     # library (csrc/debug_opts.h)
-    "small_off", "plan_small_off", "plan_small", "plan_small_max_l", "plan_mid_l", "plan_min_l", "rows_force",
+    "small_off", "plan_small", "plan_small_max_l", "plan_mid_l", "plan_min_l", "rows_force",
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",
-    "nw_group", "nw_group_fill", "nw_lds_pad", "scan_bg_tiles", "issue_thread", "issue_inline", "job_delay_us",
-    "hier_trace", "geo_own_pool", "trace_terminate", "nw_fused", "geo_batch", "plan_batch_all", "aabb_one_max", "plan_large_batch", "plan_batch_sync", "caller_join_off", "bwd_min_chunks", "geo_arena",
+    "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",
+    "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks",
     # Python side
-    "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min", "mailbox_copy",
-    "count_mailbox", "ecap_scale", "hier_pmode", "geo_trace", "nw_no_order", "aabb_ext")
+    "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",
+    "ecap_scale", "hier_pmode", "geo_trace")
 
 
 def _parse():

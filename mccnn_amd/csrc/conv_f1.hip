@@ -209,8 +209,8 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
     // (Measured and dropped: a second iteration of look-ahead -- the rows the NEXT iteration's list entries point to
     // (point, centre, feature, row bounds) gathered before this iteration's block loop: 200 VGPRs / 2 waves per SIMD, same
     // forward time 0.175 ms, pipelined step 0.607 against 0.602 ms. The loop's skeleton -- gathers, records, tail stores --
-    // measures 60-75 us on its own (MCCNN_ABL_X4_NOSCAN + NOMLP), of which the stores are ~12 us (NOTAIL / NOREC) and the
-    // prologue 5 us (NOLOOP); kernel MLP 63 us, segmented sums 18 us.)
+    // measures 60-75 us on its own (ablation builds without the segmented sums and the MLP, NOTES 5c), of which the stores
+    // are ~12 us and the prologue 5 us; kernel MLP 63 us, segmented sums 18 us.)
     int2 prN[4];
     float pdfN[4];
 #pragma unroll
@@ -219,9 +219,6 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
         prN[u] = a.packed[t];
         pdfN[u] = a.pdfs[t];
     }
-#ifdef MCCNN_ABL_X4_NOLOOP  // timing ablation only: the kernel's prologue alone
-    if (eBeg >= 0) return;
-#endif
     for (int base = eBeg; base < eEnd; base += 256) {
         const int lastPos = min(base + 256, eEnd) - 1;  // the last edge of this iteration
         float d0[4], d1[4], d2[4], sE[4];
@@ -249,12 +246,9 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
             if (a.avg) K = (float)(((pr.y + 1 < a.m) ? a.start[pr.y + 1] : a.e) - a.start[pr.y]);
             const float inv = in[u] ? __builtin_amdgcn_rcpf(pdf * K) : 0.0f;
             sE[u] = in[u] ? a.feats[j] * inv : 0.0f;
-#ifndef MCCNN_ABL_X4_NOREC
             if (recOut) recStage[4 * lane + u] = make_float4(d0[u], d1[u], d2[u], inv);  // the record f1_edge_records would compute
-#endif
             key[u] = in[u] ? pr.y + 1 : 0;
         }
-#ifndef MCCNN_ABL_X4_NOREC
         if (recOut) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -262,7 +256,6 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
                 if (t < eEnd) recOut[t] = recStage[64 * k + lane];
             }
         }
-#endif
         if (base + 256 < eEnd) {  // the list entries of the next iteration
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -327,12 +320,6 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
             float c[4][8];
             X4_PHASE();
             const float one = opaque_one();
-#ifdef MCCNN_ABL_X4_NOMLP  // timing ablation only (wrong results): no kernel MLP
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) c[u][r] = sE[u] * (r < 4 ? wr.w2lo[r] : wr.w2hi[r]) + (r & 1 ? d0[u] : d1[u]) + one;
-#else
 #pragma unroll
             for (int g = 0; g < 4; g += MCCNN_F1_X4_GROUP) {  // MCCNN_F1_X4_GROUP edges per MFMA / VALU phase
                 float h[MCCNN_F1_X4_GROUP][8];
@@ -365,7 +352,6 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
 #pragma unroll
                     for (int r = 0; r < 8; ++r) c[g + v][r] = sE[g + v] * relu1(c[g + v][r]);
             }
-#endif
             float* cq = carry + q * 8;
             {
                 f32x4 cv0 = {0.f, 0.f, 0.f, 0.f}, cv1 = cv0;
@@ -373,7 +359,6 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
 #pragma unroll
                 for (int k = 0; k < 8; ++k) c[0][k] = fmaf(mC, k < 4 ? cv0[k & 3] : cv1[k & 3], c[0][k]);
             }
-#ifndef MCCNN_ABL_X4_NOSCAN  // timing ablation only (wrong results): no segmented sums
             // the lane's own four edges, the scan over the lane totals, the prefix that enters the lane
 #pragma unroll
             for (int u = 1; u < 4; ++u)
@@ -388,18 +373,13 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
             for (int u = 0; u < 3; ++u)
 #pragma unroll
                 for (int k = 0; k < 8; ++k) c[u][k] = fmaf(op[u], cin[k], c[u][k]);
-#endif
             if (cont && lane == 63) {
                 *reinterpret_cast<f32x4*>(cq) = (f32x4){c[3][0], c[3][1], c[3][2], c[3][3]};
                 *reinterpret_cast<f32x4*>(cq + 4) = (f32x4){c[3][4], c[3][5], c[3][6], c[3][7]};
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-#ifdef MCCNN_ABL_X4_NOTAIL  // timing ablation only (wrong results): the rows are stored by the last block only
-                if (tail[u] && q == a.nb - 1) {
-#else
                 if (tail[u]) {
-#endif
                     float4* dst = reinterpret_cast<float4*>(A + (size_t)ci[u] * rowA + q * 8);
                     dst[0] = make_float4(c[u][0], c[u][1], c[u][2], c[u][3]);
                     dst[1] = make_float4(c[u][4], c[u][5], c[u][6], c[u][7]);
@@ -484,11 +464,7 @@ __global__ __launch_bounds__(256, MCCNN_F1_OCC) void f1_bwd_edges(ConvArgs a, co
     stage_weights<MCCNN_WQ_BWD>(a, wl);
     __syncthreads();
     const int waveGlobal = blockIdx.x * 4 + wave;
-#ifdef MCCNN_ABL_SAMESLICE  // timing ablation only (wrong results): every wave sweeps the first slice -> all loads hit the caches
-    const long long eBegL = ((long long)waveGlobal * cpw * 64 < a.e) ? 0 : a.e;
-#else
     const long long eBegL = (long long)waveGlobal * cpw * 64;
-#endif
     if (eBegL >= a.e) return;
     const int eBeg = (int)eBegL;
     const int eEnd = (int)min((long long)a.e, eBegL + (long long)cpw * 64);
@@ -520,18 +496,11 @@ __global__ __launch_bounds__(256, MCCNN_F1_OCC) void f1_bwd_edges(ConvArgs a, co
             const float inv = act ? rc.w : 0.f;
             // G is block-major, [q][centre][8]: inside a sweep the 32-byte pieces of consecutive centres are adjacent
             const float4* gp = reinterpret_cast<const float4*>(G + ((size_t)q * a.m + ci) * 8);
-#ifdef MCCNN_ABL_NOGATHER  // timing ablation only (wrong results): the kernel with every gather already in registers
-            const float4 g0 = make_float4(rc.x, rc.y, rc.z, rc.w), g1 = make_float4(rc.y, rc.z, rc.x, rc.w);
-            const float f = rc.z;
-            float dfOld = 0.f, gbi = 0.f;
-            (void)gp;
-#else
             const float4 g0 = gp[0], g1 = gp[1];
             const float f = a.feats[j];
             float dfOld = 0.f, gbi = 0.f;
             if (act && q > 0) dfOld = dfE[t];
             if (last) gbi = gb[ci];
-#endif
             {
                 int tn = min(t + 64, a.e - 1);  // clamped: branch-free prefetch of the next chunk
                 prN = a.packed[tn];
@@ -555,14 +524,10 @@ __global__ __launch_bounds__(256, MCCNN_F1_OCC) void f1_bwd_edges(ConvArgs a, co
             float sfg = 0.f;
 #pragma unroll
             for (int k = 0; k < 8; ++k) sfg = fmaf(Gq[k], a2[k], sfg);
-#ifndef MCCNN_ABL_NODF  // timing ablation only: no per-edge feature-gradient traffic
             if (act) {
                 if (last) atomicAdd(&featGrad[j], (dfOld + sfg + gbi) * inv);
                 else dfE[t] = dfOld + sfg;
             }
-#else
-            asm volatile("" ::"v"(sfg), "v"(dfOld), "v"(gbi));
-#endif
             // t3 = 1[pre2 >= 0] * G_i s_e ; dW2 += t3 a1^T, db2 += t3
             float t3[8];
 #pragma unroll
@@ -631,9 +596,6 @@ __global__ __launch_bounds__(256) void f1_bwd_centres(ConvArgs a, const float* _
     const int c0 = w * cPerWave;
     const int c1 = min(a.m, c0 + cPerWave);
     if (q == a.nb) {
-#ifdef MCCNN_ABL_NODOT  // timing ablation only (wrong results)
-        return;
-#endif
         for (int i = c0 + lane; i < c1; i += 64) {
             const float* row = outGrad + (size_t)i * a.outF;
             float gbv = 0.f;
@@ -692,10 +654,6 @@ __global__ __launch_bounds__(256) void f1_bwd_centres(ConvArgs a, const float* _
         dst[0] = make_float4(Gk[0], Gk[1], Gk[2], Gk[3]);
         dst[1] = make_float4(Gk[4], Gk[5], Gk[6], Gk[7]);
     }
-#ifdef MCCNN_ABL_NOBFLY  // timing ablation only (wrong results)
-    float r3 = acc[lane & 7] + acc[8 + (lane & 7)], rb = accb[lane & 7];
-    for (int k = 16; k < 64; ++k) r3 += acc[k];
-#else
     float r3 = wave_reduce64(acc, lane);
     float misc[64];
 #pragma unroll
@@ -703,7 +661,6 @@ __global__ __launch_bounds__(256) void f1_bwd_centres(ConvArgs a, const float* _
 #pragma unroll
     for (int k = 8; k < 64; ++k) misc[k] = 0.f;
     float rb = wave_reduce64(misc, lane);
-#endif
     float* pq = partials + ((size_t)w * a.nb + q) * MCCNN_F1_ROWC;
     pq[lane] = r3;
     if (lane < 8) pq[64 + lane] = rb;

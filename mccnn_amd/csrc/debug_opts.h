@@ -8,20 +8,33 @@
 // Everything else -- A/B switches of single kernels, tracing, fault injection for the soak tests -- is ONE list:
 //     MCCNN_DEBUG="key=value,key,..."      (a bare key means key=1; read once per process)
 // THE table of keys is kDebugKeys below (library keys first, then the Python side's: mccnn_amd/_env.py carries the same
-// table and tests/test_capi_cpu.py checks that the two are equal and that every key any source file queries is in it). A
-// key of MCCNN_DEBUG that is in neither is reported ONCE on stderr -- a misspelt switch must not silently time the default
-// on both sides of an A/B. Library keys (default): small_off (0) plan_small_off (0) plan_small (4096: capacity of the
-// single-workgroup plan layout, clamped to [1024, MCCNN_PLAN_SMALL]; the plan_small=8192 experiment of NOTES needed a
-// rebuild with a larger MCCNN_PLAN_SMALL) plan_small_max_l (16) plan_mid_l (16) plan_min_l (4) rows_force (0)
-// rows_min_degree (16) unsorted_max_points (32768) force_valu (0) no_f1 (0) f1_x4_min_e (2000000) f1_x4_waves_per_cu (0)
-// nw_lean (-1) nw_group (0) nw_group_fill (0) nw_lds_pad (-1) scan_bg_tiles (8) issue_thread (1) issue_inline (0)
-// job_delay_us (0) hier_trace (0) geo_own_pool (1) trace_terminate (0) nw_fused (1: lists of <= 2048 centres scan their
-// counts inside the fill pass) geo_batch (1: the geometries prefetch_step starts go out as ONE batch, one launch per kernel kind)
-// plan_batch_all (1: the pieces of all of them as one batch as well; 0 = only geometries with a small plan)
-// aabb_one_max (8192: compute_aabb in one launch up to this many points) plan_large_batch (1: large plans join the batch)
-// plan_batch_sync (0: debugging -- a synchronisation and a stderr line per launch of the plan batch) bwd_min_chunks (2: 64-edge chunks per wave
-// of conv_bwd_mfma at least) caller_join_off (0: fault
-// injection -- a geometry nobody joined does not order the caller's stream behind its events: the round-6 lifetime bug).
+// table and tests/test_capi_cpu.py checks that the two are equal, that every key any source file queries is in it and
+// that every key in it is queried). A key of MCCNN_DEBUG that is in neither is reported ONCE on stderr -- a misspelt
+// switch must not silently time the default on both sides of an A/B. Library keys (default):
+//     small_off (0)                  1 = tiny grids / lists take the kernels of the large inputs (mccnn_debug_small_kernels)
+//     plan_small (4096)              capacity of the single-workgroup plan layout, clamped to [1024, MCCNN_PLAN_SMALL]
+//     plan_small_max_l (16)          longest piece of a plan in the single-workgroup layout
+//     plan_mid_l (16)                shortest piece of a plan of a mid-size list (< 16384 rows)
+//     plan_min_l (4)                 shortest piece of a plan of a small list
+//     rows_force (0)                 1 = depth-wise layers take the row kernels wherever they apply
+//     rows_min_degree (16)           mean row length from which the backward pass of a large list takes the row kernels
+//     unsorted_max_points (32768)    levels up to this size: the row kernels read the unsorted feature rows in place
+//     force_valu (0)                 1 = spatial_conv on the VALU kernels (seeds mccnn_debug_conv_impl)
+//     no_f1 (0)                      1 = one-input-feature combin layers on the general kernels (seeds mccnn_debug_conv_impl)
+//     f1_x4_min_e (2000000)          edges from which a one-input-feature forward pass takes four edges per lane
+//     f1_x4_waves_per_cu (0)         waves per CU of that pass (0 = as many as fit)
+//     nw_lean (-1)                   1 / 0 = the lean / bounds-checked search loop (-1: lean except for background launches)
+//     nw_lds_pad (-1)                LDS bytes a neighbour search asks for (-1 = 24000 for background launches, else 0)
+//     scan_bg_tiles (8)              tiles from which a background scan takes the two-launch form (0 = never)
+//     issue_thread (1)               0 = the torch extension issues side-stream builds on the calling thread
+//     job_delay_us (0)               fault injection: a random pause of up to this many us before every helper-thread job
+//     hier_trace (0)                 1 = a stderr line per prefetched hierarchy job
+//     geo_own_pool (1)               0 = prefetched geometries take their memory from the caller's stream
+//     trace_terminate (0)            1 = a backtrace on std::terminate
+//     aabb_one_max (8192)            compute_aabb in one launch up to this many points
+//     plan_batch_sync (0)            1 = a synchronisation and a stderr line per launch of the plan batch
+//     caller_join_off (0)            fault injection: a geometry nobody joined does not order the caller's stream
+//     bwd_min_chunks (2)             64-edge chunks per wave of the edge-streaming backward passes at least
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -31,13 +44,13 @@
 namespace mccnn {
 
 #define MCCNN_DEBUG_KEYS                                                                                                   \
-    "small_off", "plan_small_off", "plan_small", "plan_small_max_l", "plan_mid_l", "plan_min_l", "rows_force",            \
+    "small_off", "plan_small", "plan_small_max_l", "plan_mid_l", "plan_min_l", "rows_force",                              \
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",      \
-    "nw_group", "nw_group_fill", "nw_lds_pad", "scan_bg_tiles", "issue_thread", "issue_inline", "job_delay_us",           \
-    "hier_trace", "geo_own_pool", "trace_terminate", "nw_fused", "geo_batch", "plan_batch_all", "aabb_one_max", "plan_large_batch", "plan_batch_sync", "caller_join_off", "bwd_min_chunks", "geo_arena",            \
+    "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",                                                       \
+    "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks", \
     /* Python side (mccnn_amd/_env.py) */                                                                                \
-    "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min", "mailbox_copy",           \
-    "count_mailbox", "ecap_scale", "hier_pmode", "geo_trace", "nw_no_order", "aabb_ext"
+    "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",                          \
+    "ecap_scale", "hier_pmode", "geo_trace"
 static const char* const kDebugKeys[] = {MCCNN_DEBUG_KEYS};
 
 // Parses MCCNN_DEBUG once; items whose key is not in kDebugKeys are reported on stderr (once per process and library).

@@ -815,8 +815,6 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
             if (!(rest & bit)) continue;
             Plan& p = g->plan[tr];
             const int rows = tr ? g->n : g->m;
-            static const int largeOn = debug_int("plan_large_batch", 1);   // A/B: 0 = large plans take their own chains
-            if (!largeOn) continue;
             if (!plan_large_batchable(rows, e, g->n, tr, g->tl_built ? 1 : 0)) continue;
             if (plan_prepare(g, tr, e)) continue;
             if (!p.buf || p.bytes < (size_t)p.total) continue;

@@ -209,11 +209,7 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                 for (int r = 0; r < MCCNN_NW_ROUNDS; ++r) {
                     if (r * 64 < total) {
                         const unsigned long long bm = mw[r];
-#ifdef MCCNN_NW_NO_INVB
-                        if ((bm >> lane) & 1ull) {
-#else
                         if (__builtin_amdgcn_inverse_ballot_w64(bm)) {
-#endif
                             const int pos = cbase + run + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
                             if (fits) out[pos] = make_int2(jr[r], cid);
                             else if (pos < capacity) out[pos] = make_int2(jr[r], cid);
@@ -230,7 +226,7 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                 // (Measured and dropped: the cell of a flat position from a bit plane of cell ends -- ds_or per non-empty
                 // cell, a population count and one v_mbcnt per round instead of the 5-step binary search: the plane's set-up
                 // per window (two more wave barriers, an LDS atomic, a scan) eats what the searches cost, -1 % on one box.
-                // MCCNN_NW_NO_INVB: the per-lane bit test instead of the inverse ballot, +2.7 % on the room. The mask words of
+                // The per-lane bit test instead of the inverse ballot: +2.7 % on the room. The mask words of
                 // the NEXT centre requested while this one is compacted (and the first before the cell searches): +3 %.)
             }
             continue;
@@ -534,16 +530,8 @@ __global__ __launch_bounds__(256) void pdf_rows(const float4* __restrict__ sc, c
 #endif
 // MCCNN_PDF_ROWS // consecutive rows per wave: the next row's points are requested while this row's tiles run
 typedef float pdf_v4f __attribute__((ext_vector_type(4)));
-#if defined(MCCNN_PDF_ABL) && MCCNN_PDF_ABL == 1   // timing ablations only (wrong results): 1 no exponentials, 2 no tiles, 3 no MFMA
-#define PDF_EXP(x) (x)
-#else
 #define PDF_EXP(x) __builtin_amdgcn_exp2f(x)
-#endif
-#if defined(MCCNN_PDF_ABL) && MCCNN_PDF_ABL == 3
-#define PDF_MFMA(a, b, c) ((c) * (a) + (b))
-#else
 #define PDF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
-#endif
 struct PdfPoint { float x, y, z; };
 __device__ __forceinline__ PdfPoint pdf_gather(const float* __restrict__ pts, int j) {
     const float* p = pts + (size_t)j * 3;
@@ -673,11 +661,7 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const float* _
             if (lane == 0) { longRows[wave * MCCNN_PDF_ROWS + rr] = PdfLongRow{rowStart, k, s, scale}; anyLong = 1; }
             continue;
         }
-#if defined(MCCNN_PDF_ABL) && MCCNN_PDF_ABL == 2
-        const int T = 0;
-#else
         const int T = (k + 15) >> 4;
-#endif
         const float ox = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me.x)));
         const float oy = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me.y)));
         const float oz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me.z)));
@@ -875,8 +859,6 @@ static bool neigh_lean() {
     return !g_background;
 }
 static int neigh_group(int m) {
-    static const int forced = debug_int("nw_group", 0);  // A/B switch, read once
-    if (forced >= 1 && forced <= 32) return forced;
     // centres per wave: more of them share a window's staging and the per-wave set-up (8 rooms, 800 k centres: 0.309 ms at
     // 8, 0.274 at 16, 0.269 at 24) -- as long as the launch still fills the chip (100 k centres: 0.0588 / 0.0580 / 0.0650)
     // (background launches keep 8: beside the convolution kernels the pipelined step of the room reads 0.596 ms at 8, 0.602-0.610 at 16)
@@ -973,12 +955,10 @@ static int find_neighbors_fill_impl(const float* centres, const int* centre_batc
     NeighWs w;
     if (!neigh_ws(ws, ws_bytes, m, n, w)) return MCCNN_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    static const int forcedFill = debug_int("nw_group_fill", 0);  // A/B switch
     // (mask rows are indexed by visiting position: the two passes may group differently -- the compaction gains little
     // from more centres per wave: 100 k centres 0.0612 ms at 8, 0.0622 at 16; 800 k centres 0.305 at 8, 0.295 at 24)
     int G = neigh_group(m);
     if (G == 16) G = MCCNN_NW_G;
-    if (forcedFill >= 1 && forcedFill <= 32) G = forcedFill;
     const float Tabs = scale_inv ? 0.0f : sqrt_threshold_host(radius);
     size_t dyn = neigh_lds_pad();
     if (scan && dyn < (size_t)m * sizeof(int)) dyn = (size_t)m * sizeof(int);
@@ -1015,8 +995,7 @@ int find_neighbors_chain(const float* centres, const int* centre_batch_ids, int 
                          const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                          float radius, int scale_inv, const int* centre_order, int* start_idx, int e_capacity, int* packed,
                          int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
-    static const bool fusedScan = debug_int("nw_fused", 1) != 0;   // A/B switch, read once
-    const bool small = fusedScan && m > 0 && m <= MCCNN_NW_SCAN_M && e_capacity > 0 && n > 0;
+    const bool small = m > 0 && m <= MCCNN_NW_SCAN_M && e_capacity > 0 && n > 0;
     int rc = find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
                                        num_cells, radius, scale_inv, centre_order, start_idx, total_dev, total_host, ws, ws_bytes,
                                        stream, small);

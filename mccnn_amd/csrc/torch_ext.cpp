@@ -218,22 +218,15 @@ public:
     // 2: row plans / transposed lists of the step's geometries (those jobs wait for edge totals)
     static Issuer& get(int which = 0) {
         static Issuer inst[3];
-        inst[which].which_ = which;
         return inst[which];
     }
     static bool enabled() {
         static const bool on = mccnn::debug_int("issue_thread", 1) != 0;
         return on;
     }
-    // (debugging: MCCNN_ISSUE_INLINE = mask of the issuers whose jobs run on the calling thread instead)
-    static bool inline_jobs(int which) {
-        static const int mask = mccnn::debug_int("issue_inline", 0);
-        return (mask >> which) & 1;
-    }
-    int which_ = 0;
     void push(std::function<void()> job) {
         bool queued = false;
-        if (!inline_jobs(which_)) {
+        {
             std::lock_guard<std::mutex> lk(m_);
             if (!stop_) {   // (retired: the job runs on the caller's thread)
                 if (!started_) {
@@ -577,11 +570,10 @@ thread_local int64_t t_arena_want[2] = {0, 0};   // bytes the last batch of this
 // `bytes` of the batch's arena `k` (allocated on first use under the caller's stream guard), or an undefined tensor: the
 // caller then allocates a block of its own (first batch, a batch larger than the last one, batches switched off)
 Tensor arena_take(int k, int64_t bytes, const Tensor& like) {
-    static const bool on = mccnn::debug_int("geo_arena", 1) != 0;   // A/B switch
     GeoBatch& b = t_geo_batch;
     const int64_t need = (bytes + 255) / 256 * 256;
     b.taken[k] += need;
-    if (!on || !b.active || t_arena_want[k] <= 0) return Tensor();
+    if (!b.active || t_arena_want[k] <= 0) return Tensor();
     if (!b.arena[k].defined()) {
         b.arena[k] = at::empty({t_arena_want[k] + t_arena_want[k] / 16 + 4096}, like.options().dtype(at::kByte));
         b.arena_off[k] = 0;
@@ -592,8 +584,7 @@ Tensor arena_take(int k, int64_t bytes, const Tensor& like) {
     return t;
 }
 void begin_geometry_batch() {
-    static const bool on = mccnn::debug_int("geo_batch", 1) != 0;   // A/B switch: 0 = every geometry its own chain
-    t_geo_batch.active = on && Issuer::enabled();
+    t_geo_batch.active = Issuer::enabled();
     t_geo_batch.side = -1;
     t_geo_batch.entries.clear();
     t_geo_batch.pieces.clear();
@@ -876,18 +867,15 @@ void prebuild_async(std::shared_ptr<Geo> g, int what, bool avg) {
         total += (b + 255) / 256 * 256;
         if (w > wsb) wsb = w;
     }
-    // a batched geometry with a small plan (either direction; the other one follows on the same stream): its pieces join the
-    // batch too, on ONE side stream (the next one after the builds')
-    static const int batch_all = mccnn::debug_int("plan_batch_all", 1);   // A/B: 0 = only geometries with a small plan join the batch
-    const bool small_batch = t_geo_batch.active && t_geo_batch.side >= 0 && g->plan_side >= 0 &&
-                             (batch_all || mccnn_rowplan_inline_records(g->m, (int)g->e_cap) || mccnn_rowplan_inline_records(g->n, (int)g->e_cap));
-    if (small_batch) g->plan_side = (t_geo_batch.side + 1) % kSideStreams;
+    // a batched geometry: its pieces join the batch too, on ONE side stream (the next one after the builds')
+    const bool batched = t_geo_batch.active && t_geo_batch.side >= 0 && g->plan_side >= 0;
+    if (batched) g->plan_side = (t_geo_batch.side + 1) % kSideStreams;
     const bool other = g->plan_side >= 0 && g->plan_side != g->side;   // (a batch build: pieces on another side stream, behind the build's event)
     hipStream_t ss = side_stream(other ? g->plan_side : g->side);
     Tensor block;
     if (g->own_pool) {
         const c10::hip::HIPStreamGuardMasqueradingAsCUDA own(as_torch_stream((void*)ss, (int)g->buf.device().index()));
-        if (small_batch) block = arena_take(1, (int64_t)total, g->buf);
+        if (batched) block = arena_take(1, (int64_t)total, g->buf);
         if (!block.defined()) block = at::empty({(int64_t)total}, g->buf.options());
     } else {
         block = at::empty({(int64_t)total}, g->buf.options());
@@ -896,7 +884,7 @@ void prebuild_async(std::shared_ptr<Geo> g, int what, bool avg) {
     g->pieces_issued.store(0, std::memory_order_release);
     char* base = (char*)block.data_ptr();
     Tensor like = g->buf;
-    if (small_batch) {
+    if (batched) {
         PieceEntry pe;
         pe.g = g; pe.what = what; pe.avg = avg; pe.base = base;
         for (int k = 0; k < 4; ++k) { pe.off[k] = off[k]; pe.len[k] = len[k]; }

@@ -198,8 +198,9 @@ def test_debug_list_parser_of_the_library(tmp_path):
 
 def test_debug_keys_one_table_and_unknown_keys_are_reported(tmp_path):
     """ONE table of MCCNN_DEBUG keys: kDebugKeys (csrc/debug_opts.h) == KNOWN_KEYS (mccnn_amd/_env.py); every key that any
-    source file queries is in it; a key that is not is reported on stderr by both sides (a misspelt A/B switch used to be
-    ignored silently -- the void-A/B failure mode of round 5)."""
+    source file queries is in it and every key in it is queried by some source file (no dead entries); a key that is not
+    in it is reported on stderr by both sides (a misspelt A/B switch used to be ignored silently -- the void-A/B failure
+    mode of round 5)."""
     import glob
     import re
     import shutil
@@ -217,6 +218,7 @@ def test_debug_keys_one_table_and_unknown_keys_are_reported(tmp_path):
             used |= set(re.findall(r'debug_(?:int|float|opt)\("([a-z0-9_]+)"', txt))
             used |= set(re.findall(r'_env\.debug\(\s*"([a-z0-9_]+)"', txt))
     assert used <= set(ckeys), sorted(used - set(ckeys))
+    assert set(ckeys) <= used, sorted(set(ckeys) - used)
     # the Python side reports an unknown key ...
     r = subprocess.run([sys.executable, "-c", "from mccnn_amd import _env; print(_env.debug('small_off', 0))"], cwd=ROOT,
                        env=dict(os.environ, MCCNN_DEBUG="small_off,plan_smal=8192"), capture_output=True, text=True)
