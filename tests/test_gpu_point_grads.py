@@ -5,28 +5,16 @@ import numpy as np
 import pytest
 
 from tests import pointgrad_ref as ref
+from tests.pointgrad_cases import RTOL, check_close  # noqa: F401  (the project's bar, shared with the edge tests)
 from tests.helpers import make_cloud, make_mlp, run_chain
 from mccnn_amd.workloads import conv_nb
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-4
-
 
 def _wrap(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def check_close(got, want, what):
-    """The project's bar: norm-wise relative error <= 1e-4, and every element within 1e-4 x the tensor's largest magnitude."""
-    got, want = np.asarray(got, np.float64).reshape(-1), np.asarray(want, np.float64).reshape(-1)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.isfinite(got).all(), what
-    scale = max(float(np.abs(want).max()), 1e-30)
-    nrm = float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
-    elem = float(np.abs(got - want).max() / scale)
-    assert nrm <= RTOL and elem <= RTOL, "%s: norm-wise %.3e, element-wise %.3e" % (what, nrm, elem)
 
 
 def _geometry(mc, n_per, B, radius, scaleInv, seed=1, mode=None):
