@@ -5,10 +5,16 @@
 // __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it. The
 // product path (mccnn_amd/) never links, imports or calls anything in oracle/.
 //
-// PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures, is
-// GPU-only (every op registered DEVICE_GPU) and needs TensorFlow 1.x + nvcc, so
-// it can neither be imported nor compiled in this image. This oracle is pinned
-// instead by (a) the structural known answers that do exist in the reference
+// PINNED AGAINST THE REFERENCE'S OWN KERNELS: the reference ships no tests, golden
+// vectors or fixtures and every op is registered DEVICE_GPU, but only its .cc op
+// wrappers need TensorFlow. Its tf_ops/*.cu files are compiled with hipcc for
+// gfx950 (not nvcc) by oracle/ref_build.py and run beside this oracle, op by op on
+// identical inputs (tests/test_gpu_reference.py): integer outputs, the box and the
+// KDE bit for bit, `indexs` and the Poisson output up to the reference's atomic
+// arrival order, the convolution and its seven gradients within 1.8e-5 (bar 1e-4).
+// Recorded reference outputs (tests/golden/ref_*.npz) hold this file to the
+// reference on any machine (tests/test_oracle_pinned_cpu.py). It is pinned
+// besides by (a) the structural known answers that do exist in the reference
 // (the two 27-entry offset tables, the Gaussian constant, the numCells formula),
 // (b) an independent NumPy float64 brute-force cross-check (tests/test_oracle_cpu.py),
 // (c) finite-difference gradient checks and (d) invariants -- see tests/.

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py; never by the product package (mccnn_amd/).
-PARITY UNPINNED: see the header of mccnn_oracle.cpp.
+PINNED against the reference's own kernels (oracle/ref_build.py, oracle/ref.py): see the header of mccnn_oracle.cpp.
 
 Function names and argument orders mirror the reference's Python op surface
 (tf_ops/MCConvModuleSrc:20-81) so the parity tests read like calls into the

@@ -11,9 +11,10 @@ Fixtures are DATA (inputs and expected outputs), never reference source:
   builder_trace.json     the op-call trace and variable shapes the REFERENCE's MCConvBuilder / MCClassS graph
                          builder emits (utils/MCConvBuilder.py, models/MCClassS.py executed with recording stubs
                          for tensorflow / MCConvModule / MCNetworkUtils) -- pins the builder counterpart;
-  chain_*.npz            outputs of the CPU oracle (oracle/mccnn_oracle.cpp) on fixed inputs. The reference's ops
-                         are GPU-only TF1 custom ops and cannot run here, so these are ORACLE outputs
-                         (regression pins), not reference outputs: parity stays "unpinned" (see oracle header).
+  chain_*.npz            outputs of the CPU oracle (oracle/mccnn_oracle.cpp) on fixed inputs: ORACLE outputs
+                         (regression pins), not reference outputs. The outputs of the reference's own kernels are
+                         the ref_*.npz next to them, written on a GPU box by `tests/ref_runner.py --golden` (not by
+                         this script); they pin the oracle itself (tests/test_oracle_pinned_cpu.py).
 """
 import json
 import math
