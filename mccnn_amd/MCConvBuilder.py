@@ -108,6 +108,11 @@ _GEO_PREFETCH_MIN = _env.debug("geo_prefetch_min", 5)
 _PLAN_PREFETCH_MAX_E = _env.debug("plan_prefetch_max_e", 10 ** 12)
 
 
+def _same_tensor(a, b):
+    """The same memory seen as the same rows (autograd may hand over another tensor OBJECT over the same storage)."""
+    return a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape)
+
+
 class _PrefetchedHierarchy:
     """Handle of PointHierarchy.prefetch(): the future of the extension and what it was requested for."""
 
@@ -123,9 +128,7 @@ class _PrefetchedHierarchy:
         return self.future.done()
 
     def check(self, points, batchIds, radiusList, batchSize, relativeRadius):
-        same = (points is self.points or (points.data_ptr() == self.points.data_ptr() and points.shape == self.points.shape)) \
-            and (batchIds is self.batchIds or (batchIds.data_ptr() == self.batchIds.data_ptr()
-                                              and batchIds.shape == self.batchIds.shape)) \
+        same = _same_tensor(points, self.points) and _same_tensor(batchIds, self.batchIds) \
             and (self.points._version, self.batchIds._version) == self.version \
             and [float(r) for r in radiusList] == self.radiusList and int(batchSize) == self.batchSize \
             and bool(relativeRadius) == self.relativeRadius
@@ -296,8 +299,7 @@ class PointHierarchy(_PlainState, torch.nn.Module):
         # the levels' feature rows came with the hierarchy when prefetch() was handed this very tensor (no gradient, unmodified)
         pf = prefetched.features
         gathered = (pf is not None and inFeatures is not None and not getattr(inFeatures, "requires_grad", True)
-                    and (inFeatures is pf or (inFeatures.data_ptr() == pf.data_ptr() and inFeatures.shape == pf.shape
-                                              and inFeatures.dtype == pf.dtype))
+                    and _same_tensor(inFeatures, pf) and inFeatures.dtype == pf.dtype
                     and pf._version == prefetched.featuresVersion)
         for lvl, currRadius in zip(levels, prefetched.radiusList):
             sampledPts, sampledBatchsIds, _sortedIdx, transformedIndexs = lvl[:4]
@@ -375,6 +377,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.prefetchTransposed_ = {}
         self.prefetchDummy_ = None
 
+    @property
+    def hipSurface_(self):
+        """True when the ops are this package's HIP op surface (not a checker handed in through `ops=`)."""
+        return getattr(self.ops_, "_ops", 0) is None
+
     # ------------------------------------------------------------------ variable store
     @property
     def variables_(self):
@@ -413,6 +420,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             lst.append(p)
 
     # ------------------------------------------------------------------ caches
+    def __geometry_defaults__(self, inPH, inLevel, outPH, outLevel, KDEWindow, relativeRadius, usePDF):
+        """-> (KDEWindow, relativeRadius, usePDF, outPH, outLevel) with the builder's defaults filled in
+        (MCConvBuilder.py:299-325)."""
+        return (self.KDEWindow_ if KDEWindow is None else KDEWindow,
+                self.relativeRadius_ if relativeRadius is None else relativeRadius,
+                self.usePDF_ if usePDF is None else usePDF,
+                inPH if outPH is None else outPH, inLevel if outLevel is None else outLevel)
+
     def __compute_dic_keys__(self, inPointHierarchy, outPointHierarchy, inPointLevel, outPointLevel, convRadius,
                              KDEWindow, relativeRadius, usePDF):
         # MCConvBuilder.py:203-238 (the strings depend on names and numbers only: memoised -- six str() of floats per call)
@@ -490,7 +505,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         state["resetEvent_"] = _record_event() if (_SIDE_EVENTS[0] and _cuda_ok()) else None
         if pf is not None:
             for kN, (kG, kP, centres, mn, mx, B, radius, rel) in self.prefetchTransposed_.items():
-                if kN in neighs and kG in grids and getattr(self.ops_, "_ops", 0) is None:
+                if kN in neighs and kG in grids and self.hipSurface_:
                     _hip_ops = _hip_ops_mod()
                     self.sideStream_.wait_event(self.resetEvent_)
                     g = grids[kG]
@@ -522,11 +537,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         transposition for their backward pass on the side stream, where it runs under the forward convolutions.
         transposed="list" (layers with 2..4 input features and multiFeatureConv=True will): the transposed list alone --
         their feature gradient is then gathered through it instead of scattered with float atomics (bit-reproducible)."""
-        currKDEWindow = self.KDEWindow_ if KDEWindow is None else KDEWindow
-        currRelativeRadius = self.relativeRadius_ if relativeRadius is None else relativeRadius
-        currUsePDF = self.usePDF_ if usePDF is None else usePDF
-        outPH = inPointHierarchy if outPointHierarchy is None else outPointHierarchy
-        outLevel = inPointLevel if outPointLevel is None else outPointLevel
+        currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
+            inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
                                                                currKDEWindow, currRelativeRadius, currUsePDF)
         pts, bids = inPointHierarchy.points_[inPointLevel], inPointHierarchy.batchIds_[inPointLevel]
@@ -561,7 +573,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             else:
                 side.wait_stream(torch.cuda.current_stream())
         bg = None
-        if getattr(self.ops_, "_ops", 0) is None:  # the HIP surface: this thread's launches are background work for a while
+        if self.hipSurface_:  # the HIP surface: this thread's launches are background work for a while
             from . import _lib as _mclib
             bg = _mclib.load()
             bg_prev = bg.mccnn_background_launches(1)
@@ -575,7 +587,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     def __prefetch_on_side__(self, side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
                              currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed):
         with torch.cuda.stream(side):
-            if keyGrid not in grids and self.fuseSort_ and getattr(self.ops_, "_ops", 0) is None and not pts.requires_grad:
+            if keyGrid not in grids and self.fuseSort_ and self.hipSurface_ and not pts.requires_grad:
                 _hip_ops = _hip_ops_mod()
                 grids[keyGrid] = _hip_ops.build_grid(pts, bids, mn, mx, B, convRadius, currRelativeRadius)
             if keyGrid not in grids:
@@ -588,7 +600,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 grids[keyGrid] = (sortPts, sortBatchs, cellIndexs, indexs)
             g = grids[keyGrid]
             deferred = None
-            if getattr(self.ops_, "_ops", 0) is None:  # the HIP op surface (not a checker handed in through `ops=`)
+            if self.hipSurface_:  # the HIP op surface (not a checker handed in through `ops=`)
                 _hip_ops = _hip_ops_mod()
                 deferred = _hip_ops.find_neighbors_pdf_deferred
             if keyNeighs not in neighs and keyPDF not in pdfs and currUsePDF and deferred is not None:
@@ -643,6 +655,56 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         biases3v = self._get_variable(convName + '_biases3', (numBlocks, blockSize), dev, zeros)
         return weights, biases, weights2v, biases2v, weights3v, biases3v, nn
 
+    def __native_inputs__(self, inPH, inLevel, outPH, outLevel):
+        """-> (inPts, inBids, centres, cBids) of a geometry over these levels, or None when the native path cannot take
+        them: an empty level, points with a gradient, the reference-arithmetic KDE, or tensors the library does not read in
+        place."""
+        inPts, inBids = inPH.points_[inLevel], inPH.batchIds_[inLevel]
+        centres, cBids = outPH.points_[outLevel], outPH.batchIds_[outLevel]
+        if inPts.shape[0] == 0 or centres.shape[0] == 0 or inPts.requires_grad or int(_hip_ops_mod().PDF_MODE) != 1:
+            return None
+        for t, dt in ((inPts, torch.float32), (centres, torch.float32), (inBids, torch.int32), (cBids, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+                return None
+        return inPts, inBids, centres, cBids
+
+    def __file_geometry__(self, geo, keyGrid, keyNeighs, keyPDF, usePDF, trace):
+        """Files a native geometry under the reference's cache keys: the geometry itself, lazy views of its grid (when it
+        owns one), neighbour list and PDFs. trace: record the ops the op-by-op path would have run for them."""
+        self.cacheGeo_[keyPDF] = geo
+        if geo.grid_owner is None:
+            self.cacheGeoGrid_[keyGrid] = geo
+            self.cacheGrids_[keyGrid] = _LazyEntry(geo, geo.grid)
+            if trace:
+                self._trace("sort_points_step1", keyGrid)
+                self._trace("sort_points_step2", keyGrid)
+        self.cacheNeighs_[keyNeighs] = _LazyEntry(geo, geo.neighbors)
+        self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
+        if trace:
+            self._trace("find_neighbors", keyNeighs)
+            if usePDF:
+                self._trace("compute_pdf", keyPDF)
+
+    def __unfile_geometry__(self, geo, keyGrid, keyNeighs=None, keyPDF=None):
+        """Takes `geo` out of the caches again: its grid (when it is the one filed under keyGrid) and, with the other two
+        keys, the geometry, its neighbour list and PDFs."""
+        if keyPDF is not None:
+            self.cacheGeo_.pop(keyPDF, None)
+            self.cachePDFs_.pop(keyPDF, None)
+            self.cacheNeighs_.pop(keyNeighs, None)
+        if self.cacheGeoGrid_.get(keyGrid) is geo:
+            self.cacheGeoGrid_.pop(keyGrid, None)
+            self.cacheGrids_.pop(keyGrid, None)
+
+    def __plan_entries__(self, ph):
+        """The geometries the last step used over a hierarchy of `ph`'s name whose levels `ph` has: (entry, keyGrid,
+        keyNeighs, keyPDF) each, the keys computed for `ph`."""
+        name, levels = ph.hierarchyName_, len(ph.points_)
+        for ent in self.geoPlan_:
+            if ent[0] != name or ent[1] >= levels or ent[2] >= levels:
+                continue
+            yield (ent,) + self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6])
+
     def __prefetch_native__(self, inPH, inLevel, convRadius, outPH, outLevel, KDEWindow, relativeRadius, usePDF, keyGrid,
                             keyNeighs, keyPDF, transposed, fork=True, pieces=0):
         """prefetch_geometry() on the native step executor: the geometry is ONE buffer, allocated on the CALLER's stream and
@@ -653,32 +715,26 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         it is still correct, the build then simply waits for them. Returns False when this call has to take the op-by-op
         prefetch (no torch extension, points with a gradient, ...)."""
         _native = _native_mod()
-        _hip_ops = _hip_ops_mod()
-        if not (self.native_ and self.fuseSort_ and getattr(self.ops_, "_ops", 0) is None and _native.side_streams_available()
-                and int(_hip_ops.PDF_MODE) == 1 and self.prefetched_ is None
-                and _env.debug("native_prefetch", True)):
+        if not (self.native_ and self.fuseSort_ and self.hipSurface_ and _native.side_streams_available()
+                and self.prefetched_ is None and _env.debug("native_prefetch", True)):
             return False
-        inPts, inBids = inPH.points_[inLevel], inPH.batchIds_[inLevel]
-        centres, cBids = outPH.points_[outLevel], outPH.batchIds_[outLevel]
-        if inPts.requires_grad or inPts.shape[0] == 0 or centres.shape[0] == 0:
+        inputs = self.__native_inputs__(inPH, inLevel, outPH, outLevel)
+        if inputs is None:
             return False
-        for t, dt in ((inPts, torch.float32), (centres, torch.float32), (inBids, torch.int32), (cBids, torch.int32)):
-            if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                return False
+        inPts, inBids, centres, cBids = inputs
         want = 0 if not transposed else (1 if transposed == "list" else 2)   # nothing | transposed list | + transposed row plan
         if keyPDF in self.prefetchedGeo_:
             ent = self.prefetchedGeo_[keyPDF]
             self.prefetchedGeo_[keyPDF] = ent[:4] + (max(ent[4], want),)
             return True
         mn, mx, B = inPH.aabbMin_, inPH.aabbMax_, inPH.batchSize_
-        nc = _hip_ops._num_cells(mn, mx, B, convRadius, relativeRadius)
+        nc = _hip_ops_mod()._num_cells(mn, mx, B, convRadius, relativeRadius)
         owners = self.__dict__.setdefault("prefetchedGridOwner_", {})   # keyGrid -> the parked geometry that owns that grid
         owner = owners.get(keyGrid)
         k = len(self.prefetchedGeo_)
         geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                      usePDF, owner, side=k, fork=fork, background=True,
                                      after=(inPH.prefetchFuture_ if inPH is outPH else None))
-        geo.uses = 0
         if owner is None:
             owners[keyGrid] = geo
         if pieces:   # row plans / transposed list the layers of the last step used: attached and issued by a helper thread
@@ -696,29 +752,20 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geometries started (0 on the first steps, while there is nothing to replay, and wherever the native path does
         not apply: nothing is lost, the next step builds what it needs itself)."""
         started = 0
-        name, levels = pointHierarchy.hierarchyName_, len(pointHierarchy.points_)
         pieces = _env.debug("plan_prefetch", True)
         _native = _native_mod()
         _native.begin_batch()   # the step's geometries go out together: one launch per kernel kind over all of them
         try:
-            started = self.__prefetch_step_entries__(pointHierarchy, name, levels, pieces)
+            for ent, keyGrid, keyNeighs, keyPDF in self.__plan_entries__(pointHierarchy):
+                _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
+                if keyPDF in self.prefetchedGeo_:
+                    continue
+                if self.__prefetch_native__(pointHierarchy, inLevel, radius, pointHierarchy, outLevel, window, rel, usePDF,
+                                            keyGrid, keyNeighs, keyPDF, False, fork=(started == 0),
+                                            pieces=(have if pieces else 0)):
+                    started += 1
         finally:
             _native.end_batch()
-        return started
-
-    def __prefetch_step_entries__(self, pointHierarchy, name, levels, pieces):
-        started = 0
-        for ent in self.geoPlan_:
-            hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
-            if hname != name or inLevel >= levels or outLevel >= levels:
-                continue
-            keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(pointHierarchy, pointHierarchy, inLevel, outLevel, radius,
-                                                                   window, rel, usePDF)
-            if keyPDF in self.prefetchedGeo_:
-                continue
-            if self.__prefetch_native__(pointHierarchy, inLevel, radius, pointHierarchy, outLevel, window, rel, usePDF, keyGrid,
-                                        keyNeighs, keyPDF, False, fork=(started == 0), pieces=(have if pieces else 0)):
-                started += 1
         return started
 
     def __install_prefetched_geometries__(self):
@@ -730,12 +777,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.__dict__["prefetchedGridOwner_"] = {}
         for keyPDF, (geo, keyGrid, keyNeighs, usePDF, transposed) in parked.items():
             geo.unverified = True   # (checked against the hierarchy's tensors at its first use)
-            self.cacheGeo_[keyPDF] = geo
-            if geo.grid_owner is None:
-                self.cacheGeoGrid_[keyGrid] = geo
-                self.cacheGrids_[keyGrid] = _LazyEntry(geo, geo.grid)
-            self.cacheNeighs_[keyNeighs] = _LazyEntry(geo, geo.neighbors)
-            self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, False)
             if transposed:
                 # (depth-wise layers: both row plans -- the forward pass then waits for the first stage only)
                 geo.prebuild((_native.NEED_PLAN_FWD | _native.NEED_PLAN_TR) if transposed == 2 else _native.NEED_TLIST,
@@ -747,48 +789,25 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         asked for; a geometry nobody asks for is dropped at the next reset()."""
         _native = _native_mod()
         _hip_ops = _hip_ops_mod()
-        plan, name = self.geoPlan_, ph.hierarchyName_
-        levels = len(ph.points_)
         mn, mx, B = ph.aabbMin_, ph.aabbMax_, ph.batchSize_
-        if int(_hip_ops.PDF_MODE) != 1:
-            return
         k = 0
         pieces = _env.debug("plan_prefetch", True)
-        for (hname, inLevel, outLevel, radius, window, rel, usePDF, have, _key) in plan:
-            if hname != name or inLevel >= levels or outLevel >= levels:
-                continue
-            keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(ph, ph, inLevel, outLevel, radius, window, rel, usePDF)
+        for ent, keyGrid, keyNeighs, keyPDF in self.__plan_entries__(ph):
+            _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
             if keyPDF in self.cacheGeo_:
                 continue
-            inPts, inBids = ph.points_[inLevel], ph.batchIds_[inLevel]
-            centres, cBids = ph.points_[outLevel], ph.batchIds_[outLevel]
-            if inPts.shape[0] == 0 or centres.shape[0] == 0 or inPts.requires_grad:
+            inputs = self.__native_inputs__(ph, inLevel, ph, outLevel)
+            if inputs is None:
                 continue
-            ok = True
-            for t, dt in ((inPts, torch.float32), (centres, torch.float32), (inBids, torch.int32), (cBids, torch.int32)):
-                if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                    ok = False
-            if not ok:
-                continue
+            inPts, inBids, centres, cBids = inputs
             nc = _hip_ops._num_cells(mn, mx, B, radius, rel)
             owner = self.cacheGeoGrid_.get(keyGrid)
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, radius, rel, window, usePDF, owner,
                                          side=k, fork=(k == 0), after=ph.prefetchFuture_)
             k += 1
-            geo.uses = 0
             if have and pieces and geo.e_cap <= _PLAN_PREFETCH_MAX_E:
                 geo.prebuild_async(have, self.useAVG_)
-            self.cacheGeo_[keyPDF] = geo
-            if owner is None:
-                self.cacheGeoGrid_[keyGrid] = geo
-                self.cacheGrids_[keyGrid] = _LazyEntry(geo, geo.grid)
-                self._trace("sort_points_step1", keyGrid)
-                self._trace("sort_points_step2", keyGrid)
-            self.cacheNeighs_[keyNeighs] = _LazyEntry(geo, geo.neighbors)
-            self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
-            self._trace("find_neighbors", keyNeighs)
-            if usePDF:
-                self._trace("compute_pdf", keyPDF)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True)
 
     def __native_convolution__(self, convName, inPH, inLevel, inFeatures, inNumFeatures, convRadius, outPH, outLevel,
                                multiFeatureConv, numOutFeatures, KDEWindow, relativeRadius, usePDF, useAVG, keyGrid,
@@ -812,19 +831,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             a = geo.args
             cen = outPH.points_[outLevel]
             pin = inPH.points_[inLevel]
-            if (a[0] is pin or (a[0].data_ptr() == pin.data_ptr() and a[0].shape == pin.shape)) and \
-                    (a[2] is cen or (a[2].data_ptr() == cen.data_ptr() and a[2].shape == cen.shape)):
+            if _same_tensor(a[0], pin) and _same_tensor(a[2], cen):
                 geo.unverified = False
             else:
                 if _GEO_TRACE:
                     print("native conv %s: parked geometry %s not for this hierarchy (built from %s / %s, asked %s / %s)" % (
                         convName, keyPDF, tuple(a[0].shape), tuple(a[2].shape), tuple(pin.shape), tuple(cen.shape)), file=sys.stderr)
-                self.cacheGeo_.pop(keyPDF, None)
-                self.cachePDFs_.pop(keyPDF, None)
-                self.cacheNeighs_.pop(keyNeighs, None)
-                if self.cacheGeoGrid_.get(keyGrid) is geo:
-                    self.cacheGeoGrid_.pop(keyGrid, None)
-                    self.cacheGrids_.pop(keyGrid, None)
+                self.__unfile_geometry__(geo, keyGrid, keyNeighs, keyPDF)
                 geo = None
         if geo is None:
             if keyGrid in self.cacheGrids_ and keyGrid not in self.cacheGeoGrid_:
@@ -837,39 +850,23 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                         convName, keyNeighs, keyPDF, keyNeighs in self.cacheNeighs_, keyPDF in self.cachePDFs_,
                         sorted(self.cacheGeo_)), file=sys.stderr)
                 return None
-            inPts, inBids = inPH.points_[inLevel], inPH.batchIds_[inLevel]
-            centres, cBids = outPH.points_[outLevel], outPH.batchIds_[outLevel]
-            if inPts.shape[0] == 0 or centres.shape[0] == 0 or int(_hip_ops.PDF_MODE) != 1:
+            inputs = self.__native_inputs__(inPH, inLevel, outPH, outLevel)
+            if inputs is None:
                 return None
-            for t, dt in ((inPts, torch.float32), (centres, torch.float32), (inBids, torch.int32), (cBids, torch.int32)):
-                if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
-                    return None
+            inPts, inBids, centres, cBids = inputs
             mn, mx, B = inPH.aabbMin_, inPH.aabbMax_, inPH.batchSize_
             nc = _hip_ops._num_cells(mn, mx, B, convRadius, relativeRadius)
             owner = self.cacheGeoGrid_.get(keyGrid)
             if owner is not None and getattr(owner, "unverified", False):
                 # (a grid started ahead for another hierarchy of this name is not shared either)
-                a0 = owner.args[0]
-                if not (a0 is inPts or (a0.data_ptr() == inPts.data_ptr() and a0.shape == inPts.shape)):
-                    self.cacheGeoGrid_.pop(keyGrid, None)
-                    self.cacheGrids_.pop(keyGrid, None)
+                if not _same_tensor(owner.args[0], inPts):
+                    self.__unfile_geometry__(owner, keyGrid)
                     owner = None
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                          usePDF, owner)
-            geo.uses = 0
-            self.cacheGeo_[keyPDF] = geo
-            if owner is None:
-                self.cacheGeoGrid_[keyGrid] = geo
-                self.cacheGrids_[keyGrid] = _LazyEntry(geo, geo.grid)
-                self._trace("sort_points_step1", keyGrid)
-                self._trace("sort_points_step2", keyGrid)
-            else:
+            if owner is not None:   # (a shared grid: the layer sorts its rows only, as on a cache hit)
                 self._trace("sort_features", keyGrid)
-            self.cacheNeighs_[keyNeighs] = _LazyEntry(geo, geo.neighbors)
-            self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
-            self._trace("find_neighbors", keyNeighs)
-            if usePDF:
-                self._trace("compute_pdf", keyPDF)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True)
         else:
             self._trace("sort_features", keyGrid)
         if inPH is outPH and keyPDF not in self.geoSeen_:
@@ -911,12 +908,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # defaults: MCConvBuilder.py:299-325
         currMultiFeatureConv = self.multiFeatureConvs_ if multiFeatureConv is None else multiFeatureConv
         currNumOutFeatures = inNumFeatures if outNumFeatures is None else outNumFeatures
-        currKDEWindow = self.KDEWindow_ if KDEWindow is None else KDEWindow
-        currRelativeRadius = self.relativeRadius_ if relativeRadius is None else relativeRadius
-        currUsePDF = self.usePDF_ if usePDF is None else usePDF
         currUseAVG = self.useAVG_ if useAVG is None else useAVG
-        currOutPointHierarchy = inPointHierarchy if outPointHierarchy is None else outPointHierarchy
-        currOutPointLevel = inPointLevel if outPointLevel is None else outPointLevel
+        currKDEWindow, currRelativeRadius, currUsePDF, currOutPointHierarchy, currOutPointLevel = self.__geometry_defaults__(
+            inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
 
         if currOutPointHierarchy.batchSize_ != inPointHierarchy.batchSize_:
             raise RuntimeError('Different batch size in the input and output point hierarchy')
@@ -931,9 +925,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                                                                        currMultiFeatureConv, currRelativeRadius,
                                                                        currUsePDF))
 
+        # HIP op surface, points that carry no gradient: the grid is built from the points alone and the feature rows are
+        # sorted inside the convolution (by the native executor's layer call, or by spatial_conv(sortIndex=) below)
         inPts = inPointHierarchy.points_[inPointLevel]
-        if (self.native_ and self.fuseSort_ and getattr(self.ops_, "_ops", 0) is None and inPts.is_cuda
-                and not inPts.requires_grad):
+        fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
+        if self.native_ and fused:
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
@@ -942,12 +938,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 return out
 
         # grid (MCConvBuilder.py:349-363)
-        # HIP op surface, points that carry no gradient: the grid is built from the points alone (one library call) and
-        # the feature rows are sorted inside the convolution's own autograd node -- per convolution one op call and one
-        # graph node less than sort_points_step2 / sort_features + spatial_conv (same kernels, same results)
+        # fused: one library call for the grid and the feature rows sorted inside the convolution's own autograd node --
+        # per convolution one op call and one graph node less than sort_points_step2 / sort_features + spatial_conv (same
+        # kernels, same results)
         sortIndex = None
-        inPts = inPointHierarchy.points_[inPointLevel]
-        fused = (self.fuseSort_ and getattr(self.ops_, "_ops", 0) is None and inPts.is_cuda and not inPts.requires_grad)
         if fused:
             if keyGrid in self.cacheGrids_:
                 currGridTuple = self.cacheGrids_[keyGrid]

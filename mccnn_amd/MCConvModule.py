@@ -95,6 +95,21 @@ def _check_aabb(mn, mx, batchSize, op):
              "%s expects bounding box points with shape (batchSize, 3)" % op)
 
 
+def _points_input(op, pts, bids, name="points", idsName="batch_ids"):
+    """Points [N,3] float32 and their batch ids [N,1] int32, typed and shape-checked."""
+    pts, bids = _f32(pts, name), _i32(bids, idsName)
+    _check_points(pts, name, op)
+    _check_batch_ids(bids, pts.shape[0], op)
+    return pts, bids
+
+
+def _box_input(op, aabbMin, aabbMax, batchSize):
+    """The boxes [batchSize,3] float32, typed and shape-checked (the last check of every wrapper)."""
+    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
+    _check_aabb(mn, mx, batchSize, op)
+    return mn, mx
+
+
 def get_block_size():
     """genCompileScript.py:46-47"""
     return int(_lib.load().mccnn_block_size())
@@ -130,24 +145,29 @@ def _remember_order(points, kind, payload):
     _ORDER_HINTS[key] = [kind, payload, None]
 
 
-def _order_hint(points):
+def _order_hint(points, length=None):
+    """The visiting order remembered for `points`, or None; with `length`, only an order of that many entries."""
     ent = _ORDER_HINTS.get(_tensor_key(points))
     if ent is None:
         return None
     if ent[0] == "order_weak":
-        return ent[1]()  # None once the grid that owns the permutation is gone
-    if ent[2] is None:
-        kind, payload = ent[0], ent[1]
-        if kind == "order":
-            ent[2] = payload
-        elif kind == "new_idx":
-            inv = torch.empty_like(payload)
-            check(_lib.load().mccnn_invert_permutation(ptr(payload), payload.shape[0], ptr(inv), stream_handle()),
-                  "invert_permutation")
-            ent[2] = inv
-        else:
-            return None
-    return ent[2]
+        order = ent[1]()  # None once the grid that owns the permutation is gone
+    else:
+        if ent[2] is None:
+            kind, payload = ent[0], ent[1]
+            if kind == "order":
+                ent[2] = payload
+            elif kind == "new_idx":
+                inv = torch.empty_like(payload)
+                check(_lib.load().mccnn_invert_permutation(ptr(payload), payload.shape[0], ptr(inv), stream_handle()),
+                      "invert_permutation")
+                ent[2] = inv
+            else:
+                return None
+        order = ent[2]
+    if order is not None and length is not None and order.shape[0] != length:
+        return None
+    return order
 
 
 _EDGE_GUESS = {}  # (device, M, N, radius, B, scaleInv) -> capacity to try first in find_neighbors
@@ -156,21 +176,24 @@ _EDGE_GUESS = {}  # (device, M, N, radius, B, scaleInv) -> capacity to try first
 _EDGE_RATIO = {}
 
 
-def _edge_guess(gkey):
-    g = _EDGE_GUESS.get(gkey, 0)
+def _edge_guess(guesses, ratios, gkey, m, first=0):
+    """Capacity to try first for a search of `m` centres (the op path's tables above, or mccnn_amd.native's own pair).
+    first: what the first search of a radius gets -- 0 = no guess, the caller waits for the count."""
+    g = guesses.get(gkey, 0)
     if g <= 0:
-        ratio = _EDGE_RATIO.get((gkey[0], gkey[3], gkey[5]), 0.0)
-        if ratio > 0.0:
-            g = int(ratio * gkey[1] * 1.25) + 1024  # sizes differ: more head room than for a repeated shape
+        ratio = ratios.get((gkey[0], gkey[3], gkey[5]), 0.0)
+        g = int(ratio * m * 1.25) + 1024 if ratio > 0.0 else first  # sizes differ: more head room than for a repeated shape
     return g
 
 
-def _remember_edges(gkey, e):
-    if len(_EDGE_GUESS) > 256:
-        _EDGE_GUESS.clear()
-    _EDGE_GUESS[gkey] = e + e // 16 + 64  # a little head room: totals of a shape vary slightly from batch to batch
-    if gkey[1] > 0:
-        _EDGE_RATIO[(gkey[0], gkey[3], gkey[5])] = e / float(gkey[1])
+def _remember_edges(guesses, ratios, gkey, m, e):
+    if len(guesses) > 256:
+        guesses.clear()
+    guesses[gkey] = e + e // 16 + 64  # a little head room: totals of a shape vary slightly from batch to batch
+    if m > 0:
+        ratios[(gkey[0], gkey[3], gkey[5])] = e / float(m)
+
+
 _TLS = threading.local()
 
 
@@ -362,9 +385,7 @@ def _row_plan(packed_obj, transposed, pts, bids, pdfs, smp, st, pk, mn, mx, n, m
         row_start = start_t
     else:
         rows, row_start = m, st
-        order = _order_hint(centre_points) if centre_points is not None else None
-        if order is not None and order.shape[0] != m:
-            order = None
+        order = _order_hint(centre_points, m) if centre_points is not None else None
     offs, total, S, cap, srows, wsb, inline_rec = _plan_layout(lib, rows, e, transposed)
     plan = RowPlan()
     plan.key, plan.event, plan.row_start = key, None, row_start
@@ -533,9 +554,7 @@ def compute_aabb(inPts, inBatchIds, batchSize, scaleInv=True):
 def _compute_aabb(inPts, inBatchIds, batchSize, scaleInv):
     op = "ComputeAabbOp"
     _req(batchSize > 0, op + " expects a positive batch size")
-    pts, bids = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    _check_points(pts, "points", op)
-    _check_batch_ids(bids, pts.shape[0], op)
+    pts, bids = _points_input(op, inPts.detach(), inBatchIds)
     lib = _lib.load()
     if CHECK_BATCH_IDS and check_batch_ids(bids, batchSize):
         check(-2, op)  # MCCNN_E_BATCHID
@@ -578,11 +597,8 @@ def sort_points_step1(inPts, inBatchIds, aabbMin, aabbMax, batchSize, cellSize, 
     op = "SortPointsStep1Op"
     _req(batchSize > 0, op + " expects a positive batch size")
     _req(cellSize > 0, op + " expects a positive cell size")
-    pts, bids = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(pts, "points", op)
-    _check_batch_ids(bids, pts.shape[0], op)
-    _check_aabb(mn, mx, batchSize, op)
+    pts, bids = _points_input(op, inPts.detach(), inBatchIds)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     lib = _lib.load()
     n = pts.shape[0]
     nc = _num_cells(mn, mx, batchSize, cellSize, scaleInv)
@@ -603,12 +619,9 @@ def build_grid(inPts, inBatchIds, aabbMin, aabbMax, batchSize, cellSize, scaleIn
     unsorted row index. Not differentiable: points that require a gradient take the two ops."""
     op = "SortPointsStep1Op"
     _req(batchSize > 0, op + " expects a positive batch size")
-    pts, bids = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(pts, "points", op)
+    pts, bids = _points_input(op, inPts.detach(), inBatchIds)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     n = pts.shape[0]
-    _check_batch_ids(bids, n, op)
-    _check_aabb(mn, mx, batchSize, op)
     lib = _lib.load()
     dev = pts.device
     nc = _num_cells(mn, mx, batchSize, cellSize, scaleInv)
@@ -651,18 +664,15 @@ class _SortPointsStep2(torch.autograd.Function):
     def forward(ctx, inPts, inBatchIds, inFeatures, keys, indexs, aabbMin, aabbMax, batchSize, cellSize, scaleInv):
         op = "SortPointsStep2Op"
         _req(batchSize > 0, op + " expects a positive batch size")
-        pts, bids = _f32(inPts, "points"), _i32(inBatchIds, "batch_ids")
+        pts, bids = _points_input(op, inPts, inBatchIds)
         feats = _feat(inFeatures, "features")
         keys, indexs = _i32(keys, "keys"), _i32(indexs, "index_new_pos")
-        mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-        _check_points(pts, "points", op)
         n = pts.shape[0]
-        _check_batch_ids(bids, n, op)
         _req(feats.dim() == 2 and feats.shape[0] == n, op + " expects features with dimensions (numPoints, numFeatures)")
         _req(feats.shape[1] > 0, op + " expects features with at least one component")
         _req(keys.dim() == 1 and keys.shape[0] == n, op + " expects the same number of keys and points")
         _req(indexs.dim() == 1 and indexs.shape[0] == n, op + " expects the same number of indexs and points")
-        _check_aabb(mn, mx, batchSize, op)
+        mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
         lib = _lib.load()
         nc = _num_cells(mn, mx, batchSize, cellSize, scaleInv)
         oP = torch.empty_like(pts)
@@ -768,23 +778,19 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     op = "FindNeighborsOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
-    c, cb = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    p2, cells = _f32(inPts2.detach(), "points2"), _i32(cellIndexs, "cell_indexs")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(c, "points", op)
-    _check_batch_ids(cb, c.shape[0], op)
+    c, cb = _points_input(op, inPts.detach(), inBatchIds)
+    p2 = _f32(inPts2.detach(), "points2")
     _check_points(p2, "points2", op)
+    cells = _i32(cellIndexs, "cell_indexs")
     _req(cells.dim() == 5 and cells.shape[0] == batchSize, op + " expects a five dimension tensor for the cell indices")
-    _check_aabb(mn, mx, batchSize, op)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     lib = _lib.load()
     m, nc = c.shape[0], cells.shape[1]
     start = torch.empty((m, 1), dtype=torch.int32, device=c.device)
     box, boxv = _host_mailbox()
     n2 = p2.shape[0]
     ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
-    order = _order_hint(inPts)
-    if order is not None and order.shape[0] != m:
-        order = None
+    order = _order_hint(inPts, m)
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
             int(bool(scaleInv)), ptr(order))
     # The size of the second output is only known on the device: the prefix sum stores the total straight into a
@@ -796,7 +802,7 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     # total of this shape BEFORE the total is read: the host round trip hides behind the kernel. Too small a guess ->
     # exact rerun.
     gkey = (c.device.index, m, n2, float(radius), int(batchSize), bool(scaleInv))
-    guess = _edge_guess(gkey)
+    guess = _edge_guess(_EDGE_GUESS, _EDGE_RATIO, gkey, m)
     packed = None
     if guess > 0:
         buf = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
@@ -811,7 +817,7 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
         packed = torch.empty((e, 2), dtype=torch.int32, device=c.device)
         check(lib.mccnn_find_neighbors_fill(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle()),
               "find_neighbors(fill)")
-    _remember_edges(gkey, e)
+    _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
     return start, packed
 
 
@@ -845,14 +851,11 @@ def _compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, wi
     _req(radius > 0.0, op + " expects a positive radius")
     _req(window > 0.0, op + " expects a positive window")
     _req(batchSize > 0, op + " expects a positive batch size")
-    p, b = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
+    p, b = _points_input(op, inPts.detach(), inBatchIds)
     st, pk = _i32(startIndexs, "start_indexs"), _i32(neighbors, "neighbors")
-    _check_points(p, "points", op)
-    _check_batch_ids(b, p.shape[0], op)
     _req(st.dim() == 2 and st.shape[1] == 1, op + " expects start indexs with dimensions (numSamples, 1)")
     _req(pk.dim() == 2 and pk.shape[1] == 2, op + " expects a neighbor list with dimensions (numNeighbors, 2)")
-    _check_aabb(mn, mx, batchSize, op)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     lib = _lib.load()
     e = pk.shape[0]
     pdfs = torch.empty((e, 1), dtype=torch.float32, device=p.device)
@@ -942,7 +945,7 @@ class DeferredNeighborsPDF:
         else:
             packed = self._args_fn(e)
             pdfs = self._pdf_fn(packed)
-        _remember_edges(self._gkey, e)
+        _remember_edges(_EDGE_GUESS, _EDGE_RATIO, self._gkey, self._gkey[1], e)
         return self.start, packed, pdfs
 
 
@@ -961,28 +964,21 @@ def find_neighbors_pdf_deferred(inPts, inBatchIds, sortedPts, sortedBatchIds, ce
         return None
     op = "FindNeighborsOp"
     _req(radius > 0.0 and window > 0.0 and batchSize > 0, op + " expects positive radius, window and batch size")
-    c, cb = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    p2, b2 = _f32(sortedPts.detach(), "points2"), _i32(sortedBatchIds, "batch_ids2")
+    c, cb = _points_input(op, inPts.detach(), inBatchIds)
+    p2, b2 = _points_input(op, sortedPts.detach(), sortedBatchIds, "points2", "batch_ids2")
     cells = _i32(cellIndexs, "cell_indexs")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(c, "points", op)
-    _check_batch_ids(cb, c.shape[0], op)
-    _check_points(p2, "points2", op)
-    _check_batch_ids(b2, p2.shape[0], op)
     _req(cells.dim() == 5 and cells.shape[0] == batchSize, op + " expects a five dimension tensor for the cell indices")
-    _check_aabb(mn, mx, batchSize, op)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     m, n2, nc = c.shape[0], p2.shape[0], cells.shape[1]
     gkey = (c.device.index, m, n2, float(radius), int(batchSize), bool(scaleInv))
-    guess = _edge_guess(gkey)
+    guess = _edge_guess(_EDGE_GUESS, _EDGE_RATIO, gkey, m)
     if guess <= 0 or m == 0:
         return None
     lib = _lib.load()
     start = torch.empty((m, 1), dtype=torch.int32, device=c.device)
     total_dev = torch.empty(1, dtype=torch.int32, device=c.device)
     ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
-    order = _order_hint(inPts)
-    if order is not None and order.shape[0] != m:
-        order = None
+    order = _order_hint(inPts, m)
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
             int(bool(scaleInv)), ptr(order))
     pool = _slot_pool()
@@ -1023,13 +1019,10 @@ def poisson_sampling(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, radius, ba
     op = "PoissonSamplingOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
-    p, b = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
+    p, b = _points_input(op, inPts.detach(), inBatchIds)
     cells = _i32(cellIndexs, "cell_indexs")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(p, "points", op)
-    _check_batch_ids(b, p.shape[0], op)
     _req(cells.dim() == 5 and cells.shape[0] == batchSize, op + " expects a five dimension tensor for the cell indices")
-    _check_aabb(mn, mx, batchSize, op)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     lib = _lib.load()
     n, nc = p.shape[0], cells.shape[1]
     wsb = lib.mccnn_poisson_sampling_workspace_bytes(n, batchSize, nc)
@@ -1108,11 +1101,8 @@ def point_hierarchy_levels(inPts, inBatchIds, aabbMin, aabbMax, radiusList, batc
     transformedIndexs [S] into the level's input order)] per level -- bit-identical to the op-by-op chain -- or None
     if a wait of the single-launch Poisson kernel timed out somewhere (the caller then runs the op-by-op chain)."""
     op = "PointHierarchy"
-    pts, bids = _f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids")
-    mn, mx = _f32(aabbMin, "aabb_min"), _f32(aabbMax, "aabb_max")
-    _check_points(pts, "points", op)
-    _check_batch_ids(bids, pts.shape[0], op)
-    _check_aabb(mn, mx, batchSize, op)
+    pts, bids = _points_input(op, inPts.detach(), inBatchIds)
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
     lib = _lib.load()
     dev, cap, L = pts.device, pts.shape[0], len(radiusList)
     if L == 0:
@@ -1302,6 +1292,7 @@ class _SpatialConv(torch.autograd.Function):
                                         numOutFeatures, combin, batchSize, radius)
         lib = _lib.load()
         outF = numOutFeatures if combin else fin
+        state = None   # (stays None on the row and bf16 paths)
         if _rows_shape(combin, fin, feats, m, e):
             # depth-wise layer on the row-per-lane kernels: forward plan of the neighbour list (built once per list)
             plan = _row_plan(packedNeighs if pk is packedNeighs else pk, False, pts, bids, pdfs, smp, st, pk, mn, mx, n, m,
@@ -1315,38 +1306,29 @@ class _SpatialConv(torch.autograd.Function):
                                                   plan.slice_off, plan.vpos_row, plan.rec, plan.other,
                                                   ptr(out), ptr(scratch), ptr(featIndex) if unsorted else None, stream_handle()),
                   "spatial_conv(rows)")
-            ctx.save_for_backward(pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3, *sx)
-            ctx.state = None
-            ctx.packed_ref = weakref.ref(packedNeighs if pk is packedNeighs else pk)
-            ctx.attrs = (numOutFeatures, bool(combin), batchSize, float(radius), bool(scaleInv), bool(avg))
-            return out
-        ws = _ws(lib.mccnn_spatial_conv_fwd_workspace_bytes(m, e, fin, numOutFeatures, int(bool(combin))), pts.device)
-        if bf16:
+        elif bf16:
             # bf16 feature storage (extension): depth-wise layers only, rows in / rows out as bf16, f32 arithmetic
             _req(not combin and fin % 8 == 0, op + ": bfloat16 feature storage needs a depth-wise layer with numFeatures % 8 == 0")
+            ws = _ws(lib.mccnn_spatial_conv_fwd_workspace_bytes(m, e, fin, numOutFeatures, int(bool(combin))), pts.device)
             out = torch.empty((m, outF), dtype=torch.bfloat16, device=pts.device)
             check(lib.mccnn_spatial_conv_fwd_bf16(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
                                                   ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
                                                   n, m, e, fin, batchSize, float(radius), int(bool(scaleInv)),
                                                   int(bool(avg)), ptr(out), ptr(ws), ws.numel(), stream_handle()),
                   "spatial_conv(bf16)")
-            ctx.save_for_backward(pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3, *sx)
-            ctx.state = None
-            ctx.packed_ref = weakref.ref(packedNeighs if pk is packedNeighs else pk)
-            ctx.attrs = (numOutFeatures, bool(combin), batchSize, float(radius), bool(scaleInv), bool(avg))
-            return out
-        out = torch.empty((m, outF), dtype=torch.float32, device=pts.device)
-        # what the backward pass can reuse: per-edge records (16 B per edge) and, for layers with one input feature, the
-        # per-centre sums; only kept when a gradient will be asked for
-        state = None
-        sbytes = lib.mccnn_spatial_conv_state_bytes(m, e, fin, numOutFeatures, int(bool(combin)))
-        if KEEP_CONV_STATE and sbytes and e > 0 and any(t.requires_grad for t in (inFeatures, w1, b1, w2, b2, w3, b3)):
-            state = torch.empty(sbytes, dtype=torch.uint8, device=pts.device)
-        check(lib.mccnn_spatial_conv_fwd(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
-                                         ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), n, m,
-                                         e, fin, numOutFeatures, int(bool(combin)), batchSize, float(radius),
-                                         int(bool(scaleInv)), int(bool(avg)), ptr(out), ptr(state), ptr(ws), ws.numel(),
-                                         stream_handle()), "spatial_conv")
+        else:
+            ws = _ws(lib.mccnn_spatial_conv_fwd_workspace_bytes(m, e, fin, numOutFeatures, int(bool(combin))), pts.device)
+            out = torch.empty((m, outF), dtype=torch.float32, device=pts.device)
+            # what the backward pass can reuse: per-edge records (16 B per edge) and, for layers with one input feature, the
+            # per-centre sums; only kept when a gradient will be asked for
+            sbytes = lib.mccnn_spatial_conv_state_bytes(m, e, fin, numOutFeatures, int(bool(combin)))
+            if KEEP_CONV_STATE and sbytes and e > 0 and any(t.requires_grad for t in (inFeatures, w1, b1, w2, b2, w3, b3)):
+                state = torch.empty(sbytes, dtype=torch.uint8, device=pts.device)
+            check(lib.mccnn_spatial_conv_fwd(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
+                                             ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), n, m,
+                                             e, fin, numOutFeatures, int(bool(combin)), batchSize, float(radius),
+                                             int(bool(scaleInv)), int(bool(avg)), ptr(out), ptr(state), ptr(ws), ws.numel(),
+                                             stream_handle()), "spatial_conv")
         ctx.save_for_backward(pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3, *sx)
         ctx.state = state
         # the builder's cached tensor OBJECT carries the transposed list (see _transposed_neighbors). A weak reference: the
@@ -1415,33 +1397,29 @@ class _SpatialConv(torch.autograd.Function):
                   "spatial_conv_grad(rows)")
             if feat_index is not None:  # the gradient rows already lie in the order the features arrived in
                 sort_index = None
-            return (None, _unsort_grad(sort_index, fg), None, None, None, None, None, None, None, dw1, db1, dw2.view(ws2), db2.view(bs2), dw3.view(ws3), db3.view(bs3),
-                    None, None, None, None, None, None, None, None, None)
-        ws = _ws(lib.mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, fin, numOutFeatures, int(combin)), pts.device)
-        start_t = perm_t = None
-        if not combin and e > 0:
-            start_t, perm_t, _ = _transposed_neighbors(packed_obj, n)
-        elif combin and 2 <= fin <= 4 and e > 0 and getattr(packed_obj, "_mccnn_transposed", None) is not None:
-            # the transposed list exists already (prefetched with the geometry): the feature gradient is then gathered
-            # through it instead of added with float atomics (deterministic, and cheaper than the atomics)
-            start_t, perm_t, _ = _transposed_neighbors(packed_obj, n)
-        if bf16:
-            check(lib.mccnn_spatial_conv_bwd_bf16(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
-                                                  ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
-                                                  ptr(og), n, m, e, fin, batchSize, radius, int(scaleInv), int(avg),
-                                                  ptr(start_t), ptr(perm_t), ptr(fg), ptr(dw1), ptr(db1), ptr(dw2),
-                                                  ptr(db2), ptr(dw3), ptr(db3), ptr(ws), ws.numel(), stream_handle()),
-                  "spatial_conv_grad(bf16)")
-            return (None, _unsort_grad(sort_index, fg), None, None, None, None, None, None, None, dw1, db1, dw2.view(ws2), db2.view(bs2), dw3.view(ws3), db3.view(bs3),
-                    None, None, None, None, None, None, None, None, None)
-        check(lib.mccnn_spatial_conv_bwd(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
-                                         ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
-                                         ptr(og), n, m, e, fin, numOutFeatures, int(combin), batchSize, radius,
-                                         int(scaleInv), int(avg), ptr(ctx.state), ptr(start_t), ptr(perm_t), ptr(fg),
-                                         ptr(dw1),
-                                         ptr(db1), ptr(dw2), ptr(db2),
-                                         ptr(dw3), ptr(db3), ptr(ws), ws.numel(), stream_handle()),
-              "spatial_conv_grad")
+        else:
+            ws = _ws(lib.mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, fin, numOutFeatures, int(combin)), pts.device)
+            start_t = perm_t = None
+            if not combin and e > 0:
+                start_t, perm_t, _ = _transposed_neighbors(packed_obj, n)
+            elif combin and 2 <= fin <= 4 and e > 0 and getattr(packed_obj, "_mccnn_transposed", None) is not None:
+                # the transposed list exists already (prefetched with the geometry): the feature gradient is then gathered
+                # through it instead of added with float atomics (deterministic, and cheaper than the atomics)
+                start_t, perm_t, _ = _transposed_neighbors(packed_obj, n)
+            if bf16:
+                check(lib.mccnn_spatial_conv_bwd_bf16(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
+                                                      ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
+                                                      ptr(og), n, m, e, fin, batchSize, radius, int(scaleInv), int(avg),
+                                                      ptr(start_t), ptr(perm_t), ptr(fg), ptr(dw1), ptr(db1), ptr(dw2),
+                                                      ptr(db2), ptr(dw3), ptr(db3), ptr(ws), ws.numel(), stream_handle()),
+                      "spatial_conv_grad(bf16)")
+            else:
+                check(lib.mccnn_spatial_conv_bwd(ptr(pts), ptr(feats), ptr(bids), ptr(pdfs), ptr(smp), ptr(st), ptr(pk),
+                                                 ptr(mn), ptr(mx), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
+                                                 ptr(og), n, m, e, fin, numOutFeatures, int(combin), batchSize, radius,
+                                                 int(scaleInv), int(avg), ptr(ctx.state), ptr(start_t), ptr(perm_t), ptr(fg),
+                                                 ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(dw3), ptr(db3), ptr(ws),
+                                                 ws.numel(), stream_handle()), "spatial_conv_grad")
         return (None, _unsort_grad(sort_index, fg), None, None, None, None, None, None, None, dw1, db1, dw2.view(ws2), db2.view(bs2), dw3.view(ws3), db3.view(bs3),
                 None, None, None, None, None, None, None, None, None)
 

@@ -15,15 +15,15 @@ import torch
 
 from . import _env, _lib
 from ._lib import check, ptr, stream_handle
+from .MCConvModule import _edge_guess, _remember_edges, _ws
+
 
 def _load_ext():
     """mccnn_amd/lib/_mccnn_torch.so (csrc/torch_ext.cpp): the same calls as below from C++, with the autograd node on the
     C++ side -- a convolution then costs the host one Python -> C++ call forward and none backward. MCCNN_TORCH_EXT=0 (or a
     tree without the built module) keeps the ctypes form."""
     import importlib.util
-    import os
-    from ._env import flag
-    if not flag("TORCH_EXT"):
+    if not _env.flag("TORCH_EXT"):
         return None
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "_mccnn_torch.so")
     if not os.path.exists(path):
@@ -119,34 +119,16 @@ def _poll_parked():
         _PARKED_LOCK.release()
 
 
-def _ws(nbytes, device):
-    from .MCConvModule import _ws as pool_ws
-    return pool_ws(nbytes, device)
-
-
 _ECAP_SCALE = _env.debug("ecap_scale", 1.0)   # (debugging: generous / starved capacity guesses)
 
 
 def _capacity_guess(gkey, m):
-    if _ECAP_SCALE != 1.0:
-        return int(_capacity_guess_(gkey, m) * _ECAP_SCALE) + 1024
-    return _capacity_guess_(gkey, m)
-
-
-def _capacity_guess_(gkey, m):
-    g = _EDGE_GUESS.get(gkey, 0)
-    if g <= 0:
-        ratio = _EDGE_RATIO.get((gkey[0], gkey[3], gkey[5]), 0.0)
-        g = int(ratio * m * 1.25) + 1024 if ratio > 0.0 else 48 * m + 1024  # first search of a radius: a plain guess
-    return g
+    g = _edge_guess(_EDGE_GUESS, _EDGE_RATIO, gkey, m, 48 * m + 1024)   # (first search of a radius: a plain guess)
+    return int(g * _ECAP_SCALE) + 1024 if _ECAP_SCALE != 1.0 else g
 
 
 def _remember(gkey, m, e):
-    if len(_EDGE_GUESS) > 256:
-        _EDGE_GUESS.clear()
-    _EDGE_GUESS[gkey] = e + e // 16 + 64
-    if m > 0:
-        _EDGE_RATIO[(gkey[0], gkey[3], gkey[5])] = e / float(m)
+    _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
 
 
 class Geometry:
