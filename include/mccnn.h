@@ -160,6 +160,33 @@ int mccnn_find_neighbors_fill(const float* centres, const int* centre_batch_ids,
                               int num_cells, float radius, int scale_inv, const int* centre_order,
                               const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
                               mccnn_stream_t stream);
+/* The search with a cap on the neighbours per centre (extension; no counterpart in the reference).
+ * max_neighbors = K > 0; 0 makes both calls the uncapped ones above, a negative value is
+ * MCCNN_E_BADARG. A centre with k <= K hits keeps its row; one with k > K keeps exactly K of them,
+ * those at the canonical ranks floor(t * k / K), t = 0 .. K-1 (64-bit integer arithmetic), in that
+ * order -- a stride over the whole row, so every cell of the 27-cell window stays represented in
+ * proportion. start_idx = exclusive prefix of min(k, K), *total_dev = E = their total, rows (j, i)
+ * at start_idx[i]: the capped list is a subsequence of the uncapped one, row by row, and the same
+ * bytes in every run (no atomics, no arrival order). Everything downstream takes the list as it is.
+ * Argument lists and protocol of mccnn_find_neighbors_count / _fill (e may be a guess; ws untouched
+ * between the calls; the same max_neighbors in both), but the workspace is the larger one of
+ * mccnn_find_neighbors_capped_workspace_bytes whenever K > 0: the count pass leaves the true row
+ * lengths there for the fill pass. */
+size_t mccnn_find_neighbors_capped_workspace_bytes(int m, int n);
+int mccnn_find_neighbors_count_capped(const float* centres, const int* centre_batch_ids, int m,
+                                      const float* sorted_pts, int n, const int* cell_indexs,
+                                      const float* aabb_min, const float* aabb_max, int batch_size,
+                                      int num_cells, float radius, int scale_inv,
+                                      const int* centre_order, int* start_idx, int* total_dev,
+                                      void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                      int max_neighbors);
+int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_batch_ids, int m,
+                                     const float* sorted_pts, int n, const int* cell_indexs,
+                                     const float* aabb_min, const float* aabb_max, int batch_size,
+                                     int num_cells, float radius, int scale_inv,
+                                     const int* centre_order, const int* start_idx, int e,
+                                     int* packed, void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                     int max_neighbors);
 /* inv[new_idx[i]] = i -- the visiting order above for same-level searches (sort_gpu.cu:332-345). */
 int mccnn_invert_permutation(const int* new_idx, int n, int* inv, mccnn_stream_t stream);
 

@@ -338,8 +338,12 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     work on the builder as on any module; `forward` is create_convolution."""
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
-                 decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None):
+                 decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
+                 maxNeighbors=0):
+        """maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
+        maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path."""
         super().__init__()
+        self.maxNeighbors_ = self.__check_cap__(maxNeighbors)
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
         # node (spatial_conv(sortIndex=)) -- fewer op calls and graph nodes per convolution, same kernels and results
@@ -420,6 +424,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             lst.append(p)
 
     # ------------------------------------------------------------------ caches
+    @staticmethod
+    def __check_cap__(maxNeighbors):
+        if not isinstance(maxNeighbors, int) or isinstance(maxNeighbors, bool) or maxNeighbors < 0:
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("maxNeighbors must be an integer >= 0 (0 = no cap)")
+        return maxNeighbors
+
     def __geometry_defaults__(self, inPH, inLevel, outPH, outLevel, KDEWindow, relativeRadius, usePDF):
         """-> (KDEWindow, relativeRadius, usePDF, outPH, outLevel) with the builder's defaults filled in
         (MCConvBuilder.py:299-325)."""
@@ -429,11 +440,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 inPH if outPH is None else outPH, inLevel if outLevel is None else outLevel)
 
     def __compute_dic_keys__(self, inPointHierarchy, outPointHierarchy, inPointLevel, outPointLevel, convRadius,
-                             KDEWindow, relativeRadius, usePDF):
+                             KDEWindow, relativeRadius, usePDF, maxNeighbors=0):
         # MCConvBuilder.py:203-238 (the strings depend on names and numbers only: memoised -- six str() of floats per call)
+        # maxNeighbors > 0 (extension): a capped list and its PDFs are other cache entries than the uncapped ones and those
+        # of another cap; the grid is the same. Without a cap the strings are the reference's.
         memo = self.__dict__.setdefault("_keyMemo", {})
         k = (inPointHierarchy.hierarchyName_, outPointHierarchy.hierarchyName_, inPointLevel, outPointLevel, convRadius, KDEWindow,
-             relativeRadius, usePDF)
+             relativeRadius, usePDF, maxNeighbors)
         try:
             hit = memo.get(k)
         except TypeError:   # (an unhashable argument: a tensor radius)
@@ -444,6 +457,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             str(relativeRadius)
         keyNeighs = keyGrid + '|' + outPointHierarchy.hierarchyName_ + '|' + str(outPointLevel)
         keyPDF = keyNeighs + '|' + str(KDEWindow) + '|' + str(usePDF)
+        if maxNeighbors > 0:
+            keyNeighs += '|' + str(maxNeighbors)
+            keyPDF += '|' + str(maxNeighbors)
         if k is not None and len(memo) < 4096:
             memo[k] = (keyGrid, keyNeighs, keyPDF)
         return keyGrid, keyNeighs, keyPDF
@@ -519,7 +535,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self.prefetchTransposed_ = {}
 
     def prefetch_geometry(self, inPointHierarchy, inPointLevel, convRadius, outPointHierarchy=None, outPointLevel=None,
-                          KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False):
+                          KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False, maxNeighbors=None):
         """Extension (no counterpart in the reference): computes the grid, the neighbour list and the PDFs that
         create_convolution() with the same arguments looks up in the caches -- for the NEXT batch, on a side stream, and
         parks them until the next reset(). Geometry depends on the points only, not on the network, so in a training
@@ -536,17 +552,21 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         transposed=True (depth-wise layers will convolve over this neighbour list): reset() also starts the list's
         transposition for their backward pass on the side stream, where it runs under the forward convolutions.
         transposed="list" (layers with 2..4 input features and multiFeatureConv=True will): the transposed list alone --
-        their feature gradient is then gathered through it instead of scattered with float atomics (bit-reproducible)."""
+        their feature gradient is then gathered through it instead of scattered with float atomics (bit-reproducible).
+
+        maxNeighbors: the cap of the create_convolution() call this prepares (None = the builder's default). A capped
+        geometry is prefetched op by op on the side stream, never by the native executor."""
         currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
             inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
+        currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
-                                                               currKDEWindow, currRelativeRadius, currUsePDF)
+                                                               currKDEWindow, currRelativeRadius, currUsePDF, currCap)
         pts, bids = inPointHierarchy.points_[inPointLevel], inPointHierarchy.batchIds_[inPointLevel]
         mn, mx, B = inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, inPointHierarchy.batchSize_
         if not pts.is_cuda:
             return  # host tensors (a CPU checker behind `ops=`): nothing to overlap, create_convolution computes inline
-        if self.__prefetch_native__(inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow,
-                                    currRelativeRadius, currUsePDF, keyGrid, keyNeighs, keyPDF, transposed):
+        if currCap == 0 and self.__prefetch_native__(inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow,
+                                                     currRelativeRadius, currUsePDF, keyGrid, keyNeighs, keyPDF, transposed):
             return
         if self.sideStream_ is None:
             self.sideStream_ = torch.cuda.Stream(device=pts.device)
@@ -579,13 +599,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             bg_prev = bg.mccnn_background_launches(1)
         try:
             self.__prefetch_on_side__(side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed)
+                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap)
         finally:
             if bg is not None:
                 bg.mccnn_background_launches(bg_prev)
 
     def __prefetch_on_side__(self, side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed):
+                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap=0):
+        capArgs = {"maxNeighbors": currCap} if currCap > 0 else {}   # (a checker behind `ops=` need not know the keyword)
         with torch.cuda.stream(side):
             if keyGrid not in grids and self.fuseSort_ and self.hipSurface_ and not pts.requires_grad:
                 _hip_ops = _hip_ops_mod()
@@ -600,7 +621,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 grids[keyGrid] = (sortPts, sortBatchs, cellIndexs, indexs)
             g = grids[keyGrid]
             deferred = None
-            if self.hipSurface_:  # the HIP op surface (not a checker handed in through `ops=`)
+            if self.hipSurface_ and currCap == 0:  # the HIP op surface (not a checker handed in through `ops=`); no capped form
                 _hip_ops = _hip_ops_mod()
                 deferred = _hip_ops.find_neighbors_pdf_deferred
             if keyNeighs not in neighs and keyPDF not in pdfs and currUsePDF and deferred is not None:
@@ -616,7 +637,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                                                        currRelativeRadius)
             if keyNeighs not in neighs:
                 neighs[keyNeighs] = tuple(self.ops_.find_neighbors(outPH.points_[outLevel], outPH.batchIds_[outLevel], g[0],
-                                                                   g[2], mn, mx, convRadius, B, currRelativeRadius))
+                                                                   g[2], mn, mx, convRadius, B, currRelativeRadius, **capArgs))
             nb = neighs[keyNeighs]
             if keyPDF not in pdfs:
                 if currUsePDF:
@@ -904,8 +925,12 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     # ------------------------------------------------------------------ create_convolution
     def create_convolution(self, convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                            outPointHierarchy=None, outPointLevel=None, multiFeatureConv=None, outNumFeatures=None,
-                           KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None):
+                           KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None, maxNeighbors=None):
         # defaults: MCConvBuilder.py:299-325
+        # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
+        # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
+        # like one whose points require a gradient.
+        currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         currMultiFeatureConv = self.multiFeatureConvs_ if multiFeatureConv is None else multiFeatureConv
         currNumOutFeatures = inNumFeatures if outNumFeatures is None else outNumFeatures
         currUseAVG = self.useAVG_ if useAVG is None else useAVG
@@ -920,7 +945,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(
             inPointHierarchy, currOutPointHierarchy, inPointLevel, currOutPointLevel, convRadius, currKDEWindow,
-            currRelativeRadius, currUsePDF)
+            currRelativeRadius, currUsePDF, currCap)
         _log("Convolution: %s (KDE: %s | MF: %s | Rel: %s | PDF: %s)" % (convName, currKDEWindow,
                                                                        currMultiFeatureConv, currRelativeRadius,
                                                                        currUsePDF))
@@ -929,7 +954,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # sorted inside the convolution (by the native executor's layer call, or by spatial_conv(sortIndex=) below)
         inPts = inPointHierarchy.points_[inPointLevel]
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
-        if self.native_ and fused:
+        if self.native_ and fused and currCap == 0:
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
@@ -974,7 +999,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self._trace("sort_points_step2", keyGrid)
 
         # neighbours (MCConvBuilder.py:366-376)
-        if fused and currUsePDF and keyNeighs not in self.cacheNeighs_ and keyPDF not in self.cachePDFs_:
+        if fused and currCap == 0 and currUsePDF and keyNeighs not in self.cacheNeighs_ and keyPDF not in self.cachePDFs_:
             # search + KDE enqueued back to back (list sizes from the last total of this shape), ONE wait for the edge
             # count at the end instead of a wait between the two ops; None on the first call of a shape
             _hip_ops = _hip_ops_mod()
@@ -994,7 +1019,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             startIndexs, packedNeighs = self.ops_.find_neighbors(
                 currOutPointHierarchy.points_[currOutPointLevel], currOutPointHierarchy.batchIds_[currOutPointLevel],
                 currGridTuple[0], currGridTuple[2], inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, convRadius,
-                inPointHierarchy.batchSize_, currRelativeRadius)
+                inPointHierarchy.batchSize_, currRelativeRadius, **({"maxNeighbors": currCap} if currCap > 0 else {}))
             currNeighTuple = (startIndexs, packedNeighs)
             self.cacheNeighs_[keyNeighs] = currNeighTuple
             self._trace("find_neighbors", keyNeighs)

@@ -772,12 +772,17 @@ def transform_indexs(inIndexs, inNewPositions):
     return out
 
 
-def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv):
+def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv, maxNeighbors=0):
     """FindNeighbors (MCConvModuleSrc:51, find_neighbors.cc:80-185) -> (startIndexs [M,1], packedNeighs [E,2]).
-    Reads E back to the host to size the second output, like the reference (find_neighbors.cu:307-309)."""
+    Reads E back to the host to size the second output, like the reference (find_neighbors.cu:307-309).
+    maxNeighbors (extension): K > 0 caps the neighbours per centre -- a row of k > K hits keeps the K hits at the canonical
+    ranks floor(t * k / K), t = 0 .. K-1, a stride over the whole row; shorter rows are unchanged. The capped list is a
+    subsequence of the uncapped one and the same bytes in every run. 0 = no cap (the reference's list)."""
     op = "FindNeighborsOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
+    _req(isinstance(maxNeighbors, int) and not isinstance(maxNeighbors, bool) and 0 <= maxNeighbors < 2 ** 31,
+         op + " expects maxNeighbors to be an integer >= 0 (0 = no cap)")
     c, cb = _points_input(op, inPts.detach(), inBatchIds)
     p2 = _f32(inPts2.detach(), "points2")
     _check_points(p2, "points2", op)
@@ -789,25 +794,33 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     start = torch.empty((m, 1), dtype=torch.int32, device=c.device)
     box, boxv = _host_mailbox()
     n2 = p2.shape[0]
-    ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
+    cap = int(maxNeighbors)
+    if cap > 0:   # the capped passes: entries of their own, a workspace that also holds the true row lengths
+        ws = _ws(lib.mccnn_find_neighbors_capped_workspace_bytes(m, n2), c.device)
+        tail = (cap,)
+        count_fn, fill_fn = lib.mccnn_find_neighbors_count_capped, lib.mccnn_find_neighbors_fill_capped
+    else:
+        ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
+        tail = ()
+        count_fn, fill_fn = lib.mccnn_find_neighbors_count, lib.mccnn_find_neighbors_fill
     order = _order_hint(inPts, m)
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
             int(bool(scaleInv)), ptr(order))
     # The size of the second output is only known on the device: the prefix sum stores the total straight into a
     # pinned host word (no copy is enqueued) and the host polls it.
     boxv[0] = -1
-    check(lib.mccnn_find_neighbors_count(*args, ptr(start), box.data_ptr(), ptr(ws), ws.numel(), stream_handle()),
-          "find_neighbors(count)")
+    check(count_fn(*args, ptr(start), box.data_ptr(), ptr(ws), ws.numel(), stream_handle(), *tail), "find_neighbors(count)")
     # Searches repeat with the same shapes step after step, so the fill is launched into a buffer sized from the last
     # total of this shape BEFORE the total is read: the host round trip hides behind the kernel. Too small a guess ->
     # exact rerun.
     gkey = (c.device.index, m, n2, float(radius), int(batchSize), bool(scaleInv))
+    if cap > 0:   # capped searches keep guesses of their own, per cap (the ratio table is keyed by gkey[3] and gkey[5])
+        gkey = gkey[:5] + ((bool(scaleInv), cap),)
     guess = _edge_guess(_EDGE_GUESS, _EDGE_RATIO, gkey, m)
     packed = None
     if guess > 0:
         buf = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
-        check(lib.mccnn_find_neighbors_fill(*args, ptr(start), guess, ptr(buf), ptr(ws), ws.numel(), stream_handle()),
-              "find_neighbors(fill)")
+        check(fill_fn(*args, ptr(start), guess, ptr(buf), ptr(ws), ws.numel(), stream_handle(), *tail), "find_neighbors(fill)")
         e = _await_mailbox(boxv)
         if e <= guess:
             packed = buf[:e]
@@ -815,8 +828,7 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
         e = _await_mailbox(boxv)
     if packed is None:
         packed = torch.empty((e, 2), dtype=torch.int32, device=c.device)
-        check(lib.mccnn_find_neighbors_fill(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle()),
-              "find_neighbors(fill)")
+        check(fill_fn(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle(), *tail), "find_neighbors(fill)")
     _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
     return start, packed
 

@@ -75,8 +75,24 @@ __device__ __forceinline__ float readlane_f(float v, int l) {
 // and stores them with ONE instruction per (centre, segment). Faster alone (count pass on the room 35 -> 26 us), but its
 // denser LDS-read / VALU bursts cost the convolution kernels it runs beside more than the search saves (pipelined step
 // 0.640 -> 0.672 ms): background launches (mccnn_background_launches) keep the plain loop.
+// CAPPED (mccnn_find_neighbors_*_capped): rows of more than K hits keep the K hits at canonical ranks floor(t * k / K),
+// t = 0 .. K-1 -- a stride over the whole row, so all 27 cells of the window stay represented in proportion. The count
+// pass leaves the true row length in `kfull` and emits min(k, K) for the prefix sum; the fill pass, which knows every
+// hit's canonical rank from its ballot / mbcnt compaction, writes the kept ones at their slot t. No atomics, no arrival
+// order: the capped list is a subsequence of the uncapped one and the same bytes in every run. The uncapped
+// instantiations carry none of this (if constexpr).
+// Slot of the hit at canonical rank r of a row of k > K hits, or -1 when the cap drops it: t = ceil(r * K / k) is the only
+// candidate, kept iff floor(t * k / K) == r. k and K are wave-uniform: 32-bit division where the products fit.
+__device__ __forceinline__ int cap_slot(int r, int k, int K) {
+    if ((unsigned long long)k * ((unsigned long long)K + 1ull) <= 0xffffffffull) {
+        const unsigned t = ((unsigned)r * (unsigned)K + (unsigned)k - 1u) / (unsigned)k;
+        return (t < (unsigned)K && (t * (unsigned)k) / (unsigned)K == (unsigned)r) ? (int)t : -1;
+    }
+    const unsigned long long t = ((unsigned long long)r * (unsigned long long)K + (unsigned long long)k - 1ull) / (unsigned long long)k;
+    return (t < (unsigned long long)K && (t * (unsigned long long)k) / (unsigned long long)K == (unsigned long long)r) ? (int)t : -1;
+}
 // (the kernel's body: workgroup `blk` of `nblk` -- the single launch, and one geometry's share of a batch launch)
-template <int MODE, bool LEAN>
+template <int MODE, bool LEAN, bool CAPPED = false>
 __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk, const float* __restrict__ centres, const int* __restrict__ cb, int m,
                                                     const float* __restrict__ pts, const int* __restrict__ cells,
                                                     const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
@@ -86,7 +102,9 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                                                     int capacity, unsigned long long* __restrict__ zeroWords, int numZero,
                                                     int G /* centres per wave, 1 .. 32 */, float Tabs,
                                                     const int* __restrict__ scanCnt, int* __restrict__ startOut,
-                                                    int* __restrict__ totalDev, int* __restrict__ totalHost) {
+                                                    int* __restrict__ totalDev, int* __restrict__ totalHost,
+                                                    const int capK = 0 /* CAPPED: hits kept per centre, > 0 (not `K`: the round lambdas below have a K of their own) */,
+                                                    int* __restrict__ kfull = nullptr /* CAPPED: [m] true row lengths, count -> fill */) {
     constexpr bool FILL = MODE == 1;
     // the status words of the prefix sum that follows the count pass (scan.hip): cleared here, no launch of their own
     if (!FILL && blk == 0)
@@ -142,6 +160,8 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
     const int key = own ? ((c.b * nc + c.x) * nc + c.y) * nc + c.z : -1;
     int count = 0;                                   // hits of this lane's centre so far
     const int base = (FILL && own) ? (scanCnt ? scanLds[i] : startIdx[i]) : 0;
+    int krow = 0;                                    // CAPPED fill: the true row length of this lane's centre
+    if constexpr (CAPPED && FILL) krow = own ? kfull[i] : 0;
     unsigned todo = (unsigned)(__ballot(own) & ((1ull << G) - 1));
     const int2* ct = reinterpret_cast<const int2*>(cells);
     int2* out = reinterpret_cast<int2*>(packed);
@@ -210,9 +230,15 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                     if (r * 64 < total) {
                         const unsigned long long bm = mw[r];
                         if (__builtin_amdgcn_inverse_ballot_w64(bm)) {
-                            const int pos = cbase + run + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
-                            if (fits) out[pos] = make_int2(jr[r], cid);
-                            else if (pos < capacity) out[pos] = make_int2(jr[r], cid);
+                            const int rank = run + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
+                            if constexpr (CAPPED) {
+                                const int slot = hits > capK ? cap_slot(rank, hits, capK) : rank;   // (hits: the row's true length)
+                                if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(jr[r], cid);
+                            } else {
+                                const int pos = cbase + rank;
+                                if (fits) out[pos] = make_int2(jr[r], cid);
+                                else if (pos < capacity) out[pos] = make_int2(jr[r], cid);
+                            }
                         }
                         run += __builtin_popcountll(bm);
                     }
@@ -301,6 +327,8 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                 const int cid = __builtin_amdgcn_readlane(i, cl);
                 int cbase = 0, ccount = __builtin_amdgcn_readlane(count, cl);
                 if (FILL) cbase = __builtin_amdgcn_readlane(base, cl);
+                int ck = 0;   // CAPPED fill: the row's true length; ccount carries the canonical rank across segments
+                if constexpr (CAPPED && FILL) ck = __builtin_amdgcn_readlane(krow, cl);
                 // (Measured and withdrawn: this loop without bounds -- the last round padded with unreachable points -- unrolled
                 // over the four rounds of a segment, the ballots kept in lanes 0..3 and stored once per segment: the count pass
                 // alone 35 -> 26 us and a sequential step 0.740 -> 0.728 ms, but the PIPELINED step 0.640 -> 0.672 ms, whatever
@@ -315,8 +343,14 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                         const bool hit = point_dist2(p.x, p.y, p.z, cx, cy, cz) < T;
                         const unsigned long long bm = __ballot(hit);
                         if (FILL && hit) {
-                            const int pos = cbase + ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
-                            if (pos < capacity) out[pos] = make_int2(__float_as_int(p.w), cid);  // capacity < E: see _fill
+                            const int rank = ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
+                            if constexpr (CAPPED) {
+                                const int slot = ck > capK ? cap_slot(rank, ck, capK) : rank;
+                                if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(__float_as_int(p.w), cid);
+                            } else {
+                                const int pos = cbase + rank;
+                                if (pos < capacity) out[pos] = make_int2(__float_as_int(p.w), cid);  // capacity < E: see _fill
+                            }
                         }
                         if (!FILL) {
                             writelane_u<K>(mlo, (unsigned)bm);
@@ -349,8 +383,14 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                     const bool hit = t < segN && point_dist2(p.x, p.y, p.z, cx, cy, cz) < T;
                     const unsigned long long bm = __ballot(hit);
                     if (FILL && hit) {
-                        const int pos = cbase + ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
-                        if (pos < capacity) out[pos] = make_int2(__float_as_int(p.w), cid);  // capacity < E: see _fill
+                        const int rank = ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
+                        if constexpr (CAPPED) {
+                            const int slot = ck > capK ? cap_slot(rank, ck, capK) : rank;
+                            if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(__float_as_int(p.w), cid);
+                        } else {
+                            const int pos = cbase + rank;
+                            if (pos < capacity) out[pos] = make_int2(__float_as_int(p.w), cid);  // capacity < E: see _fill
+                        }
                     }
                     if (!FILL) {
                         const int round = (seg + r) >> 6;
@@ -367,7 +407,14 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
             __builtin_amdgcn_wave_barrier();
         }
     }
-    if (!FILL && own) cnt[i] = count;
+    if constexpr (CAPPED) {
+        if (!FILL && own) {
+            kfull[i] = count;
+            cnt[i] = min(count, capK);
+        }
+    } else {
+        if (!FILL && own) cnt[i] = count;
+    }
 }
 
 template <int MODE, bool LEAN>
@@ -383,6 +430,24 @@ __global__ __launch_bounds__(256) void neigh_window(const float* __restrict__ ce
                                                     int* __restrict__ totalDev, int* __restrict__ totalHost) {
     neigh_window_body<MODE, LEAN>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv, order, cnt,
                                   masks, startIdx, packed, capacity, zeroWords, numZero, G, Tabs, scanCnt, startOut, totalDev, totalHost);
+}
+
+// The capped passes (mccnn_find_neighbors_count_capped / _fill_capped): kernels of their own, so that the uncapped ones
+// keep their argument lists and their code.
+template <int MODE, bool LEAN>
+__global__ __launch_bounds__(256) void neigh_window_capped(const float* __restrict__ centres, const int* __restrict__ cb, int m,
+                                                           const float* __restrict__ pts, const int* __restrict__ cells,
+                                                           const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
+                                                           float radius, int scaleInv, const int* __restrict__ order,
+                                                           int* __restrict__ cnt, unsigned long long* __restrict__ masks,
+                                                           const int* __restrict__ startIdx, int* __restrict__ packed,
+                                                           int capacity, unsigned long long* __restrict__ zeroWords, int numZero,
+                                                           int G, float Tabs, const int* __restrict__ scanCnt,
+                                                           int* __restrict__ startOut, int* __restrict__ totalDev,
+                                                           int* __restrict__ totalHost, int K, int* __restrict__ kfull) {
+    neigh_window_body<MODE, LEAN, true>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv, order,
+                                        cnt, masks, startIdx, packed, capacity, zeroWords, numZero, G, Tabs, scanCnt, startOut, totalDev,
+                                        totalHost, K, kfull);
 }
 
 // One launch for the count (or the fill) pass of a BATCH of searches (mccnn_geometry_build_batch): the plain loop of the
@@ -825,6 +890,11 @@ size_t mccnn_find_neighbors_workspace_bytes(int m, int n) {
     (void)n;
     return align_up(m1 * 4) + scan_workspace_bytes((int)m1) + align_up(m1 * MCCNN_NW_ROUNDS * sizeof(unsigned long long)) + 256;
 }
+// ... of the capped passes: the same layout, then the true row lengths (one int per centre)
+size_t mccnn_find_neighbors_capped_workspace_bytes(int m, int n) {
+    size_t m1 = (size_t)(m > 0 ? m : 1);
+    return mccnn_find_neighbors_workspace_bytes(m, n) + align_up(m1 * 4);
+}
 
 // Centres per wave: 8 consecutive centres of the visiting order share most of their windows on a large list (~8 points
 // per cell), but a list with few centres needs the waves -- 6 344 pooling centres with ~900 candidates each ran 139 us per
@@ -870,15 +940,19 @@ struct NeighWs {
     int* cnt;  // hits per centre
     void* scanws;
     unsigned long long* masks;  // per centre: the ballots of its first MCCNN_NW_ROUNDS candidate rounds (count -> fill)
+    int* kfull;  // capped passes only: true hits per centre (count -> fill)
 };
-static bool neigh_ws(void* ws, size_t ws_bytes, int m, int n, NeighWs& w) {
-    if (!ws || ws_bytes < mccnn_find_neighbors_workspace_bytes(m, n)) return false;
+static bool neigh_ws(void* ws, size_t ws_bytes, int m, int n, NeighWs& w, bool capped = false) {
+    if (!ws || ws_bytes < (capped ? mccnn_find_neighbors_capped_workspace_bytes(m, n) : mccnn_find_neighbors_workspace_bytes(m, n)))
+        return false;
     size_t m1 = (size_t)(m > 0 ? m : 1);
     Arena a(ws, ws_bytes);
     w.cnt = a.take<int>(m1);
     w.scanws = a.take<char>(scan_workspace_bytes((int)m1));
     w.masks = a.take<unsigned long long>(m1 * MCCNN_NW_ROUNDS);
     (void)n;
+    w.kfull = capped ? a.take<int>(m1) : nullptr;
+    if (capped && !w.kfull) return false;
     return w.cnt && w.scanws && w.masks;
 }
 
@@ -886,7 +960,7 @@ static int find_neighbors_count_impl(const float* centres, const int* centre_bat
                                int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
                                int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                int* start_idx, int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream,
-                               bool skip_scan = false);
+                               bool skip_scan = false, int max_neighbors = 0);
 
 int mccnn_find_neighbors_count(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
                                int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
@@ -910,8 +984,9 @@ static int find_neighbors_count_impl(const float* centres, const int* centre_bat
                                int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
                                int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                int* start_idx, int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream,
-                               bool skip_scan) {
-    if (m < 0 || n < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || !total_dev) return MCCNN_E_BADARG;
+                               bool skip_scan, int max_neighbors) {
+    if (m < 0 || n < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || !total_dev || max_neighbors < 0) return MCCNN_E_BADARG;
+    const bool capped = max_neighbors > 0;
     hipStream_t s = (hipStream_t)stream;
     if (m == 0) {
         int rc = launch_zero_words(total_dev, 1, s);
@@ -921,12 +996,23 @@ static int find_neighbors_count_impl(const float* centres, const int* centre_bat
     if (!centres || !centre_batch_ids || !cell_indexs || !aabb_min || !aabb_max || !start_idx || (n > 0 && !sorted_pts))
         return MCCNN_E_BADARG;
     NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w)) return MCCNN_E_WORKSPACE;
+    if (!neigh_ws(ws, ws_bytes, m, n, w, capped)) return MCCNN_E_WORKSPACE;
     const int G = neigh_group(m);
     const float Tabs = scale_inv ? 0.0f : sqrt_threshold_host(radius);
     unsigned long long* zw = (unsigned long long*)w.scanws;
     const int nz = (int)(scan_status_bytes(m) / sizeof(unsigned long long));
-    if (neigh_lean())
+    if (capped) {
+        if (neigh_lean())
+            neigh_window_capped<0, true><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr, max_neighbors,
+                w.kfull);
+        else
+            neigh_window_capped<0, false><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr, max_neighbors,
+                w.kfull);
+    } else if (neigh_lean())
         neigh_window<0, true><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
                                                      aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
                                                      w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr);
@@ -945,15 +1031,17 @@ static int find_neighbors_fill_impl(const float* centres, const int* centre_batc
                               int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
                               int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                               const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
-                              mccnn_stream_t stream, int* scan_start_out, int* scan_total_dev, int* scan_total_host) {
-    if (m < 0 || n < 0 || e < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f)) return MCCNN_E_BADARG;
+                              mccnn_stream_t stream, int* scan_start_out, int* scan_total_dev, int* scan_total_host,
+                              int max_neighbors = 0) {
+    if (m < 0 || n < 0 || e < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || max_neighbors < 0) return MCCNN_E_BADARG;
+    const bool capped = max_neighbors > 0;
     const bool scan = scan_start_out != nullptr;   // the counts of a skip_scan count pass are still in `ws`: scanned here
     if (scan && (m > MCCNN_NW_SCAN_M || !scan_total_dev)) return MCCNN_E_BADARG;
     if (m == 0 || e == 0) return 0;
     if (!centres || !centre_batch_ids || !sorted_pts || !cell_indexs || !aabb_min || !aabb_max || (!scan && !start_idx) || !packed)
         return MCCNN_E_BADARG;
     NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w)) return MCCNN_E_WORKSPACE;
+    if (!neigh_ws(ws, ws_bytes, m, n, w, capped)) return MCCNN_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // (mask rows are indexed by visiting position: the two passes may group differently -- the compaction gains little
     // from more centres per wave: 100 k centres 0.0612 ms at 8, 0.0622 at 16; 800 k centres 0.305 at 8, 0.295 at 24)
@@ -963,7 +1051,18 @@ static int find_neighbors_fill_impl(const float* centres, const int* centre_batc
     size_t dyn = neigh_lds_pad();
     if (scan && dyn < (size_t)m * sizeof(int)) dyn = (size_t)m * sizeof(int);
     const int* scanCnt = scan ? w.cnt : nullptr;
-    if (neigh_lean())
+    if (capped) {
+        if (neigh_lean())
+            neigh_window_capped<1, true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out, scan_total_dev,
+                scan_total_host, max_neighbors, w.kfull);
+        else
+            neigh_window_capped<1, false><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out, scan_total_dev,
+                scan_total_host, max_neighbors, w.kfull);
+    } else if (neigh_lean())
         neigh_window<1, true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
                                                      aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
                                                      nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out,
@@ -985,6 +1084,29 @@ int mccnn_find_neighbors_fill(const float* centres, const int* centre_batch_ids,
     return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
                                     num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
                                     nullptr, nullptr);
+}
+
+// The capped search (max_neighbors = K > 0; 0 = the passes above): count -> scan -> fill at every list size, like the
+// uncapped pair. (The form whose prefix sum rides in the fill pass belongs to find_neighbors_chain, the native executor's
+// geometry build, which takes no cap.)
+int mccnn_find_neighbors_count_capped(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
+                                      int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
+                                      int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
+                                      int* start_idx, int* total_dev, void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                      int max_neighbors) {
+    return find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
+                                     num_cells, radius, scale_inv, centre_order, start_idx, total_dev, nullptr, ws, ws_bytes, stream,
+                                     false, max_neighbors);
+}
+
+int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
+                                     int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
+                                     int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
+                                     const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
+                                     mccnn_stream_t stream, int max_neighbors) {
+    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
+                                    num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
+                                    nullptr, nullptr, max_neighbors);
 }
 
 }  // extern "C"
