@@ -187,6 +187,25 @@ int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_bat
                                      const int* centre_order, const int* start_idx, int e,
                                      int* packed, void* ws, size_t ws_bytes, mccnn_stream_t stream,
                                      int max_neighbors);
+/* The capped fill pass with a fresh stratified sample instead of the canonical ranks (extension).
+ * After mccnn_find_neighbors_count_capped with the same max_neighbors = K > 0, over the same
+ * workspace; the count pass, start_idx and the total do not depend on the seed. The strata of a row
+ * of k > K hits are the canonical ranks [lo_t, lo_{t+1}), lo_t = floor(t * k / K), t = 0 .. K-1
+ * (mccnn_find_neighbors_fill_capped keeps offset 0 of each). Slot t holds the hit at rank
+ * lo_t + off_t with, all in uint32 arithmetic modulo 2^32,
+ *     mix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *     h = mix(mix(seed + 0x9E3779B9 * (i + 1)) + t)       i = the centre's index in `centres`
+ *     off_t = (h * (lo_{t+1} - lo_t)) >> 32               a 64-bit product
+ * Rows of k <= K hits are untouched. The list is a subsequence of the uncapped one in canonical
+ * order; no atomics and no generator state: the same (inputs, K, seed) give the same bytes in
+ * every run. max_neighbors <= 0 is MCCNN_E_BADARG. */
+int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_batch_ids, int m,
+                                      const float* sorted_pts, int n, const int* cell_indexs,
+                                      const float* aabb_min, const float* aabb_max, int batch_size,
+                                      int num_cells, float radius, int scale_inv,
+                                      const int* centre_order, const int* start_idx, int e,
+                                      int* packed, void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                      int max_neighbors, unsigned seed);
 /* inv[new_idx[i]] = i -- the visiting order above for same-level searches (sort_gpu.cu:332-345). */
 int mccnn_invert_permutation(const int* new_idx, int n, int* inv, mccnn_stream_t stream);
 

@@ -14,6 +14,7 @@ import math
 import os
 import sys
 import time
+import zlib
 import torch
 
 from . import _env
@@ -339,11 +340,15 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0):
+                 maxNeighbors=0, sampleSeed=None):
         """maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
-        maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path."""
+        maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path.
+        sampleSeed (extension): None, or an integer in [0, 2^32) -- the capped layers then draw a stratified sample of
+        their over-full rows (find_neighbors(sampleSeed=)) instead of the canonical ranks. The attribute sampleSeed_ may be
+        reassigned between steps (typically to the step number, followed by reset()); layers without a cap ignore it."""
         super().__init__()
         self.maxNeighbors_ = self.__check_cap__(maxNeighbors)
+        self.sampleSeed_ = self.__check_seed__(sampleSeed)
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
         # node (spatial_conv(sortIndex=)) -- fewer op calls and graph nodes per convolution, same kernels and results
@@ -431,6 +436,35 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             raise InvalidArgumentError("maxNeighbors must be an integer >= 0 (0 = no cap)")
         return maxNeighbors
 
+    @staticmethod
+    def __check_seed__(sampleSeed):
+        if sampleSeed is not None and (not isinstance(sampleSeed, int) or isinstance(sampleSeed, bool)
+                                       or not 0 <= sampleSeed < 2 ** 32):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("sampleSeed must be None or an integer in [0, 2^32)")
+        return sampleSeed
+
+    def __layer_seed__(self, currCap, sampleSeed):
+        """The seed of a layer with cap currCap: its own (which needs a cap) or the builder's (capped layers only)."""
+        if sampleSeed is not None:
+            if currCap == 0:
+                from .MCConvModule import InvalidArgumentError
+                raise InvalidArgumentError("sampleSeed needs a cap (maxNeighbors > 0)")
+            return self.__check_seed__(sampleSeed)
+        return self.__check_seed__(self.sampleSeed_) if currCap > 0 else None
+
+    @staticmethod
+    def __search_args__(currCap, currSeed, keyNeighs):
+        """Keywords of the find_neighbors call of a geometry (none without a cap: a checker behind `ops=` need not know
+        them). The op's seed is the layer's plus the CRC-32 of the geometry's neighbour key without the seed part, so that
+        two layers over the same centres do not draw the same offsets."""
+        if currCap == 0:
+            return {}
+        if currSeed is None:
+            return {"maxNeighbors": currCap}
+        base = keyNeighs[:-len('|s' + str(currSeed))]
+        return {"maxNeighbors": currCap, "sampleSeed": (currSeed + zlib.crc32(base.encode())) & 0xffffffff}
+
     def __geometry_defaults__(self, inPH, inLevel, outPH, outLevel, KDEWindow, relativeRadius, usePDF):
         """-> (KDEWindow, relativeRadius, usePDF, outPH, outLevel) with the builder's defaults filled in
         (MCConvBuilder.py:299-325)."""
@@ -440,13 +474,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 inPH if outPH is None else outPH, inLevel if outLevel is None else outLevel)
 
     def __compute_dic_keys__(self, inPointHierarchy, outPointHierarchy, inPointLevel, outPointLevel, convRadius,
-                             KDEWindow, relativeRadius, usePDF, maxNeighbors=0):
+                             KDEWindow, relativeRadius, usePDF, maxNeighbors=0, sampleSeed=None):
         # MCConvBuilder.py:203-238 (the strings depend on names and numbers only: memoised -- six str() of floats per call)
         # maxNeighbors > 0 (extension): a capped list and its PDFs are other cache entries than the uncapped ones and those
-        # of another cap; the grid is the same. Without a cap the strings are the reference's.
+        # of another cap; the grid is the same. Without a cap the strings are the reference's. sampleSeed (with a cap): the
+        # draw is part of the neighbour and PDF keys, after the cap.
         memo = self.__dict__.setdefault("_keyMemo", {})
         k = (inPointHierarchy.hierarchyName_, outPointHierarchy.hierarchyName_, inPointLevel, outPointLevel, convRadius, KDEWindow,
-             relativeRadius, usePDF, maxNeighbors)
+             relativeRadius, usePDF, maxNeighbors, sampleSeed)
         try:
             hit = memo.get(k)
         except TypeError:   # (an unhashable argument: a tensor radius)
@@ -460,6 +495,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if maxNeighbors > 0:
             keyNeighs += '|' + str(maxNeighbors)
             keyPDF += '|' + str(maxNeighbors)
+            if sampleSeed is not None:
+                keyNeighs += '|s' + str(sampleSeed)
+                keyPDF += '|s' + str(sampleSeed)
         if k is not None and len(memo) < 4096:
             memo[k] = (keyGrid, keyNeighs, keyPDF)
         return keyGrid, keyNeighs, keyPDF
@@ -535,7 +573,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self.prefetchTransposed_ = {}
 
     def prefetch_geometry(self, inPointHierarchy, inPointLevel, convRadius, outPointHierarchy=None, outPointLevel=None,
-                          KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False, maxNeighbors=None):
+                          KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False, maxNeighbors=None,
+                          sampleSeed=None):
         """Extension (no counterpart in the reference): computes the grid, the neighbour list and the PDFs that
         create_convolution() with the same arguments looks up in the caches -- for the NEXT batch, on a side stream, and
         parks them until the next reset(). Geometry depends on the points only, not on the network, so in a training
@@ -555,12 +594,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         their feature gradient is then gathered through it instead of scattered with float atomics (bit-reproducible).
 
         maxNeighbors: the cap of the create_convolution() call this prepares (None = the builder's default). A capped
-        geometry is prefetched op by op on the side stream, never by the native executor."""
+        geometry is prefetched op by op on the side stream, never by the native executor.
+        sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call)."""
         currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
             inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
+        currSeed = self.__layer_seed__(currCap, sampleSeed)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
-                                                               currKDEWindow, currRelativeRadius, currUsePDF, currCap)
+                                                               currKDEWindow, currRelativeRadius, currUsePDF, currCap, currSeed)
         pts, bids = inPointHierarchy.points_[inPointLevel], inPointHierarchy.batchIds_[inPointLevel]
         mn, mx, B = inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, inPointHierarchy.batchSize_
         if not pts.is_cuda:
@@ -599,14 +640,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             bg_prev = bg.mccnn_background_launches(1)
         try:
             self.__prefetch_on_side__(side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap)
+                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap, currSeed)
         finally:
             if bg is not None:
                 bg.mccnn_background_launches(bg_prev)
 
     def __prefetch_on_side__(self, side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap=0):
-        capArgs = {"maxNeighbors": currCap} if currCap > 0 else {}   # (a checker behind `ops=` need not know the keyword)
+                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap=0, currSeed=None):
+        capArgs = self.__search_args__(currCap, currSeed, keyNeighs)
         with torch.cuda.stream(side):
             if keyGrid not in grids and self.fuseSort_ and self.hipSurface_ and not pts.requires_grad:
                 _hip_ops = _hip_ops_mod()
@@ -925,12 +966,15 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     # ------------------------------------------------------------------ create_convolution
     def create_convolution(self, convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                            outPointHierarchy=None, outPointLevel=None, multiFeatureConv=None, outNumFeatures=None,
-                           KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None, maxNeighbors=None):
+                           KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None, maxNeighbors=None,
+                           sampleSeed=None):
         # defaults: MCConvBuilder.py:299-325
         # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
         # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
-        # like one whose points require a gradient.
+        # like one whose points require a gradient. sampleSeed (extension; None = the builder's sampleSeed_): the capped
+        # search draws a stratified sample of the over-full rows; a seed of the layer's own needs a cap.
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
+        currSeed = self.__layer_seed__(currCap, sampleSeed)
         currMultiFeatureConv = self.multiFeatureConvs_ if multiFeatureConv is None else multiFeatureConv
         currNumOutFeatures = inNumFeatures if outNumFeatures is None else outNumFeatures
         currUseAVG = self.useAVG_ if useAVG is None else useAVG
@@ -945,7 +989,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(
             inPointHierarchy, currOutPointHierarchy, inPointLevel, currOutPointLevel, convRadius, currKDEWindow,
-            currRelativeRadius, currUsePDF, currCap)
+            currRelativeRadius, currUsePDF, currCap, currSeed)
         _log("Convolution: %s (KDE: %s | MF: %s | Rel: %s | PDF: %s)" % (convName, currKDEWindow,
                                                                        currMultiFeatureConv, currRelativeRadius,
                                                                        currUsePDF))
@@ -1019,7 +1063,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             startIndexs, packedNeighs = self.ops_.find_neighbors(
                 currOutPointHierarchy.points_[currOutPointLevel], currOutPointHierarchy.batchIds_[currOutPointLevel],
                 currGridTuple[0], currGridTuple[2], inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, convRadius,
-                inPointHierarchy.batchSize_, currRelativeRadius, **({"maxNeighbors": currCap} if currCap > 0 else {}))
+                inPointHierarchy.batchSize_, currRelativeRadius, **self.__search_args__(currCap, currSeed, keyNeighs))
             currNeighTuple = (startIndexs, packedNeighs)
             self.cacheNeighs_[keyNeighs] = currNeighTuple
             self._trace("find_neighbors", keyNeighs)

@@ -772,17 +772,25 @@ def transform_indexs(inIndexs, inNewPositions):
     return out
 
 
-def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv, maxNeighbors=0):
+def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv, maxNeighbors=0,
+                   sampleSeed=None):
     """FindNeighbors (MCConvModuleSrc:51, find_neighbors.cc:80-185) -> (startIndexs [M,1], packedNeighs [E,2]).
     Reads E back to the host to size the second output, like the reference (find_neighbors.cu:307-309).
     maxNeighbors (extension): K > 0 caps the neighbours per centre -- a row of k > K hits keeps the K hits at the canonical
     ranks floor(t * k / K), t = 0 .. K-1, a stride over the whole row; shorter rows are unchanged. The capped list is a
-    subsequence of the uncapped one and the same bytes in every run. 0 = no cap (the reference's list)."""
+    subsequence of the uncapped one and the same bytes in every run. 0 = no cap (the reference's list).
+    sampleSeed (extension, needs a cap): an integer in [0, 2^32) draws a stratified sample instead -- slot t of a row of
+    k > K hits holds the hit at rank floor(t * k / K) + off_t, off_t hashed from (seed, centre index, t) inside stratum t
+    (neighbors.hip: sample_slot). Same startIndexs, still a subsequence in canonical order, the same bytes for the same
+    (inputs, K, seed); None = the canonical ranks above."""
     op = "FindNeighborsOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
     _req(isinstance(maxNeighbors, int) and not isinstance(maxNeighbors, bool) and 0 <= maxNeighbors < 2 ** 31,
          op + " expects maxNeighbors to be an integer >= 0 (0 = no cap)")
+    _req(sampleSeed is None or (isinstance(sampleSeed, int) and not isinstance(sampleSeed, bool) and 0 <= sampleSeed < 2 ** 32),
+         op + " expects sampleSeed to be None or an integer in [0, 2^32)")
+    _req(sampleSeed is None or maxNeighbors > 0, op + " expects a cap (maxNeighbors > 0) with a sampleSeed")
     c, cb = _points_input(op, inPts.detach(), inBatchIds)
     p2 = _f32(inPts2.detach(), "points2")
     _check_points(p2, "points2", op)
@@ -797,11 +805,14 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     cap = int(maxNeighbors)
     if cap > 0:   # the capped passes: entries of their own, a workspace that also holds the true row lengths
         ws = _ws(lib.mccnn_find_neighbors_capped_workspace_bytes(m, n2), c.device)
-        tail = (cap,)
+        tail = ftail = (cap,)
         count_fn, fill_fn = lib.mccnn_find_neighbors_count_capped, lib.mccnn_find_neighbors_fill_capped
+        if sampleSeed is not None:   # the count pass does not depend on the seed: the capped one, then a fill of its own
+            ftail = (cap, int(sampleSeed))
+            fill_fn = lib.mccnn_find_neighbors_fill_sampled
     else:
         ws = _ws(lib.mccnn_find_neighbors_workspace_bytes(m, n2), c.device)
-        tail = ()
+        tail = ftail = ()
         count_fn, fill_fn = lib.mccnn_find_neighbors_count, lib.mccnn_find_neighbors_fill
     order = _order_hint(inPts, m)
     args = (ptr(c), ptr(cb), m, ptr(p2), n2, ptr(cells), ptr(mn), ptr(mx), batchSize, nc, float(radius),
@@ -820,7 +831,7 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     packed = None
     if guess > 0:
         buf = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
-        check(fill_fn(*args, ptr(start), guess, ptr(buf), ptr(ws), ws.numel(), stream_handle(), *tail), "find_neighbors(fill)")
+        check(fill_fn(*args, ptr(start), guess, ptr(buf), ptr(ws), ws.numel(), stream_handle(), *ftail), "find_neighbors(fill)")
         e = _await_mailbox(boxv)
         if e <= guess:
             packed = buf[:e]
@@ -828,7 +839,7 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
         e = _await_mailbox(boxv)
     if packed is None:
         packed = torch.empty((e, 2), dtype=torch.int32, device=c.device)
-        check(fill_fn(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle(), *tail), "find_neighbors(fill)")
+        check(fill_fn(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle(), *ftail), "find_neighbors(fill)")
     _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
     return start, packed
 

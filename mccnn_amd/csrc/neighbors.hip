@@ -1,6 +1,7 @@
 // Fixed-radius neighbour search over the 27-cell window and the per-edge kernel density
 // estimate. Replaces tf_ops/find_neighbors.cu and tf_ops/compute_pdf.cu.
 #include "batch.h"
+#include "neigh_sample.h"
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
@@ -91,8 +92,16 @@ __device__ __forceinline__ int cap_slot(int r, int k, int K) {
     const unsigned long long t = ((unsigned long long)r * (unsigned long long)K + (unsigned long long)k - 1ull) / (unsigned long long)k;
     return (t < (unsigned long long)K && (t * (unsigned long long)k) / (unsigned long long)K == (unsigned long long)r) ? (int)t : -1;
 }
+// SAMPLED (mccnn_find_neighbors_fill_sampled; a fill pass only, after the capped count pass): slot t keeps the hit at
+// offset off_t of stratum t instead of offset 0 -- sample_slot (neigh_sample.h), hashed from the seed, the centre's index and
+// t. The capped and the uncapped instantiations carry none of it.
+template <bool SAMPLED>
+__device__ __forceinline__ int kept_slot(int r, int k, int cap, unsigned rowh) {
+    if constexpr (SAMPLED) return sample_slot(r, k, cap, rowh);
+    else return cap_slot(r, k, cap);
+}
 // (the kernel's body: workgroup `blk` of `nblk` -- the single launch, and one geometry's share of a batch launch)
-template <int MODE, bool LEAN, bool CAPPED = false>
+template <int MODE, bool LEAN, bool CAPPED = false, bool SAMPLED = false>
 __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk, const float* __restrict__ centres, const int* __restrict__ cb, int m,
                                                     const float* __restrict__ pts, const int* __restrict__ cells,
                                                     const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
@@ -104,8 +113,10 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                                                     const int* __restrict__ scanCnt, int* __restrict__ startOut,
                                                     int* __restrict__ totalDev, int* __restrict__ totalHost,
                                                     const int capK = 0 /* CAPPED: hits kept per centre, > 0 (not `K`: the round lambdas below have a K of their own) */,
-                                                    int* __restrict__ kfull = nullptr /* CAPPED: [m] true row lengths, count -> fill */) {
+                                                    int* __restrict__ kfull = nullptr /* CAPPED: [m] true row lengths, count -> fill */,
+                                                    const unsigned sseed = 0 /* SAMPLED: the seed of the draw */) {
     constexpr bool FILL = MODE == 1;
+    static_assert(!SAMPLED || (CAPPED && FILL), "the sample is a form of the capped fill pass");
     // the status words of the prefix sum that follows the count pass (scan.hip): cleared here, no launch of their own
     if (!FILL && blk == 0)
         for (int k = threadIdx.x; k < numZero; k += blockDim.x) zeroWords[k] = 0ull;
@@ -217,6 +228,8 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                 unsigned long long mw[MCCNN_NW_ROUNDS];
 #pragma unroll
                 for (int r = 0; r < MCCNN_NW_ROUNDS; ++r) mw[r] = mrow[r];
+                unsigned rowh = 0;   // SAMPLED: the row's half of the hash (wave-uniform)
+                if constexpr (SAMPLED) rowh = sample_row_hash(sseed, cid);
                 // the hit lanes of a round come straight from the saved ballot (s_and_saveexec: no per-lane bit test); the
                 // capacity is checked per centre, per lane only for the one centre that straddles it
                 int hits = 0;
@@ -232,7 +245,7 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                         if (__builtin_amdgcn_inverse_ballot_w64(bm)) {
                             const int rank = run + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
                             if constexpr (CAPPED) {
-                                const int slot = hits > capK ? cap_slot(rank, hits, capK) : rank;   // (hits: the row's true length)
+                                const int slot = hits > capK ? kept_slot<SAMPLED>(rank, hits, capK, rowh) : rank;   // (hits: the row's true length)
                                 if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(jr[r], cid);
                             } else {
                                 const int pos = cbase + rank;
@@ -329,6 +342,8 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                 if (FILL) cbase = __builtin_amdgcn_readlane(base, cl);
                 int ck = 0;   // CAPPED fill: the row's true length; ccount carries the canonical rank across segments
                 if constexpr (CAPPED && FILL) ck = __builtin_amdgcn_readlane(krow, cl);
+                unsigned rowh = 0;   // SAMPLED: the row's half of the hash (wave-uniform)
+                if constexpr (SAMPLED) rowh = sample_row_hash(sseed, cid);
                 // (Measured and withdrawn: this loop without bounds -- the last round padded with unreachable points -- unrolled
                 // over the four rounds of a segment, the ballots kept in lanes 0..3 and stored once per segment: the count pass
                 // alone 35 -> 26 us and a sequential step 0.740 -> 0.728 ms, but the PIPELINED step 0.640 -> 0.672 ms, whatever
@@ -345,7 +360,7 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                         if (FILL && hit) {
                             const int rank = ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
                             if constexpr (CAPPED) {
-                                const int slot = ck > capK ? cap_slot(rank, ck, capK) : rank;
+                                const int slot = ck > capK ? kept_slot<SAMPLED>(rank, ck, capK, rowh) : rank;
                                 if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(__float_as_int(p.w), cid);
                             } else {
                                 const int pos = cbase + rank;
@@ -385,7 +400,7 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                     if (FILL && hit) {
                         const int rank = ccount + __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0));
                         if constexpr (CAPPED) {
-                            const int slot = ck > capK ? cap_slot(rank, ck, capK) : rank;
+                            const int slot = ck > capK ? kept_slot<SAMPLED>(rank, ck, capK, rowh) : rank;
                             if (slot >= 0 && cbase + slot < capacity) out[cbase + slot] = make_int2(__float_as_int(p.w), cid);
                         } else {
                             const int pos = cbase + rank;
@@ -448,6 +463,24 @@ __global__ __launch_bounds__(256) void neigh_window_capped(const float* __restri
     neigh_window_body<MODE, LEAN, true>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv, order,
                                         cnt, masks, startIdx, packed, capacity, zeroWords, numZero, G, Tabs, scanCnt, startOut, totalDev,
                                         totalHost, K, kfull);
+}
+
+// The sampled fill pass (mccnn_find_neighbors_fill_sampled), after neigh_window_capped<0, .>: the capped fill's arguments
+// and the seed.
+template <bool LEAN>
+__global__ __launch_bounds__(256) void neigh_window_sampled(const float* __restrict__ centres, const int* __restrict__ cb, int m,
+                                                            const float* __restrict__ pts, const int* __restrict__ cells,
+                                                            const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
+                                                            float radius, int scaleInv, const int* __restrict__ order,
+                                                            const unsigned long long* __restrict__ masks,
+                                                            const int* __restrict__ startIdx, int* __restrict__ packed,
+                                                            int capacity, int G, float Tabs, const int* __restrict__ scanCnt,
+                                                            int* __restrict__ startOut, int* __restrict__ totalDev,
+                                                            int* __restrict__ totalHost, int capK, const int* __restrict__ kfull,
+                                                            unsigned seed) {
+    neigh_window_body<1, LEAN, true, true>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv,
+                                           order, nullptr, const_cast<unsigned long long*>(masks), startIdx, packed, capacity, nullptr, 0,
+                                           G, Tabs, scanCnt, startOut, totalDev, totalHost, capK, const_cast<int*>(kfull), seed);
 }
 
 // One launch for the count (or the fill) pass of a BATCH of searches (mccnn_geometry_build_batch): the plain loop of the
@@ -1032,7 +1065,7 @@ static int find_neighbors_fill_impl(const float* centres, const int* centre_batc
                               int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                               const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
                               mccnn_stream_t stream, int* scan_start_out, int* scan_total_dev, int* scan_total_host,
-                              int max_neighbors = 0) {
+                              int max_neighbors = 0, bool sampled = false, unsigned seed = 0) {
     if (m < 0 || n < 0 || e < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || max_neighbors < 0) return MCCNN_E_BADARG;
     const bool capped = max_neighbors > 0;
     const bool scan = scan_start_out != nullptr;   // the counts of a skip_scan count pass are still in `ws`: scanned here
@@ -1051,7 +1084,18 @@ static int find_neighbors_fill_impl(const float* centres, const int* centre_batc
     size_t dyn = neigh_lds_pad();
     if (scan && dyn < (size_t)m * sizeof(int)) dyn = (size_t)m * sizeof(int);
     const int* scanCnt = scan ? w.cnt : nullptr;
-    if (capped) {
+    if (sampled) {
+        if (neigh_lean())
+            neigh_window_sampled<true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, w.masks, start_idx, packed, e, G, Tabs, scanCnt, scan_start_out, scan_total_dev, scan_total_host,
+                max_neighbors, w.kfull, seed);
+        else
+            neigh_window_sampled<false><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
+                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
+                centre_order, w.masks, start_idx, packed, e, G, Tabs, scanCnt, scan_start_out, scan_total_dev, scan_total_host,
+                max_neighbors, w.kfull, seed);
+    } else if (capped) {
         if (neigh_lean())
             neigh_window_capped<1, true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
                 centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
@@ -1107,6 +1151,20 @@ int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_bat
     return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
                                     num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
                                     nullptr, nullptr, max_neighbors);
+}
+
+// The fill pass that draws a stratified sample of the capped rows (neigh_sample.h) instead of their canonical ranks: after
+// mccnn_find_neighbors_count_capped with the same max_neighbors, over the same workspace. The count pass, start_idx and
+// the total do not depend on the seed.
+int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
+                                      int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
+                                      int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
+                                      const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
+                                      mccnn_stream_t stream, int max_neighbors, unsigned seed) {
+    if (max_neighbors <= 0) return MCCNN_E_BADARG;
+    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
+                                    num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
+                                    nullptr, nullptr, max_neighbors, true, seed);
 }
 
 }  // extern "C"
