@@ -522,7 +522,8 @@ int mccnn_spatial_conv_bwd_rows(const float* sorted_pts, const void* sorted_feat
  * returns MCCNN_E_CAPACITY and the caller builds again with a larger buffer. grid_from: optional geometry over the same
  * points, boxes and cell count whose grid is shared instead of built again (keyGrid hit with another output level);
  * it has to outlive this one. use_pdf == 0: PDFs of 1 (MCConvBuilder.py:388-390). All input pointers are borrowed
- * until the geometry is destroyed or built again. */
+ * until the geometry is destroyed or built again. The *_capped entries further down build the same geometry over a
+ * capped (or sampled) neighbour list. */
 #define MCCNN_E_CAPACITY (-6)   /* neighbour list longer than the e_capacity a geometry was built with */
 typedef struct mccnn_geometry mccnn_geometry_t;
 mccnn_geometry_t* mccnn_geometry_create(void);
@@ -551,6 +552,28 @@ typedef struct mccnn_geometry_request {
     int* total_host;
 } mccnn_geometry_request;
 int mccnn_geometry_build_batch(const mccnn_geometry_request* requests, int count, mccnn_stream_t stream);
+
+/* The same geometries over a CAPPED neighbour list (extension; mccnn_find_neighbors_count_capped / _fill_capped /
+ * _fill_sampled in the geometry's chain): at most max_neighbors rows per centre, the canonical ranks floor(t k / K) of an
+ * over-full row or, with sampled != 0, the stratified sample of `seed`. max_neighbors == 0: no cap (the entries above are
+ * these with no cap); sampled != 0 with max_neighbors == 0: MCCNN_E_BADARG. A capped list has at most m * max_neighbors
+ * rows: an e_capacity of that size never overflows. The buffer of a capped geometry is sized by
+ * mccnn_geometry_bytes_capped (the capped search keeps m more words: mccnn_find_neighbors_capped_workspace_bytes); with
+ * max_neighbors == 0 it equals mccnn_geometry_bytes. Lists of <= 4096 centres run count -> fill (the fill pass scans the
+ * capped counts itself), larger ones count -> scan -> fill, as without a cap; the bytes are those of the op-level capped
+ * calls. A geometry that shares a grid (grid_from) may be capped or not independently of the grid's owner.
+ * mccnn_geometry_build_batch_capped: caps[k] belongs to requests[k]; caps == NULL: no request is capped. The count and the
+ * fill pass go out once per KIND present in a chunk (uncapped, capped, sampled -- a sampled item's count pass is the
+ * capped one); a batch without a capped request issues the launches of mccnn_geometry_build_batch. */
+typedef struct mccnn_neighbor_cap { int max_neighbors; int sampled; unsigned seed; } mccnn_neighbor_cap;
+size_t mccnn_geometry_bytes_capped(int n, int m, int batch_size, int num_cells, int e_capacity, int with_grid, int max_neighbors);
+int mccnn_geometry_build_capped(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                                const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max,
+                                int batch_size, int num_cells, float radius, int scale_inv, float window, int use_pdf,
+                                int e_capacity, const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes,
+                                int* total_host, mccnn_stream_t stream, const mccnn_neighbor_cap* cap);
+int mccnn_geometry_build_batch_capped(const mccnn_geometry_request* requests, const mccnn_neighbor_cap* caps, int count,
+                                      mccnn_stream_t stream);
 /* E, or -1 while the count pass has not retired (wait_us: 0 = look once, < 0 = wait, > 0 = wait at most that long). */
 int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
 /* out[0..7]: device addresses of sortPts [n,3], sortBatchs [n], cellIndexs [B,nc,nc,nc,2], index_new_pos [n], its

@@ -340,15 +340,23 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0, sampleSeed=None):
+                 maxNeighbors=0, sampleSeed=None, capNative=False):
         """maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
-        maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path.
+        maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path unless capNative is set.
+        capNative (extension, default False): True sends capped layers through the native step executor like uncapped
+        ones -- one library call per geometry (mccnn_geometry_build_capped), learned prefetch and the batch form
+        included -- with the bytes of the op-by-op path, filed under the same capped cache keys. The attribute
+        capNative_ may be reassigned between steps (followed by reset()).
         sampleSeed (extension): None, or an integer in [0, 2^32) -- the capped layers then draw a stratified sample of
         their over-full rows (find_neighbors(sampleSeed=)) instead of the canonical ranks. The attribute sampleSeed_ may be
         reassigned between steps (typically to the step number, followed by reset()); layers without a cap ignore it."""
         super().__init__()
         self.maxNeighbors_ = self.__check_cap__(maxNeighbors)
         self.sampleSeed_ = self.__check_seed__(sampleSeed)
+        if not isinstance(capNative, bool):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("capNative must be True or False")
+        self.capNative_ = capNative
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
         # node (spatial_conv(sortIndex=)) -- fewer op calls and graph nodes per convolution, same kernels and results
@@ -531,7 +539,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             plan = []
             for key, ent in self.geoSeen_.items():
                 geo = self.cacheGeo_.get(key)
-                plan.append(ent + ((geo.have & 7) if geo is not None else 0, key))
+                # (a capped layer's entry carries its cap behind the seven geometry arguments -- not its seed)
+                plan.append(ent[:7] + ((geo.have & 7) if geo is not None else 0, key) + ent[7:])
             state["geoPlan_"], state["geoSeen_"] = plan, {}
         state["cacheGeo_"], state["cacheGeoGrid_"] = {}, {}
         if self.prefetchedGeo_:
@@ -594,7 +603,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         their feature gradient is then gathered through it instead of scattered with float atomics (bit-reproducible).
 
         maxNeighbors: the cap of the create_convolution() call this prepares (None = the builder's default). A capped
-        geometry is prefetched op by op on the side stream, never by the native executor.
+        geometry is prefetched op by op on the side stream, or -- with capNative_ -- by the native executor like an
+        uncapped one.
         sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call)."""
         currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
             inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
@@ -606,8 +616,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         mn, mx, B = inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, inPointHierarchy.batchSize_
         if not pts.is_cuda:
             return  # host tensors (a CPU checker behind `ops=`): nothing to overlap, create_convolution computes inline
-        if currCap == 0 and self.__prefetch_native__(inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow,
-                                                     currRelativeRadius, currUsePDF, keyGrid, keyNeighs, keyPDF, transposed):
+        if (currCap == 0 or self.capNative_) and self.__prefetch_native__(
+                inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow, currRelativeRadius, currUsePDF,
+                keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed):
             return
         if self.sideStream_ is None:
             self.sideStream_ = torch.cuda.Stream(device=pts.device)
@@ -662,7 +673,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 grids[keyGrid] = (sortPts, sortBatchs, cellIndexs, indexs)
             g = grids[keyGrid]
             deferred = None
-            if self.hipSurface_ and currCap == 0:  # the HIP op surface (not a checker handed in through `ops=`); no capped form
+            if self.hipSurface_ and currCap == 0:  # the HIP op surface (not a checker handed in through `ops=`); the deferred op has no capped form
                 _hip_ops = _hip_ops_mod()
                 deferred = _hip_ops.find_neighbors_pdf_deferred
             if keyNeighs not in neighs and keyPDF not in pdfs and currUsePDF and deferred is not None:
@@ -758,17 +769,21 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self.cacheGeoGrid_.pop(keyGrid, None)
             self.cacheGrids_.pop(keyGrid, None)
 
-    def __plan_entries__(self, ph):
+    def __plan_entries__(self, ph, sampleSeed=None):
         """The geometries the last step used over a hierarchy of `ph`'s name whose levels `ph` has: (entry, keyGrid,
-        keyNeighs, keyPDF) each, the keys computed for `ph`."""
+        keyNeighs, keyPDF, search keywords) each, the keys computed for `ph`. The plan knows the cap of a capped layer, not
+        its seed: sampleSeed is the layers' seed of the step the geometries are for (part of the capped keys)."""
         name, levels = ph.hierarchyName_, len(ph.points_)
         for ent in self.geoPlan_:
             if ent[0] != name or ent[1] >= levels or ent[2] >= levels:
                 continue
-            yield (ent,) + self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6])
+            cap = ent[9] if len(ent) > 9 else 0
+            seed = sampleSeed if cap > 0 else None
+            keys = self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6], cap, seed)
+            yield (ent,) + keys + (self.__search_args__(cap, seed, keys[1]),)
 
     def __prefetch_native__(self, inPH, inLevel, convRadius, outPH, outLevel, KDEWindow, relativeRadius, usePDF, keyGrid,
-                            keyNeighs, keyPDF, transposed, fork=True, pieces=0):
+                            keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None):
         """prefetch_geometry() on the native step executor: the geometry is ONE buffer, allocated on the CALLER's stream and
         written on a side stream that starts behind everything the caller's stream holds at this moment; the layers that
         use it order their stream behind its event. No reference counting decides anything: the buffer goes back to the
@@ -796,7 +811,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         k = len(self.prefetchedGeo_)
         geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                      usePDF, owner, side=k, fork=fork, background=True,
-                                     after=(inPH.prefetchFuture_ if inPH is outPH else None))
+                                     after=(inPH.prefetchFuture_ if inPH is outPH else None),
+                                     **self.__search_args__(currCap, currSeed, keyNeighs))
         if owner is None:
             owners[keyGrid] = geo
         if pieces:   # row plans / transposed list the layers of the last step used: attached and issued by a helper thread
@@ -804,7 +820,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.prefetchedGeo_[keyPDF] = (geo, keyGrid, keyNeighs, usePDF, want)
         return True
 
-    def prefetch_step(self, pointHierarchy):
+    def prefetch_step(self, pointHierarchy, sampleSeed=None):
         """Extension: everything the LAST step built over a hierarchy of this name -- every grid, neighbour list and PDF, and
         the row plans / transposed lists its layers used -- started now for `pointHierarchy`, the NEXT batch's hierarchy, on
         side streams under the current batch's convolutions; parked until the next reset(). The learned form of
@@ -812,19 +828,27 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         next batch's hierarchy at hand (PointHierarchy.prefetch two batches ahead) calls this right after reset(); the
         step after it then finds its geometry built and runs its convolutions back to back. Returns the number of
         geometries started (0 on the first steps, while there is nothing to replay, and wherever the native path does
-        not apply: nothing is lost, the next step builds what it needs itself)."""
+        not apply: nothing is lost, the next step builds what it needs itself).
+        sampleSeed: the seed the NEXT step's capped layers will run with (capNative_; None = the current sampleSeed_) -- the
+        geometries are filed under that seed's keys, so `cb.prefetch_step(ph_next, sampleSeed=step + 1)` followed by
+        `cb.sampleSeed_ = step + 1; cb.reset()` finds them. One prefetched with another seed is never asked for and is
+        dropped at the reset() after."""
         started = 0
+        seed = self.__check_seed__(self.sampleSeed_ if sampleSeed is None else sampleSeed)
         pieces = _env.debug("plan_prefetch", True)
         _native = _native_mod()
         _native.begin_batch()   # the step's geometries go out together: one launch per kernel kind over all of them
         try:
-            for ent, keyGrid, keyNeighs, keyPDF in self.__plan_entries__(pointHierarchy):
+            for ent, keyGrid, keyNeighs, keyPDF, capArgs in self.__plan_entries__(pointHierarchy, seed):
                 _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
                 if keyPDF in self.prefetchedGeo_:
                     continue
+                if capArgs and not self.capNative_:
+                    continue
                 if self.__prefetch_native__(pointHierarchy, inLevel, radius, pointHierarchy, outLevel, window, rel, usePDF,
                                             keyGrid, keyNeighs, keyPDF, False, fork=(started == 0),
-                                            pieces=(have if pieces else 0)):
+                                            pieces=(have if pieces else 0), currCap=(ent[9] if len(ent) > 9 else 0),
+                                            currSeed=(seed if len(ent) > 9 else None)):
                     started += 1
         finally:
             _native.end_batch()
@@ -854,9 +878,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         mn, mx, B = ph.aabbMin_, ph.aabbMax_, ph.batchSize_
         k = 0
         pieces = _env.debug("plan_prefetch", True)
-        for ent, keyGrid, keyNeighs, keyPDF in self.__plan_entries__(ph):
+        for ent, keyGrid, keyNeighs, keyPDF, capArgs in self.__plan_entries__(ph, self.__check_seed__(self.sampleSeed_)):
             _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
             if keyPDF in self.cacheGeo_:
+                continue
+            if capArgs and not self.capNative_:
                 continue
             inputs = self.__native_inputs__(ph, inLevel, ph, outLevel)
             if inputs is None:
@@ -865,7 +891,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             nc = _hip_ops._num_cells(mn, mx, B, radius, rel)
             owner = self.cacheGeoGrid_.get(keyGrid)
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, radius, rel, window, usePDF, owner,
-                                         side=k, fork=(k == 0), after=ph.prefetchFuture_)
+                                         side=k, fork=(k == 0), after=ph.prefetchFuture_, **capArgs)
             k += 1
             if have and pieces and geo.e_cap <= _PLAN_PREFETCH_MAX_E:
                 geo.prebuild_async(have, self.useAVG_)
@@ -873,11 +899,12 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __native_convolution__(self, convName, inPH, inLevel, inFeatures, inNumFeatures, convRadius, outPH, outLevel,
                                multiFeatureConv, numOutFeatures, KDEWindow, relativeRadius, usePDF, useAVG, keyGrid,
-                               keyNeighs, keyPDF):
+                               keyNeighs, keyPDF, currCap=0, currSeed=None):
         """create_convolution on the native step executor (mccnn_amd.native): the geometry of (keyGrid, keyNeighs, keyPDF)
         is ONE library call (no host wait), the layer one call per direction with the feature sort inside. Returns None
         when this call has to take the op-by-op path: a cache entry of that path exists already (prefetch_geometry), the
-        level is empty, or the features are not rows the library reads in place."""
+        level is empty, or the features are not rows the library reads in place. currCap / currSeed (capNative_): the
+        layer's cap and seed -- the geometry's search is the capped one, with the seed the op would get (__search_args__)."""
         _native = _native_mod()
         _hip_ops = _hip_ops_mod()
         # (a step with a handful of geometries gains nothing: the hops between the streams cost what the overlap saves --
@@ -925,14 +952,15 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                     self.__unfile_geometry__(owner, keyGrid)
                     owner = None
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
-                                         usePDF, owner)
+                                         usePDF, owner, **self.__search_args__(currCap, currSeed, keyNeighs))
             if owner is not None:   # (a shared grid: the layer sorts its rows only, as on a cache hit)
                 self._trace("sort_features", keyGrid)
             self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True)
         else:
             self._trace("sort_features", keyGrid)
         if inPH is outPH and keyPDF not in self.geoSeen_:
-            self.geoSeen_[keyPDF] = (inPH.hierarchyName_, inLevel, outLevel, convRadius, KDEWindow, relativeRadius, usePDF)
+            self.geoSeen_[keyPDF] = (inPH.hierarchyName_, inLevel, outLevel, convRadius, KDEWindow, relativeRadius, usePDF) + \
+                ((currCap,) if currCap > 0 else ())
         feats = inFeatures
         if _GEO_TRACE and feats.dim() == 2 and feats.shape[0] != geo.n:
             print("native conv %s: %d feature rows for a geometry over %d points (key %s, unverified %s, built from %s, level has %s)" % (
@@ -971,7 +999,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # defaults: MCConvBuilder.py:299-325
         # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
         # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
-        # like one whose points require a gradient. sampleSeed (extension; None = the builder's sampleSeed_): the capped
+        # like one whose points require a gradient, unless the builder was made with capNative=True (capNative_): then it
+        # runs through the native executor like an uncapped one, with the same bytes. sampleSeed (extension; None = the builder's sampleSeed_): the capped
         # search draws a stratified sample of the over-full rows; a seed of the layer's own needs a cap.
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         currSeed = self.__layer_seed__(currCap, sampleSeed)
@@ -998,11 +1027,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # sorted inside the convolution (by the native executor's layer call, or by spatial_conv(sortIndex=) below)
         inPts = inPointHierarchy.points_[inPointLevel]
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
-        if self.native_ and fused and currCap == 0:
+        if self.native_ and fused and (currCap == 0 or self.capNative_):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
-                                              keyGrid, keyNeighs, keyPDF)
+                                              keyGrid, keyNeighs, keyPDF, currCap, currSeed)
             if out is not None:
                 return out
 
@@ -1043,6 +1072,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self._trace("sort_points_step2", keyGrid)
 
         # neighbours (MCConvBuilder.py:366-376)
+        # (uncapped lists only: the deferred op has no capped form -- a capped layer that did not take the native executor
+        # above runs find_neighbors + compute_pdf)
         if fused and currCap == 0 and currUsePDF and keyNeighs not in self.cacheNeighs_ and keyPDF not in self.cachePDFs_:
             # search + KDE enqueued back to back (list sizes from the last total of this shape), ONE wait for the edge
             # count at the end instead of a wait between the two ops; None on the first call of a shape

@@ -176,12 +176,18 @@ _EDGE_GUESS = {}  # (device, M, N, radius, B, scaleInv) -> capacity to try first
 _EDGE_RATIO = {}
 
 
+def _ratio_key(gkey):
+    """Key of the edges-per-centre table for a guess key (device, n, m, radius, B, scaleInv[, cap]): device, radius,
+    scaleInv, and whatever follows them (mccnn_amd.native appends the cap of a capped search)."""
+    return (gkey[0], gkey[3], gkey[5]) + tuple(gkey[6:])
+
+
 def _edge_guess(guesses, ratios, gkey, m, first=0):
     """Capacity to try first for a search of `m` centres (the op path's tables above, or mccnn_amd.native's own pair).
     first: what the first search of a radius gets -- 0 = no guess, the caller waits for the count."""
     g = guesses.get(gkey, 0)
     if g <= 0:
-        ratio = ratios.get((gkey[0], gkey[3], gkey[5]), 0.0)
+        ratio = ratios.get(_ratio_key(gkey), 0.0)
         g = int(ratio * m * 1.25) + 1024 if ratio > 0.0 else first  # sizes differ: more head room than for a repeated shape
     return g
 
@@ -191,7 +197,7 @@ def _remember_edges(guesses, ratios, gkey, m, e):
         guesses.clear()
     guesses[gkey] = e + e // 16 + 64  # a little head room: totals of a shape vary slightly from batch to batch
     if m > 0:
-        ratios[(gkey[0], gkey[3], gkey[5])] = e / float(m)
+        ratios[_ratio_key(gkey)] = e / float(m)
 
 
 _TLS = threading.local()

@@ -23,6 +23,11 @@ struct NeighItem {
     float radius, Tabs;
 };
 struct NeighBatch { NeighItem it[MCCNN_BATCH_MAX]; };
+// the cap of a search (mccnn_geometry_build_batch_capped): beside NeighBatch, item k of one belongs to item k of the other.
+// capK == 0: no cap; sampled: the fill pass draws the stratified sample of `seed` (neigh_sample.h)
+struct NeighCapItem { int* kfull; int capK; unsigned seed; int sampled; };
+struct NeighCapBatch { NeighCapItem it[MCCNN_BATCH_MAX]; };
+static_assert(sizeof(NeighBatch) + sizeof(NeighCapBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched search: < 4 KB");
 
 // one kernel-density estimate
 struct PdfItem {
@@ -101,8 +106,10 @@ bool neigh_batch_eligible(int m, int n);
 int neigh_batch_item(NeighItem& it, ScanItem& sc, const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
                      int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                      float radius, int scale_inv, const int* order, int* start_idx, int e_capacity, int* packed, int* total_dev,
-                     int* total_host, void* ws, size_t ws_bytes);
-int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s);        // 0 count, 1 fill
+                     int* total_host, void* ws, size_t ws_bytes, NeighCapItem* cap = nullptr, int max_neighbors = 0, int sampled = 0,
+                     unsigned seed = 0);
+// caps == nullptr (or no capped item among them): the uncapped launch alone
+int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s, const NeighCapBatch* caps = nullptr);   // 0 count, 1 fill
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,
                     float radius, int scale_inv, float* pdfs);

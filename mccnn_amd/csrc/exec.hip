@@ -3,6 +3,8 @@
 //   * mccnn_geometry_build : sort_points_step1/2 of the input level, find_neighbors (count, scan, fill into a buffer sized by
 //     the caller's guess) and compute_pdf, enqueued back to back into ONE caller-provided device buffer, without a host
 //     wait -- the geometry one (level, radius, output level) cache entry of the builder stands for (:349-391);
+//     mccnn_geometry_build_capped / _build_batch_capped: the same with a cap on the neighbours per centre (and, optionally,
+//     the seed of a stratified sample) handed to the search -- the capped passes of find_neighbors in the same chain;
 //   * mccnn_conv_forward / mccnn_conv_backward : the convolution of one layer over a geometry, INCLUDING the feature sort
 //     (sort_features / its gradient, MCConvModuleSrc:35-45), the choice of the kernel family (row-per-lane depth-wise,
 //     factored Fin = 1, edge streaming) and the row plans / transposed list a family needs, built on first use and kept
@@ -44,7 +46,8 @@ bool transpose_small(int e, int n);
 int find_neighbors_chain(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts, int n,
                          const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                          float radius, int scale_inv, const int* centre_order, int* start_idx, int e_capacity, int* packed,
-                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream);
+                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream, int max_neighbors,
+                         bool sampled, unsigned seed);
 }
 
 using namespace mccnn;
@@ -75,6 +78,8 @@ struct mccnn_geometry {
     const float* mx = nullptr;
     int n = 0, m = 0, B = 0, nc = 0, scale_inv = 0, use_pdf = 1, same_level = 0;
     float radius = 0.f, window = 0.f;
+    int cap_k = 0, cap_sampled = 0;  // the search's cap (0 = none) and whether it draws the sample of cap_seed
+    unsigned cap_seed = 0;
     // the geometry buffer
     char* buf = nullptr;
     size_t bytes = 0;
@@ -112,7 +117,7 @@ size_t cells_of(int B, int nc) { return (size_t)B * nc * nc * nc; }
 constexpr int MCCNN_ORDER_MIN_M = 16384;  // foreign centres get a visiting order of their own from this many on
 
 // byte offsets of the pieces of a geometry buffer; total_bytes == 0: the grid does not fit 32-bit keys
-GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid) {
+GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int max_neighbors = 0) {
     GeoLayout L;
     memset(&L, 0, sizeof(L));
     const size_t n1 = n > 0 ? n : 1, m1 = m > 0 ? m : 1, e1 = e_cap > 0 ? e_cap : 1;
@@ -147,6 +152,8 @@ GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid) {
     if (mccnn_sort_step1_workspace_bytes(m, B, nc) == 0) return L;   // (32-bit keys)
     const size_t p = mccnn_compute_pdf_workspace_bytes(e_cap, 1);
     if (p > w) w = p;
+    // (the capped search keeps m more words behind whatever stage sets the size: mccnn_find_neighbors_capped_workspace_bytes)
+    if (max_neighbors > 0) w = al(w) + (mccnn_find_neighbors_capped_workspace_bytes(m, n) - mccnn_find_neighbors_workspace_bytes(m, n));
     L.ws = o;
     L.ws_bytes = al(w) + 256;
     o += L.ws_bytes;
@@ -308,6 +315,12 @@ size_t mccnn_geometry_bytes(int n, int m, int batch_size, int num_cells, int e_c
     return geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid != 0).total_bytes;
 }
 
+size_t mccnn_geometry_bytes_capped(int n, int m, int batch_size, int num_cells, int e_capacity, int with_grid, int max_neighbors) {
+    if (n < 0 || m < 0 || batch_size <= 0 || num_cells <= 0 || e_capacity < 0 || max_neighbors < 0) return 0;
+    if (cells_of(batch_size, num_cells) > 0x7fffffffULL) return 0;
+    return geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid != 0, max_neighbors).total_bytes;
+}
+
 }  // extern "C"
 namespace {
 // Argument checks + the struct of a geometry over the caller's buffer (nothing is launched). `in_batch`: the grid owner may
@@ -315,22 +328,25 @@ namespace {
 int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                    const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                    float radius, int scale_inv, float window, int use_pdf, int e_capacity, const mccnn_geometry_t* grid_from,
-                   void* buffer, size_t buffer_bytes, int* total_host, bool in_batch) {
+                   void* buffer, size_t buffer_bytes, int* total_host, bool in_batch, const mccnn_neighbor_cap* cap) {
     if (!g || !pts || !batch_ids || !centres || !centre_batch_ids || !aabb_min || !aabb_max || !buffer || !total_host)
         return MCCNN_E_BADARG;
     if (n <= 0 || m <= 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.f) || e_capacity <= 0) return MCCNN_E_BADARG;
     if (use_pdf && !(window > 0.f)) return MCCNN_E_BADARG;
+    if (cap && (cap->max_neighbors < 0 || (cap->sampled && cap->max_neighbors == 0))) return MCCNN_E_BADARG;
+    const int cap_k = cap ? cap->max_neighbors : 0;
     if (grid_from && (grid_from->n != n || grid_from->nc != num_cells || grid_from->B != batch_size ||
                       !(grid_owner(grid_from)->built || (in_batch && grid_owner(grid_from)->s_pts))))
         return MCCNN_E_BADARG;
     const bool with_grid = grid_from == nullptr;
-    const GeoLayout L = geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid);
+    const GeoLayout L = geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid, cap_k);
     if (L.total_bytes == 0) return MCCNN_E_TOOLARGE;
     if (buffer_bytes < L.total_bytes || (((uintptr_t)buffer) & 255)) return MCCNN_E_WORKSPACE;
     *g = mccnn_geometry();
     g->pts = pts; g->bids = batch_ids; g->centres = centres; g->cbids = centre_batch_ids; g->mn = aabb_min; g->mx = aabb_max;
     g->n = n; g->m = m; g->B = batch_size; g->nc = num_cells; g->scale_inv = scale_inv ? 1 : 0; g->use_pdf = use_pdf ? 1 : 0;
     g->radius = radius; g->window = window;
+    g->cap_k = cap_k; g->cap_sampled = (cap && cap_k > 0 && cap->sampled) ? 1 : 0; g->cap_seed = g->cap_sampled ? cap->seed : 0u;
     g->same_level = (centres == pts && m == n) ? 1 : 0;
     g->buf = (char*)buffer; g->bytes = buffer_bytes;
     char* b = g->buf;
@@ -395,7 +411,7 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
     }
     rc = find_neighbors_chain(g->centres, g->cbids, m, go->s_pts, n, go->cells, g->mn, g->mx, batch_size, num_cells, g->radius,
                               g->scale_inv, order, g->start, g->e_cap, g->packed, g->total_dev, const_cast<int*>((volatile int*)g->total_host),
-                              g->ws, g->ws_bytes, stream);
+                              g->ws, g->ws_bytes, stream, g->cap_k, g->cap_sampled != 0, g->cap_seed);
     if (rc) return rc;
     if (g->use_pdf) {
         rc = mccnn_compute_pdf_dn(go->s_pts, go->s_bids, g->start, m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, batch_size,
@@ -417,6 +433,8 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     GridBatch gridB;
     ScanBatch scanG, scanN;
     NeighBatch neighB;
+    NeighCapBatch capB;
+    bool anyCap = false;
     PdfBatch pdfB;
     SpanBatch spans;
     spans.count = 0;
@@ -459,15 +477,18 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
         const int* order = g->same_level ? go->inv_idx : g->order;
         rc = neigh_batch_item(neighB.it[k], scanN.it[k], g->centres, g->cbids, g->m, go->s_pts, g->n, go->cells, g->mn, g->mx, g->B, g->nc,
                               g->radius, g->scale_inv, order, g->start, g->e_cap, g->packed, g->total_dev,
-                              const_cast<int*>((volatile int*)g->total_host), g->ws, g->ws_bytes);
+                              const_cast<int*>((volatile int*)g->total_host), g->ws, g->ws_bytes, &capB.it[k], g->cap_k, g->cap_sampled,
+                              g->cap_seed);
         if (rc) return rc;
+        anyCap = anyCap || g->cap_k > 0;
         if (g->use_pdf)
             pdf_batch_item(pdfB.it[nPdf++], go->s_pts, go->s_bids, g->start, g->m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, g->B,
                            g->window, g->radius, g->scale_inv, g->pdfs);
     }
-    if ((rc = launch_neigh_batch(neighB, count, 0, s))) return rc;
+    // (a chunk without a capped geometry: the uncapped launches alone; otherwise one launch per kind that is present)
+    if ((rc = launch_neigh_batch(neighB, count, 0, s, anyCap ? &capB : nullptr))) return rc;
     if ((rc = launch_scan_batch(scanN, count, s))) return rc;
-    if ((rc = launch_neigh_batch(neighB, count, 1, s))) return rc;
+    if ((rc = launch_neigh_batch(neighB, count, 1, s, anyCap ? &capB : nullptr))) return rc;
     if (nPdf && (rc = launch_pdf_batch(pdfB, nPdf, s))) return rc;
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];
@@ -482,26 +503,44 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
 }  // namespace
 extern "C" {
 
+// (the uncapped entries are the capped ones with no cap)
+int mccnn_geometry_build_capped(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                                const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
+                                int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
+                                const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
+                                mccnn_stream_t stream, const mccnn_neighbor_cap* cap) {
+    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
+                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false, cap);
+    if (rc) return rc;
+    return geometry_issue_single(g, stream);
+}
+
 int mccnn_geometry_build(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                          const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
                          int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
                          const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
                          mccnn_stream_t stream) {
-    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
-                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false);
-    if (rc) return rc;
-    return geometry_issue_single(g, stream);
+    return mccnn_geometry_build_capped(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells,
+                                       radius, scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host,
+                                       stream, nullptr);
 }
 
 // Several geometries of a step at once (a grid owner BEFORE the geometries that share its grid): one launch per kernel
 // kind over chunks of the requests; a geometry too large for the batch form (> 2 M cells or centres) takes its own chain.
 int mccnn_geometry_build_batch(const mccnn_geometry_request* req, int count, mccnn_stream_t stream) {
+    return mccnn_geometry_build_batch_capped(req, nullptr, count, stream);
+}
+
+// caps[k]: the cap of req[k] (caps == NULL: none is capped). A capped geometry may share the grid of an uncapped one and
+// the reverse: the cap belongs to the search alone.
+int mccnn_geometry_build_batch_capped(const mccnn_geometry_request* req, const mccnn_neighbor_cap* caps, int count,
+                                      mccnn_stream_t stream) {
     if (!req || count < 0) return MCCNN_E_BADARG;
     for (int k = 0; k < count; ++k) {
         const mccnn_geometry_request& r = req[k];
         int rc = geometry_setup(r.geometry, r.pts, r.batch_ids, r.n, r.centres, r.centre_batch_ids, r.m, r.aabb_min, r.aabb_max,
                                 r.batch_size, r.num_cells, r.radius, r.scale_inv, r.window, r.use_pdf, r.e_capacity, r.grid_from,
-                                r.buffer, r.buffer_bytes, r.total_host, true);
+                                r.buffer, r.buffer_bytes, r.total_host, true, caps ? &caps[k] : nullptr);
         if (rc) return rc;
     }
     mccnn_geometry_t* chunk[MCCNN_BATCH_MAX];

@@ -494,6 +494,28 @@ __global__ __launch_bounds__(256) void neigh_window_batch(NeighBatch nbt, BatchB
                                    nullptr, nullptr);
 }
 
+// The capped and the sampled searches of a batch (mccnn_geometry_build_batch_capped): kernels of their own over the same body,
+// so that neigh_window_batch keeps its arguments and its code. The cap of item k travels beside it (NeighCapBatch).
+template <int MODE>
+__global__ __launch_bounds__(256) void neigh_window_batch_capped(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
+    int local, blocks;
+    const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
+    const NeighItem& g = nbt.it[k];
+    const NeighCapItem& c = caps.it[k];
+    neigh_window_body<MODE, false, true>(local, blocks, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv,
+                                         g.order, g.cnt, g.masks, g.startIdx, g.packed, g.capacity, g.zeroWords, g.numZero, g.G, g.Tabs,
+                                         nullptr, nullptr, nullptr, nullptr, c.capK, c.kfull);
+}
+__global__ __launch_bounds__(256) void neigh_window_batch_sampled(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
+    int local, blocks;
+    const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
+    const NeighItem& g = nbt.it[k];
+    const NeighCapItem& c = caps.it[k];
+    neigh_window_body<1, false, true, true>(local, blocks, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius,
+                                            g.scaleInv, g.order, nullptr, g.masks, g.startIdx, g.packed, g.capacity, nullptr, 0, g.G,
+                                            g.Tabs, nullptr, nullptr, nullptr, nullptr, c.capK, c.kfull, c.seed);
+}
+
 __global__ __launch_bounds__(256) void invert_perm_k(const int* __restrict__ newIdx, int n, int* __restrict__ inv) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) inv[newIdx[i]] = i;
@@ -1132,7 +1154,7 @@ int mccnn_find_neighbors_fill(const float* centres, const int* centre_batch_ids,
 
 // The capped search (max_neighbors = K > 0; 0 = the passes above): count -> scan -> fill at every list size, like the
 // uncapped pair. (The form whose prefix sum rides in the fill pass belongs to find_neighbors_chain, the native executor's
-// geometry build, which takes no cap.)
+// geometry build.)
 int mccnn_find_neighbors_count_capped(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
                                       int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
                                       int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
@@ -1171,18 +1193,23 @@ int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_ba
 namespace mccnn {
 // Both passes of a search back to back (the native executor's geometry chain). Lists of at most MCCNN_NW_SCAN_M centres:
 // count -> fill, the prefix sum of the counts rides in the fill pass (two launches); larger ones: count -> scan -> fill.
+// max_neighbors > 0: the capped passes over the capped workspace layout (the counts the fill pass scans are min(k, K));
+// sampled: the fill pass draws the stratified sample of `seed`.
 int find_neighbors_chain(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts, int n,
                          const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                          float radius, int scale_inv, const int* centre_order, int* start_idx, int e_capacity, int* packed,
-                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream, int max_neighbors,
+                         bool sampled, unsigned seed) {
+    if (max_neighbors < 0 || (sampled && max_neighbors == 0)) return MCCNN_E_BADARG;
     const bool small = m > 0 && m <= MCCNN_NW_SCAN_M && e_capacity > 0 && n > 0;
     int rc = find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
                                        num_cells, radius, scale_inv, centre_order, start_idx, total_dev, total_host, ws, ws_bytes,
-                                       stream, small);
+                                       stream, small, max_neighbors);
     if (rc) return rc;
     return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
                                     num_cells, radius, scale_inv, centre_order, start_idx, e_capacity, packed, ws, ws_bytes, stream,
-                                    small ? start_idx : nullptr, small ? total_dev : nullptr, small ? total_host : nullptr);
+                                    small ? start_idx : nullptr, small ? total_dev : nullptr, small ? total_host : nullptr,
+                                    max_neighbors, sampled, seed);
 }
 }  // namespace mccnn
 extern "C" {
@@ -1195,10 +1222,12 @@ bool neigh_batch_eligible(int m, int n) { return m > 0 && n > 0 && (long long)m 
 int neigh_batch_item(NeighItem& it, ScanItem& sc, const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
                      int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                      float radius, int scale_inv, const int* order, int* start_idx, int e_capacity, int* packed, int* total_dev,
-                     int* total_host, void* ws, size_t ws_bytes) {
+                     int* total_host, void* ws, size_t ws_bytes, NeighCapItem* cap, int max_neighbors, int sampled, unsigned seed) {
     if (!neigh_batch_eligible(m, n)) return MCCNN_E_TOOLARGE;
+    if (max_neighbors < 0 || (sampled && max_neighbors == 0) || (max_neighbors > 0 && !cap)) return MCCNN_E_BADARG;
     NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w)) return MCCNN_E_WORKSPACE;
+    if (!neigh_ws(ws, ws_bytes, m, n, w, max_neighbors > 0)) return MCCNN_E_WORKSPACE;
+    if (cap) *cap = NeighCapItem{w.kfull, max_neighbors, seed, sampled ? 1 : 0};
     const int tiles = ceil_div(m, 2048);
     const int G = m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1));   // (neigh_group of background launches)
     it = NeighItem{centres, centre_batch_ids, sorted_pts, cell_indexs, aabb_min, aabb_max, order, w.cnt, w.masks, start_idx, packed,
@@ -1207,16 +1236,59 @@ int neigh_batch_item(NeighItem& it, ScanItem& sc, const float* centres, const in
     sc = ScanItem{w.cnt, start_idx, reinterpret_cast<unsigned long long*>(w.scanws), total_dev, total_host, m, tiles};
     return 0;
 }
-int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s) {
-    BatchBlocks bb;
+// the workgroups of the first `count` items of a batch -> the grid size
+static int neigh_batch_blocks(const NeighBatch& nbt, int count, BatchBlocks& bb) {
     bb.count = count;
     int run = 0;
     for (int k = 0; k < count; ++k) { bb.first[k] = run; run += ceil_div(nbt.it[k].m, 4 * nbt.it[k].G); }
     for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
-    if (run == 0) return 0;
-    if (mode == 0) neigh_window_batch<0><<<run, 256, 24000, s>>>(nbt, bb);   // (the LDS pad of background launches: neigh_lds_pad)
-    else neigh_window_batch<1><<<run, 256, 24000, s>>>(nbt, bb);
-    MCCNN_LAUNCHED();
+    return run;
+}
+int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s, const NeighCapBatch* caps) {
+    bool any = false;
+    for (int k = 0; caps && k < count; ++k) any = any || caps->it[k].capK > 0;
+    if (!any) {
+        BatchBlocks bb;
+        const int run = neigh_batch_blocks(nbt, count, bb);
+        if (run == 0) return 0;
+        if (mode == 0) neigh_window_batch<0><<<run, 256, 24000, s>>>(nbt, bb);   // (the LDS pad of background launches: neigh_lds_pad)
+        else neigh_window_batch<1><<<run, 256, 24000, s>>>(nbt, bb);
+        MCCNN_LAUNCHED();
+        return 0;
+    }
+    // a chunk with capped items: the items of each kind -- 0 uncapped, 1 capped, 2 sampled (its count pass is the capped
+    // one) -- go out together, one launch per kind that is present
+    // (Items are independent searches over buffers of their own: their order inside a kind's launch does not matter. The
+    // copies below are ~2.5 KB of host memory per kind and pass.)
+    for (int kind = 0; kind < 3; ++kind) {
+        NeighBatch sub;
+        NeighCapBatch subc;
+        int cnt = 0;
+        for (int k = 0; k < count; ++k) {
+            const NeighCapItem& c = caps->it[k];
+            int kd = c.capK > 0 ? (c.sampled ? 2 : 1) : 0;
+            if (mode == 0 && kd == 2) kd = 1;
+            if (kd != kind) continue;
+            sub.it[cnt] = nbt.it[k];
+            subc.it[cnt] = c;
+            ++cnt;
+        }
+        if (cnt == 0) continue;
+        for (int k = cnt; k < MCCNN_BATCH_MAX; ++k) { sub.it[k] = sub.it[0]; subc.it[k] = subc.it[0]; }   // (never addressed: defined bytes)
+        BatchBlocks bb;
+        const int run = neigh_batch_blocks(sub, cnt, bb);
+        if (run == 0) continue;
+        if (kind == 0) {
+            if (mode == 0) neigh_window_batch<0><<<run, 256, 24000, s>>>(sub, bb);
+            else neigh_window_batch<1><<<run, 256, 24000, s>>>(sub, bb);
+        } else if (kind == 1) {
+            if (mode == 0) neigh_window_batch_capped<0><<<run, 256, 24000, s>>>(sub, subc, bb);
+            else neigh_window_batch_capped<1><<<run, 256, 24000, s>>>(sub, subc, bb);
+        } else {
+            neigh_window_batch_sampled<<<run, 256, 24000, s>>>(sub, subc, bb);
+        }
+        MCCNN_LAUNCHED();
+    }
     return 0;
 }
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,

@@ -544,6 +544,7 @@ bool hierarchy_owns(const std::shared_ptr<HierFuture>& f, const Tensor& t);
 struct BatchEntry {
     std::shared_ptr<Geo> g, grid_from;
     mccnn_geometry_request req;
+    mccnn_neighbor_cap cap;   // of the request's search (max_neighbors 0: none)
 };
 struct PieceEntry {   // row plans / transposed list of a batched geometry whose list is small: built as a batch as well
     std::shared_ptr<Geo> g;
@@ -606,7 +607,10 @@ void end_geometry_batch() {
     Issuer::get().push([entries, stream, background, dev] {
         enter_device(dev);
         std::vector<mccnn_geometry_request> reqs;
+        std::vector<mccnn_neighbor_cap> caps;
+        bool any_cap = false;
         reqs.reserve(entries->size());
+        caps.reserve(entries->size());
         for (BatchEntry& e : *entries) {
             // a grid owner outside this batch has to be issued; one inside it is set up by the same library call
             bool inside = false;
@@ -614,9 +618,11 @@ void end_geometry_batch() {
                 for (BatchEntry& o : *entries) inside = inside || (o.g.get() == e.grid_from.get());
             if (e.grid_from && !inside) e.grid_from->wait_issued_nothrow();
             reqs.push_back(e.req);
+            caps.push_back(e.cap);
+            any_cap = any_cap || e.cap.max_neighbors > 0;
         }
         const int prev = background ? mccnn_background_launches(1) : 0;
-        int rc = mccnn_geometry_build_batch(reqs.data(), (int)reqs.size(), (void*)stream);
+        int rc = mccnn_geometry_build_batch_capped(reqs.data(), any_cap ? caps.data() : nullptr, (int)reqs.size(), (void*)stream);
         if (background) mccnn_background_launches(prev);
         for (BatchEntry& e : *entries) {
             int r = rc;
@@ -693,7 +699,8 @@ void end_geometry_batch() {
 std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const Tensor& centres, const Tensor& cbids,
                                     const Tensor& mn, const Tensor& mx, int64_t B, int64_t nc, double radius, bool scale_inv,
                                     double window, bool use_pdf, int64_t capacity, std::shared_ptr<Geo> grid_from,
-                                    int64_t side, bool fork, bool background, std::shared_ptr<HierFuture> after) {
+                                    int64_t side, bool fork, bool background, std::shared_ptr<HierFuture> after,
+                                    int64_t max_neighbors, int64_t sample_seed /* < 0: none */) {
     check_dev(pts, at::kFloat, "points");
     check_dev(centres, at::kFloat, "sample points");
     check_dev(bids, at::kInt, "batch ids");
@@ -703,7 +710,11 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     const DevGuard device_guard((int)pts.device().index());
     const int n = (int)pts.size(0), m = (int)centres.size(0);
     if (grid_from && grid_from->grid_owner) grid_from = grid_from->grid_owner;
-    const size_t bytes = mccnn_geometry_bytes(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1);
+    TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= 0x7fffffffLL, "geometry: maxNeighbors must be >= 0");
+    TORCH_CHECK(sample_seed < 0 || (max_neighbors > 0 && sample_seed <= 0xffffffffLL), "geometry: sampleSeed needs a cap and lies in [0, 2^32)");
+    // the cap of the search (by value into the helper thread's job / the batch entry)
+    const mccnn_neighbor_cap cap{(int)max_neighbors, sample_seed >= 0 ? 1 : 0, sample_seed >= 0 ? (unsigned)sample_seed : 0u};
+    const size_t bytes = mccnn_geometry_bytes_capped(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors);
     TORCH_CHECK(bytes > 0, "geometry: batch_size * num_cells^3 does not fit 32-bit keys");
     auto g = std::make_shared<Geo>();
     g->h = mccnn_geometry_create();
@@ -807,18 +818,19 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
             e.grid_from = grid_from;
             e.req = mccnn_geometry_request{g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
                                            grid_from ? grid_from->h : nullptr, bufp, bytes, slotp};
+            e.cap = cap;
             t_geo_batch.entries.push_back(std::move(e));
             g->plan_side = asked_side;   // the pieces built ahead keep the spread over the side streams the builds gave up
             return g;
         }
-        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev] {
+        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev, cap] {
             enter_device(dev);
             if (grid_from) grid_from->wait_issued_nothrow();
             // background: these launches run beside kernels a step waits for (the convolutions of the current batch) --
             // the search kernels then hold back (mccnn_background_launches, thread-local: set on THIS thread)
             const int prev = background ? mccnn_background_launches(1) : 0;
-            int rc = mccnn_geometry_build(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
-                                          grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream);
+            int rc = mccnn_geometry_build_capped(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
+                                                 grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream, &cap);
             if (background) mccnn_background_launches(prev);
             if (rc == 0 && hipEventRecord(g->event, (hipStream_t)stream) != hipSuccess) rc = (int)hipErrorUnknown;
             g->build_rc = rc;
@@ -832,11 +844,11 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
         bool on; int prev;
         ~Restore() { if (on) mccnn_background_launches(prev); }
     } restore{background && g->side >= 0, prev_bg};
-    check(mccnn_geometry_build(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
-                               cbids.data_ptr<int>(), m, mn.data_ptr<float>(), mx.data_ptr<float>(), (int)B, (int)nc,
-                               (float)radius, scale_inv ? 1 : 0, (float)window, use_pdf ? 1 : 0, (int)capacity,
-                               grid_from ? grid_from->h : nullptr, g->buf.data_ptr(), bytes, g->slot.data_ptr<int>(),
-                               stream),
+    check(mccnn_geometry_build_capped(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
+                                      cbids.data_ptr<int>(), m, mn.data_ptr<float>(), mx.data_ptr<float>(), (int)B, (int)nc,
+                                      (float)radius, scale_inv ? 1 : 0, (float)window, use_pdf ? 1 : 0, (int)capacity,
+                                      grid_from ? grid_from->h : nullptr, g->buf.data_ptr(), bytes, g->slot.data_ptr<int>(),
+                                      stream, &cap),
           "geometry_build");
     if (g->side >= 0) {
         g->event = take_event();
@@ -1568,7 +1580,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("mn"), py::arg("mx"), py::arg("B"), py::arg("nc"), py::arg("radius"), py::arg("scale_inv"),
             py::arg("window"), py::arg("use_pdf"), py::arg("capacity"), py::arg("grid_from").none(true),
             py::arg("side") = -1, py::arg("fork") = false, py::arg("background") = false,
-            py::arg("after").none(true) = py::none(), py::call_guard<py::gil_scoped_release>());
+            py::arg("after").none(true) = py::none(), py::arg("max_neighbors") = 0, py::arg("sample_seed") = -1,
+            py::call_guard<py::gil_scoped_release>());
     mod.def("sampled_features", &sampled_features, py::call_guard<py::gil_scoped_release>());
     mod.def("begin_geometry_batch", &begin_geometry_batch);
     mod.def("end_geometry_batch", &end_geometry_batch, py::call_guard<py::gil_scoped_release>());

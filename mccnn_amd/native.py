@@ -54,8 +54,8 @@ E_CAPACITY = -6
 NEED_PLAN_FWD, NEED_PLAN_TR, NEED_TLIST, NEED_RECORDS = 1, 2, 4, 8
 
 _TLS = threading.local()
-_EDGE_GUESS = {}   # (device, n, m, radius, B, scaleInv) -> capacity to try first
-_EDGE_RATIO = {}   # (device, radius, scaleInv) -> edges per centre of the last search with this radius
+_EDGE_GUESS = {}   # (device, n, m, radius, B, scaleInv[, maxNeighbors]) -> capacity to try first
+_EDGE_RATIO = {}   # (device, radius, scaleInv[, maxNeighbors]) -> edges per centre of the last search with this radius
 
 
 def _slot():
@@ -131,6 +131,11 @@ def _remember(gkey, m, e):
     _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
 
 
+class _NeighborCap(C.Structure):
+    """mccnn_neighbor_cap (include/mccnn.h)"""
+    _fields_ = [("max_neighbors", C.c_int), ("sampled", C.c_int), ("seed", C.c_uint)]
+
+
 class Geometry:
     """One convolution geometry: the grid of the input level at the convolution radius, the neighbour list of the
     output level's points in it and its PDFs, in ONE device buffer (mccnn_geometry_t). Tensor views of its arrays are
@@ -148,6 +153,7 @@ class Geometry:
         self.e = -1
         self.gkey = None
         self.args = None
+        self.cap = (0, None)    # (maxNeighbors, sampleSeed) of the search
         self.uses = 0           # layers convolved over this geometry so far (the builder counts)
 
     def __del__(self):
@@ -182,8 +188,10 @@ class Geometry:
     def _rebuild(self, capacity):
         """The neighbour list was longer than the guess: exact repeat (first batch of a shape)."""
         inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF = self.args
+        if self.cap[0] > 0:   # (a capped list never holds more)
+            capacity = min(capacity, self.m * self.cap[0])
         _build_into(self, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity,
-                    self.grid_owner)
+                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1])
         e = self.core.edges(-1) if self.core is not None else _lib.load().mccnn_geometry_edges(self.handle, -1)
         if e < 0 or e > self.e_cap:
             raise _lib.MCCNNError("geometry: rebuilt list still does not fit (%d > %d)" % (e, self.e_cap))
@@ -252,13 +260,14 @@ class Geometry:
 
 
 def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity, grid_from,
-                side=-1, fork=False, background=False, after=None):
+                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None):
     n, m = inPts.shape[0], centres.shape[0]
+    g.cap = (int(maxNeighbors), None if sampleSeed is None else int(sampleSeed))   # (a rebuild repeats them: _rebuild)
     if _EXT is not None:
         uses = g.core.uses if g.core is not None else 0
         g.core = _EXT.build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, float(radius), bool(scaleInv), float(window),
                                      bool(usePDF), capacity, grid_from.core if grid_from is not None else None, side, fork,
-                                     background, after)
+                                     background, after, int(maxNeighbors), -1 if sampleSeed is None else int(sampleSeed))
         g.core.uses = uses
         g.buf = g.core.buf
         g.grid_owner = grid_from
@@ -268,7 +277,7 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     lib = _lib.load()
     dev = inPts.device
     with_grid = 0 if grid_from is not None else 1
-    nbytes = lib.mccnn_geometry_bytes(n, m, B, nc, capacity, with_grid)
+    nbytes = lib.mccnn_geometry_bytes_capped(n, m, B, nc, capacity, with_grid, int(maxNeighbors))
     if nbytes == 0:
         raise _lib.MCCNNError("geometry: batch_size * num_cells^3 does not fit 32-bit keys")
     if g.handle is None:
@@ -283,10 +292,11 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     g.grid_owner = grid_from
     g.n, g.m, g.nc, g.B, g.e_cap, g.e = n, m, nc, B, capacity, -1
     g.args = (inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF)
-    check(lib.mccnn_geometry_build(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B, nc,
-                                   float(radius), int(bool(scaleInv)), float(window), int(bool(usePDF)), capacity,
-                                   grid_from.handle if grid_from is not None else None, g.buf.data_ptr(), nbytes,
-                                   g.slot.data_ptr(), stream_handle()), "geometry_build")
+    cap = _NeighborCap(int(maxNeighbors), 0 if sampleSeed is None else 1, 0 if sampleSeed is None else int(sampleSeed))
+    check(lib.mccnn_geometry_build_capped(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B,
+                                          nc, float(radius), int(bool(scaleInv)), float(window), int(bool(usePDF)), capacity,
+                                          grid_from.handle if grid_from is not None else None, g.buf.data_ptr(), nbytes,
+                                          g.slot.data_ptr(), stream_handle(), C.addressof(cap)), "geometry_build")
 
 
 def begin_batch():
@@ -307,22 +317,36 @@ def side_streams_available():
 
 
 def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, grid_from=None,
-                   side=-1, fork=False, background=False, after=None):
+                   side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None):
     """Enqueues grid + search + KDE of one convolution geometry; no host wait. nc: cells per axis
     (MCConvModule._num_cells). grid_from: a Geometry over the same points / radius whose grid is shared. side >= 0
     (torch extension only): the build runs on side stream `side` -- behind everything the current stream holds at the
     first call that says fork=True -- and the first layer that uses the geometry orders its stream behind it.
     after: the future of the ADOPTED prefetched hierarchy that every input of this build belongs to; a side-stream build
-    then waits for that hierarchy only and takes its memory from its own stream's pool (torch_ext.cpp, Geo::own_pool)."""
+    then waits for that hierarchy only and takes its memory from its own stream's pool (torch_ext.cpp, Geo::own_pool).
+    maxNeighbors > 0: the search keeps at most that many neighbours per centre (find_neighbors(maxNeighbors=), the same
+    bytes); sampleSeed (needs a cap): the seed the capped search draws its stratified sample with, as the op takes it. The
+    list then holds at most m * maxNeighbors rows: a capacity of that size cannot overflow, and the guess an uncapped list
+    of the shape would get is used only where it is smaller."""
     n, m = inPts.shape[0], centres.shape[0]
+    maxNeighbors = int(maxNeighbors)
+    if maxNeighbors < 0 or (sampleSeed is not None and (maxNeighbors == 0 or not 0 <= int(sampleSeed) < 2 ** 32)):
+        raise ValueError("build_geometry: maxNeighbors >= 0; sampleSeed needs a cap and lies in [0, 2^32)")
     gkey = (inPts.device.index, n, m, float(radius), int(B), bool(scaleInv))
+    if maxNeighbors > 0:
+        # (capped totals never shrink the guess of an uncapped geometry of the shape, or the reverse: the cap is a seventh
+        # element of the key, which _edge_guess / _remember_edges carry into the key of the edges-per-centre table)
+        gkey = gkey + (maxNeighbors,)
     g = Geometry()
     g.gkey = gkey
     if grid_from is not None and grid_from.grid_owner is not None:
         grid_from = grid_from.grid_owner
+    capacity = _capacity_guess(gkey, m)
+    if maxNeighbors > 0:
+        capacity = max(1, min(m * maxNeighbors, capacity))
     _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF,
-                _capacity_guess(gkey, m), grid_from, side if _EXT is not None else -1, fork, background,
-                after if _EXT is not None else None)
+                capacity, grid_from, side if _EXT is not None else -1, fork, background,
+                after if _EXT is not None else None, maxNeighbors, sampleSeed)
     return g
 
 
