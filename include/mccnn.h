@@ -233,6 +233,30 @@ int mccnn_compute_pdf_dn(const float* sorted_pts, const int* sorted_batch_ids, c
                          const float* aabb_max, int batch_size, float window, float radius, int scale_inv,
                          float* pdfs, void* ws, size_t ws_bytes, mccnn_stream_t stream);
 
+/* The per-POINT kernel density estimate (extension, pdfMode = 'point'; pdf_points.hip). For every sorted point j of
+ * cloud b, over its own ball N(j) = { l of the same cloud : sqrt(d2) < R_b }, R_b = radius * maxExtent_b (scale_inv)
+ * or radius -- exactly the row find_neighbors gives with the sorted points as their own centres (the same f32
+ * predicate, d2 without FMA against the same threshold):
+ *   counts[j]  = |N(j)|
+ *   density[j] = sum over l in N(j) of prod_a (1/h) 0.39894228 exp(-0.5 ((p_l,a - p_j,a) / (R_b h))^2),  h = window
+ * (single precision, one exp per pair like modes 1 and 2 of mccnn_compute_pdf; 0 for an empty set, which only a cloud
+ * of zero extent under a relative radius has). cell_indexs is the grid of sorted_pts (num_cells per axis, built at this
+ * radius). ONE launch, no workspace, no memset, no atomics; the kernel writes every element of density[n] and counts[n],
+ * the same bytes in every run. Batch ids are clamped to [0, batch_size). n == 0 returns 0 without a launch; n < 0,
+ * batch_size <= 0, num_cells <= 0, radius <= 0, window <= 0 or a null pointer: MCCNN_E_BADARG. */
+int mccnn_compute_pdf_points(const float* sorted_pts, const int* sorted_batch_ids, int n, const int* cell_indexs,
+                             const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
+                             float window, float radius, int scale_inv, float* density, int* counts,
+                             mccnn_stream_t stream);
+/* The per-point density spread over the edges of an UNCAPPED neighbour list over the same grid:
+ *   pdfs[t] = density[packed[2t]] / float(len_i),  i = packed[2t + 1],
+ * len_i = start_idx[i + 1] - start_idx[i] (e - start_idx[m - 1] for the last centre) -- the reference's division by
+ * the row length (compute_pdf.cu:92), one correctly rounded f32 divide. On a cloud that lies inside every one of its
+ * balls this is mccnn_compute_pdf. One launch, one thread per edge. e == 0 returns 0 without a launch; m < 0, e < 0,
+ * m == 0 with e > 0 or a null pointer: MCCNN_E_BADARG. */
+int mccnn_expand_pdf(const float* density, const int* start_idx, int m, const int* packed, int e,
+                     float* pdfs, mccnn_stream_t stream);
+
 /* PoissonSampling -- poisson_sampling.cc:26,109-211, poisson_sampling.cu:51-230.
  * count: runs the 27 colour phases, leaves the selection in ws and writes the
  * number of samples S to *total_dev.  fill: emits pts[S,3], batch ids[S] and

@@ -43,15 +43,18 @@ def _hip_ops_mod():
 
 from .MCConvModule import (compute_aabb, sort_points_step1, sort_points_step2, sort_features, sort_features_back,
                            compute_pdf, poisson_sampling, get_sampled_features, spatial_conv, get_block_size,
-                           transform_indexs, find_neighbors)
+                           transform_indexs, find_neighbors, compute_pdf_points, expand_pdf)
 
 _OP_NAMES = ("compute_aabb", "sort_points_step1", "sort_points_step2", "sort_features", "sort_features_back",
              "compute_pdf", "poisson_sampling", "get_sampled_features", "spatial_conv", "get_block_size",
-             "transform_indexs", "find_neighbors")
+             "transform_indexs", "find_neighbors",
+             # extension (pdfMode='point'): asked of an `ops=` object only by a layer in that mode
+             "compute_pdf_points", "expand_pdf")
 
 
 class _Ops:
-    """The twelve names the reference builder imports from MCConvModule (MCConvBuilder.py:20-21). By default they are
+    """The twelve names the reference builder imports from MCConvModule (MCConvBuilder.py:20-21) and the two ops of the
+    per-point density. By default they are
     this module's own imports of the HIP op surface, looked up at call time; a caller may hand the builder classes
     another object with the same names (`ops=`) -- the parity tests run the identical graph through the CPU checker."""
 
@@ -340,8 +343,12 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0, sampleSeed=None, capNative=False):
-        """maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
+                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge'):
+        """pdfMode (extension): 'edge' (default) -- the reference's density, a Gaussian sum over the centre's row for every
+        edge (compute_pdf); 'point' -- the density of every point over its OWN ball, computed once per (grid, KDEWindow)
+        and shared by every list over that grid (compute_pdf_points + expand_pdf). A 'point' layer with usePDF takes the
+        op-by-op path, needs an uncapped list and points without a gradient; without usePDF the mode has no effect.
+        maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
         maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path unless capNative is set.
         capNative (extension, default False): True sends capped layers through the native step executor like uncapped
         ones -- one library call per geometry (mccnn_geometry_build_capped), learned prefetch and the batch form
@@ -357,6 +364,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("capNative must be True or False")
         self.capNative_ = capNative
+        self.pdfMode_ = self.__check_pdf_mode__(pdfMode)
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
         # node (spatial_conv(sortIndex=)) -- fewer op calls and graph nodes per convolution, same kernels and results
@@ -367,6 +375,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.cacheGrids_ = {}
         self.cacheNeighs_ = {}
         self.cachePDFs_ = {}
+        self.cachePointPDFs_ = {}   # keyGrid|KDEWindow -> (density, counts) of the grid's points (pdfMode='point')
         self.cacheGeo_ = {}         # keyPDF -> native.Geometry; keyGrid -> the Geometry that owns the grid
         self.cacheGeoGrid_ = {}
         self.layers_ = {}           # convName -> (spec, variables): the fast path of a repeated create_convolution
@@ -452,6 +461,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             raise InvalidArgumentError("sampleSeed must be None or an integer in [0, 2^32)")
         return sampleSeed
 
+    @staticmethod
+    def __check_pdf_mode__(pdfMode):
+        if not isinstance(pdfMode, str) or pdfMode not in ('edge', 'point'):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("pdfMode must be 'edge' or 'point'")
+        return pdfMode
+
     def __layer_seed__(self, currCap, sampleSeed):
         """The seed of a layer with cap currCap: its own (which needs a cap) or the builder's (capped layers only)."""
         if sampleSeed is not None:
@@ -533,6 +549,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 _M.HOST_WAIT_S[0] += dt
                 _M.HOST_LAG_WAIT_S[0] += dt
         state["cacheGrids_"], state["cacheNeighs_"], state["cachePDFs_"] = {}, {}, {}
+        state["cachePointPDFs_"] = {}
         if self.geoSeen_:
             # the geometries the step's layers USED (built by them, prebuilt, or started a step ago by prefetch_step) and
             # the pieces they attached to each (row plans, transposed list): what the next step asks for ahead
@@ -583,7 +600,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def prefetch_geometry(self, inPointHierarchy, inPointLevel, convRadius, outPointHierarchy=None, outPointLevel=None,
                           KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False, maxNeighbors=None,
-                          sampleSeed=None):
+                          sampleSeed=None, pdfMode=None):
         """Extension (no counterpart in the reference): computes the grid, the neighbour list and the PDFs that
         create_convolution() with the same arguments looks up in the caches -- for the NEXT batch, on a side stream, and
         parks them until the next reset(). Geometry depends on the points only, not on the network, so in a training
@@ -605,9 +622,15 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         maxNeighbors: the cap of the create_convolution() call this prepares (None = the builder's default). A capped
         geometry is prefetched op by op on the side stream, or -- with capNative_ -- by the native executor like an
         uncapped one.
-        sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call)."""
+        sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call).
+        pdfMode: the mode of that call (None = the builder's). The per-point density has no prefetched form: 'point' with
+        usePDF raises."""
         currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
             inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
+        if self.__check_pdf_mode__(self.pdfMode_ if pdfMode is None else pdfMode) == 'point' and currUsePDF:
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("prefetch_geometry: pdfMode='point' has no prefetched form (its layers build their "
+                                       "geometry themselves, op by op)")
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         currSeed = self.__layer_seed__(currCap, sampleSeed)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
@@ -832,7 +855,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         sampleSeed: the seed the NEXT step's capped layers will run with (capNative_; None = the current sampleSeed_) -- the
         geometries are filed under that seed's keys, so `cb.prefetch_step(ph_next, sampleSeed=step + 1)` followed by
         `cb.sampleSeed_ = step + 1; cb.reset()` finds them. One prefetched with another seed is never asked for and is
-        dropped at the reset() after."""
+        dropped at the reset() after.
+        Layers with pdfMode='point' (and usePDF) are skipped: they never enter the plan, which lists what the native
+        executor built."""
         started = 0
         seed = self.__check_seed__(self.sampleSeed_ if sampleSeed is None else sampleSeed)
         pieces = _env.debug("plan_prefetch", True)
@@ -995,8 +1020,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     def create_convolution(self, convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                            outPointHierarchy=None, outPointLevel=None, multiFeatureConv=None, outNumFeatures=None,
                            KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None, maxNeighbors=None,
-                           sampleSeed=None):
+                           sampleSeed=None, pdfMode=None):
         # defaults: MCConvBuilder.py:299-325
+        # pdfMode (extension; None = the builder's pdfMode_): 'point' with usePDF takes the density of every point over its
+        # own ball (one compute_pdf_points per grid and window, cachePointPDFs_) and spreads it over the list's edges
+        # (expand_pdf, filed under keyPDF + '|pt') instead of compute_pdf -- on the op-by-op path below, like a capped
+        # layer: no native executor, no deferred search + KDE, no learned prefetch. It needs an uncapped list and points
+        # without a gradient. Without usePDF the mode has no effect.
         # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
         # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
         # like one whose points require a gradient, unless the builder was made with capNative=True (capNative_): then it
@@ -1004,6 +1034,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # search draws a stratified sample of the over-full rows; a seed of the layer's own needs a cap.
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         currSeed = self.__layer_seed__(currCap, sampleSeed)
+        currPDFMode = self.__check_pdf_mode__(self.pdfMode_ if pdfMode is None else pdfMode)
         currMultiFeatureConv = self.multiFeatureConvs_ if multiFeatureConv is None else multiFeatureConv
         currNumOutFeatures = inNumFeatures if outNumFeatures is None else outNumFeatures
         currUseAVG = self.useAVG_ if useAVG is None else useAVG
@@ -1026,8 +1057,17 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # HIP op surface, points that carry no gradient: the grid is built from the points alone and the feature rows are
         # sorted inside the convolution (by the native executor's layer call, or by spatial_conv(sortIndex=) below)
         inPts = inPointHierarchy.points_[inPointLevel]
+        pointPDF = currPDFMode == 'point' and bool(currUsePDF)
+        if pointPDF:
+            from .MCConvModule import InvalidArgumentError
+            if currCap > 0:
+                raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0): on a capped "
+                                           "row the per-point density is unbiased but far noisier than the per-edge one")
+            if inPts.requires_grad or currOutPointHierarchy.points_[currOutPointLevel].requires_grad:
+                raise InvalidArgumentError("pdfMode='point' is not differentiable with respect to the points: they must not "
+                                           "require a gradient")
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
-        if self.native_ and fused and (currCap == 0 or self.capNative_):
+        if self.native_ and fused and not pointPDF and (currCap == 0 or self.capNative_):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
@@ -1074,7 +1114,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # neighbours (MCConvBuilder.py:366-376)
         # (uncapped lists only: the deferred op has no capped form -- a capped layer that did not take the native executor
         # above runs find_neighbors + compute_pdf)
-        if fused and currCap == 0 and currUsePDF and keyNeighs not in self.cacheNeighs_ and keyPDF not in self.cachePDFs_:
+        if fused and currCap == 0 and currUsePDF and not pointPDF and keyNeighs not in self.cacheNeighs_ \
+                and keyPDF not in self.cachePDFs_:
             # search + KDE enqueued back to back (list sizes from the last total of this shape), ONE wait for the edge
             # count at the end instead of a wait between the two ops; None on the first call of a shape
             _hip_ops = _hip_ops_mod()
@@ -1100,7 +1141,24 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self._trace("find_neighbors", keyNeighs)
 
         # pdf (MCConvBuilder.py:379-391)
-        if keyPDF in self.cachePDFs_:
+        if pointPDF:
+            keyPointPDF = keyPDF + '|pt'
+            if keyPointPDF in self.cachePDFs_:
+                currPDFs = self.cachePDFs_[keyPointPDF]
+            else:
+                keyDensity = keyGrid + '|' + str(currKDEWindow)
+                if keyDensity in self.cachePointPDFs_:
+                    currDensity = self.cachePointPDFs_[keyDensity]
+                else:
+                    currDensity = tuple(self.ops_.compute_pdf_points(
+                        currGridTuple[0], currGridTuple[1], currGridTuple[2], inPointHierarchy.aabbMin_,
+                        inPointHierarchy.aabbMax_, currKDEWindow, convRadius, inPointHierarchy.batchSize_, currRelativeRadius))
+                    self.cachePointPDFs_[keyDensity] = currDensity
+                    self._trace("compute_pdf_points", keyDensity)
+                currPDFs = self.ops_.expand_pdf(currDensity[0], currNeighTuple[0], currNeighTuple[1])
+                self.cachePDFs_[keyPointPDF] = currPDFs
+                self._trace("expand_pdf", keyPointPDF)
+        elif keyPDF in self.cachePDFs_:
             currPDFs = self.cachePDFs_[keyPDF]
         else:
             if currUsePDF:

@@ -896,6 +896,48 @@ def _compute_pdf(inPts, inBatchIds, aabbMin, aabbMax, startIndexs, neighbors, wi
     return pdfs
 
 
+def compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize, scaleInv):
+    """Extension (pdfMode='point'; no counterpart in the reference) -> (density [N,1] f32, counts [N,1] i32): the Gaussian
+    KDE of every SORTED point over its own ball -- the row find_neighbors gives with the sorted points as their own
+    centres, same f32 predicate -- and that row's length. inPts / inBatchIds are a sorted list, cellIndexs its cell table
+    (sort_points_step2 / build_grid at this radius). Depends on (grid, window) only. One launch, no atomics: the same
+    bytes in every run. Non differentiable."""
+    op = "ComputePDFPointsOp"
+    _req(radius > 0.0, op + " expects a positive radius")
+    _req(window > 0.0, op + " expects a positive window")
+    _req(batchSize > 0, op + " expects a positive batch size")
+    p, b = _points_input(op, inPts.detach(), inBatchIds)
+    cells = _i32(cellIndexs, "cell_indexs")
+    _req(cells.dim() == 5 and cells.shape[0] == batchSize and cells.shape[4] == 2
+         and cells.shape[1] == cells.shape[2] == cells.shape[3],
+         op + " expects a five dimension tensor for the cell indices")
+    mn, mx = _box_input(op, aabbMin, aabbMax, batchSize)
+    n = p.shape[0]
+    density = torch.empty((n, 1), dtype=torch.float32, device=p.device)
+    counts = torch.empty((n, 1), dtype=torch.int32, device=p.device)
+    check(_lib.load().mccnn_compute_pdf_points(ptr(p), ptr(b), n, ptr(cells), ptr(mn), ptr(mx), batchSize, cells.shape[1],
+                                               float(window), float(radius), int(bool(scaleInv)), ptr(density), ptr(counts),
+                                               stream_handle()), "compute_pdf_points")
+    return density, counts
+
+
+def expand_pdf(density, startIndexs, packedNeighs):
+    """Extension (pdfMode='point') -> pdfs [E,1]: pdfs[e] = density[j] / float(len_i) for every edge e = (j, i) of an
+    UNCAPPED neighbour list over the grid `density` was computed on; len_i is the length of centre i's row (the reference's
+    division, compute_pdf.cu:92). Non differentiable."""
+    op = "ExpandPDFOp"
+    d = _f32(density.detach(), "density")
+    _req(d.dim() == 2 and d.shape[1] == 1, op + " expects a density with dimensions (numPoints, 1)")
+    st, pk = _i32(startIndexs, "start_indexs"), _i32(packedNeighs, "neighbors")
+    _req(st.dim() == 2 and st.shape[1] == 1, op + " expects start indexs with dimensions (numSamples, 1)")
+    _req(pk.dim() == 2 and pk.shape[1] == 2, op + " expects a neighbor list with dimensions (numNeighbors, 2)")
+    e = pk.shape[0]
+    _req(e == 0 or (st.shape[0] > 0 and d.shape[0] > 0), op + " expects centres and points for a non-empty neighbor list")
+    pdfs = torch.empty((e, 1), dtype=torch.float32, device=d.device)
+    check(_lib.load().mccnn_expand_pdf(ptr(d), ptr(st), st.shape[0], ptr(pk), e, ptr(pdfs), stream_handle()), "expand_pdf")
+    return pdfs
+
+
 def _edge_grads_to_points(dp_edge, packed_obj, n):
     """Per-point sums of per-edge position gradients [E,3] -> [n,3], gathered through the transposed neighbour list in a
     fixed order (bit-reproducible, no float atomics)."""
