@@ -23,10 +23,14 @@ struct NeighItem {
     float radius, Tabs;
 };
 struct NeighBatch { NeighItem it[MCCNN_BATCH_MAX]; };
-// the cap of a search (mccnn_geometry_build_batch_capped): beside NeighBatch, item k of one belongs to item k of the other.
+// the cap of a search: beside NeighItem (in a batch: NeighCapBatch, item k of one belongs to item k of the other).
 // capK == 0: no cap; sampled: the fill pass draws the stratified sample of `seed` (neigh_sample.h)
 struct NeighCapItem { int* kfull; int capK; unsigned seed; int sampled; };
 struct NeighCapBatch { NeighCapItem it[MCCNN_BATCH_MAX]; };
+// the prefix sum of the counts inside the fill pass of a small list (single launches; all null in a batch)
+struct NeighScan { const int* scanCnt; int* startOut; int* totalDev; int* totalHost; };
+// the kind of a search's kernels: which of the three records above an instantiation reads
+enum { NEIGH_PLAIN = 0, NEIGH_CAPPED = 1, NEIGH_SAMPLED = 2 };
 static_assert(sizeof(NeighBatch) + sizeof(NeighCapBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched search: < 4 KB");
 
 // one kernel-density estimate
@@ -102,14 +106,23 @@ int grid_batch_item(GridItem& g, ScanItem& sc, ClearSpan& head, const float* pts
 int order_batch_item(GridItem& g, ScanItem& sc, ClearSpan& head, const float* pts, const int* batch_ids, const float* aabb_min,
                      const float* aabb_max, int m, int batch_size, int num_cells, int* order, void* ws, size_t ws_bytes);
 int launch_grid_batch_phase(const GridBatch& gb, int count, int phase, hipStream_t s);   // 0 keys + histogram, 1 park, 2 rank + move + cells
+// One search as the host describes it: what the mccnn_find_neighbors_* entries take as parameters and exec.hip reads from
+// a geometry. Every host function of the search takes this; neigh_item (neighbors.hip) turns it into the kernels' records.
+struct NeighSearch {
+    const float* centres; const int* cbids; int m;      // the centres and their batch ids
+    const float* pts; int n; const int* cells;           // the sorted points and the cell table
+    const float* mn; const float* mx; int B, nc;          // the boxes
+    float radius; int scale_inv;
+    const int* order;                                     // visiting order of the centres (nullptr: by index)
+    int* start_idx; int capacity; int* packed;
+    int* total_dev; int* total_host;                      // the edge total: device word, pinned host word (or nullptr)
+    void* ws; size_t ws_bytes;
+    int max_neighbors, sampled; unsigned seed;            // the cap: 0 = none; sampled: the draw of `seed`
+};
+int find_neighbors_chain(const NeighSearch& q, hipStream_t s);   // count (scan) fill, back to back
 bool neigh_batch_eligible(int m, int n);
-int neigh_batch_item(NeighItem& it, ScanItem& sc, const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
-                     int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
-                     float radius, int scale_inv, const int* order, int* start_idx, int e_capacity, int* packed, int* total_dev,
-                     int* total_host, void* ws, size_t ws_bytes, NeighCapItem* cap = nullptr, int max_neighbors = 0, int sampled = 0,
-                     unsigned seed = 0);
-// caps == nullptr (or no capped item among them): the uncapped launch alone
-int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s, const NeighCapBatch* caps = nullptr);   // 0 count, 1 fill
+int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q);
+int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s);   // 0 count, 1 fill
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,
                     float radius, int scale_inv, float* pdfs);

@@ -33,7 +33,6 @@ size_t visiting_order_workspace_bytes(int m, int batch_size, int num_cells);
 ClearSpan visiting_order_head_span(int m, int batch_size, int num_cells, void* ws, size_t ws_bytes);
 int visiting_order(const float* pts, const int* batch_ids, const float* aabb_min, const float* aabb_max, int m, int batch_size,
                    int num_cells, int* order, void* ws, size_t ws_bytes, hipStream_t s, bool cleared);
-// neighbors.hip: count + (scan) + fill; lists of few centres scan their counts inside the fill pass
 // conv_rows.hip: small row plans as batch items
 bool plan_batchable(int rows, int e, int transposed);
 size_t plan_batch_tr_ws_bytes(int n, int e);
@@ -43,11 +42,6 @@ int plan_batch_items(int transposed, const float* sorted_pts, const int* sorted_
                      int tlist_ready, void* plan_buffer, void* tws, size_t tws_bytes, TrSmallItem* tr, bool* use_tr,
                      PlanSmallItem& lay, SellFillItem& fill);
 bool transpose_small(int e, int n);
-int find_neighbors_chain(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts, int n,
-                         const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
-                         float radius, int scale_inv, const int* centre_order, int* start_idx, int e_capacity, int* packed,
-                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream, int max_neighbors,
-                         bool sampled, unsigned seed);
 }
 
 using namespace mccnn;
@@ -382,6 +376,22 @@ int head_ws(const mccnn_geometry_t* g, HeadWs& h) {
     return 0;
 }
 
+// the search of a geometry as neighbors.hip takes it (batch.h), for its own chain and as a batch item alike
+NeighSearch geometry_search(const mccnn_geometry_t* g, const int* order) {
+    const mccnn_geometry* go = grid_owner(g);
+    NeighSearch q{};
+    q.centres = g->centres; q.cbids = g->cbids; q.m = g->m;
+    q.pts = go->s_pts; q.n = g->n; q.cells = go->cells;
+    q.mn = g->mn; q.mx = g->mx; q.B = g->B; q.nc = g->nc;
+    q.radius = g->radius; q.scale_inv = g->scale_inv;
+    q.order = order;
+    q.start_idx = g->start; q.capacity = g->e_cap; q.packed = g->packed;
+    q.total_dev = g->total_dev; q.total_host = const_cast<int*>((volatile int*)g->total_host);
+    q.ws = g->ws; q.ws_bytes = g->ws_bytes;
+    q.max_neighbors = g->cap_k; q.sampled = g->cap_sampled; q.seed = g->cap_seed;
+    return q;
+}
+
 // the chain of ONE geometry: [head clear] grid build (4 launches) [visiting order (3)] count (scan) fill KDE
 int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -409,9 +419,7 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
         if (rc) return rc;
         order = g->order;
     }
-    rc = find_neighbors_chain(g->centres, g->cbids, m, go->s_pts, n, go->cells, g->mn, g->mx, batch_size, num_cells, g->radius,
-                              g->scale_inv, order, g->start, g->e_cap, g->packed, g->total_dev, const_cast<int*>((volatile int*)g->total_host),
-                              g->ws, g->ws_bytes, stream, g->cap_k, g->cap_sampled != 0, g->cap_seed);
+    rc = find_neighbors_chain(geometry_search(g, order), s);
     if (rc) return rc;
     if (g->use_pdf) {
         rc = mccnn_compute_pdf_dn(go->s_pts, go->s_bids, g->start, m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, batch_size,
@@ -434,7 +442,6 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     ScanBatch scanG, scanN;
     NeighBatch neighB;
     NeighCapBatch capB;
-    bool anyCap = false;
     PdfBatch pdfB;
     SpanBatch spans;
     spans.count = 0;
@@ -475,20 +482,16 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
         mccnn_geometry_t* g = gs[k];
         const mccnn_geometry* go = grid_owner(g);
         const int* order = g->same_level ? go->inv_idx : g->order;
-        rc = neigh_batch_item(neighB.it[k], scanN.it[k], g->centres, g->cbids, g->m, go->s_pts, g->n, go->cells, g->mn, g->mx, g->B, g->nc,
-                              g->radius, g->scale_inv, order, g->start, g->e_cap, g->packed, g->total_dev,
-                              const_cast<int*>((volatile int*)g->total_host), g->ws, g->ws_bytes, &capB.it[k], g->cap_k, g->cap_sampled,
-                              g->cap_seed);
+        rc = neigh_batch_item(neighB.it[k], capB.it[k], scanN.it[k], geometry_search(g, order));
         if (rc) return rc;
-        anyCap = anyCap || g->cap_k > 0;
         if (g->use_pdf)
             pdf_batch_item(pdfB.it[nPdf++], go->s_pts, go->s_bids, g->start, g->m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, g->B,
                            g->window, g->radius, g->scale_inv, g->pdfs);
     }
-    // (a chunk without a capped geometry: the uncapped launches alone; otherwise one launch per kind that is present)
-    if ((rc = launch_neigh_batch(neighB, count, 0, s, anyCap ? &capB : nullptr))) return rc;
+    // (one launch per kind of search that is present: a chunk without a capped geometry makes the plain launches alone)
+    if ((rc = launch_neigh_batch(neighB, capB, count, 0, s))) return rc;
     if ((rc = launch_scan_batch(scanN, count, s))) return rc;
-    if ((rc = launch_neigh_batch(neighB, count, 1, s, anyCap ? &capB : nullptr))) return rc;
+    if ((rc = launch_neigh_batch(neighB, capB, count, 1, s))) return rc;
     if (nPdf && (rc = launch_pdf_batch(pdfB, nPdf, s))) return rc;
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];

@@ -100,9 +100,12 @@ __device__ __forceinline__ int kept_slot(int r, int k, int cap, unsigned rowh) {
     if constexpr (SAMPLED) return sample_slot(r, k, cap, rowh);
     else return cap_slot(r, k, cap);
 }
-// (the kernel's body: workgroup `blk` of `nblk` -- the single launch, and one geometry's share of a batch launch)
-template <int MODE, bool LEAN, bool CAPPED = false, bool SAMPLED = false>
-__device__ __forceinline__ void neigh_window_body(const int blk, const int nblk, const float* __restrict__ centres, const int* __restrict__ cb, int m,
+// (the kernel's statements: workgroup `blk` of `nblk` -- the single launch, and one geometry's share of a batch launch.
+// Called from neigh_window_body below and from nowhere else; the pointers are parameters because `__restrict__` holds for
+// parameters only -- bound to locals instead, the fill pass's mask, cell and point loads may alias its stores: 66 VGPRs
+// instead of 56 and 7 waves per SIMD instead of 8.)
+template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED>
+__device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk, const float* __restrict__ centres, const int* __restrict__ cb, int m,
                                                     const float* __restrict__ pts, const int* __restrict__ cells,
                                                     const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
                                                     float radius, int scaleInv, const int* __restrict__ order,
@@ -112,9 +115,9 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
                                                     int G /* centres per wave, 1 .. 32 */, float Tabs,
                                                     const int* __restrict__ scanCnt, int* __restrict__ startOut,
                                                     int* __restrict__ totalDev, int* __restrict__ totalHost,
-                                                    const int capK = 0 /* CAPPED: hits kept per centre, > 0 (not `K`: the round lambdas below have a K of their own) */,
-                                                    int* __restrict__ kfull = nullptr /* CAPPED: [m] true row lengths, count -> fill */,
-                                                    const unsigned sseed = 0 /* SAMPLED: the seed of the draw */) {
+                                                    const int capK /* CAPPED: hits kept per centre, > 0 (not `K`: the round lambdas below have a K of their own) */,
+                                                    int* __restrict__ kfull /* CAPPED: [m] true row lengths, count -> fill */,
+                                                    const unsigned sseed /* SAMPLED: the seed of the draw */) {
     constexpr bool FILL = MODE == 1;
     static_assert(!SAMPLED || (CAPPED && FILL), "the sample is a form of the capped fill pass");
     // the status words of the prefix sum that follows the count pass (scan.hip): cleared here, no launch of their own
@@ -432,88 +435,33 @@ __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk,
     }
 }
 
-template <int MODE, bool LEAN>
-__global__ __launch_bounds__(256) void neigh_window(const float* __restrict__ centres, const int* __restrict__ cb, int m,
-                                                    const float* __restrict__ pts, const int* __restrict__ cells,
-                                                    const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
-                                                    float radius, int scaleInv, const int* __restrict__ order,
-                                                    int* __restrict__ cnt, unsigned long long* __restrict__ masks,
-                                                    const int* __restrict__ startIdx, int* __restrict__ packed,
-                                                    int capacity, unsigned long long* __restrict__ zeroWords, int numZero,
-                                                    int G /* centres per wave, 1 .. 32 */, float Tabs,
-                                                    const int* __restrict__ scanCnt, int* __restrict__ startOut,
-                                                    int* __restrict__ totalDev, int* __restrict__ totalHost) {
-    neigh_window_body<MODE, LEAN>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv, order, cnt,
-                                  masks, startIdx, packed, capacity, zeroWords, numZero, G, Tabs, scanCnt, startOut, totalDev, totalHost);
+// The kernel's body over the records of batch.h: the search `g`, the in-fill prefix sum `ps` (all null in a batch) and the
+// cap `cp`, which only the CAPPED instantiations read. The one place that spells the statements' argument list.
+template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED>
+__device__ __forceinline__ void neigh_window_body(const int blk, const int nblk, const NeighItem& g, const NeighScan& ps,
+                                                    const NeighCapItem& cp) {
+    neigh_window_impl<MODE, LEAN, CAPPED, SAMPLED>(blk, nblk, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv,
+                                                   g.order, g.cnt, g.masks, g.startIdx, g.packed, g.capacity, g.zeroWords, g.numZero, g.G,
+                                                   g.Tabs, ps.scanCnt, ps.startOut, ps.totalDev, ps.totalHost, CAPPED ? cp.capK : 0,
+                                                   CAPPED ? cp.kfull : nullptr, SAMPLED ? cp.seed : 0u);
 }
 
-// The capped passes (mccnn_find_neighbors_count_capped / _fill_capped): kernels of their own, so that the uncapped ones
-// keep their argument lists and their code.
-template <int MODE, bool LEAN>
-__global__ __launch_bounds__(256) void neigh_window_capped(const float* __restrict__ centres, const int* __restrict__ cb, int m,
-                                                           const float* __restrict__ pts, const int* __restrict__ cells,
-                                                           const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
-                                                           float radius, int scaleInv, const int* __restrict__ order,
-                                                           int* __restrict__ cnt, unsigned long long* __restrict__ masks,
-                                                           const int* __restrict__ startIdx, int* __restrict__ packed,
-                                                           int capacity, unsigned long long* __restrict__ zeroWords, int numZero,
-                                                           int G, float Tabs, const int* __restrict__ scanCnt,
-                                                           int* __restrict__ startOut, int* __restrict__ totalDev,
-                                                           int* __restrict__ totalHost, int K, int* __restrict__ kfull) {
-    neigh_window_body<MODE, LEAN, true>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv, order,
-                                        cnt, masks, startIdx, packed, capacity, zeroWords, numZero, G, Tabs, scanCnt, startOut, totalDev,
-                                        totalHost, K, kfull);
+// The two kernels of the search, over the records of batch.h. KIND (NEIGH_PLAIN / _CAPPED / _SAMPLED) picks the body's
+// CAPPED / SAMPLED form; a plain instantiation never reads its cap record.
+// One search per launch (mccnn_find_neighbors_*, find_neighbors_chain): the plain or the lean loop.
+template <int MODE, bool LEAN, int KIND>
+__global__ __launch_bounds__(256) void neigh_window(NeighItem g, NeighScan ps, NeighCapItem cp) {
+    neigh_window_body<MODE, LEAN, KIND != NEIGH_PLAIN, KIND == NEIGH_SAMPLED>((int)blockIdx.x, (int)gridDim.x, g, ps, cp);
 }
 
-// The sampled fill pass (mccnn_find_neighbors_fill_sampled), after neigh_window_capped<0, .>: the capped fill's arguments
-// and the seed.
-template <bool LEAN>
-__global__ __launch_bounds__(256) void neigh_window_sampled(const float* __restrict__ centres, const int* __restrict__ cb, int m,
-                                                            const float* __restrict__ pts, const int* __restrict__ cells,
-                                                            const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
-                                                            float radius, int scaleInv, const int* __restrict__ order,
-                                                            const unsigned long long* __restrict__ masks,
-                                                            const int* __restrict__ startIdx, int* __restrict__ packed,
-                                                            int capacity, int G, float Tabs, const int* __restrict__ scanCnt,
-                                                            int* __restrict__ startOut, int* __restrict__ totalDev,
-                                                            int* __restrict__ totalHost, int capK, const int* __restrict__ kfull,
-                                                            unsigned seed) {
-    neigh_window_body<1, LEAN, true, true>((int)blockIdx.x, (int)gridDim.x, centres, cb, m, pts, cells, mn, mx, B, nc, radius, scaleInv,
-                                           order, nullptr, const_cast<unsigned long long*>(masks), startIdx, packed, capacity, nullptr, 0,
-                                           G, Tabs, scanCnt, startOut, totalDev, totalHost, capK, const_cast<int*>(kfull), seed);
-}
-
-// One launch for the count (or the fill) pass of a BATCH of searches (mccnn_geometry_build_batch): the plain loop of the
-// background launches, the prefix sum of the counts a launch of its own in between (scan.hip's batch form).
-template <int MODE>
-__global__ __launch_bounds__(256) void neigh_window_batch(NeighBatch nbt, BatchBlocks bb) {
-    int local, blocks;
-    const NeighItem& g = nbt.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
-    neigh_window_body<MODE, false>(local, blocks, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv, g.order,
-                                   g.cnt, g.masks, g.startIdx, g.packed, g.capacity, g.zeroWords, g.numZero, g.G, g.Tabs, nullptr, nullptr,
-                                   nullptr, nullptr);
-}
-
-// The capped and the sampled searches of a batch (mccnn_geometry_build_batch_capped): kernels of their own over the same body,
-// so that neigh_window_batch keeps its arguments and its code. The cap of item k travels beside it (NeighCapBatch).
-template <int MODE>
-__global__ __launch_bounds__(256) void neigh_window_batch_capped(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
+// One launch for the count (or the fill) pass of a BATCH of searches of one kind (mccnn_geometry_build_batch): the plain
+// loop of the background launches, the prefix sum of the counts a launch of its own in between (scan.hip's batch form).
+// The cap of item k travels beside it (NeighCapBatch).
+template <int MODE, int KIND>
+__global__ __launch_bounds__(256) void neigh_window_batch(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
     int local, blocks;
     const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
-    const NeighItem& g = nbt.it[k];
-    const NeighCapItem& c = caps.it[k];
-    neigh_window_body<MODE, false, true>(local, blocks, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv,
-                                         g.order, g.cnt, g.masks, g.startIdx, g.packed, g.capacity, g.zeroWords, g.numZero, g.G, g.Tabs,
-                                         nullptr, nullptr, nullptr, nullptr, c.capK, c.kfull);
-}
-__global__ __launch_bounds__(256) void neigh_window_batch_sampled(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
-    int local, blocks;
-    const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
-    const NeighItem& g = nbt.it[k];
-    const NeighCapItem& c = caps.it[k];
-    neigh_window_body<1, false, true, true>(local, blocks, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius,
-                                            g.scaleInv, g.order, nullptr, g.masks, g.startIdx, g.packed, g.capacity, nullptr, 0, g.G,
-                                            g.Tabs, nullptr, nullptr, nullptr, nullptr, c.capK, c.kfull, c.seed);
+    neigh_window_body<MODE, false, KIND != NEIGH_PLAIN, KIND == NEIGH_SAMPLED>(local, blocks, nbt.it[k], NeighScan{}, caps.it[k]);
 }
 
 __global__ __launch_bounds__(256) void invert_perm_k(const int* __restrict__ newIdx, int n, int* __restrict__ inv) {
@@ -700,12 +648,18 @@ __device__ __forceinline__ void pdf_row_long(const float* __restrict__ pts, cons
 
 struct PdfLongRow { int rowStart, k; float s, scale; };
 template <int WAVES>  // 4: lists of many rows (4 rows per wave); 16: lists of few rows (one row per wave)
-__device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const float* __restrict__ pts, const int* __restrict__ bids,
-                                                     const int2* __restrict__ packed, const int* __restrict__ startIdx,
-                                                     int m, int e, const float* __restrict__ mn,
-                                                     const float* __restrict__ mx, int B, float window, float radius,
-                                                     int scaleInv, float* __restrict__ pdfs,
-                                                     const int* __restrict__ eDev, int rowsPerWave) {
+__device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem& g) {
+    const float* __restrict__ pts = g.pts;
+    const int* __restrict__ bids = g.bids;
+    const int2* __restrict__ packed = g.packed;
+    const int* __restrict__ startIdx = g.startIdx;
+    const float* __restrict__ mn = g.mn;
+    const float* __restrict__ mx = g.mx;
+    float* __restrict__ pdfs = g.pdfs;
+    const int* __restrict__ eDev = g.eDev;
+    const int m = g.m, B = g.B, scaleInv = g.scaleInv, rowsPerWave = g.rowsPerWave;
+    int e = g.e;   // (cut to the device-side edge count below)
+    const float window = g.window, radius = g.radius;
     __shared__ __attribute__((aligned(16))) float planes[WAVES][5 * MCCNN_PDF_CAP];  // per wave: ux, uy, uz, q, ones
     // rows longer than the planes: set aside here and walked by ALL waves of the workgroup afterwards (pdf_row_long)
     __shared__ PdfLongRow longRows[WAVES * MCCNN_PDF_ROWS];
@@ -916,13 +870,8 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const float* _
 }
 
 template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void pdf_rows_mfma(const float* __restrict__ pts, const int* __restrict__ bids,
-                                                     const int2* __restrict__ packed, const int* __restrict__ startIdx,
-                                                     int m, int e, const float* __restrict__ mn,
-                                                     const float* __restrict__ mx, int B, float window, float radius,
-                                                     int scaleInv, float* __restrict__ pdfs,
-                                                     const int* __restrict__ eDev, int rowsPerWave) {
-    pdf_rows_mfma_body<WAVES>((int)blockIdx.x, pts, bids, packed, startIdx, m, e, mn, mx, B, window, radius, scaleInv, pdfs, eDev, rowsPerWave);
+__global__ __launch_bounds__(WAVES * 64) void pdf_rows_mfma(PdfItem g) {
+    pdf_rows_mfma_body<WAVES>((int)blockIdx.x, g);
 }
 
 // One launch for the KDE of a BATCH of lists (mccnn_geometry_build_batch): 16 waves per workgroup for every list (the
@@ -930,8 +879,7 @@ __global__ __launch_bounds__(WAVES * 64) void pdf_rows_mfma(const float* __restr
 __global__ __launch_bounds__(1024) void pdf_rows_mfma_batch(PdfBatch pb, BatchBlocks bb) {
     int local, blocks;
     const PdfItem& g = pb.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
-    pdf_rows_mfma_body<16>(local, g.pts, g.bids, g.packed, g.startIdx, g.m, g.e, g.mn, g.mx, g.B, g.window, g.radius, g.scaleInv, g.pdfs,
-                           g.eDev, g.rowsPerWave);
+    pdf_rows_mfma_body<16>(local, g);
 }
 
 }  // namespace mccnn
@@ -983,12 +931,13 @@ static bool neigh_lean() {
     if (forced >= 0) return forced != 0;
     return !g_background;
 }
+static int neigh_group_background(int m) { return m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1)); }
 static int neigh_group(int m) {
     // centres per wave: more of them share a window's staging and the per-wave set-up (8 rooms, 800 k centres: 0.309 ms at
     // 8, 0.274 at 16, 0.269 at 24) -- as long as the launch still fills the chip (100 k centres: 0.0588 / 0.0580 / 0.0650)
     // (background launches keep 8: beside the convolution kernels the pipelined step of the room reads 0.596 ms at 8, 0.602-0.610 at 16)
-    if (g_background) return m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1));
-    return m >= 400000 ? 24 : (m >= 65536 ? 16 : (m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1))));
+    if (g_background || m < 65536) return neigh_group_background(m);
+    return m >= 400000 ? 24 : 16;
 }
 
 struct NeighWs {
@@ -1011,18 +960,115 @@ static bool neigh_ws(void* ws, size_t ws_bytes, int m, int n, NeighWs& w, bool c
     return w.cnt && w.scanws && w.masks;
 }
 
-static int find_neighbors_count_impl(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
-                               int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
-                               int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
-                               int* start_idx, int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream,
-                               bool skip_scan = false, int max_neighbors = 0);
+}  // extern "C"
+
+// The kernels' records of a search: the workspace carve-up (neigh_ws), the one threshold of an absolute radius, the status
+// words the count pass clears for the prefix sum that follows it, the centres per wave. A batch item (`batch`) takes the
+// settings of background launches and the status words of scan.hip's batch form. Both passes of a search build the same
+// records (mask rows are indexed by visiting position, so the fill pass may group differently: find_neighbors_fill_impl).
+static int neigh_item(const NeighSearch& q, bool batch, NeighItem& it, NeighCapItem& cap, NeighWs& w) {
+    if (!neigh_ws(q.ws, q.ws_bytes, q.m, q.n, w, q.max_neighbors > 0)) return MCCNN_E_WORKSPACE;
+    it.centres = q.centres; it.cb = q.cbids; it.pts = q.pts; it.cells = q.cells; it.mn = q.mn; it.mx = q.mx; it.order = q.order;
+    it.cnt = w.cnt; it.masks = w.masks; it.startIdx = q.start_idx; it.packed = q.packed;
+    it.zeroWords = reinterpret_cast<unsigned long long*>(w.scanws);
+    it.m = q.m; it.B = q.B; it.nc = q.nc; it.scaleInv = q.scale_inv; it.capacity = q.capacity;
+    it.G = batch ? neigh_group_background(q.m) : neigh_group(q.m);
+    it.numZero = batch ? ceil_div(q.m, 2048) + 1 : (int)(scan_status_bytes(q.m) / sizeof(unsigned long long));
+    it.radius = q.radius;
+    it.Tabs = q.scale_inv ? 0.0f : sqrt_threshold_host(q.radius);
+    cap.kfull = w.kfull; cap.capK = q.max_neighbors; cap.seed = q.seed; cap.sampled = q.sampled ? 1 : 0;
+    return 0;
+}
+static int neigh_kind(int max_neighbors, int sampled) { return max_neighbors > 0 ? (sampled ? NEIGH_SAMPLED : NEIGH_CAPPED) : NEIGH_PLAIN; }
+
+// The one place that names the instantiations of the search kernels: (pass, kind) -> `launch(MODE, KIND)`, both compile-time
+// constants. Its two users follow: the launch of one search and the launch of a batch of one kind.
+template <class F>
+static void neigh_pick(int mode, int kind, F launch) {
+    using std::integral_constant;
+    if (mode == 0) {   // (the count pass of a sampled search is the capped one)
+        if (kind == NEIGH_PLAIN) launch(integral_constant<int, 0>{}, integral_constant<int, NEIGH_PLAIN>{});
+        else launch(integral_constant<int, 0>{}, integral_constant<int, NEIGH_CAPPED>{});
+    } else if (kind == NEIGH_PLAIN) launch(integral_constant<int, 1>{}, integral_constant<int, NEIGH_PLAIN>{});
+    else if (kind == NEIGH_CAPPED) launch(integral_constant<int, 1>{}, integral_constant<int, NEIGH_CAPPED>{});
+    else launch(integral_constant<int, 1>{}, integral_constant<int, NEIGH_SAMPLED>{});
+}
+static int launch_neigh(int mode, bool lean, int kind, int grid, size_t dyn, hipStream_t s, const NeighItem& it, const NeighScan& ps,
+                        const NeighCapItem& cap) {
+    neigh_pick(mode, kind, [&](auto m, auto k) {
+        constexpr int MODE = decltype(m)::value, KIND = decltype(k)::value;
+        if (lean) neigh_window<MODE, true, KIND><<<grid, 256, dyn, s>>>(it, ps, cap);
+        else neigh_window<MODE, false, KIND><<<grid, 256, dyn, s>>>(it, ps, cap);
+    });
+    MCCNN_LAUNCHED();
+    return 0;
+}
+static int launch_neigh_kind(int mode, int kind, int grid, size_t dyn, hipStream_t s, const NeighBatch& nbt, const NeighCapBatch& caps,
+                             const BatchBlocks& bb) {
+    neigh_pick(mode, kind, [&](auto m, auto k) {
+        neigh_window_batch<decltype(m)::value, decltype(k)::value><<<grid, 256, dyn, s>>>(nbt, caps, bb);   // (background launches: the plain loop)
+    });
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+// skip_scan: the fill pass that follows in the same chain scans the counts itself (find_neighbors_fill_impl, `scan`)
+static int find_neighbors_count_impl(const NeighSearch& q, hipStream_t s, bool skip_scan = false) {
+    if (q.m < 0 || q.n < 0 || q.B <= 0 || q.nc <= 0 || !(q.radius > 0.0f) || !q.total_dev || q.max_neighbors < 0) return MCCNN_E_BADARG;
+    if (q.m == 0) {
+        int rc = launch_zero_words(q.total_dev, 1, s);
+        if (!rc && q.total_host) rc = launch_zero_words(q.total_host, 1, s);   // (a pinned word the device can write)
+        return rc;
+    }
+    if (!q.centres || !q.cbids || !q.cells || !q.mn || !q.mx || !q.start_idx || (q.n > 0 && !q.pts)) return MCCNN_E_BADARG;
+    NeighItem it;
+    NeighCapItem cap;
+    NeighWs w;
+    int rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    rc = launch_neigh(0, neigh_lean(), neigh_kind(q.max_neighbors, q.sampled), ceil_div(q.m, 4 * it.G), neigh_lds_pad(), s, it, NeighScan{}, cap);
+    if (rc || skip_scan) return rc;
+    return exclusive_scan_i32(w.cnt, q.start_idx, q.m, q.total_dev, w.scanws, s, true, q.total_host);
+}
+
+// scan: the counts of a skip_scan count pass are still in `ws` and are scanned here (start_idx and the totals are outputs)
+static int find_neighbors_fill_impl(const NeighSearch& q, hipStream_t s, bool scan = false) {
+    if (q.m < 0 || q.n < 0 || q.capacity < 0 || q.B <= 0 || q.nc <= 0 || !(q.radius > 0.0f) || q.max_neighbors < 0) return MCCNN_E_BADARG;
+    if (scan && (q.m > MCCNN_NW_SCAN_M || !q.total_dev)) return MCCNN_E_BADARG;
+    if (q.m == 0 || q.capacity == 0) return 0;
+    if (!q.centres || !q.cbids || !q.pts || !q.cells || !q.mn || !q.mx || !q.start_idx || !q.packed) return MCCNN_E_BADARG;
+    NeighItem it;
+    NeighCapItem cap;
+    NeighWs w;
+    int rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    // (mask rows are indexed by visiting position: the two passes may group differently -- the compaction gains little
+    // from more centres per wave: 100 k centres 0.0612 ms at 8, 0.0622 at 16; 800 k centres 0.305 at 8, 0.295 at 24)
+    if (it.G == 16) it.G = MCCNN_NW_G;
+    size_t dyn = neigh_lds_pad();
+    if (scan && dyn < (size_t)q.m * sizeof(int)) dyn = (size_t)q.m * sizeof(int);
+    const NeighScan ps = scan ? NeighScan{w.cnt, q.start_idx, q.total_dev, q.total_host} : NeighScan{};
+    return launch_neigh(1, neigh_lean(), neigh_kind(q.max_neighbors, q.sampled), ceil_div(q.m, 4 * it.G), dyn, s, it, ps, cap);
+}
+
+extern "C" {
+
+// The parameters every mccnn_find_neighbors_* entry shares, by their names in mccnn.h, as a NeighSearch `q`; an entry adds
+// what it has beyond them. (The const_cast is for the fill entries alone: they take start_idx read-only, and the fill pass
+// writes through it only in the scan mode of find_neighbors_chain, which owns the array.)
+#define MCCNN_NEIGH_SEARCH(q)                                                                                          \
+    NeighSearch q{};                                                                                                   \
+    q.centres = centres; q.cbids = centre_batch_ids; q.m = m; q.pts = sorted_pts; q.n = n; q.cells = cell_indexs;      \
+    q.mn = aabb_min; q.mx = aabb_max; q.B = batch_size; q.nc = num_cells; q.radius = radius; q.scale_inv = scale_inv;  \
+    q.order = centre_order; q.start_idx = const_cast<int*>(start_idx); q.ws = ws; q.ws_bytes = ws_bytes
 
 int mccnn_find_neighbors_count(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
                                int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
                                int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                int* start_idx, int* total_dev, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
-    return find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                     num_cells, radius, scale_inv, centre_order, start_idx, total_dev, nullptr, ws, ws_bytes, stream);
+    MCCNN_NEIGH_SEARCH(q);
+    q.total_dev = total_dev;
+    return find_neighbors_count_impl(q, (hipStream_t)stream);
 }
 
 int mccnn_find_neighbors_count2(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
@@ -1030,116 +1076,10 @@ int mccnn_find_neighbors_count2(const float* centres, const int* centre_batch_id
                                 int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                 int* start_idx, int* total_dev, int* total_host, void* ws, size_t ws_bytes,
                                 mccnn_stream_t stream) {
-    return find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                     num_cells, radius, scale_inv, centre_order, start_idx, total_dev, total_host, ws, ws_bytes,
-                                     stream);
-}
-
-static int find_neighbors_count_impl(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
-                               int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
-                               int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
-                               int* start_idx, int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream,
-                               bool skip_scan, int max_neighbors) {
-    if (m < 0 || n < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || !total_dev || max_neighbors < 0) return MCCNN_E_BADARG;
-    const bool capped = max_neighbors > 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (m == 0) {
-        int rc = launch_zero_words(total_dev, 1, s);
-        if (!rc && total_host) rc = launch_zero_words(total_host, 1, s);   // (a pinned word the device can write)
-        return rc;
-    }
-    if (!centres || !centre_batch_ids || !cell_indexs || !aabb_min || !aabb_max || !start_idx || (n > 0 && !sorted_pts))
-        return MCCNN_E_BADARG;
-    NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w, capped)) return MCCNN_E_WORKSPACE;
-    const int G = neigh_group(m);
-    const float Tabs = scale_inv ? 0.0f : sqrt_threshold_host(radius);
-    unsigned long long* zw = (unsigned long long*)w.scanws;
-    const int nz = (int)(scan_status_bytes(m) / sizeof(unsigned long long));
-    if (capped) {
-        if (neigh_lean())
-            neigh_window_capped<0, true><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr, max_neighbors,
-                w.kfull);
-        else
-            neigh_window_capped<0, false><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr, max_neighbors,
-                w.kfull);
-    } else if (neigh_lean())
-        neigh_window<0, true><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
-                                                     aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
-                                                     w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr);
-    else
-        neigh_window<0, false><<<ceil_div(m, 4 * G), 256, neigh_lds_pad(), s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
-                                                     aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
-                                                     w.cnt, w.masks, nullptr, nullptr, 0, zw, nz, G, Tabs, nullptr, nullptr, nullptr, nullptr);
-    MCCNN_LAUNCHED();
-    if (skip_scan) return 0;   // (the fill pass that follows in the same chain scans the counts itself: find_neighbors_fill_impl)
-    int rc = exclusive_scan_i32(w.cnt, start_idx, m, total_dev, w.scanws, s, true, total_host);
-    if (rc) return rc;
-    return 0;
-}
-
-static int find_neighbors_fill_impl(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
-                              int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
-                              int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
-                              const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
-                              mccnn_stream_t stream, int* scan_start_out, int* scan_total_dev, int* scan_total_host,
-                              int max_neighbors = 0, bool sampled = false, unsigned seed = 0) {
-    if (m < 0 || n < 0 || e < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || max_neighbors < 0) return MCCNN_E_BADARG;
-    const bool capped = max_neighbors > 0;
-    const bool scan = scan_start_out != nullptr;   // the counts of a skip_scan count pass are still in `ws`: scanned here
-    if (scan && (m > MCCNN_NW_SCAN_M || !scan_total_dev)) return MCCNN_E_BADARG;
-    if (m == 0 || e == 0) return 0;
-    if (!centres || !centre_batch_ids || !sorted_pts || !cell_indexs || !aabb_min || !aabb_max || (!scan && !start_idx) || !packed)
-        return MCCNN_E_BADARG;
-    NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w, capped)) return MCCNN_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    // (mask rows are indexed by visiting position: the two passes may group differently -- the compaction gains little
-    // from more centres per wave: 100 k centres 0.0612 ms at 8, 0.0622 at 16; 800 k centres 0.305 at 8, 0.295 at 24)
-    int G = neigh_group(m);
-    if (G == 16) G = MCCNN_NW_G;
-    const float Tabs = scale_inv ? 0.0f : sqrt_threshold_host(radius);
-    size_t dyn = neigh_lds_pad();
-    if (scan && dyn < (size_t)m * sizeof(int)) dyn = (size_t)m * sizeof(int);
-    const int* scanCnt = scan ? w.cnt : nullptr;
-    if (sampled) {
-        if (neigh_lean())
-            neigh_window_sampled<true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, w.masks, start_idx, packed, e, G, Tabs, scanCnt, scan_start_out, scan_total_dev, scan_total_host,
-                max_neighbors, w.kfull, seed);
-        else
-            neigh_window_sampled<false><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, w.masks, start_idx, packed, e, G, Tabs, scanCnt, scan_start_out, scan_total_dev, scan_total_host,
-                max_neighbors, w.kfull, seed);
-    } else if (capped) {
-        if (neigh_lean())
-            neigh_window_capped<1, true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out, scan_total_dev,
-                scan_total_host, max_neighbors, w.kfull);
-        else
-            neigh_window_capped<1, false><<<ceil_div(m, 4 * G), 256, dyn, s>>>(
-                centres, centre_batch_ids, m, sorted_pts, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv,
-                centre_order, nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out, scan_total_dev,
-                scan_total_host, max_neighbors, w.kfull);
-    } else if (neigh_lean())
-        neigh_window<1, true><<<ceil_div(m, 4 * G), 256, dyn, s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
-                                                     aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
-                                                     nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out,
-                                                     scan_total_dev, scan_total_host);
-    else
-        neigh_window<1, false><<<ceil_div(m, 4 * G), 256, dyn, s>>>(centres, centre_batch_ids, m, sorted_pts, cell_indexs,
-                                                     aabb_min, aabb_max, batch_size, num_cells, radius, scale_inv, centre_order,
-                                                     nullptr, w.masks, start_idx, packed, e, nullptr, 0, G, Tabs, scanCnt, scan_start_out,
-                                                     scan_total_dev, scan_total_host);
-    MCCNN_LAUNCHED();
-    return 0;
+    MCCNN_NEIGH_SEARCH(q);
+    q.total_dev = total_dev;
+    q.total_host = total_host;
+    return find_neighbors_count_impl(q, (hipStream_t)stream);
 }
 
 int mccnn_find_neighbors_fill(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
@@ -1147,9 +1087,10 @@ int mccnn_find_neighbors_fill(const float* centres, const int* centre_batch_ids,
                               int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                               const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
                               mccnn_stream_t stream) {
-    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                    num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
-                                    nullptr, nullptr);
+    MCCNN_NEIGH_SEARCH(q);
+    q.capacity = e;
+    q.packed = packed;
+    return find_neighbors_fill_impl(q, (hipStream_t)stream);
 }
 
 // The capped search (max_neighbors = K > 0; 0 = the passes above): count -> scan -> fill at every list size, like the
@@ -1160,9 +1101,10 @@ int mccnn_find_neighbors_count_capped(const float* centres, const int* centre_ba
                                       int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                       int* start_idx, int* total_dev, void* ws, size_t ws_bytes, mccnn_stream_t stream,
                                       int max_neighbors) {
-    return find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                     num_cells, radius, scale_inv, centre_order, start_idx, total_dev, nullptr, ws, ws_bytes, stream,
-                                     false, max_neighbors);
+    MCCNN_NEIGH_SEARCH(q);
+    q.total_dev = total_dev;
+    q.max_neighbors = max_neighbors;
+    return find_neighbors_count_impl(q, (hipStream_t)stream);
 }
 
 int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
@@ -1170,9 +1112,11 @@ int mccnn_find_neighbors_fill_capped(const float* centres, const int* centre_bat
                                      int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
                                      const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
                                      mccnn_stream_t stream, int max_neighbors) {
-    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                    num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
-                                    nullptr, nullptr, max_neighbors);
+    MCCNN_NEIGH_SEARCH(q);
+    q.capacity = e;
+    q.packed = packed;
+    q.max_neighbors = max_neighbors;
+    return find_neighbors_fill_impl(q, (hipStream_t)stream);
 }
 
 // The fill pass that draws a stratified sample of the capped rows (neigh_sample.h) instead of their canonical ranks: after
@@ -1184,10 +1128,15 @@ int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_ba
                                       const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
                                       mccnn_stream_t stream, int max_neighbors, unsigned seed) {
     if (max_neighbors <= 0) return MCCNN_E_BADARG;
-    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                    num_cells, radius, scale_inv, centre_order, start_idx, e, packed, ws, ws_bytes, stream, nullptr,
-                                    nullptr, nullptr, max_neighbors, true, seed);
+    MCCNN_NEIGH_SEARCH(q);
+    q.capacity = e;
+    q.packed = packed;
+    q.max_neighbors = max_neighbors;
+    q.sampled = 1;
+    q.seed = seed;
+    return find_neighbors_fill_impl(q, (hipStream_t)stream);
 }
+#undef MCCNN_NEIGH_SEARCH
 
 }  // extern "C"
 namespace mccnn {
@@ -1195,45 +1144,24 @@ namespace mccnn {
 // count -> fill, the prefix sum of the counts rides in the fill pass (two launches); larger ones: count -> scan -> fill.
 // max_neighbors > 0: the capped passes over the capped workspace layout (the counts the fill pass scans are min(k, K));
 // sampled: the fill pass draws the stratified sample of `seed`.
-int find_neighbors_chain(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts, int n,
-                         const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
-                         float radius, int scale_inv, const int* centre_order, int* start_idx, int e_capacity, int* packed,
-                         int* total_dev, int* total_host, void* ws, size_t ws_bytes, mccnn_stream_t stream, int max_neighbors,
-                         bool sampled, unsigned seed) {
-    if (max_neighbors < 0 || (sampled && max_neighbors == 0)) return MCCNN_E_BADARG;
-    const bool small = m > 0 && m <= MCCNN_NW_SCAN_M && e_capacity > 0 && n > 0;
-    int rc = find_neighbors_count_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                       num_cells, radius, scale_inv, centre_order, start_idx, total_dev, total_host, ws, ws_bytes,
-                                       stream, small, max_neighbors);
+int find_neighbors_chain(const NeighSearch& q, hipStream_t s) {
+    if (q.max_neighbors < 0 || (q.sampled && q.max_neighbors == 0)) return MCCNN_E_BADARG;
+    const bool small = q.m > 0 && q.m <= MCCNN_NW_SCAN_M && q.capacity > 0 && q.n > 0;
+    int rc = find_neighbors_count_impl(q, s, small);
     if (rc) return rc;
-    return find_neighbors_fill_impl(centres, centre_batch_ids, m, sorted_pts, n, cell_indexs, aabb_min, aabb_max, batch_size,
-                                    num_cells, radius, scale_inv, centre_order, start_idx, e_capacity, packed, ws, ws_bytes, stream,
-                                    small ? start_idx : nullptr, small ? total_dev : nullptr, small ? total_host : nullptr,
-                                    max_neighbors, sampled, seed);
+    return find_neighbors_fill_impl(q, s, small);
 }
-}  // namespace mccnn
-extern "C" {
 
-}  // extern "C"
-namespace mccnn {
 // ---- host side of the batch form (mccnn_geometry_build_batch): one item per search / KDE, the workspace layout of the
 // single calls (neigh_ws); background settings (plain loop, centres per wave by the list's size)
 bool neigh_batch_eligible(int m, int n) { return m > 0 && n > 0 && (long long)m <= 2048LL * 1024; }
-int neigh_batch_item(NeighItem& it, ScanItem& sc, const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
-                     int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
-                     float radius, int scale_inv, const int* order, int* start_idx, int e_capacity, int* packed, int* total_dev,
-                     int* total_host, void* ws, size_t ws_bytes, NeighCapItem* cap, int max_neighbors, int sampled, unsigned seed) {
-    if (!neigh_batch_eligible(m, n)) return MCCNN_E_TOOLARGE;
-    if (max_neighbors < 0 || (sampled && max_neighbors == 0) || (max_neighbors > 0 && !cap)) return MCCNN_E_BADARG;
+int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q) {
+    if (!neigh_batch_eligible(q.m, q.n)) return MCCNN_E_TOOLARGE;
+    if (q.max_neighbors < 0 || (q.sampled && q.max_neighbors == 0)) return MCCNN_E_BADARG;
     NeighWs w;
-    if (!neigh_ws(ws, ws_bytes, m, n, w, max_neighbors > 0)) return MCCNN_E_WORKSPACE;
-    if (cap) *cap = NeighCapItem{w.kfull, max_neighbors, seed, sampled ? 1 : 0};
-    const int tiles = ceil_div(m, 2048);
-    const int G = m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1));   // (neigh_group of background launches)
-    it = NeighItem{centres, centre_batch_ids, sorted_pts, cell_indexs, aabb_min, aabb_max, order, w.cnt, w.masks, start_idx, packed,
-                   reinterpret_cast<unsigned long long*>(w.scanws), m, batch_size, num_cells, scale_inv, e_capacity, G, tiles + 1,
-                   radius, scale_inv ? 0.0f : sqrt_threshold_host(radius)};
-    sc = ScanItem{w.cnt, start_idx, reinterpret_cast<unsigned long long*>(w.scanws), total_dev, total_host, m, tiles};
+    int rc = neigh_item(q, true, it, cap, w);
+    if (rc) return rc;
+    sc = ScanItem{w.cnt, q.start_idx, it.zeroWords, q.total_dev, q.total_host, q.m, it.numZero - 1};
     return 0;
 }
 // the workgroups of the first `count` items of a batch -> the grid size
@@ -1244,30 +1172,19 @@ static int neigh_batch_blocks(const NeighBatch& nbt, int count, BatchBlocks& bb)
     for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
     return run;
 }
-int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s, const NeighCapBatch* caps) {
-    bool any = false;
-    for (int k = 0; caps && k < count; ++k) any = any || caps->it[k].capK > 0;
-    if (!any) {
-        BatchBlocks bb;
-        const int run = neigh_batch_blocks(nbt, count, bb);
-        if (run == 0) return 0;
-        if (mode == 0) neigh_window_batch<0><<<run, 256, 24000, s>>>(nbt, bb);   // (the LDS pad of background launches: neigh_lds_pad)
-        else neigh_window_batch<1><<<run, 256, 24000, s>>>(nbt, bb);
-        MCCNN_LAUNCHED();
-        return 0;
-    }
-    // a chunk with capped items: the items of each kind -- 0 uncapped, 1 capped, 2 sampled (its count pass is the capped
-    // one) -- go out together, one launch per kind that is present
+int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s) {
+    // The items of each kind -- plain, capped, sampled (its count pass is the capped one) -- go out together, one launch per
+    // kind that is present: a chunk without a capped item is the one plain launch over all its items.
     // (Items are independent searches over buffers of their own: their order inside a kind's launch does not matter. The
     // copies below are ~2.5 KB of host memory per kind and pass.)
-    for (int kind = 0; kind < 3; ++kind) {
+    for (int kind = NEIGH_PLAIN; kind <= NEIGH_SAMPLED; ++kind) {
         NeighBatch sub;
         NeighCapBatch subc;
         int cnt = 0;
         for (int k = 0; k < count; ++k) {
-            const NeighCapItem& c = caps->it[k];
-            int kd = c.capK > 0 ? (c.sampled ? 2 : 1) : 0;
-            if (mode == 0 && kd == 2) kd = 1;
+            const NeighCapItem& c = caps.it[k];
+            int kd = neigh_kind(c.capK, c.sampled);
+            if (mode == 0 && kd == NEIGH_SAMPLED) kd = NEIGH_CAPPED;
             if (kd != kind) continue;
             sub.it[cnt] = nbt.it[k];
             subc.it[cnt] = c;
@@ -1278,16 +1195,8 @@ int launch_neigh_batch(const NeighBatch& nbt, int count, int mode, hipStream_t s
         BatchBlocks bb;
         const int run = neigh_batch_blocks(sub, cnt, bb);
         if (run == 0) continue;
-        if (kind == 0) {
-            if (mode == 0) neigh_window_batch<0><<<run, 256, 24000, s>>>(sub, bb);
-            else neigh_window_batch<1><<<run, 256, 24000, s>>>(sub, bb);
-        } else if (kind == 1) {
-            if (mode == 0) neigh_window_batch_capped<0><<<run, 256, 24000, s>>>(sub, subc, bb);
-            else neigh_window_batch_capped<1><<<run, 256, 24000, s>>>(sub, subc, bb);
-        } else {
-            neigh_window_batch_sampled<<<run, 256, 24000, s>>>(sub, subc, bb);
-        }
-        MCCNN_LAUNCHED();
+        int rc = launch_neigh_kind(mode, kind, run, 24000, s, sub, subc, bb);   // (the LDS pad of background launches: neigh_lds_pad)
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1350,13 +1259,12 @@ static int compute_pdf_impl(const float* sorted_pts, const int* sorted_batch_ids
             // rows per wave: 4 consecutive rows let the next row's points fly under this row's tiles, but a list with few
             // (long) rows needs the waves -- 279 centres of 141 neighbours (BASELINE cfg1 Conv_2) ran 123 us on 70 waves
             // (and 16 waves per workgroup: a row longer than the tile planes is walked by all of them)
-            if (m >= 16384)
-                pdf_rows_mfma<4><<<ceil_div(m, 4 * MCCNN_PDF_ROWS), 256, 0, s>>>(sorted_pts, sorted_batch_ids, pk, start_idx, m, e, aabb_min,
-                                                                                aabb_max, batch_size, window, radius, scale_inv, pdfs,
-                                                                                e_dev, MCCNN_PDF_ROWS);
-            else
-                pdf_rows_mfma<16><<<ceil_div(m, 16), 1024, 0, s>>>(sorted_pts, sorted_batch_ids, pk, start_idx, m, e, aabb_min, aabb_max,
-                                                                  batch_size, window, radius, scale_inv, pdfs, e_dev, 1);
+            PdfItem it;
+            pdf_batch_item(it, sorted_pts, sorted_batch_ids, start_idx, m, packed, e, e_dev, aabb_min, aabb_max, batch_size, window, radius,
+                           scale_inv, pdfs);
+            static_assert(MCCNN_PDF_ROWS > 1, "rowsPerWave > 1 tells the list of many rows (4 waves per workgroup) from the one of few");
+            if (it.rowsPerWave > 1) pdf_rows_mfma<4><<<ceil_div(m, 4 * it.rowsPerWave), 256, 0, s>>>(it);
+            else pdf_rows_mfma<16><<<ceil_div(m, 16), 1024, 0, s>>>(it);
         }
     }
     MCCNN_LAUNCHED();
