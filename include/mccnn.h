@@ -561,7 +561,8 @@ int mccnn_geometry_build(mccnn_geometry_t* g, const float* pts, const int* batch
 
 /* Several geometries of a network step in ONE call (extension): one launch per kernel KIND over all of them -- head clear,
  * keys + histogram, prefix sums of the cell counters, park, rank + move + cell tables, count pass, prefix sums of the counts,
- * fill pass, KDE: nine launches whatever `count` is (per geometry the chain of mccnn_geometry_build is nine as well) -- with
+ * fill pass, KDE: nine launches whatever `count` is (per geometry the chain of mccnn_geometry_build is nine as well; requests
+ * with a per-point density add two kinds, the density sweep and the expansion: mccnn_geometry_build_batch_point) -- with
  * results identical to mccnn_geometry_build bit for bit. A request that shares the grid of another request names that
  * request's geometry in grid_from and comes AFTER it. */
 typedef struct mccnn_geometry_request {
@@ -598,6 +599,31 @@ int mccnn_geometry_build_capped(mccnn_geometry_t* g, const float* pts, const int
                                 int* total_host, mccnn_stream_t stream, const mccnn_neighbor_cap* cap);
 int mccnn_geometry_build_batch_capped(const mccnn_geometry_request* requests, const mccnn_neighbor_cap* caps, int count,
                                       mccnn_stream_t stream);
+/* The PDFs of a geometry from a per-point density (pdfMode='point'): density [n] f32 and counts [n] i32 are the
+ * caller's buffers for the grid's points at this window.
+ * ready == 0: the build computes them (once, right after the grid) and expands them over the list.
+ * ready != 0: they already hold the density of this grid and window, written by work ordered before this call on `stream`,
+ *             and the build only expands.
+ * The chain of one geometry then is [head clear] grid build [density sweep] [visiting order] count (scan) fill expansion:
+ * the sweep is mccnn_compute_pdf_points (the same bytes), the expansion mccnn_expand_pdf reading the edge total from the
+ * geometry's device word, in the place of the KDE -- whose workspace stays unused; the geometry buffer is that of
+ * mccnn_geometry_bytes, the density lives outside it. point == NULL, points == NULL or an entry with density == NULL: edge
+ * mode, the launches and bytes of the entries above. A point request needs use_pdf != 0 and no cap, and both pointers:
+ * MCCNN_E_BADARG otherwise (a per-point density over a capped row is far noisier than the per-edge one, see README).
+ * mccnn_geometry_build_batch_point: points[k] belongs to requests[k]. Beside the nine launches of a chunk there are two
+ * further kinds: ONE density sweep behind the grid phases over the distinct `density` pointers of the chunk that are not
+ * ready, and ONE expansion over its point geometries in front of the KDE launch of its edge geometries (which is left out
+ * when there is none). Several requests may name the same density: the first one that is not ready computes it, the others
+ * come AFTER it in the array and only expand (the rule of grid_from), in whichever chunk or chain they end up. */
+typedef struct mccnn_point_pdf { float* density; int* counts; int ready; } mccnn_point_pdf;
+int mccnn_geometry_build_point(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                               const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max,
+                               int batch_size, int num_cells, float radius, int scale_inv, float window, int use_pdf,
+                               int e_capacity, const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes,
+                               int* total_host, mccnn_stream_t stream, const mccnn_neighbor_cap* cap,
+                               const mccnn_point_pdf* point);
+int mccnn_geometry_build_batch_point(const mccnn_geometry_request* requests, const mccnn_neighbor_cap* caps,
+                                     const mccnn_point_pdf* points, int count, mccnn_stream_t stream);
 /* E, or -1 while the count pass has not retired (wait_us: 0 = look once, < 0 = wait, > 0 = wait at most that long). */
 int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
 /* out[0..7]: device addresses of sortPts [n,3], sortBatchs [n], cellIndexs [B,nc,nc,nc,2], index_new_pos [n], its

@@ -343,11 +343,17 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge'):
+                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False):
         """pdfMode (extension): 'edge' (default) -- the reference's density, a Gaussian sum over the centre's row for every
         edge (compute_pdf); 'point' -- the density of every point over its OWN ball, computed once per (grid, KDEWindow)
         and shared by every list over that grid (compute_pdf_points + expand_pdf). A 'point' layer with usePDF takes the
-        op-by-op path, needs an uncapped list and points without a gradient; without usePDF the mode has no effect.
+        op-by-op path unless pointNative is set, needs an uncapped list and points without a gradient; without usePDF the
+        mode has no effect.
+        pointNative (extension, default False): True sends 'point' layers through the native step executor like 'edge'
+        ones -- one library call per geometry (mccnn_geometry_build_point: the density sweep once per grid and window right
+        behind the grid, its expansion in the place of the KDE), learned prefetch, prefetch_step, prefetch_geometry and the
+        batch form included -- with the bytes of the op-by-op path; the geometry is filed in cacheGeo_ under keyPDF + '|pt'.
+        The attribute pointNative_ may be reassigned between steps (followed by reset()).
         maxNeighbors (extension): the default cap on the neighbours per centre of every layer's search (find_neighbors(
         maxNeighbors=)); 0 = no cap. A capped layer takes the op-by-op path unless capNative is set.
         capNative (extension, default False): True sends capped layers through the native step executor like uncapped
@@ -364,6 +370,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("capNative must be True or False")
         self.capNative_ = capNative
+        if not isinstance(pointNative, bool):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("pointNative must be True or False")
+        self.pointNative_ = pointNative
         self.pdfMode_ = self.__check_pdf_mode__(pdfMode)
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
@@ -385,7 +395,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.geoPrefetch_ = _env.flag("GEO_PREFETCH")
         self.geoSeen_ = {}
         self.geoPlan_ = []
-        self.prefetchedGeo_ = {}    # prefetch_geometry() on the native path: keyPDF -> (Geometry, keyGrid, keyNeighs, usePDF, transposed)
+        self.prefetchedGeo_ = {}    # prefetch_geometry() on the native path: keyPDF [+ '|pt'] -> (Geometry, keyGrid, keyNeighs, usePDF, transposed, point, KDEWindow, keyPDF)
         self.multiFeatureConvs_ = multiFeatureConvs
         self.KDEWindow_ = KDEWindow
         self.relativeRadius_ = relativeRadius
@@ -623,15 +633,20 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geometry is prefetched op by op on the side stream, or -- with capNative_ -- by the native executor like an
         uncapped one.
         sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call).
-        pdfMode: the mode of that call (None = the builder's). The per-point density has no prefetched form: 'point' with
-        usePDF raises."""
+        pdfMode: the mode of that call (None = the builder's). The per-point density has a prefetched form on the native
+        executor only: 'point' with usePDF raises unless pointNative_ is set, and then parks a native point geometry (where
+        the native executor cannot take the levels nothing is started: create_convolution computes them itself)."""
         currKDEWindow, currRelativeRadius, currUsePDF, outPH, outLevel = self.__geometry_defaults__(
             inPointHierarchy, inPointLevel, outPointHierarchy, outPointLevel, KDEWindow, relativeRadius, usePDF)
-        if self.__check_pdf_mode__(self.pdfMode_ if pdfMode is None else pdfMode) == 'point' and currUsePDF:
+        pointPDF = self.__check_pdf_mode__(self.pdfMode_ if pdfMode is None else pdfMode) == 'point' and bool(currUsePDF)
+        if pointPDF and not self.pointNative_:
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("prefetch_geometry: pdfMode='point' has no prefetched form (its layers build their "
                                        "geometry themselves, op by op)")
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
+        if pointPDF and currCap > 0:
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0)")
         currSeed = self.__layer_seed__(currCap, sampleSeed)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
                                                                currKDEWindow, currRelativeRadius, currUsePDF, currCap, currSeed)
@@ -641,8 +656,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             return  # host tensors (a CPU checker behind `ops=`): nothing to overlap, create_convolution computes inline
         if (currCap == 0 or self.capNative_) and self.__prefetch_native__(
                 inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow, currRelativeRadius, currUsePDF,
-                keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed):
+                keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed, point=pointPDF):
             return
+        if pointPDF:
+            return  # (no op-by-op prefetched form)
         if self.sideStream_ is None:
             self.sideStream_ = torch.cuda.Stream(device=pts.device)
         _SIDE_EVENTS[0] = True   # (hierarchies and reset()s record their events from here on)
@@ -764,9 +781,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 return None
         return inPts, inBids, centres, cBids
 
-    def __file_geometry__(self, geo, keyGrid, keyNeighs, keyPDF, usePDF, trace):
+    def __file_geometry__(self, geo, keyGrid, keyNeighs, keyPDF, usePDF, trace, point=False, window=None):
         """Files a native geometry under the reference's cache keys: the geometry itself, lazy views of its grid (when it
-        owns one), neighbour list and PDFs. trace: record the ops the op-by-op path would have run for them."""
+        owns one), neighbour list and PDFs. trace: record the ops the op-by-op path would have run for them. point
+        (pointNative_): geometry and PDFs go under keyPDF + '|pt', the density pair the grid shares at `window` under
+        keyGrid + '|' + str(window) -- filed (and traced) by the first geometry that names it."""
+        if point:
+            keyPDF = keyPDF + '|pt'
         self.cacheGeo_[keyPDF] = geo
         if geo.grid_owner is None:
             self.cacheGeoGrid_[keyGrid] = geo
@@ -778,12 +799,21 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
         if trace:
             self._trace("find_neighbors", keyNeighs)
-            if usePDF:
-                self._trace("compute_pdf", keyPDF)
+        if point:
+            keyDensity = keyGrid + '|' + str(window)
+            if keyDensity not in self.cachePointPDFs_:
+                self.cachePointPDFs_[keyDensity] = _LazyEntry(geo, geo.point_density)
+                if trace:
+                    self._trace("compute_pdf_points", keyDensity)
+            if trace:
+                self._trace("expand_pdf", keyPDF)
+        elif trace and usePDF:
+            self._trace("compute_pdf", keyPDF)
 
     def __unfile_geometry__(self, geo, keyGrid, keyNeighs=None, keyPDF=None):
-        """Takes `geo` out of the caches again: its grid (when it is the one filed under keyGrid) and, with the other two
-        keys, the geometry, its neighbour list and PDFs."""
+        """Takes `geo` out of the caches again: its grid (when it is the one filed under keyGrid, with the per-point
+        densities over it) and, with the other two keys (keyPDF: the key the geometry is filed under), the geometry, its
+        neighbour list and PDFs."""
         if keyPDF is not None:
             self.cacheGeo_.pop(keyPDF, None)
             self.cachePDFs_.pop(keyPDF, None)
@@ -791,10 +821,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if self.cacheGeoGrid_.get(keyGrid) is geo:
             self.cacheGeoGrid_.pop(keyGrid, None)
             self.cacheGrids_.pop(keyGrid, None)
+            for k, v in list(self.cachePointPDFs_.items()):
+                if isinstance(v, _LazyEntry) and (v.geo.grid_owner or v.geo) is geo:
+                    self.cachePointPDFs_.pop(k, None)
 
     def __plan_entries__(self, ph, sampleSeed=None):
         """The geometries the last step used over a hierarchy of `ph`'s name whose levels `ph` has: (entry, keyGrid,
-        keyNeighs, keyPDF, search keywords) each, the keys computed for `ph`. The plan knows the cap of a capped layer, not
+        keyNeighs, keyPDF, search keywords, point mode) each, the keys computed for `ph`. The plan knows the cap of a capped layer, not
         its seed: sampleSeed is the layers' seed of the step the geometries are for (part of the capped keys)."""
         name, levels = ph.hierarchyName_, len(ph.points_)
         for ent in self.geoPlan_:
@@ -803,10 +836,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             cap = ent[9] if len(ent) > 9 else 0
             seed = sampleSeed if cap > 0 else None
             keys = self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6], cap, seed)
-            yield (ent,) + keys + (self.__search_args__(cap, seed, keys[1]),)
+            yield (ent,) + keys + (self.__search_args__(cap, seed, keys[1]), len(ent) > 10 and ent[10] == 'point')
 
     def __prefetch_native__(self, inPH, inLevel, convRadius, outPH, outLevel, KDEWindow, relativeRadius, usePDF, keyGrid,
-                            keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None):
+                            keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None, point=False):
         """prefetch_geometry() on the native step executor: the geometry is ONE buffer, allocated on the CALLER's stream and
         written on a side stream that starts behind everything the caller's stream holds at this moment; the layers that
         use it order their stream behind its event. No reference counting decides anything: the buffer goes back to the
@@ -823,9 +856,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             return False
         inPts, inBids, centres, cBids = inputs
         want = 0 if not transposed else (1 if transposed == "list" else 2)   # nothing | transposed list | + transposed row plan
-        if keyPDF in self.prefetchedGeo_:
-            ent = self.prefetchedGeo_[keyPDF]
-            self.prefetchedGeo_[keyPDF] = ent[:4] + (max(ent[4], want),)
+        keyGeo = keyPDF + '|pt' if point else keyPDF
+        if keyGeo in self.prefetchedGeo_:
+            ent = self.prefetchedGeo_[keyGeo]
+            self.prefetchedGeo_[keyGeo] = ent[:4] + (max(ent[4], want),) + ent[5:]
             return True
         mn, mx, B = inPH.aabbMin_, inPH.aabbMax_, inPH.batchSize_
         nc = _hip_ops_mod()._num_cells(mn, mx, B, convRadius, relativeRadius)
@@ -834,13 +868,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         k = len(self.prefetchedGeo_)
         geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                      usePDF, owner, side=k, fork=fork, background=True,
-                                     after=(inPH.prefetchFuture_ if inPH is outPH else None),
+                                     after=(inPH.prefetchFuture_ if inPH is outPH else None), pointPDF=point,
                                      **self.__search_args__(currCap, currSeed, keyNeighs))
         if owner is None:
             owners[keyGrid] = geo
         if pieces:   # row plans / transposed list the layers of the last step used: attached and issued by a helper thread
             geo.prebuild_async(pieces, self.useAVG_)
-        self.prefetchedGeo_[keyPDF] = (geo, keyGrid, keyNeighs, usePDF, want)
+        self.prefetchedGeo_[keyGeo] = (geo, keyGrid, keyNeighs, usePDF, want, point, KDEWindow, keyPDF)
         return True
 
     def prefetch_step(self, pointHierarchy, sampleSeed=None):
@@ -856,24 +890,24 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geometries are filed under that seed's keys, so `cb.prefetch_step(ph_next, sampleSeed=step + 1)` followed by
         `cb.sampleSeed_ = step + 1; cb.reset()` finds them. One prefetched with another seed is never asked for and is
         dropped at the reset() after.
-        Layers with pdfMode='point' (and usePDF) are skipped: they never enter the plan, which lists what the native
-        executor built."""
+        Layers with pdfMode='point' (and usePDF) are part of the plan under pointNative_ (the plan remembers a layer's
+        mode); without it they never enter the plan, which lists what the native executor built."""
         started = 0
         seed = self.__check_seed__(self.sampleSeed_ if sampleSeed is None else sampleSeed)
         pieces = _env.debug("plan_prefetch", True)
         _native = _native_mod()
         _native.begin_batch()   # the step's geometries go out together: one launch per kernel kind over all of them
         try:
-            for ent, keyGrid, keyNeighs, keyPDF, capArgs in self.__plan_entries__(pointHierarchy, seed):
+            for ent, keyGrid, keyNeighs, keyPDF, capArgs, point in self.__plan_entries__(pointHierarchy, seed):
                 _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
-                if keyPDF in self.prefetchedGeo_:
+                if (keyPDF + '|pt' if point else keyPDF) in self.prefetchedGeo_:
                     continue
-                if capArgs and not self.capNative_:
+                if (capArgs and not self.capNative_) or (point and not self.pointNative_):
                     continue
                 if self.__prefetch_native__(pointHierarchy, inLevel, radius, pointHierarchy, outLevel, window, rel, usePDF,
                                             keyGrid, keyNeighs, keyPDF, False, fork=(started == 0),
                                             pieces=(have if pieces else 0), currCap=(ent[9] if len(ent) > 9 else 0),
-                                            currSeed=(seed if len(ent) > 9 else None)):
+                                            currSeed=(seed if len(ent) > 9 else None), point=point):
                     started += 1
         finally:
             _native.end_batch()
@@ -886,9 +920,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         _native = _native_mod()
         parked, self.prefetchedGeo_ = self.prefetchedGeo_, {}
         self.__dict__["prefetchedGridOwner_"] = {}
-        for keyPDF, (geo, keyGrid, keyNeighs, usePDF, transposed) in parked.items():
+        for _keyGeo, (geo, keyGrid, keyNeighs, usePDF, transposed, point, window, keyPDF) in parked.items():
             geo.unverified = True   # (checked against the hierarchy's tensors at its first use)
-            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, False)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, False, point, window)
             if transposed:
                 # (depth-wise layers: both row plans -- the forward pass then waits for the first stage only)
                 geo.prebuild((_native.NEED_PLAN_FWD | _native.NEED_PLAN_TR) if transposed == 2 else _native.NEED_TLIST,
@@ -903,11 +937,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         mn, mx, B = ph.aabbMin_, ph.aabbMax_, ph.batchSize_
         k = 0
         pieces = _env.debug("plan_prefetch", True)
-        for ent, keyGrid, keyNeighs, keyPDF, capArgs in self.__plan_entries__(ph, self.__check_seed__(self.sampleSeed_)):
+        for ent, keyGrid, keyNeighs, keyPDF, capArgs, point in self.__plan_entries__(ph, self.__check_seed__(self.sampleSeed_)):
             _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
-            if keyPDF in self.cacheGeo_:
+            if (keyPDF + '|pt' if point else keyPDF) in self.cacheGeo_:
                 continue
-            if capArgs and not self.capNative_:
+            if (capArgs and not self.capNative_) or (point and not self.pointNative_):
                 continue
             inputs = self.__native_inputs__(ph, inLevel, ph, outLevel)
             if inputs is None:
@@ -916,20 +950,23 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             nc = _hip_ops._num_cells(mn, mx, B, radius, rel)
             owner = self.cacheGeoGrid_.get(keyGrid)
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, radius, rel, window, usePDF, owner,
-                                         side=k, fork=(k == 0), after=ph.prefetchFuture_, **capArgs)
+                                         side=k, fork=(k == 0), after=ph.prefetchFuture_, pointPDF=point, **capArgs)
             k += 1
             if have and pieces and geo.e_cap <= _PLAN_PREFETCH_MAX_E:
                 geo.prebuild_async(have, self.useAVG_)
-            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True, point, window)
 
     def __native_convolution__(self, convName, inPH, inLevel, inFeatures, inNumFeatures, convRadius, outPH, outLevel,
                                multiFeatureConv, numOutFeatures, KDEWindow, relativeRadius, usePDF, useAVG, keyGrid,
-                               keyNeighs, keyPDF, currCap=0, currSeed=None):
+                               keyNeighs, keyPDF, currCap=0, currSeed=None, point=False):
         """create_convolution on the native step executor (mccnn_amd.native): the geometry of (keyGrid, keyNeighs, keyPDF)
         is ONE library call (no host wait), the layer one call per direction with the feature sort inside. Returns None
         when this call has to take the op-by-op path: a cache entry of that path exists already (prefetch_geometry), the
         level is empty, or the features are not rows the library reads in place. currCap / currSeed (capNative_): the
-        layer's cap and seed -- the geometry's search is the capped one, with the seed the op would get (__search_args__)."""
+        layer's cap and seed -- the geometry's search is the capped one, with the seed the op would get (__search_args__).
+        point (pointNative_): the PDFs are the grid's per-point density expanded over the list; the geometry and its PDFs
+        are filed under keyPDF + '|pt'."""
+        keyGeo = keyPDF + '|pt' if point else keyPDF
         _native = _native_mod()
         _hip_ops = _hip_ops_mod()
         # (a step with a handful of geometries gains nothing: the hops between the streams cost what the overlap saves --
@@ -937,7 +974,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if (not self.cacheGeo_ and self.geoPrefetch_ and len(self.geoPlan_) >= _GEO_PREFETCH_MIN and inPH is outPH and self.prefetched_ is None
                 and not self.cacheGrids_ and _native.side_streams_available()):
             self.__prebuild_geometries__(inPH)
-        geo = self.cacheGeo_.get(keyPDF)
+        geo = self.cacheGeo_.get(keyGeo)
         if geo is not None and getattr(geo, "unverified", False):
             # a geometry started ahead (prefetch_geometry / prefetch_step) is filed under the reference's cache keys -- names,
             # levels, radii -- like everything else; before its first use it is checked against the tensors it was built
@@ -951,14 +988,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 if _GEO_TRACE:
                     print("native conv %s: parked geometry %s not for this hierarchy (built from %s / %s, asked %s / %s)" % (
                         convName, keyPDF, tuple(a[0].shape), tuple(a[2].shape), tuple(pin.shape), tuple(cen.shape)), file=sys.stderr)
-                self.__unfile_geometry__(geo, keyGrid, keyNeighs, keyPDF)
+                self.__unfile_geometry__(geo, keyGrid, keyNeighs, keyGeo)
                 geo = None
         if geo is None:
             if keyGrid in self.cacheGrids_ and keyGrid not in self.cacheGeoGrid_:
                 if _GEO_TRACE:
                     print("native conv %s: grid %s owned by the op path" % (convName, keyGrid), file=sys.stderr)
                 return None   # the op-by-op path (or a prefetch) owns this grid
-            if keyNeighs in self.cacheNeighs_ or keyPDF in self.cachePDFs_:
+            if keyNeighs in self.cacheNeighs_ or keyGeo in self.cachePDFs_:
                 if _GEO_TRACE:
                     print("native conv %s: list %s / pdf %s cached without a geometry (%s %s); geometries: %s" % (
                         convName, keyNeighs, keyPDF, keyNeighs in self.cacheNeighs_, keyPDF in self.cachePDFs_,
@@ -977,15 +1014,16 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                     self.__unfile_geometry__(owner, keyGrid)
                     owner = None
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
-                                         usePDF, owner, **self.__search_args__(currCap, currSeed, keyNeighs))
+                                         usePDF, owner, pointPDF=point, **self.__search_args__(currCap, currSeed, keyNeighs))
             if owner is not None:   # (a shared grid: the layer sorts its rows only, as on a cache hit)
                 self._trace("sort_features", keyGrid)
-            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True)
+            self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True, point, KDEWindow)
         else:
             self._trace("sort_features", keyGrid)
-        if inPH is outPH and keyPDF not in self.geoSeen_:
-            self.geoSeen_[keyPDF] = (inPH.hierarchyName_, inLevel, outLevel, convRadius, KDEWindow, relativeRadius, usePDF) + \
-                ((currCap,) if currCap > 0 else ())
+        if inPH is outPH and keyGeo not in self.geoSeen_:
+            # (the plan remembers a layer's cap and, behind it, its mode)
+            self.geoSeen_[keyGeo] = (inPH.hierarchyName_, inLevel, outLevel, convRadius, KDEWindow, relativeRadius, usePDF) + \
+                ((0, 'point') if point else ((currCap,) if currCap > 0 else ()))
         feats = inFeatures
         if _GEO_TRACE and feats.dim() == 2 and feats.shape[0] != geo.n:
             print("native conv %s: %d feature rows for a geometry over %d points (key %s, unverified %s, built from %s, level has %s)" % (
@@ -1025,8 +1063,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # pdfMode (extension; None = the builder's pdfMode_): 'point' with usePDF takes the density of every point over its
         # own ball (one compute_pdf_points per grid and window, cachePointPDFs_) and spreads it over the list's edges
         # (expand_pdf, filed under keyPDF + '|pt') instead of compute_pdf -- on the op-by-op path below, like a capped
-        # layer: no native executor, no deferred search + KDE, no learned prefetch. It needs an uncapped list and points
-        # without a gradient. Without usePDF the mode has no effect.
+        # layer: no native executor, no deferred search + KDE, no learned prefetch -- unless the builder was made with
+        # pointNative=True (pointNative_): then it runs through the native executor like an 'edge' layer, with the same
+        # bytes. It needs an uncapped list and points without a gradient. Without usePDF the mode has no effect.
         # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
         # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
         # like one whose points require a gradient, unless the builder was made with capNative=True (capNative_): then it
@@ -1067,11 +1106,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 raise InvalidArgumentError("pdfMode='point' is not differentiable with respect to the points: they must not "
                                            "require a gradient")
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
-        if self.native_ and fused and not pointPDF and (currCap == 0 or self.capNative_):
+        if self.native_ and fused and (not pointPDF or self.pointNative_) and (currCap == 0 or self.capNative_):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
-                                              keyGrid, keyNeighs, keyPDF, currCap, currSeed)
+                                              keyGrid, keyNeighs, keyPDF, currCap, currSeed, pointPDF)
             if out is not None:
                 return out
 

@@ -41,6 +41,21 @@ struct PdfItem {
     float window, radius;
 };
 struct PdfBatch { PdfItem it[MCCNN_BATCH_MAX]; };
+// one per-point density sweep (pdf_points.hip): the sorted points of a grid, its cell table and boxes -> density, counts
+struct PointPdfItem {
+    const float* pts; const int* bids; const int* cells; const float* mn; const float* mx; float* density; int* counts;
+    int n, B, nc, scaleInv;
+    float window, radius, Tabs;
+};
+struct PointPdfBatch { PointPdfItem it[MCCNN_BATCH_MAX]; };
+// one expansion of a density over a list whose edge total lives in a device word: pdfs[e] = density[j] / len_i, e < min(*totalDev, eCap)
+struct ExpandItem {
+    const float* density; const int* startIdx; const int2* packed; const int* totalDev; float* pdfs;
+    int n, m, eCap;
+};
+struct ExpandBatch { ExpandItem it[MCCNN_BATCH_MAX]; };
+static_assert(sizeof(PointPdfBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched density sweep: < 4 KB");
+static_assert(sizeof(ExpandBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched expansion: < 4 KB");
 
 // ---- small row plans of a step (mccnn_geometry_prebuild_batch): transposition, layout and fill of every small list as one
 // launch each. (12 items per launch: the fill's item carries the geometry an inline record is evaluated from.)
@@ -127,5 +142,15 @@ void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batc
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,
                     float radius, int scale_inv, float* pdfs);
 int launch_pdf_batch(const PdfBatch& pb, int count, hipStream_t s);
+// pdf_points.hip: the per-point density and its expansion as items (single launches take the same records)
+int point_pdf_item(PointPdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, int n, const int* cell_indexs,
+                   const float* aabb_min, const float* aabb_max, int batch_size, int num_cells, float window, float radius,
+                   int scale_inv, float* density, int* counts);
+int launch_point_pdf(const PointPdfItem& it, hipStream_t s);
+int launch_point_pdf_batch(const PointPdfBatch& pb, int count, hipStream_t s);
+int expand_item(ExpandItem& it, const float* density, int n, const int* start_idx, int m, const int* packed, int e_capacity,
+                const int* total_dev, float* pdfs);
+int launch_expand_dn(const ExpandItem& it, hipStream_t s);
+int launch_expand_batch(const ExpandBatch& eb, int count, hipStream_t s);
 
 }  // namespace mccnn

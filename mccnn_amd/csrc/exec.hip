@@ -5,6 +5,8 @@
 //     wait -- the geometry one (level, radius, output level) cache entry of the builder stands for (:349-391);
 //     mccnn_geometry_build_capped / _build_batch_capped: the same with a cap on the neighbours per centre (and, optionally,
 //     the seed of a stratified sample) handed to the search -- the capped passes of find_neighbors in the same chain;
+//     mccnn_geometry_build_point / _build_batch_point: the same with the PDFs taken from a per-point density (pdfMode='point':
+//     mccnn_compute_pdf_points once per grid and window, its expansion over the list in the place of compute_pdf);
 //   * mccnn_conv_forward / mccnn_conv_backward : the convolution of one layer over a geometry, INCLUDING the feature sort
 //     (sort_features / its gradient, MCConvModuleSrc:35-45), the choice of the kernel family (row-per-lane depth-wise,
 //     factored Fin = 1, edge streaming) and the row plans / transposed list a family needs, built on first use and kept
@@ -74,6 +76,10 @@ struct mccnn_geometry {
     float radius = 0.f, window = 0.f;
     int cap_k = 0, cap_sampled = 0;  // the search's cap (0 = none) and whether it draws the sample of cap_seed
     unsigned cap_seed = 0;
+    // the per-point density the PDFs are expanded from (the caller's buffers; nullptr: edge mode) and whether it is there already
+    float* pp_density = nullptr;
+    int* pp_counts = nullptr;
+    bool pp_ready = false;
     // the geometry buffer
     char* buf = nullptr;
     size_t bytes = 0;
@@ -322,13 +328,17 @@ namespace {
 int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                    const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                    float radius, int scale_inv, float window, int use_pdf, int e_capacity, const mccnn_geometry_t* grid_from,
-                   void* buffer, size_t buffer_bytes, int* total_host, bool in_batch, const mccnn_neighbor_cap* cap) {
+                   void* buffer, size_t buffer_bytes, int* total_host, bool in_batch, const mccnn_neighbor_cap* cap,
+                   const mccnn_point_pdf* point) {
     if (!g || !pts || !batch_ids || !centres || !centre_batch_ids || !aabb_min || !aabb_max || !buffer || !total_host)
         return MCCNN_E_BADARG;
     if (n <= 0 || m <= 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.f) || e_capacity <= 0) return MCCNN_E_BADARG;
     if (use_pdf && !(window > 0.f)) return MCCNN_E_BADARG;
     if (cap && (cap->max_neighbors < 0 || (cap->sampled && cap->max_neighbors == 0))) return MCCNN_E_BADARG;
     const int cap_k = cap ? cap->max_neighbors : 0;
+    // a per-point density: both buffers, PDFs asked for, no cap (both null: edge mode)
+    const bool pp = point && (point->density || point->counts);
+    if (pp && (!point->density || !point->counts || !use_pdf || cap_k > 0)) return MCCNN_E_BADARG;
     if (grid_from && (grid_from->n != n || grid_from->nc != num_cells || grid_from->B != batch_size ||
                       !(grid_owner(grid_from)->built || (in_batch && grid_owner(grid_from)->s_pts))))
         return MCCNN_E_BADARG;
@@ -341,6 +351,7 @@ int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, 
     g->n = n; g->m = m; g->B = batch_size; g->nc = num_cells; g->scale_inv = scale_inv ? 1 : 0; g->use_pdf = use_pdf ? 1 : 0;
     g->radius = radius; g->window = window;
     g->cap_k = cap_k; g->cap_sampled = (cap && cap_k > 0 && cap->sampled) ? 1 : 0; g->cap_seed = g->cap_sampled ? cap->seed : 0u;
+    if (pp) { g->pp_density = point->density; g->pp_counts = point->counts; g->pp_ready = point->ready != 0; }
     g->same_level = (centres == pts && m == n) ? 1 : 0;
     g->buf = (char*)buffer; g->bytes = buffer_bytes;
     char* b = g->buf;
@@ -392,7 +403,18 @@ NeighSearch geometry_search(const mccnn_geometry_t* g, const int* order) {
     return q;
 }
 
-// the chain of ONE geometry: [head clear] grid build (4 launches) [visiting order (3)] count (scan) fill KDE
+// the density sweep / the expansion of a point geometry as pdf_points.hip takes them (single launch and batch item alike)
+int geometry_point_item(const mccnn_geometry_t* g, PointPdfItem& it) {
+    const mccnn_geometry* go = grid_owner(g);
+    return point_pdf_item(it, go->s_pts, go->s_bids, g->n, go->cells, g->mn, g->mx, g->B, g->nc, g->window, g->radius, g->scale_inv,
+                          g->pp_density, g->pp_counts);
+}
+int geometry_expand_item(const mccnn_geometry_t* g, ExpandItem& it) {
+    return expand_item(it, g->pp_density, g->n, g->start, g->m, g->packed, g->e_cap, g->total_dev, g->pdfs);
+}
+
+// the chain of ONE geometry: [head clear] grid build (4 launches) [density sweep] [visiting order (3)] count (scan) fill
+// KDE | expansion
 int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const int n = g->n, m = g->m, batch_size = g->B, num_cells = g->nc;
@@ -410,6 +432,12 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
         if (rc) return rc;
     }
     const mccnn_geometry* go = grid_owner(g);
+    if (g->pp_density && !g->pp_ready) {   // once per grid and window: right behind the grid (no workspace of its own)
+        PointPdfItem it;
+        if ((rc = geometry_point_item(g, it))) return rc;
+        if ((rc = launch_point_pdf(it, s))) return rc;
+        g->pp_ready = true;
+    }
     const int* order = nullptr;
     if (g->same_level) {
         order = go->inv_idx;
@@ -421,7 +449,11 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
     }
     rc = find_neighbors_chain(geometry_search(g, order), s);
     if (rc) return rc;
-    if (g->use_pdf) {
+    if (g->pp_density) {
+        ExpandItem it;
+        if ((rc = geometry_expand_item(g, it))) return rc;
+        if ((rc = launch_expand_dn(it, s))) return rc;
+    } else if (g->use_pdf) {
         rc = mccnn_compute_pdf_dn(go->s_pts, go->s_bids, g->start, m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, batch_size,
                                   g->window, g->radius, g->scale_inv, g->pdfs, g->ws, g->ws_bytes, stream);
         if (rc) return rc;
@@ -435,7 +467,10 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
 
 // ONE launch per kernel kind over a chunk of <= MCCNN_BATCH_MAX geometries (and <= MCCNN_BATCH_MAX counting sorts): head
 // clear, keys + histogram, prefix sums of the cell counters, park, rank + move + cell tables, count pass, prefix sums of
-// the counts, fill pass, KDE -- nine launches whatever the number of geometries (a step of BASELINE cfg4 has fourteen).
+// the counts, fill pass, KDE -- nine launches whatever the number of geometries (a step of BASELINE cfg4 has fourteen). Point
+// geometries add two kinds: ONE density sweep behind the grid phases over the densities of the chunk that are not there
+// yet (distinct pointers: mccnn_geometry_build_batch_point marks every later user of a density ready), ONE expansion behind
+// the fill pass; the KDE launch then covers the edge geometries alone and is left out when there is none.
 int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     GridBatch gridB;
@@ -443,9 +478,11 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     NeighBatch neighB;
     NeighCapBatch capB;
     PdfBatch pdfB;
+    PointPdfBatch ppB;
+    ExpandBatch exB;
     SpanBatch spans;
     spans.count = 0;
-    int nGrid = 0, nPdf = 0;
+    int nGrid = 0, nPdf = 0, nPp = 0, nEx = 0;
     int rc;
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];
@@ -480,11 +517,20 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     }
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];
+        if (!g->pp_density || g->pp_ready) continue;
+        if ((rc = geometry_point_item(g, ppB.it[nPp++]))) return rc;
+        g->pp_ready = true;
+    }
+    if (nPp && (rc = launch_point_pdf_batch(ppB, nPp, s))) return rc;
+    for (int k = 0; k < count; ++k) {
+        mccnn_geometry_t* g = gs[k];
         const mccnn_geometry* go = grid_owner(g);
         const int* order = g->same_level ? go->inv_idx : g->order;
         rc = neigh_batch_item(neighB.it[k], capB.it[k], scanN.it[k], geometry_search(g, order));
         if (rc) return rc;
-        if (g->use_pdf)
+        if (g->pp_density) {
+            if ((rc = geometry_expand_item(g, exB.it[nEx++]))) return rc;
+        } else if (g->use_pdf)
             pdf_batch_item(pdfB.it[nPdf++], go->s_pts, go->s_bids, g->start, g->m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, g->B,
                            g->window, g->radius, g->scale_inv, g->pdfs);
     }
@@ -492,6 +538,7 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     if ((rc = launch_neigh_batch(neighB, capB, count, 0, s))) return rc;
     if ((rc = launch_scan_batch(scanN, count, s))) return rc;
     if ((rc = launch_neigh_batch(neighB, capB, count, 1, s))) return rc;
+    if (nEx && (rc = launch_expand_batch(exB, nEx, s))) return rc;
     if (nPdf && (rc = launch_pdf_batch(pdfB, nPdf, s))) return rc;
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];
@@ -506,16 +553,26 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
 }  // namespace
 extern "C" {
 
-// (the uncapped entries are the capped ones with no cap)
+// (the uncapped entries are the capped ones with no cap, the capped ones the point ones with no point record)
+int mccnn_geometry_build_point(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                               const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
+                               int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
+                               const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
+                               mccnn_stream_t stream, const mccnn_neighbor_cap* cap, const mccnn_point_pdf* point) {
+    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
+                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false, cap, point);
+    if (rc) return rc;
+    return geometry_issue_single(g, stream);
+}
+
 int mccnn_geometry_build_capped(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                                 const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
                                 int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
                                 const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
                                 mccnn_stream_t stream, const mccnn_neighbor_cap* cap) {
-    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
-                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false, cap);
-    if (rc) return rc;
-    return geometry_issue_single(g, stream);
+    return mccnn_geometry_build_point(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells,
+                                      radius, scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host,
+                                      stream, cap, nullptr);
 }
 
 int mccnn_geometry_build(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
@@ -538,14 +595,29 @@ int mccnn_geometry_build_batch(const mccnn_geometry_request* req, int count, mcc
 // the reverse: the cap belongs to the search alone.
 int mccnn_geometry_build_batch_capped(const mccnn_geometry_request* req, const mccnn_neighbor_cap* caps, int count,
                                       mccnn_stream_t stream) {
+    return mccnn_geometry_build_batch_point(req, caps, nullptr, count, stream);
+}
+
+// points[k]: the per-point density of req[k] (points == NULL, or density == NULL: edge mode). A density named by several
+// requests is computed by the first of them that is not ready; the later ones are marked ready HERE, before anything is
+// issued -- whichever chunk or chain each ends up in, the sweep goes out once and the stream orders the rest.
+int mccnn_geometry_build_batch_point(const mccnn_geometry_request* req, const mccnn_neighbor_cap* caps, const mccnn_point_pdf* points,
+                                     int count, mccnn_stream_t stream) {
     if (!req || count < 0) return MCCNN_E_BADARG;
     for (int k = 0; k < count; ++k) {
         const mccnn_geometry_request& r = req[k];
         int rc = geometry_setup(r.geometry, r.pts, r.batch_ids, r.n, r.centres, r.centre_batch_ids, r.m, r.aabb_min, r.aabb_max,
                                 r.batch_size, r.num_cells, r.radius, r.scale_inv, r.window, r.use_pdf, r.e_capacity, r.grid_from,
-                                r.buffer, r.buffer_bytes, r.total_host, true, caps ? &caps[k] : nullptr);
+                                r.buffer, r.buffer_bytes, r.total_host, true, caps ? &caps[k] : nullptr, points ? &points[k] : nullptr);
         if (rc) return rc;
     }
+    if (points)
+        for (int k = 1; k < count; ++k) {
+            mccnn_geometry_t* g = req[k].geometry;
+            if (!g->pp_density || g->pp_ready) continue;
+            for (int j = 0; j < k && !g->pp_ready; ++j)
+                if (points[j].density == g->pp_density && !points[j].ready) g->pp_ready = true;
+        }
     mccnn_geometry_t* chunk[MCCNN_BATCH_MAX];
     int nc = 0, sorts = 0;
     auto flush = [&]() -> int {

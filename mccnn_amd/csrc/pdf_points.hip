@@ -2,7 +2,7 @@
 // per point, and its expansion to the edges of a neighbour list. The per-edge form (neighbors.hip: compute_pdf) sums over
 // the CENTRE's row for every edge -- sum of k_i^2 pair terms; this one sweeps the 27-cell window once per point and depends
 // on (grid, window) only, so every list over the same grid shares it.
-#include "common.h"
+#include "batch.h"
 #include <cstring>
 #include <cmath>
 
@@ -23,17 +23,24 @@ namespace mccnn {
 // without FMA (point_dist2) against T = sqrt_threshold(R_b), or the host's threshold for an absolute radius.
 // (The other mapping -- lanes = points, candidates broadcast from LDS -- needs one LDS read per pair step and leaves the
 // lanes beyond a cell's population idle: ~8 points per cell on a room.)
+// (One body, two thin kernels: `a` is the record the host fills -- PointPdfItem, batch.h -- and (blk, nblk) the workgroup's
+// place among the workgroups of ITS item; the single form hands in its own grid, the batch form what batch_item finds.)
 template <int G>
-__global__ __launch_bounds__(256) void pdf_points_k(const float* __restrict__ pts, const int* __restrict__ bids, int n,
-                                                    const int* __restrict__ cells, const float* __restrict__ mn,
-                                                    const float* __restrict__ mx, int B, int nc, float window, float radius,
-                                                    int scaleInv, float Tabs, float* __restrict__ density,
-                                                    int* __restrict__ counts) {
+__device__ __forceinline__ void pdf_points_body(const PointPdfItem& a, int blk, int nblk) {
+    const float* __restrict__ pts = a.pts;
+    const int* __restrict__ bids = a.bids;
+    const int* __restrict__ cells = a.cells;
+    const float* __restrict__ mn = a.mn;
+    const float* __restrict__ mx = a.mx;
+    float* __restrict__ density = a.density;
+    int* __restrict__ counts = a.counts;
+    const int n = a.n, B = a.B, nc = a.nc, scaleInv = a.scaleInv;
+    const float window = a.window, radius = a.radius, Tabs = a.Tabs;
     static_assert(G >= 1 && G <= 8, "members per wave: lanes 0 .. G-1, accumulators in registers");
     __shared__ float4 win[4][MCCNN_PP_CAP];
     __shared__ int2 ctab[4][32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g0 = (xcd_contiguous((int)blockIdx.x, (int)gridDim.x) * 4 + wave) * G;
+    const int g0 = (xcd_contiguous(blk, nblk) * 4 + wave) * G;
     if (g0 >= n) return;
     float4* lw = win[wave];
     int2* tab = ctab[wave];
@@ -147,6 +154,20 @@ __global__ __launch_bounds__(256) void pdf_points_k(const float* __restrict__ pt
     }
 }
 
+template <int G>
+__global__ __launch_bounds__(256) void pdf_points_k(PointPdfItem a) {
+    pdf_points_body<G>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// One launch over the points of up to MCCNN_BATCH_MAX grids (mccnn_geometry_build_batch_point): ONE G for all items -- a
+// point's density does not depend on it (see above), so every item gets the bytes of its single form.
+template <int G>
+__global__ __launch_bounds__(256) void pdf_points_batch_k(PointPdfBatch pb, BatchBlocks bb) {
+    int local, blocks;
+    const PointPdfItem& a = pb.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
+    pdf_points_body<G>(a, local, blocks);
+}
+
 // One thread per edge (j, i): pdfs[e] = density[j] / float(len_i), the reference's division by the row length
 // (compute_pdf.cu:92), one correctly rounded f32 divide.
 __global__ __launch_bounds__(256) void expand_pdf_k(const float* __restrict__ density, const int* __restrict__ startIdx, int m,
@@ -160,6 +181,34 @@ __global__ __launch_bounds__(256) void expand_pdf_k(const float* __restrict__ de
     pdfs[t] = density[pr.x] / (float)(i1 - i0);
 }
 
+// The same inside a geometry's chain, where the edge total exists only in the device word: grid-stride over
+// E = min(*total_dev, e_capacity) edges, the last row ends at E; nothing is written beyond E. A list that overflowed its
+// capacity (the geometry is rebuilt afterwards) holds rows cut at the capacity and start indices beyond it: every index is
+// clamped into its buffer (n points, m rows) and such a row's values are never used.
+__device__ __forceinline__ void expand_pdf_dn_body(const ExpandItem& a, int blk, int nblk) {
+    const int E = min(max(*a.totalDev, 0), a.eCap);
+    const int2* __restrict__ packed = a.packed;
+    const int* __restrict__ startIdx = a.startIdx;
+    const float* __restrict__ density = a.density;
+    float* __restrict__ pdfs = a.pdfs;
+    const int m = a.m, n = a.n;
+    const long long stride = (long long)nblk * 256;
+    for (long long t = (long long)blk * 256 + threadIdx.x; t < E; t += stride) {
+        const int2 pr = packed[t];
+        const int i = max(0, min(pr.y, m - 1));
+        const int j = max(0, min(pr.x, n - 1));
+        const int i0 = startIdx[i];
+        const int i1 = (i < m - 1) ? min(startIdx[i + 1], E) : E;
+        pdfs[t] = density[j] / (float)(i1 - i0);
+    }
+}
+__global__ __launch_bounds__(256) void expand_pdf_dn_k(ExpandItem a) { expand_pdf_dn_body(a, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void expand_pdf_dn_batch_k(ExpandBatch eb, BatchBlocks bb) {
+    int local, blocks;
+    const ExpandItem& a = eb.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
+    expand_pdf_dn_body(a, local, blocks);
+}
+
 // sqrt_threshold (common.h) on the host: the same float operations, both square roots correctly rounded (as
 // neighbors.hip's: an absolute radius has ONE threshold, computed once per call)
 static float pp_sqrt_threshold_host(float R) {
@@ -169,6 +218,86 @@ static float pp_sqrt_threshold_host(float R) {
     for (int it = 0; it < 8 && t > 0.0f && sqrtf(prev(t)) >= R; ++it) t = prev(t);
     for (int it = 0; it < 8 && sqrtf(t) < R; ++it) t = next(t);
     return t;
+}
+
+// points per wave: 8 share most of their windows on a large level, a small one needs the waves (neigh_group of the search)
+static int pp_group(long long n) { return n >= 32768 ? 8 : n >= 16384 ? 4 : n >= 8192 ? 2 : 1; }
+
+int point_pdf_item(PointPdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, int n, const int* cell_indexs,
+                   const float* aabb_min, const float* aabb_max, int batch_size, int num_cells, float window, float radius,
+                   int scale_inv, float* density, int* counts) {
+    if (n <= 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || !(window > 0.0f)) return MCCNN_E_BADARG;
+    if (!sorted_pts || !sorted_batch_ids || !cell_indexs || !aabb_min || !aabb_max || !density || !counts) return MCCNN_E_BADARG;
+    it = PointPdfItem{sorted_pts, sorted_batch_ids, cell_indexs, aabb_min, aabb_max, density, counts, n, batch_size, num_cells,
+                      scale_inv ? 1 : 0, window, radius, scale_inv ? 0.0f : pp_sqrt_threshold_host(radius)};
+    return 0;
+}
+
+int launch_point_pdf(const PointPdfItem& it, hipStream_t s) {
+#define MCCNN_PP_LAUNCH(G) pdf_points_k<G><<<ceil_div(it.n, 4 * G), 256, 0, s>>>(it)
+    switch (pp_group(it.n)) {
+        case 8: MCCNN_PP_LAUNCH(8); break;
+        case 4: MCCNN_PP_LAUNCH(4); break;
+        case 2: MCCNN_PP_LAUNCH(2); break;
+        default: MCCNN_PP_LAUNCH(1); break;
+    }
+#undef MCCNN_PP_LAUNCH
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+// ONE G for the launch, from the points of all its items together (what fills the chip is their sum)
+int launch_point_pdf_batch(const PointPdfBatch& pb, int count, hipStream_t s) {
+    if (count <= 0) return 0;
+    if (count > MCCNN_BATCH_MAX) return MCCNN_E_BADARG;
+    long long total = 0;
+    for (int k = 0; k < count; ++k) total += pb.it[k].n;
+    const int G = pp_group(total);
+    BatchBlocks bb;
+    bb.count = count;
+    int run = 0;
+    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += ceil_div(pb.it[k].n, 4 * G); }
+    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    if (run == 0) return 0;
+#define MCCNN_PP_LAUNCH(G) pdf_points_batch_k<G><<<run, 256, 0, s>>>(pb, bb)
+    switch (G) {
+        case 8: MCCNN_PP_LAUNCH(8); break;
+        case 4: MCCNN_PP_LAUNCH(4); break;
+        case 2: MCCNN_PP_LAUNCH(2); break;
+        default: MCCNN_PP_LAUNCH(1); break;
+    }
+#undef MCCNN_PP_LAUNCH
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+// workgroups of one expansion: one per 1024 edges of the capacity (four grid-stride steps each), at most 1024
+static int expand_blocks(int e_cap) { return max(1, min(ceil_div(e_cap, 1024), 1024)); }
+
+int expand_item(ExpandItem& it, const float* density, int n, const int* start_idx, int m, const int* packed, int e_capacity,
+                const int* total_dev, float* pdfs) {
+    if (n <= 0 || m <= 0 || e_capacity <= 0 || !density || !start_idx || !packed || !total_dev || !pdfs) return MCCNN_E_BADARG;
+    it = ExpandItem{density, start_idx, reinterpret_cast<const int2*>(packed), total_dev, pdfs, n, m, e_capacity};
+    return 0;
+}
+
+int launch_expand_dn(const ExpandItem& it, hipStream_t s) {
+    expand_pdf_dn_k<<<expand_blocks(it.eCap), 256, 0, s>>>(it);
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+int launch_expand_batch(const ExpandBatch& eb, int count, hipStream_t s) {
+    if (count <= 0) return 0;
+    if (count > MCCNN_BATCH_MAX) return MCCNN_E_BADARG;
+    BatchBlocks bb;
+    bb.count = count;
+    int run = 0;
+    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += expand_blocks(eb.it[k].eCap); }
+    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    expand_pdf_dn_batch_k<<<run, 256, 0, s>>>(eb, bb);
+    MCCNN_LAUNCHED();
+    return 0;
 }
 
 }  // namespace mccnn
@@ -182,20 +311,11 @@ int mccnn_compute_pdf_points(const float* sorted_pts, const int* sorted_batch_id
                              float radius, int scale_inv, float* density, int* counts, mccnn_stream_t stream) {
     if (n < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f) || !(window > 0.0f)) return MCCNN_E_BADARG;
     if (n == 0) return 0;
-    if (!sorted_pts || !sorted_batch_ids || !cell_indexs || !aabb_min || !aabb_max || !density || !counts) return MCCNN_E_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    const float Tabs = scale_inv ? 0.0f : pp_sqrt_threshold_host(radius);
-    // points per wave: 8 share most of their windows on a large level, a small one needs the waves (neigh_group of the search)
-#define MCCNN_PP_LAUNCH(G)                                                                                                  \
-    pdf_points_k<G><<<ceil_div(n, 4 * G), 256, 0, s>>>(sorted_pts, sorted_batch_ids, n, cell_indexs, aabb_min, aabb_max,    \
-                                                      batch_size, num_cells, window, radius, scale_inv, Tabs, density, counts)
-    if (n >= 32768) MCCNN_PP_LAUNCH(8);
-    else if (n >= 16384) MCCNN_PP_LAUNCH(4);
-    else if (n >= 8192) MCCNN_PP_LAUNCH(2);
-    else MCCNN_PP_LAUNCH(1);
-#undef MCCNN_PP_LAUNCH
-    MCCNN_LAUNCHED();
-    return 0;
+    PointPdfItem it;
+    int rc = point_pdf_item(it, sorted_pts, sorted_batch_ids, n, cell_indexs, aabb_min, aabb_max, batch_size, num_cells, window,
+                            radius, scale_inv, density, counts);
+    if (rc) return rc;
+    return launch_point_pdf(it, (hipStream_t)stream);
 }
 
 int mccnn_expand_pdf(const float* density, const int* start_idx, int m, const int* packed, int e, float* pdfs,

@@ -289,8 +289,46 @@ void count_wait(std::chrono::steady_clock::time_point t0);
 // regression check of NOTES round-6 item 6c -- zero would mean the waits are being skipped again)
 std::atomic<long long> g_caller_orderings{0};
 
+// The per-point density of ONE (grid, window) -- pdfMode='point': density [n,1] f32 and counts [n,1] i32 of the grid's sorted
+// points. The grid's owner keeps one per window (mccnn_amd.native: Geometry.point_density) and every geometry over that grid
+// and window holds it: the first build computes it, later ones only expand it over their lists. `ev` is recorded behind the
+// build that wrote it; a sharer on another stream waits for it (the join of a grid_from sharer behind its owner's grid, for
+// the density). The tensors come from the pool of the writer's buffers (`alloc_stream`); every other stream that reads them
+// is made known to the allocator (record_stream), like the grid arrays of a geometry that has a pool of its own.
+struct PointPdf {
+    Tensor density, counts;
+    void* alloc_stream = nullptr;
+    void* write_stream = nullptr;       // the stream the sweep runs on
+    hipEvent_t ev = nullptr;
+    std::atomic<int> recorded{0};       // 0 while the helper thread has not issued the writer's build yet
+    void wait_recorded() {
+        int spins = 0;
+        while (!recorded.load(std::memory_order_acquire))
+            if (++spins > 2000) std::this_thread::yield();
+    }
+    void mark(void* stream) {            // behind the writer's build, on its stream
+        if (ev && hipEventRecord(ev, (hipStream_t)stream) != hipSuccess) { give_event_fwd(ev); ev = nullptr; }
+        recorded.store(1, std::memory_order_release);
+    }
+    // `stream` reads (or expands) the density: ordered behind the sweep, and known to the allocator
+    void order(void* stream) {
+        if (stream == write_stream && stream == alloc_stream) return;
+        if (stream != write_stream) {
+            wait_recorded();
+            if (ev && hipStreamWaitEvent((hipStream_t)stream, ev, 0) != hipSuccess) throw std::runtime_error("point density: hipStreamWaitEvent");
+        }
+        if (stream != alloc_stream) {
+            const c10::Stream reader = as_torch_stream(stream, (int)density.device().index());
+            density.record_stream(reader);
+            counts.record_stream(reader);
+        }
+    }
+    ~PointPdf() { if (ev) give_event_fwd(ev); }
+};
+
 struct Geo {
     mccnn_geometry_t* h = nullptr;
+    std::shared_ptr<PointPdf> pp;   // the per-point density its PDFs are expanded from (null: edge mode)
     std::atomic<int> issued{1};    // 0 while the helper thread has not issued this geometry's build yet
     int build_rc = 0;
     hipEvent_t event = nullptr;    // recorded behind a build on a side stream; its consumers wait for it once
@@ -545,6 +583,8 @@ struct BatchEntry {
     std::shared_ptr<Geo> g, grid_from;
     mccnn_geometry_request req;
     mccnn_neighbor_cap cap;   // of the request's search (max_neighbors 0: none)
+    mccnn_point_pdf point;    // its per-point density (density null: edge mode)
+    bool writes_point = false;   // this request computes the density: its event is recorded behind the batch
 };
 struct PieceEntry {   // row plans / transposed list of a batched geometry whose list is small: built as a batch as well
     std::shared_ptr<Geo> g;
@@ -608,9 +648,11 @@ void end_geometry_batch() {
         enter_device(dev);
         std::vector<mccnn_geometry_request> reqs;
         std::vector<mccnn_neighbor_cap> caps;
-        bool any_cap = false;
+        std::vector<mccnn_point_pdf> points;
+        bool any_cap = false, any_point = false;
         reqs.reserve(entries->size());
         caps.reserve(entries->size());
+        points.reserve(entries->size());
         for (BatchEntry& e : *entries) {
             // a grid owner outside this batch has to be issued; one inside it is set up by the same library call
             bool inside = false;
@@ -620,11 +662,15 @@ void end_geometry_batch() {
             reqs.push_back(e.req);
             caps.push_back(e.cap);
             any_cap = any_cap || e.cap.max_neighbors > 0;
+            points.push_back(e.point);
+            any_point = any_point || e.point.density != nullptr;
         }
         const int prev = background ? mccnn_background_launches(1) : 0;
-        int rc = mccnn_geometry_build_batch_capped(reqs.data(), any_cap ? caps.data() : nullptr, (int)reqs.size(), (void*)stream);
+        int rc = any_point ? mccnn_geometry_build_batch_point(reqs.data(), any_cap ? caps.data() : nullptr, points.data(), (int)reqs.size(), (void*)stream)
+                           : mccnn_geometry_build_batch_capped(reqs.data(), any_cap ? caps.data() : nullptr, (int)reqs.size(), (void*)stream);
         if (background) mccnn_background_launches(prev);
         for (BatchEntry& e : *entries) {
+            if (e.writes_point) e.g->pp->mark((void*)stream);
             int r = rc;
             if (r == 0 && hipEventRecord(e.g->event, stream) != hipSuccess) r = (int)hipErrorUnknown;
             e.g->build_rc = r;
@@ -700,7 +746,8 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
                                     const Tensor& mn, const Tensor& mx, int64_t B, int64_t nc, double radius, bool scale_inv,
                                     double window, bool use_pdf, int64_t capacity, std::shared_ptr<Geo> grid_from,
                                     int64_t side, bool fork, bool background, std::shared_ptr<HierFuture> after,
-                                    int64_t max_neighbors, int64_t sample_seed /* < 0: none */) {
+                                    int64_t max_neighbors, int64_t sample_seed /* < 0: none */, bool point_pdf,
+                                    std::shared_ptr<PointPdf> point_from /* the density of this grid and window, when it exists */) {
     check_dev(pts, at::kFloat, "points");
     check_dev(centres, at::kFloat, "sample points");
     check_dev(bids, at::kInt, "batch ids");
@@ -712,6 +759,19 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     if (grid_from && grid_from->grid_owner) grid_from = grid_from->grid_owner;
     TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= 0x7fffffffLL, "geometry: maxNeighbors must be >= 0");
     TORCH_CHECK(sample_seed < 0 || (max_neighbors > 0 && sample_seed <= 0xffffffffLL), "geometry: sampleSeed needs a cap and lies in [0, 2^32)");
+    TORCH_CHECK(!(point_pdf || point_from) || (use_pdf && max_neighbors == 0), "geometry: a per-point density needs usePDF and an uncapped list");
+    TORCH_CHECK(!point_from || (point_from->density.defined() && point_from->density.size(0) == n), "geometry: the per-point density is of another grid");
+    std::shared_ptr<PointPdf> pp = point_from;
+    const bool pp_ready = pp != nullptr;
+    // a density that does not exist yet: allocated with the geometry's buffer (same pool, same stream), written by this build
+    auto make_pp = [&](void* alloc_stream) {
+        if (!point_pdf || pp) return;
+        pp = std::make_shared<PointPdf>();
+        pp->density = at::empty({(int64_t)n, 1}, pts.options());
+        pp->counts = at::empty({(int64_t)n, 1}, pts.options().dtype(at::kInt));
+        pp->alloc_stream = alloc_stream;
+        pp->ev = take_event();
+    };
     // the cap of the search (by value into the helper thread's job / the batch entry)
     const mccnn_neighbor_cap cap{(int)max_neighbors, sample_seed >= 0 ? 1 : 0, sample_seed >= 0 ? (unsigned)sample_seed : 0u};
     const size_t bytes = mccnn_geometry_bytes_capped(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors);
@@ -740,6 +800,12 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     static const bool own_pools = mccnn::debug_int("geo_own_pool", 1) != 0;
     hipEvent_t ready = (side >= 0 && own_pools && Issuer::enabled()) ? hierarchy_ready_event(after) : nullptr;
     if (ready && grid_from && !grid_from->own_pool) ready = nullptr;
+    if (ready && pp && pp->alloc_stream != (void*)side_stream((int)side)) {
+        // (a density of another pool: this build reads memory the allocator knows from another stream -- fork like any other)
+        bool pool_side = false;
+        for (int k = 0; k < kSideStreams; ++k) pool_side = pool_side || pp->alloc_stream == (void*)side_stream(k);
+        if (!pool_side) ready = nullptr;
+    }
     // ... and only then: an input that is NOT the hierarchy's own memory (a re-made-contiguous copy of a level, a tensor
     // the caller produced on its stream) is ordered by the calling stream alone -- such a build forks behind it like any other
     if (ready)
@@ -754,6 +820,7 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
             const c10::hip::HIPStreamGuardMasqueradingAsCUDA own(as_torch_stream((void*)ss, (int)pts.device().index()));
             if (batched) g->buf = arena_take(0, (int64_t)bytes, pts);
             if (!g->buf.defined()) g->buf = at::empty({(int64_t)bytes}, pts.options().dtype(at::kByte));
+            make_pp((void*)ss);
         }
         g->own_pool = true;
         g->caller_stream = stream;
@@ -769,6 +836,7 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
         stream = ss;
     } else if (side >= 0) {
         g->buf = at::empty({(int64_t)bytes}, pts.options().dtype(at::kByte));
+        make_pp(stream);
         hipStream_t ss = side_stream((int)side);
         if (ss) {
             // the side stream starts behind everything the calling stream held at the last fork (the point hierarchy;
@@ -794,8 +862,19 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
         }
     } else {
         g->buf = at::empty({(int64_t)bytes}, pts.options().dtype(at::kByte));
+        make_pp(stream);
         if (grid_from) grid_from->join(stream);
     }
+    // the density: its writer runs on `stream`; a sharer's stream is ordered behind the sweep (an event wait, when the
+    // streams differ) and made known to the allocator of the density's pool
+    mccnn_point_pdf point{nullptr, nullptr, 0};
+    if (pp) {
+        g->pp = pp;
+        if (!pp_ready) pp->write_stream = stream;
+        pp->order(stream);
+        point = mccnn_point_pdf{pp->density.data_ptr<float>(), pp->counts.data_ptr<int>(), pp_ready ? 1 : 0};
+    }
+    const bool writes_point = pp && !pp_ready;
     if (g->side >= 0 && Issuer::enabled()) {
         // the helper thread issues the launches and records the event; whoever touches the geometry waits for `issued`
         g->event = take_event();
@@ -819,19 +898,22 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
             e.req = mccnn_geometry_request{g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
                                            grid_from ? grid_from->h : nullptr, bufp, bytes, slotp};
             e.cap = cap;
+            e.point = point;
+            e.writes_point = writes_point;
             t_geo_batch.entries.push_back(std::move(e));
             g->plan_side = asked_side;   // the pieces built ahead keep the spread over the side streams the builds gave up
             return g;
         }
-        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev, cap] {
+        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev, cap, point, writes_point] {
             enter_device(dev);
             if (grid_from) grid_from->wait_issued_nothrow();
             // background: these launches run beside kernels a step waits for (the convolutions of the current batch) --
             // the search kernels then hold back (mccnn_background_launches, thread-local: set on THIS thread)
             const int prev = background ? mccnn_background_launches(1) : 0;
-            int rc = mccnn_geometry_build_capped(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
-                                                 grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream, &cap);
+            int rc = mccnn_geometry_build_point(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
+                                                grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream, &cap, &point);
             if (background) mccnn_background_launches(prev);
+            if (writes_point) g->pp->mark(stream);
             if (rc == 0 && hipEventRecord(g->event, (hipStream_t)stream) != hipSuccess) rc = (int)hipErrorUnknown;
             g->build_rc = rc;
             g->issued.store(1, std::memory_order_release);
@@ -844,12 +926,13 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
         bool on; int prev;
         ~Restore() { if (on) mccnn_background_launches(prev); }
     } restore{background && g->side >= 0, prev_bg};
-    check(mccnn_geometry_build_capped(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
-                                      cbids.data_ptr<int>(), m, mn.data_ptr<float>(), mx.data_ptr<float>(), (int)B, (int)nc,
-                                      (float)radius, scale_inv ? 1 : 0, (float)window, use_pdf ? 1 : 0, (int)capacity,
-                                      grid_from ? grid_from->h : nullptr, g->buf.data_ptr(), bytes, g->slot.data_ptr<int>(),
-                                      stream, &cap),
-          "geometry_build");
+    const int build_rc = mccnn_geometry_build_point(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
+                                                    cbids.data_ptr<int>(), m, mn.data_ptr<float>(), mx.data_ptr<float>(), (int)B, (int)nc,
+                                                    (float)radius, scale_inv ? 1 : 0, (float)window, use_pdf ? 1 : 0, (int)capacity,
+                                                    grid_from ? grid_from->h : nullptr, g->buf.data_ptr(), bytes,
+                                                    g->slot.data_ptr<int>(), stream, &cap, &point);
+    if (writes_point) pp->mark(stream);
+    check(build_rc, "geometry_build");
     if (g->side >= 0) {
         g->event = take_event();
         hip_check(hipEventRecord(g->event, (hipStream_t)stream), "hipEventRecord");
@@ -1567,6 +1650,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
         .def_readwrite("uses", &Geo::uses)
         .def_readonly("side", &Geo::side)
         .def_readonly("have", &Geo::have)
+        .def_readonly("point", &Geo::pp)
         // (none of the calls below touches a Python object, and all of them may wait -- for a helper thread's job, which can
         // in turn wait for a device-side edge total, or for the device itself: the GIL is released for their whole
         // duration, so data-loader threads keep running and a helper thread that drops the last reference to a tensor
@@ -1576,11 +1660,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
              py::call_guard<py::gil_scoped_release>())
         .def("edges", &Geo::edges, py::arg("wait_us") = -1, py::call_guard<py::gil_scoped_release>())
         .def("info", &Geo::info, py::call_guard<py::gil_scoped_release>());
+    py::class_<PointPdf, std::shared_ptr<PointPdf>>(mod, "PointPdf")
+        .def_readonly("density", &PointPdf::density)
+        .def_readonly("counts", &PointPdf::counts)
+        // whoever reads the tensors does so on the current stream: behind the sweep, known to the density's allocator
+        .def("join", [](PointPdf& p) { p.order(cur_stream(p.density)); }, py::call_guard<py::gil_scoped_release>());
     mod.def("build_geometry", &build_geometry, py::arg("pts"), py::arg("bids"), py::arg("centres"), py::arg("cbids"),
             py::arg("mn"), py::arg("mx"), py::arg("B"), py::arg("nc"), py::arg("radius"), py::arg("scale_inv"),
             py::arg("window"), py::arg("use_pdf"), py::arg("capacity"), py::arg("grid_from").none(true),
             py::arg("side") = -1, py::arg("fork") = false, py::arg("background") = false,
             py::arg("after").none(true) = py::none(), py::arg("max_neighbors") = 0, py::arg("sample_seed") = -1,
+            py::arg("point_pdf") = false, py::arg("point_from").none(true) = py::none(),
             py::call_guard<py::gil_scoped_release>());
     mod.def("sampled_features", &sampled_features, py::call_guard<py::gil_scoped_release>());
     mod.def("begin_geometry_batch", &begin_geometry_batch);

@@ -136,6 +136,11 @@ class _NeighborCap(C.Structure):
     _fields_ = [("max_neighbors", C.c_int), ("sampled", C.c_int), ("seed", C.c_uint)]
 
 
+class _PointPdf(C.Structure):
+    """mccnn_point_pdf (include/mccnn.h)"""
+    _fields_ = [("density", C.c_void_p), ("counts", C.c_void_p), ("ready", C.c_int)]
+
+
 class Geometry:
     """One convolution geometry: the grid of the input level at the convolution radius, the neighbour list of the
     output level's points in it and its PDFs, in ONE device buffer (mccnn_geometry_t). Tensor views of its arrays are
@@ -154,6 +159,11 @@ class Geometry:
         self.gkey = None
         self.args = None
         self.cap = (0, None)    # (maxNeighbors, sampleSeed) of the search
+        self.point = False      # the PDFs are expanded from the per-point density of (grid, window): pdfMode='point'
+        self.window = None
+        # a grid owner: window -> (density [n,1] f32, counts [n,1] i32, handle of the extension or None) of its sorted points --
+        # ONE pair per window, shared by every geometry over this grid (alive as long as the owner is)
+        self.pointPairs = {}
         self.uses = 0           # layers convolved over this geometry so far (the builder counts)
 
     def __del__(self):
@@ -190,8 +200,9 @@ class Geometry:
         inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF = self.args
         if self.cap[0] > 0:   # (a capped list never holds more)
             capacity = min(capacity, self.m * self.cap[0])
+        # (a per-point density does not depend on the list: the one that exists is expanded again, not computed again)
         _build_into(self, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity,
-                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1])
+                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1], pointPDF=self.point)
         e = self.core.edges(-1) if self.core is not None else _lib.load().mccnn_geometry_edges(self.handle, -1)
         if e < 0 or e > self.e_cap:
             raise _lib.MCCNNError("geometry: rebuilt list still does not fit (%d > %d)" % (e, self.e_cap))
@@ -253,21 +264,41 @@ class Geometry:
                 self._view(self.buf, i[6], e * 8, torch.int32, (e, 2)))
 
     def pdfs(self):
+        """[E,1]: the KDE of the list, or (a geometry built with pointPDF) the per-point density expanded over it"""
         e = self.edges()
         self._join()
         i = self._info()
         return self._view(self.buf, i[7], e * 4, torch.float32, (e, 1))
 
+    def point_density(self, window=None):
+        """(density [n,1] f32, counts [n,1] i32) of the grid's sorted points at `window` (None: this geometry's own): the
+        pair every point geometry over this grid and window shares -- the same tensors whichever of them is asked. Readable
+        on the current stream."""
+        w = float(self.window if window is None else window)
+        pair = (self.grid_owner or self).pointPairs.get(w)
+        if pair is None:
+            raise KeyError("geometry: no per-point density at window %r over this grid" % (w,))
+        if pair[2] is not None:
+            pair[2].join()
+        return pair[0], pair[1]
+
 
 def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity, grid_from,
-                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None):
+                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False):
     n, m = inPts.shape[0], centres.shape[0]
     g.cap = (int(maxNeighbors), None if sampleSeed is None else int(sampleSeed))   # (a rebuild repeats them: _rebuild)
+    g.point, g.window = bool(pointPDF), float(window)
+    pairs = (grid_from if grid_from is not None else g).pointPairs   # (the grid's owner keeps the densities)
+    pair = pairs.get(g.window) if pointPDF else None
     if _EXT is not None:
         uses = g.core.uses if g.core is not None else 0
         g.core = _EXT.build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, float(radius), bool(scaleInv), float(window),
                                      bool(usePDF), capacity, grid_from.core if grid_from is not None else None, side, fork,
-                                     background, after, int(maxNeighbors), -1 if sampleSeed is None else int(sampleSeed))
+                                     background, after, int(maxNeighbors), -1 if sampleSeed is None else int(sampleSeed),
+                                     bool(pointPDF), pair[2] if pair is not None else None)
+        if pointPDF and pair is None:
+            pp = g.core.point
+            pairs[g.window] = (pp.density, pp.counts, pp)
         g.core.uses = uses
         g.buf = g.core.buf
         g.grid_owner = grid_from
@@ -293,10 +324,18 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     g.n, g.m, g.nc, g.B, g.e_cap, g.e = n, m, nc, B, capacity, -1
     g.args = (inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF)
     cap = _NeighborCap(int(maxNeighbors), 0 if sampleSeed is None else 1, 0 if sampleSeed is None else int(sampleSeed))
-    check(lib.mccnn_geometry_build_capped(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B,
-                                          nc, float(radius), int(bool(scaleInv)), float(window), int(bool(usePDF)), capacity,
-                                          grid_from.handle if grid_from is not None else None, g.buf.data_ptr(), nbytes,
-                                          g.slot.data_ptr(), stream_handle(), C.addressof(cap)), "geometry_build")
+    point = _PointPdf(None, None, 0)
+    if pointPDF:   # (everything of this binding runs on the current stream: the density lies in stream order before its users)
+        ready = pair is not None
+        if not ready:
+            pair = (torch.empty((n, 1), dtype=torch.float32, device=dev), torch.empty((n, 1), dtype=torch.int32, device=dev), None)
+        point = _PointPdf(pair[0].data_ptr(), pair[1].data_ptr(), 1 if ready else 0)
+    check(lib.mccnn_geometry_build_point(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B,
+                                         nc, float(radius), int(bool(scaleInv)), float(window), int(bool(usePDF)), capacity,
+                                         grid_from.handle if grid_from is not None else None, g.buf.data_ptr(), nbytes,
+                                         g.slot.data_ptr(), stream_handle(), C.addressof(cap), C.addressof(point)), "geometry_build")
+    if pointPDF:
+        pairs[g.window] = pair
 
 
 def begin_batch():
@@ -317,7 +356,7 @@ def side_streams_available():
 
 
 def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, grid_from=None,
-                   side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None):
+                   side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False):
     """Enqueues grid + search + KDE of one convolution geometry; no host wait. nc: cells per axis
     (MCConvModule._num_cells). grid_from: a Geometry over the same points / radius whose grid is shared. side >= 0
     (torch extension only): the build runs on side stream `side` -- behind everything the current stream holds at the
@@ -327,11 +366,17 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     maxNeighbors > 0: the search keeps at most that many neighbours per centre (find_neighbors(maxNeighbors=), the same
     bytes); sampleSeed (needs a cap): the seed the capped search draws its stratified sample with, as the op takes it. The
     list then holds at most m * maxNeighbors rows: a capacity of that size cannot overflow, and the guess an uncapped list
-    of the shape would get is used only where it is smaller."""
+    of the shape would get is used only where it is smaller.
+    pointPDF (needs usePDF and no cap): the PDFs are the per-point density of (grid, window) expanded over the list --
+    compute_pdf_points + expand_pdf of the op surface, the same bytes -- instead of the KDE of the list. The grid's owner keeps
+    ONE (density, counts) pair per window (Geometry.point_density); the first build over a grid and window computes it
+    right behind the grid, every later one, whatever its centres and stream, only expands it."""
     n, m = inPts.shape[0], centres.shape[0]
     maxNeighbors = int(maxNeighbors)
     if maxNeighbors < 0 or (sampleSeed is not None and (maxNeighbors == 0 or not 0 <= int(sampleSeed) < 2 ** 32)):
         raise ValueError("build_geometry: maxNeighbors >= 0; sampleSeed needs a cap and lies in [0, 2^32)")
+    if pointPDF and (maxNeighbors > 0 or not usePDF):
+        raise ValueError("build_geometry: pointPDF needs usePDF and an uncapped list")
     gkey = (inPts.device.index, n, m, float(radius), int(B), bool(scaleInv))
     if maxNeighbors > 0:
         # (capped totals never shrink the guess of an uncapped geometry of the shape, or the reverse: the cap is a seventh
@@ -346,7 +391,7 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
         capacity = max(1, min(m * maxNeighbors, capacity))
     _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF,
                 capacity, grid_from, side if _EXT is not None else -1, fork, background,
-                after if _EXT is not None else None, maxNeighbors, sampleSeed)
+                after if _EXT is not None else None, maxNeighbors, sampleSeed, pointPDF)
     return g
 
 
