@@ -256,6 +256,30 @@ int mccnn_compute_pdf_points(const float* sorted_pts, const int* sorted_batch_id
  * m == 0 with e > 0 or a null pointer: MCCNN_E_BADARG. */
 int mccnn_expand_pdf(const float* density, const int* start_idx, int m, const int* packed, int e,
                      float* pdfs, mccnn_stream_t stream);
+/* Gradients of the two with respect to positions (extension). Every discrete decision of the forward is held fixed:
+ * cells, sort order, membership d2 < T, row lengths, the longest box axis. With s_b = 1 / (R_b h),
+ * norm = ((1/h) 0.39894228)^3 and w_jl = exp(-0.5 s_b^2 d2_jl):
+ *   dpts[j]    = -s_b^2 norm sum_{l in N(j)} (density_grad[j] + density_grad[l]) w_jl (p_j - p_l)
+ *   dradius[b] = sum over the points j of cloud b of density_grad[j] norm (s_b^2 / R_b) sum_{l in N(j)} w_jl d2_jl
+ * -- the forward's sweep again in gather form (the ball relation is symmetric inside a cloud, so the wave that owns j sums
+ * everything that depends on p_j): one launch, no atomics, no per-edge rows, no transposed list; dpts [n, 3] is written
+ * whole, a point with an empty ball gets zeros. dradius [batch_size] (dL/dR_b) may be null; non-null needs scale_inv and
+ * a workspace of mccnn_compute_pdf_points_bwd_workspace_bytes(n, batch_size) bytes (one float per point, summed per cloud
+ * in a fixed order by a second launch; sorted_batch_ids must be non-decreasing, as a sorted list's are). The same bytes
+ * in every run. n == 0 returns 0 without a launch; otherwise the argument checks of mccnn_compute_pdf_points
+ * (MCCNN_E_BADARG), dradius without scale_inv: MCCNN_E_BADARG, a missing or short workspace: MCCNN_E_WORKSPACE. */
+size_t mccnn_compute_pdf_points_bwd_workspace_bytes(int n, int batch_size);
+int mccnn_compute_pdf_points_bwd(const float* sorted_pts, const int* sorted_batch_ids, int n, const int* cell_indexs,
+                                 const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
+                                 float window, float radius, int scale_inv, const float* density_grad, float* dpts,
+                                 float* dradius, void* ws, size_t ws_bytes, mccnn_stream_t stream);
+/* density_grad[j] = sum over the edges t whose point is j of pdfs_grad[t] / float(len_i), i the centre of t, gathered
+ * through the transposed list (start_t [n + 1], perm_t [e]: mccnn_transpose_neighbors) in its order: no float atomics,
+ * the same bytes in every run. Every density_grad[j], j < n, is written; a point that no edge names gets 0.f. One launch.
+ * n == 0 or e == 0 returns 0 without a launch (nothing is written); m < 0, e < 0, n < 0, m == 0 with e > 0 or a null
+ * pointer: MCCNN_E_BADARG. */
+int mccnn_expand_pdf_bwd(float* density_grad, const float* pdfs_grad, const int* start_idx, int m, const int* packed,
+                         int e, const int* start_t, const int* perm_t, int n, mccnn_stream_t stream);
 
 /* PoissonSampling -- poisson_sampling.cc:26,109-211, poisson_sampling.cu:51-230.
  * count: runs the 27 colour phases, leaves the selection in ws and writes the

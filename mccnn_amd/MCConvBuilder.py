@@ -343,12 +343,17 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False):
+                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False, pointGrad=False):
         """pdfMode (extension): 'edge' (default) -- the reference's density, a Gaussian sum over the centre's row for every
         edge (compute_pdf); 'point' -- the density of every point over its OWN ball, computed once per (grid, KDEWindow)
         and shared by every list over that grid (compute_pdf_points + expand_pdf). A 'point' layer with usePDF takes the
-        op-by-op path unless pointNative is set, needs an uncapped list and points without a gradient; without usePDF the
-        mode has no effect.
+        op-by-op path unless pointNative is set, needs an uncapped list and (unless pointGrad is set) points without a
+        gradient; without usePDF the mode has no effect.
+        pointGrad (extension, default False): True lets a 'point' layer take points that require a gradient (HIP op surface
+        only): such a layer runs op by op like every position-gradient layer -- differentiable sort_points_step2,
+        find_neighbors, compute_pdf_points once per grid and window (its graph shared by the layers that read it),
+        expand_pdf, spatial_conv -- whatever pointNative_ says. False keeps the error. Layers whose points carry no gradient
+        are not affected. The attribute pointGrad_ may be reassigned between steps (followed by reset()).
         pointNative (extension, default False): True sends 'point' layers through the native step executor like 'edge'
         ones -- one library call per geometry (mccnn_geometry_build_point: the density sweep once per grid and window right
         behind the grid, its expansion in the place of the KDE), learned prefetch, prefetch_step, prefetch_geometry and the
@@ -374,6 +379,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("pointNative must be True or False")
         self.pointNative_ = pointNative
+        if not isinstance(pointGrad, bool):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("pointGrad must be True or False")
+        self.pointGrad_ = pointGrad
         self.pdfMode_ = self.__check_pdf_mode__(pdfMode)
         self.ops_ = _Ops(ops)
         # extension: grids from the points alone (MCConvModule.build_grid), feature rows sorted inside the convolution's
@@ -1065,7 +1074,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # (expand_pdf, filed under keyPDF + '|pt') instead of compute_pdf -- on the op-by-op path below, like a capped
         # layer: no native executor, no deferred search + KDE, no learned prefetch -- unless the builder was made with
         # pointNative=True (pointNative_): then it runs through the native executor like an 'edge' layer, with the same
-        # bytes. It needs an uncapped list and points without a gradient. Without usePDF the mode has no effect.
+        # bytes. It needs an uncapped list and, unless pointGrad_ is set (HIP op surface), points without a gradient. Without
+        # usePDF the mode has no effect.
         # maxNeighbors (extension; None = the builder's default): cap on the neighbours per centre, see find_neighbors. A
         # capped layer takes the op-by-op path below -- no native executor, no deferred search + KDE, no learned prefetch --
         # like one whose points require a gradient, unless the builder was made with capNative=True (capNative_): then it
@@ -1097,16 +1107,21 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # sorted inside the convolution (by the native executor's layer call, or by spatial_conv(sortIndex=) below)
         inPts = inPointHierarchy.points_[inPointLevel]
         pointPDF = currPDFMode == 'point' and bool(currUsePDF)
+        pointGradLayer = False
         if pointPDF:
             from .MCConvModule import InvalidArgumentError
             if currCap > 0:
                 raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0): on a capped "
                                            "row the per-point density is unbiased but far noisier than the per-edge one")
             if inPts.requires_grad or currOutPointHierarchy.points_[currOutPointLevel].requires_grad:
-                raise InvalidArgumentError("pdfMode='point' is not differentiable with respect to the points: they must not "
-                                           "require a gradient")
+                if not (self.pointGrad_ and self.hipSurface_):
+                    raise InvalidArgumentError("pdfMode='point' is not differentiable with respect to the points: they must "
+                                               "not require a gradient (ConvolutionBuilder(pointGrad=True) on the HIP op "
+                                               "surface differentiates it)")
+                pointGradLayer = True   # op by op below, whatever pointNative_ says
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
-        if self.native_ and fused and (not pointPDF or self.pointNative_) and (currCap == 0 or self.capNative_):
+        if self.native_ and fused and (not pointPDF or (self.pointNative_ and not pointGradLayer)) \
+                and (currCap == 0 or self.capNative_):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,

@@ -901,7 +901,15 @@ def compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, 
     KDE of every SORTED point over its own ball -- the row find_neighbors gives with the sorted points as their own
     centres, same f32 predicate -- and that row's length. inPts / inBatchIds are a sorted list, cellIndexs its cell table
     (sort_points_step2 / build_grid at this radius). Depends on (grid, window) only. One launch, no atomics: the same
-    bytes in every run. Non differentiable."""
+    bytes in every run. Differentiable with respect to the points (and, with scaleInv, the box) when they require a
+    gradient -- the closed-form f32 derivative, the same sweep again (mccnn_compute_pdf_points_bwd); the forward values are
+    those of the plain call and counts carries no gradient. Otherwise non differentiable."""
+    if torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in (inPts, aabbMin, aabbMax)):
+        return _ComputePDFPoints.apply(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize, scaleInv)
+    return _compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize, scaleInv)
+
+
+def _compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize, scaleInv):
     op = "ComputePDFPointsOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(window > 0.0, op + " expects a positive window")
@@ -924,7 +932,15 @@ def compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, 
 def expand_pdf(density, startIndexs, packedNeighs):
     """Extension (pdfMode='point') -> pdfs [E,1]: pdfs[e] = density[j] / float(len_i) for every edge e = (j, i) of an
     UNCAPPED neighbour list over the grid `density` was computed on; len_i is the length of centre i's row (the reference's
-    division, compute_pdf.cu:92). Non differentiable."""
+    division, compute_pdf.cu:92). Differentiable with respect to `density` when it requires a gradient: a gather through
+    the transposed list in a fixed order (mccnn_expand_pdf_bwd), a point that no edge names gets 0. Otherwise non
+    differentiable."""
+    if torch.is_grad_enabled() and getattr(density, "requires_grad", False):
+        return _ExpandPDF.apply(density, startIndexs, packedNeighs)
+    return _expand_pdf(density, startIndexs, packedNeighs)
+
+
+def _expand_pdf(density, startIndexs, packedNeighs):
     op = "ExpandPDFOp"
     d = _f32(density.detach(), "density")
     _req(d.dim() == 2 and d.shape[1] == 1, op + " expects a density with dimensions (numPoints, 1)")
@@ -990,6 +1006,66 @@ class _ComputePDF(torch.autograd.Function):
         if want_box:
             dMin, dMax = _box_grads(mn, mx, dR, radius)
         return (dPts, None, dMin if need[2] else None, dMax if need[3] else None, None, None, None, None, None, None, None)
+
+
+class _ComputePDFPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize, scaleInv):
+        density, counts = _compute_pdf_points(inPts, inBatchIds, cellIndexs, aabbMin, aabbMax, window, radius, batchSize,
+                                              scaleInv)
+        ctx.save_for_backward(_f32(inPts.detach(), "points"), _i32(inBatchIds, "batch_ids"), _i32(cellIndexs, "cell_indexs"),
+                              _f32(aabbMin.detach(), "aabb_min"), _f32(aabbMax.detach(), "aabb_max"))
+        ctx.attrs = (float(window), float(radius), int(batchSize), bool(scaleInv))
+        ctx.mark_non_differentiable(counts)
+        return density, counts
+
+    @staticmethod
+    def backward(ctx, gDensity, _gCounts):
+        pts, bids, cells, mn, mx = ctx.saved_tensors
+        window, radius, batchSize, scaleInv = ctx.attrs
+        need = ctx.needs_input_grad
+        want_box = scaleInv and (need[3] or need[4])
+        lib = _lib.load()
+        n = pts.shape[0]
+        dPts = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
+        dR = ws = None
+        if want_box:
+            # (n == 0: no launch, the sums are empty)
+            dR = (torch.empty if n else torch.zeros)(batchSize, dtype=torch.float32, device=pts.device)
+            ws = _ws(lib.mccnn_compute_pdf_points_bwd_workspace_bytes(n, batchSize), pts.device)
+        g = _f32(gDensity, "density_grad")
+        check(lib.mccnn_compute_pdf_points_bwd(ptr(pts), ptr(bids), n, ptr(cells), ptr(mn), ptr(mx), batchSize, cells.shape[1],
+                                               window, radius, int(scaleInv), ptr(g), ptr(dPts), ptr(dR), ptr(ws),
+                                               0 if ws is None else ws.numel(), stream_handle()), "compute_pdf_points_grad")
+        dMin = dMax = None
+        if want_box:
+            dMin, dMax = _box_grads(mn, mx, dR, radius)
+        return (dPts if need[0] else None, None, None, dMin if need[3] else None, dMax if need[4] else None, None, None, None,
+                None)
+
+
+class _ExpandPDF(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, density, startIndexs, packedNeighs):
+        pdfs = _expand_pdf(density, startIndexs, packedNeighs)
+        ctx.save_for_backward(_i32(startIndexs, "start_indexs"), _i32(packedNeighs, "neighbors"))
+        ctx.packed_ref = weakref.ref(packedNeighs)   # the list OBJECT carries its transposed form (_transposed_neighbors)
+        ctx.n = density.shape[0]
+        return pdfs
+
+    @staticmethod
+    def backward(ctx, gPdfs):
+        st, pk = ctx.saved_tensors
+        n, m, e = ctx.n, st.shape[0], pk.shape[0]
+        if n == 0 or e == 0:
+            return torch.zeros((n, 1), dtype=torch.float32, device=pk.device), None, None
+        packed_obj = ctx.packed_ref()
+        start_t, perm_t, _ = _transposed_neighbors(pk if packed_obj is None else packed_obj, n)
+        g = _f32(gPdfs, "pdfs_grad")
+        gd = torch.empty((n, 1), dtype=torch.float32, device=pk.device)
+        check(_lib.load().mccnn_expand_pdf_bwd(ptr(gd), ptr(g), ptr(st), m, ptr(pk), e, ptr(start_t), ptr(perm_t), n,
+                                               stream_handle()), "expand_pdf_grad")
+        return gd, None, None
 
 
 class DeferredNeighborsPDF:

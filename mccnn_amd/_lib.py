@@ -63,6 +63,9 @@ SIGNATURES = {
     "mccnn_compute_pdf_dn": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _sz, _vp]),
     "mccnn_compute_pdf_points": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     "mccnn_expand_pdf": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "mccnn_compute_pdf_points_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_compute_pdf_points_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_expand_pdf_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp]),
     "mccnn_poisson_sampling_workspace_bytes": (_sz, [_i, _i, _i]),
     "mccnn_poisson_sampling_count": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "mccnn_poisson_sampling_fill": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

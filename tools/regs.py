@@ -16,11 +16,11 @@ for line in out.splitlines():
         cur = {"name": re.sub(r"\(.*", "", name).replace("mccnn::", "").replace("void ", "")}
         rows.append(cur)
         continue
-    for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("sgpr", r" SGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+    for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("sgpr", r"TotalSGPRs: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                      ("spill", r"VGPRs Spill: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
         m = re.search(pat, line)
         if m and cur is not None:
             cur[key] = int(m.group(1))
-print("%-60s %5s %5s %5s %7s %5s %4s %6s" % ("kernel", "vgpr", "agpr", "sgpr", "scratch", "spill", "occ", "lds"))
+print("%-60s %5s %5s %5s %6s %7s %5s %4s %6s" % ("kernel", "vgpr", "agpr", "sgpr", "sspill", "scratch", "spill", "occ", "lds"))
 for r in rows:
-    print("%-60s %5s %5s %5s %7s %5s %4s %6s" % (r["name"][:60], r.get("vgpr"), r.get("agpr"), r.get("sgpr"), r.get("scratch"), r.get("spill"), r.get("occ"), r.get("lds")))
+    print("%-60s %5s %5s %5s %6s %7s %5s %4s %6s" % (r["name"][:60], r.get("vgpr"), r.get("agpr"), r.get("sgpr"), r.get("sspill"), r.get("scratch"), r.get("spill"), r.get("occ"), r.get("lds")))
