@@ -3,7 +3,10 @@
 (models/MCClassS.py:25-77, models/MCNormS.py:25-58) written against mccnn_amd's builder and dense helpers, plus a
 tiny synthetic training loop. The graph builders keep the reference's structure line by line; only `tf.` is gone.
 
-    python examples/mcclass_s.py [--steps 20]
+    python examples/mcclass_s.py [--steps 20] [--device-loader]
+
+--device-loader builds the batches on the GPU (mccnn_amd.device_batcher.DeviceBatcher: a pool of synthetic models uploaded
+once, non-uniform sampling and rotation per batch on the device) instead of uploading host arrays.
 """
 import argparse
 import math
@@ -116,8 +119,33 @@ def synthetic_batch(batchSize, nPts, numCat, rng, device):
     return P, Bi, torch.ones((P.shape[0], 1), dtype=torch.float32, device=device), t(np.array(labels, np.int64))
 
 
+def device_loader(batchSize, nPts, numCat, rng, device, batchesPerEpoch=8):
+    """-> a function returning (points, batch ids, features, labels) like synthetic_batch, from a DeviceBatcher over a pool of
+    batchesPerEpoch * batchSize ellipsoids (every batch is full) of 4 * nPts points with normals: uniform, split, gradient
+    and lambert sampling, random rotations about the y axis. check=False: nothing is read back, the host only plans."""
+    from mccnn_amd.device_batcher import DeviceBatcher
+    models, cats = [], []
+    for _ in range(batchesPerEpoch * batchSize):
+        c = int(rng.integers(0, numCat))
+        axes = np.array([1.0, 0.3 + 0.7 * c / max(numCat - 1, 1), 0.3 + 0.7 * ((c * 3) % numCat) / max(numCat - 1, 1)])
+        v = rng.normal(size=(4 * nPts, 3))
+        v /= np.linalg.norm(v, axis=1, keepdims=True)
+        p = v * axes
+        models.append({"pts": (p - p.min(0)) / (p.max(0) - p.min(0)).max(), "normals": v})
+        cats.append(c)
+    db = DeviceBatcher(models, nPts, 0.8, batchSize, [0, 1, 2, 3], categories=cats, augment=True, seed=0, device=device)
+
+    def batch():
+        if not db.has_more_batches():
+            db.start_iteration()
+        _, P, Bi, F, _, y, _, _ = db.get_next_batch(check=False)
+        return P, Bi, F, y
+    return batch
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device-loader", action="store_true", help="build the batches on the GPU (DeviceBatcher)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--points", type=int, default=1024)
@@ -129,19 +157,21 @@ def main():
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
     net = MCClassS(1, args.batch, 16, 4, device)
-    P, Bi, F, y = synthetic_batch(args.batch, args.points, 4, rng, device)
+    make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \
+        (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
+    P, Bi, F, y = make_batch()
     net(P, Bi, F, True)  # creates the variables
     opt = torch.optim.Adam(net.parameters(), lr=5e-3)
     # the loader runs two batches ahead: the hierarchy of batch k + 2 is requested (helper thread, own stream) while batch
     # k trains; the one of batch k + 1 is complete by then, and its geometry is started under batch k's layers
-    cur = synthetic_batch(args.batch, args.points, 4, rng, device)
-    nxt = synthetic_batch(args.batch, args.points, 4, rng, device)
+    cur = make_batch()
+    nxt = make_batch()
     ph_cur = net.hierarchy(cur[0], cur[1], cur[2])
     fut_nxt = net.prefetch_hierarchy(nxt[0], nxt[1])
     for step in range(args.steps):
         P, Bi, F, y = cur
         ph_nxt = net.hierarchy(nxt[0], nxt[1], nxt[2], prefetched=fut_nxt)
-        after = synthetic_batch(args.batch, args.points, 4, rng, device)
+        after = make_batch()
         fut_after = net.prefetch_hierarchy(after[0], after[1])
         logits = net(P, Bi, F, True, hierarchy=ph_cur, nextHierarchy=ph_nxt)
         cur, nxt, ph_cur, fut_nxt = nxt, after, ph_nxt, fut_after

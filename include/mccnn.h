@@ -700,6 +700,59 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
                         const float* b3, void* feat_grad, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
                         float* db3, void* ws, size_t ws_bytes, mccnn_stream_t stream);
 
+/* TRAINING BATCHES BUILT ON THE DEVICE (extension; the reference's loader, utils/DataSet.py:711-842, is host Python).
+ * The models live in a STORE on the device: their points concatenated, store_pts [store_rows, 3] f32, and optionally
+ * their normals, store_normals [store_rows, 3] f32. A batch is described by one HOST record per slot; the kernel selects
+ * the points of every slot by its sampling protocol, rotates them and writes
+ *   out_pts [out_rows, 3], out_batch_ids [out_rows], out_src [out_rows] (the store row behind every output row: feature,
+ *   label and normal rows follow through it with mccnn_permute_gather), counts [num_slots], status [num_slots].
+ * Record: the model is store rows [offset, offset + length) with box [bmin, bmax] (f32 minimum / maximum of its points);
+ * the slot owns output rows [out_base, out_base + rows) and writes batch_id into each; rot is the row-major 3 x 3 matrix R
+ * of out = p R, evaluated as x * r00 + y * r10 + z * r20 left to right in f32. protocol (DataSet.py:666-671), all in f32:
+ *   0 uniform   row t of K = rows reads point lo_t + off_t of the first n = n_sel points: lo_t = floor(t n / K),
+ *               off_t = (mix(a + t) (lo_{t+1} - lo_t)) >> 32 -- one point per stratum, K distinct ascending indices;
+ *               n < K: point (mix(a + t) n) >> 32 (with replacement). a = mix(seed + 0x9E3779B9), mix as in
+ *               mccnn_find_neighbors_fill_sampled. counts = K.
+ *   1 split     prob = (x - min) / size > 0.5 ? 1 : 0.25 along the longest box axis (the first of equal ones);
+ *   2 gradient  prob = sqrt(clip((x - min - 0.2 size) / (0.6 size), 0.01, 1));
+ *   3 lambert   prob = sqrt(clip(view . normal, 0, 1));
+ *               pass t = 0, 1, .. visits the model in index order and accepts point i when u < prob,
+ *               u = (mix(mix(seed + 0x9E3779B9 (t + 1)) + i) >> 8) 2^-24; accepted points are appended in index order.
+ *   4 occlusion the orthographic 128 x 128 z-buffer of the points whose normal faces the view (view . normal < 0): a
+ *               facing point is kept when its depth lies within 0.01 of its pixel's minimum; no random numbers.
+ * exact != 0: the slot produces exactly `rows` rows -- protocols 1-3 repeat passes until they are collected (the last pass
+ * is cut at the row that completes them), at most mccnn_batch_max_passes() of them; protocol 4 cycles over its kept points.
+ * exact == 0: one pass, counts[slot] <= length rows are written from out_base on (rows >= length is required), the rest of
+ * the slot's rows is left untouched and the caller cuts the result by the counts.
+ * status[slot]: MCCNN_BATCH_OK; MCCNN_BATCH_NO_POINT: an exact slot whose first pass accepted nothing (no normal faces the
+ * view, an empty model); MCCNN_BATCH_PASS_BOUND: short of its rows after the last pass. A slot that gives up fills the rows
+ * it did not produce with its model's row 0 (zeros for an empty model): no output byte of an exact slot is undefined.
+ * One workgroup per slot, mccnn_batch_sample_chunk() points per iteration; the records travel by value in the kernel
+ * arguments, 32 per launch. No workspace, no memset, no float atomics: the same (store, records) give the same bytes.
+ * Every record is checked on the host against store_rows and out_rows before anything is launched (MCCNN_E_BADARG, also
+ * for protocols 3 and 4 without normals). */
+#define MCCNN_BATCH_OK 0
+#define MCCNN_BATCH_NO_POINT 1
+#define MCCNN_BATCH_PASS_BOUND 2
+typedef struct mccnn_batch_slot {
+    int offset, length;      /* the model's rows in the store */
+    int protocol;            /* 0 .. 4 */
+    int rows;                /* output rows the slot owns (exact: produces) */
+    int out_base;            /* its first output row */
+    int batch_id;            /* written into out_batch_ids */
+    int n_sel;               /* protocol 0: draw from the first n_sel <= length points */
+    int exact;
+    unsigned seed;
+    float view[3];
+    float rot[9];
+    float bmin[3], bmax[3];
+} mccnn_batch_slot;
+int mccnn_batch_sample_chunk(void);
+int mccnn_batch_max_passes(void);
+int mccnn_batch_sample(const float* store_pts, const float* store_normals, int store_rows,
+                       const mccnn_batch_slot* slots_host, int num_slots, int out_rows, float* out_pts,
+                       int* out_batch_ids, int* out_src, int* counts, int* status, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; 0 = product default). Returns the previous mask. Initial value: MCCNN_FORCE_VALU /

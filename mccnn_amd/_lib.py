@@ -120,6 +120,10 @@ SIGNATURES = {
     "mccnn_conv_prepare": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_longlong),
                                 C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(_i)]),
     "mccnn_conv_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp, _vp, _sz, _vp, _sz, _vp]),
+    # training batches built on the device (batch_sample.hip)
+    "mccnn_batch_sample_chunk": (_i, []),
+    "mccnn_batch_max_passes": (_i, []),
+    "mccnn_batch_sample": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 
