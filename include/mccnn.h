@@ -755,8 +755,10 @@ int mccnn_batch_sample(const float* store_pts, const float* store_normals, int s
 
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
- * layers; 0 = product default). Returns the previous mask. Initial value: MCCNN_FORCE_VALU /
- * MCCNN_NO_F1 in the environment, read once. */
+ * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:
+ * they take it whenever the block count is even, whatever the list length; 0 = product default).
+ * With bit 4 set the call writes bits 0-1 only and leaves bits 2-3 as they are. Returns the previous mask. Initial value: MCCNN_DEBUG keys force_valu / no_f1 / f1_coop_off /
+ * f1_coop_force in the environment, read once. */
 int mccnn_debug_conv_impl(int mask);
 
 /* Diagnostics: number of kernel launches the library has issued in this process (all streams). bench.py prints the

@@ -503,11 +503,13 @@ _DEBUG_IMPL = 0
 
 def debug_conv_impl(mask):
     """Test hook: bit 0 = VALU fallback kernels, bit 1 = general MFMA kernels for Fin = 1, bit 2 (this layer only) = the
-    edge-streaming MFMA kernels for depth-wise layers instead of the row-per-lane ones. Returns the previous mask."""
+    edge-streaming MFMA kernels for depth-wise layers instead of the row-per-lane ones. Returns the previous mask.
+    (The library's own bits 2 / 3 -- which backward edge kernel a one-input-feature layer takes, set through
+    mccnn_debug_conv_impl itself or MCCNN_DEBUG=f1_coop_off / f1_coop_force -- are left as they are.)"""
     global _DEBUG_IMPL
     prev = _DEBUG_IMPL
     _DEBUG_IMPL = int(mask)
-    _lib.load().mccnn_debug_conv_impl(int(mask) & 3)
+    _lib.load().mccnn_debug_conv_impl((int(mask) & 3) | 16)  # bit 4: bits 0-1 only
     return prev
 
 

@@ -38,6 +38,7 @@ KNOWN_KEYS = (
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",
     "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",
     "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks",
+    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force",
     # Python side
     "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",
     "ecap_scale", "hier_pmode", "geo_trace")

@@ -1150,7 +1150,8 @@ int conv_fill_args(ConvArgs& a, const float* sorted_pts, const float* sorted_fea
 }
 
 std::atomic<int>& conv_impl_override() {
-    static std::atomic<int> v{(debug_int("force_valu", 0) ? 1 : 0) | (debug_int("no_f1", 0) ? 2 : 0)};
+    static std::atomic<int> v{(debug_int("force_valu", 0) ? 1 : 0) | (debug_int("no_f1", 0) ? 2 : 0) |
+                              (debug_int("f1_coop_off", 0) ? 4 : 0) | (debug_int("f1_coop_force", 0) ? 8 : 0)};
     return v;
 }
 
@@ -1209,7 +1210,14 @@ static int launch_conv_stream(const ConvArgs& a, bool combin, bool vec, bool bf1
 
 extern "C" {
 
-int mccnn_debug_conv_impl(int mask) { return conv_impl_override().exchange(mask & 3); }
+int mccnn_debug_conv_impl(int mask) {
+    std::atomic<int>& v = conv_impl_override();
+    if (!(mask & 16)) return v.exchange(mask & 15);
+    // bit 4: set bits 0-1 only and keep bits 2-3 (which Fin = 1 backward edge kernel) as they are, in one step
+    int old = v.load(std::memory_order_relaxed);
+    while (!v.compare_exchange_weak(old, (mask & 3) | (old & 12))) {}
+    return old;
+}
 
 // combin layers with one input feature take the factored path of conv_f1.hip (f1_*)
 static bool f1_shape(int num_in_feats, int num_out_feats, int combin) {

@@ -570,6 +570,157 @@ __global__ __launch_bounds__(256, MCCNN_F1_OCC) void f1_bwd_edges(ConvArgs a, co
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Backward, edge pass, cooperative form: the W waves of a workgroup walk the SAME 64-edge chunks in the same order and
+// wave w computes block q = s W + w of sweep s (nb = k W: k sweeps; the headline, nb = 8 = W, is one sweep). A wave's
+// block is then invariant for a whole sweep: its weights live in registers (read from global memory once, no LDS
+// copy, no LDS reads in the loop), the 104 accumulators are zeroed and reduced once per sweep instead of once per
+// block, and the per-edge feature gradient of a sweep is summed inside the workgroup instead of through the dfE plane:
+// every wave leaves its block's G_i[q] . a2_e in an LDS exchange buffer [2][W][64], and after ONE workgroup barrier per
+// chunk the chunk's owner wave (chunk % W) adds the W partials in ascending q -- the same chain as the running sum of
+// f1_bwd_edges -- and issues the one atomic per edge. The buffer alternates with the parity of a trip counter that
+// runs on across sweeps: a wave can write trip k + 2 only after the barrier of trip k + 1, which the owner of trip k
+// reaches after it has read. With more than one sweep the owner carries the per-edge sum between sweeps in dfE (the
+// same lane writes and reads it). Every wave of a workgroup runs the same number of trips; tail lanes are masked,
+// never returned early. Partial row per (workgroup, block) in the layout f1_reduce reads.
+// The gathers take 32-bit byte offsets from wave-uniform bases (the host sends only lists whose arrays stay below
+// 4 GB this way: f1_coop_fits).
+// ---------------------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ T ld_off32(const void* base, unsigned byteOff) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byteOff);
+}
+template <int W>
+__global__ __launch_bounds__(W * 64, MCCNN_F1_OCC) void f1_bwd_edges_coop(ConvArgs a, const float4* __restrict__ rec,
+                                                       const float* __restrict__ G, const float* __restrict__ gb,
+                                                       float* __restrict__ featGrad, float* __restrict__ dfE, int cpg,
+                                                       float* __restrict__ partials) {
+    __shared__ float xch[2][W][64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i4 = lane & 3;
+    const long long eBegL = (long long)blockIdx.x * cpg * 64;
+    if (eBegL >= a.e) return;  // the whole workgroup
+    const int eBeg = (int)eBegL;
+    const int eEnd = (int)min((long long)a.e, eBegL + (long long)cpg * 64);
+    const int trips = (eEnd - eBeg + 63) >> 6;
+    const int sweeps = a.nb / W;
+    const unsigned tLast = (unsigned)a.e - 1u;
+    int parity = 0;
+
+    for (int s = 0; s < sweeps; ++s) {
+        const int q = s * W + wave;
+        const bool first = (s == 0), last = (s == sweeps - 1);
+        BwdBlockWeights wr;
+        load_bwd_block_weights(a, q, i4, wr);
+        const float* Gq = G + (size_t)q * a.m * 8;  // block-major: [q][centre][8]
+        float gw2[64], gb2[8], gw1[24], gb1[8];
+#pragma unroll
+        for (int k = 0; k < 64; ++k) gw2[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { gb2[k] = 0.f; gb1[k] = 0.f; }
+#pragma unroll
+        for (int k = 0; k < 24; ++k) gw1[k] = 0.f;
+
+        int2 prN;
+        float4 rcN;
+        {
+            const unsigned t0 = min((unsigned)(eBeg + lane), tLast);
+            prN = ld_off32<int2>(a.packed, t0 * 8u);
+            rcN = ld_off32<float4>(rec, t0 * 16u);
+        }
+        for (int k = 0; k < trips; ++k) {
+            const int t = eBeg + k * 64 + lane;
+            const bool act = t < eEnd;
+            const bool own = (k & (W - 1)) == wave;
+            const int2 pr = prN;
+            const float4 rc = rcN;
+            const int j = pr.x, ci = pr.y;
+            const float inv = act ? rc.w : 0.f;
+            const float4 g0 = ld_off32<float4>(Gq, (unsigned)ci * 32u), g1 = ld_off32<float4>(Gq, (unsigned)ci * 32u + 16u);
+            const float f = ld_off32<float>(a.feats, (unsigned)j * 4u);
+            float tot = 0.f, gbi = 0.f;
+            if (own) {
+#ifndef MCCNN_F1_COOP_SWEEP_ATOMIC
+                if (act && !first) tot = dfE[t];
+#endif
+                if (last) gbi = ld_off32<float>(gb, (unsigned)ci * 4u);
+            }
+            {
+                const unsigned tn = min((unsigned)t + 64u, tLast);  // clamped: branch-free prefetch of the next chunk
+                prN = ld_off32<int2>(a.packed, tn * 8u);
+                rcN = ld_off32<float4>(rec, tn * 16u);
+            }
+            const float Gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            const float sE = f * inv;
+            float a1[8], a2[8];
+            bool p1[8], p2[8];  // pre-activation >= 0 (ReLU' of the reference: spatial_conv.cu:404,429)
+            {
+                float pre1[8], pre2[8];
+                mlp_block_l12_regs(wr, rc.x, rc.y, rc.z, pre1, a1, pre2, a2);
+#pragma unroll
+                for (int r = 0; r < 8; ++r) { p1[r] = pre1[r] >= 0.0f; p2[r] = pre2[r] >= 0.0f; }
+            }
+            // this block's share of the feature gradient, G_i[q] . a2_e, for the chunk's owner
+            float sfg = 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) sfg = fmaf(Gv[r], a2[r], sfg);
+            xch[parity][wave][lane] = sfg;
+            // t3 = 1[pre2 >= 0] * G_i s_e ; dW2 += t3 a1^T, db2 += t3
+            float t3[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) t3[r] = p2[r] ? Gv[r] * sE : 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+#pragma unroll
+                for (int l = 0; l < 8; ++l) gw2[r * 8 + l] = fmaf(t3[r], a1[l], gw2[r * 8 + l]);
+                gb2[r] += t3[r];
+            }
+            // t4 = 1[pre1 >= 0] * W2^T t3 ; dW1 += t4 delta^T, db1 += t4
+            float t4[8];
+            MCCNN_PHASE();
+            layer8_regs<false>(wr.w2tlo, wr.w2thi, 0.f, 0.f, t3, t4);
+            MCCNN_PHASE();
+#pragma unroll
+            for (int l = 0; l < 8; ++l) {
+                const float v = p1[l] ? t4[l] : 0.f;
+                gw1[l * 3] = fmaf(v, rc.x, gw1[l * 3]);
+                gw1[l * 3 + 1] = fmaf(v, rc.y, gw1[l * 3 + 1]);
+                gw1[l * 3 + 2] = fmaf(v, rc.z, gw1[l * 3 + 2]);
+                gb1[l] += v;
+            }
+            // the barrier sits at the END of the trip: the waves have the second half of the chunk to arrive
+            __syncthreads();
+            if (own) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) tot += xch[parity][w][lane];
+                if (act) {
+#ifdef MCCNN_F1_COOP_SWEEP_ATOMIC  // A/B build: one atomic per edge and SWEEP instead of the running sum in dfE (NOTES: 2 % faster on the room, slower on 8 rooms and cfg3)
+                    atomicAdd(&featGrad[j], (tot + gbi) * inv);
+#else
+                    if (last) atomicAdd(&featGrad[j], (tot + gbi) * inv);
+                    else dfE[t] = tot;
+#endif
+                }
+            }
+            parity ^= 1;
+        }
+        {
+            float r2 = wave_reduce64(gw2, lane);
+            float misc[64];
+#pragma unroll
+            for (int k = 0; k < 24; ++k) misc[k] = gw1[k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { misc[24 + k] = gb1[k]; misc[32 + k] = gb2[k]; }
+#pragma unroll
+            for (int k = 40; k < 64; ++k) misc[k] = 0.f;
+            float rm = wave_reduce64(misc, lane);
+            float* pq = partials + ((size_t)blockIdx.x * a.nb + q) * MCCNN_F1_ROW;
+            pq[32 + lane] = r2;
+            if (lane < 32) pq[lane] = rm;                 // w1, b1
+            else if (lane < 40) pq[96 + lane - 32] = rm;  // b2
+        }
+    }
+}
+
 // Backward, centre pass (runs before the edge pass): G_i[q] = W3_q^T g_i[q] and gb_i = g_i . b3 for the edges, and the
 // layer-3 gradients dW3 = sum_i g_i (x) A_i, db3 = sum_i g_i S_i. Waves own slices of centres, q-outer with the 72 sums
 // of a block in registers; partial row per (wave, block): w3[64] b3[8].
@@ -728,6 +879,44 @@ static void f1_bwd_partition(int e, int& cpw, int& waves) {
     waves = (int)((chunks + cpw - 1) / cpw);
     if (waves < 1) waves = 1;
 }
+// The cooperative form. W = the largest of {8, 4, 2} that divides nb (0: odd nb, no cooperative form); a workgroup owns
+// cpg consecutive chunks, `groups` workgroups cover the list. The window rule of f1_bwd_partition applies to the W-wave
+// workgroup (W times the chunks of a wave's slice) -- also with ONE sweep, which reads its slice once: the W waves
+// gather from W planes of G at a time, and with one round of long slices spread over the whole list all of G is hot
+// (8 rooms, 8 blocks: 205 MB of G, 2.85 ms, no faster than the slice kernel); rounds dispatched in slice order keep
+// the centres of the workgroups in flight inside one window.
+static int f1_coop_width(int nb) { return nb % 8 == 0 ? 8 : nb % 4 == 0 ? 4 : nb % 2 == 0 ? 2 : 0; }
+static long long f1_coop_resident(int W) { return (long long)num_cus() * 4 * MCCNN_F1_OCC / W; }
+static void f1_coop_partition(int e, int W, int& cpg, int& groups) {
+    const long long chunks = ((long long)e + 63) / 64;
+    const long long resident = f1_coop_resident(W);
+    cpg = (int)((chunks + resident - 1) / resident);
+    if (cpg > 48 * W) {
+        const long long rounds = (cpg + 32 * W - 1) / (32 * W);
+        cpg = (int)((chunks + resident * rounds - 1) / (resident * rounds));
+    }
+    static const int minChunks = debug_int("bwd_min_chunks", 2);
+    if (cpg < minChunks) cpg = minChunks < 1 ? 1 : minChunks;
+    groups = (int)((chunks + cpg - 1) / cpg);
+    if (groups < 1) groups = 1;
+}
+// 32-bit byte offsets: 16 B records and 8 B list entries per edge, 32 B of G per centre, 4 B per point
+static bool f1_coop_fits(int n, int m, int e) { return e < (1 << 27) && m < (1 << 26) && n < (1 << 29); }
+#ifndef MCCNN_F1_COOP_MIN_CHUNKS
+#define MCCNN_F1_COOP_MIN_CHUNKS 3
+#endif
+// Which form runs (mccnn_debug_conv_impl: bit 2 = never the cooperative one, bit 3 = whenever nb is even). By default
+// lists that give a workgroup at least f1_coop_min_chunks chunks with the whole chip in use; shorter ones keep one
+// wave per slice (more, shorter slices to spread).
+static int f1_coop_choice(int n, int m, int e, int nb) {
+    const int W = f1_coop_width(nb);
+    const int mask = conv_impl_override().load(std::memory_order_relaxed);
+    if (W == 0 || (mask & 4) || !f1_coop_fits(n, m, e)) return 0;
+    if (mask & 8) return W;
+    static const int minChunks = debug_int("f1_coop_min_chunks", MCCNN_F1_COOP_MIN_CHUNKS);
+    const long long chunks = ((long long)e + 63) / 64;
+    return chunks >= f1_coop_resident(W) * minChunks ? W : 0;
+}
 #ifndef MCCNN_F1_CENTRE_WAVES
 #define MCCNN_F1_CENTRE_WAVES 1024
 #endif
@@ -792,7 +981,13 @@ size_t f1_bwd_workspace_bytes(int m, int e, int nb) {
     size_t b = f1_state_bytes(m, nb);                                               // (A, S) when the caller kept no state
     b += align_up((size_t)m * nb * 8 * sizeof(float)) + align_up((size_t)m * sizeof(float));  // G, gb
     b += align_up((size_t)e * sizeof(float4)) + align_up((size_t)e * sizeof(float));          // records, per-edge dFeat
-    b += align_up((size_t)(wavesE + 3) / 4 * 4 * nb * MCCNN_F1_ROW * sizeof(float));
+    size_t rowsE = (size_t)(wavesE + 3) / 4 * 4;
+    if (const int W = f1_coop_width(nb)) {  // the larger of the two forms: the choice can be switched at run time
+        int cpg, groups;
+        f1_coop_partition(e, W, cpg, groups);
+        if ((size_t)groups > rowsE) rowsE = (size_t)groups;
+    }
+    b += align_up(rowsE * nb * MCCNN_F1_ROW * sizeof(float));
     b += align_up((size_t)(wavesC + 3) / 4 * 4 * nb * MCCNN_F1_ROWC * sizeof(float));
     return b + 256;
 }
@@ -805,13 +1000,17 @@ int f1_backward(const ConvArgs& a, const float* out_grad, const float4* rec_in, 
     f1_bwd_partition(a.e, cpw, wavesE);
     f1_centre_partition(a.m, cPerWave, wavesC);
     const int blocksE = (wavesE + 3) / 4, blocksC = (wavesC + 3) / 4;
+    const int coopW = f1_coop_choice(a.n, a.m, a.e, a.nb);
+    int cpg = 0, groups = 0;
+    if (coopW) f1_coop_partition(a.e, coopW, cpg, groups);
+    const size_t rowsE = (size_t)groups > (size_t)blocksE * 4 ? (size_t)groups : (size_t)blocksE * 4;
     Arena ar(ws, ws_bytes);
     void* own = ar.take<char>(f1_state_bytes(a.m, a.nb));
     float* G = ar.take<float>((size_t)a.m * a.nb * 8);
     float* gb = ar.take<float>((size_t)a.m);
     float4* rec = ar.take<float4>((size_t)a.e);
     float* dfE = ar.take<float>((size_t)a.e);
-    float* pe = ar.take<float>((size_t)blocksE * 4 * a.nb * MCCNN_F1_ROW);
+    float* pe = ar.take<float>(rowsE * a.nb * MCCNN_F1_ROW);
     float* pc = ar.take<float>((size_t)blocksC * 4 * a.nb * MCCNN_F1_ROWC);
     if (!own || !G || !gb || !rec || !dfE || !pe || !pc) return MCCNN_E_WORKSPACE;
     float *A, *S;
@@ -831,10 +1030,15 @@ int f1_backward(const ConvArgs& a, const float* out_grad, const float4* rec_in, 
         f1_edge_records<<<ceil_div(a.e, 256), 256, 0, s>>>(a, rec);
         MCCNN_LAUNCHED();
     }
-    const size_t ldsE = (size_t)a.nb * MCCNN_WQ_BWD * sizeof(float);
-    f1_bwd_edges<<<blocksE, 256, ldsE, s>>>(a, recUse, G, gb, feat_grad, dfE, cpw, pe);
+    if (coopW == 8) f1_bwd_edges_coop<8><<<groups, 512, 0, s>>>(a, recUse, G, gb, feat_grad, dfE, cpg, pe);
+    else if (coopW == 4) f1_bwd_edges_coop<4><<<groups, 256, 0, s>>>(a, recUse, G, gb, feat_grad, dfE, cpg, pe);
+    else if (coopW == 2) f1_bwd_edges_coop<2><<<groups, 128, 0, s>>>(a, recUse, G, gb, feat_grad, dfE, cpg, pe);
+    else {
+        const size_t ldsE = (size_t)a.nb * MCCNN_WQ_BWD * sizeof(float);
+        f1_bwd_edges<<<blocksE, 256, ldsE, s>>>(a, recUse, G, gb, feat_grad, dfE, cpw, pe);
+    }
     MCCNN_LAUNCHED();
-    f1_reduce<<<ceil_div((long long)a.nb * 176, 16), 1024, 0, s>>>(pe, wavesE, pc, wavesC, a.nb, dw1, db1, dw2, db2, dw3, db3);
+    f1_reduce<<<ceil_div((long long)a.nb * 176, 16), 1024, 0, s>>>(pe, coopW ? groups : wavesE, pc, wavesC, a.nb, dw1, db1, dw2, db2, dw3, db3);
     MCCNN_LAUNCHED();
     return 0;
 }

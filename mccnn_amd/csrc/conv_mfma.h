@@ -147,6 +147,59 @@ __device__ __forceinline__ void layer8_regs(const float* al, const float* ah, fl
     for (int r = 0; r < 4; ++r) { y[r] = lo[r]; y[4 + r] = hi[r]; }
 }
 
+// Layer 1 from registers: lo / hi = (w0, w1, w2, b1) of neurons i4 / 4 + i4; the chain of layer1_mfma.
+__device__ __forceinline__ void layer1_regs(const float* lo4, const float* hi4, float d0, float d1, float d2, float* pre1) {
+    f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
+    const float one = opaque_one();
+    lo = MFMA4(lo4[0], d0, lo);
+    hi = MFMA4(hi4[0], d0, hi);
+    lo = MFMA4(lo4[1], d1, lo);
+    hi = MFMA4(hi4[1], d1, hi);
+    lo = MFMA4(lo4[2], d2, lo);
+    hi = MFMA4(hi4[2], d2, hi);
+    lo = MFMA4(lo4[3], one, lo);
+    hi = MFMA4(hi4[3], one, hi);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { pre1[r] = lo[r]; pre1[4 + r] = hi[r]; }
+}
+
+// One block's weights as a lane of the Fin = 1 backward edge pass needs them (42 VGPRs), read straight from the flat
+// tensors: rows i4 and 4 + i4 of W1 | b1, of W2 with b2 and of W2^T (row l of W2^T = column l of W2).
+struct BwdBlockWeights {
+    float w1lo[4], w1hi[4];
+    float w2lo[8], w2hi[8], b2lo, b2hi;
+    float w2tlo[8], w2thi[8];
+};
+__device__ __forceinline__ void load_bwd_block_weights(const ConvArgs& a, int q, int i4, BwdBlockWeights& w) {
+    const int nl = q * 8 + i4, nh = nl + 4;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { w.w1lo[c] = a.w1[nl * 3 + c]; w.w1hi[c] = a.w1[nh * 3 + c]; }
+    w.w1lo[3] = a.b1[nl]; w.w1hi[3] = a.b1[nh];
+    const float* w2 = a.w2 + (size_t)q * 64;
+    const float4* r2l = reinterpret_cast<const float4*>(w2 + i4 * 8);
+    const float4* r2h = reinterpret_cast<const float4*>(w2 + (4 + i4) * 8);
+    const float4 a0 = r2l[0], a1 = r2l[1], b0 = r2h[0], b1 = r2h[1];
+    w.w2lo[0] = a0.x; w.w2lo[1] = a0.y; w.w2lo[2] = a0.z; w.w2lo[3] = a0.w; w.w2lo[4] = a1.x; w.w2lo[5] = a1.y; w.w2lo[6] = a1.z; w.w2lo[7] = a1.w;
+    w.w2hi[0] = b0.x; w.w2hi[1] = b0.y; w.w2hi[2] = b0.z; w.w2hi[3] = b0.w; w.w2hi[4] = b1.x; w.w2hi[5] = b1.y; w.w2hi[6] = b1.z; w.w2hi[7] = b1.w;
+    w.b2lo = a.b2[nl]; w.b2hi = a.b2[nh];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { w.w2tlo[k] = w2[k * 8 + i4]; w.w2thi[k] = w2[k * 8 + 4 + i4]; }
+}
+// Layers 1 and 2 from those registers: identical chains (and bits) as mlp_block_l12.
+__device__ __forceinline__ void mlp_block_l12_regs(const BwdBlockWeights& w, float d0, float d1, float d2,
+                                                   float* pre1, float* a1, float* pre2, float* a2) {
+    layer1_regs(w.w1lo, w.w1hi, d0, d1, d2, pre1);
+    MCCNN_PHASE();
+#pragma unroll
+    for (int r = 0; r < 8; ++r) a1[r] = relu1(pre1[r]);
+    MCCNN_PHASE();
+    layer8_regs<true>(w.w2lo, w.w2hi, w.b2lo, w.b2hi, a1, pre2);
+    MCCNN_PHASE();
+#pragma unroll
+    for (int r = 0; r < 8; ++r) a2[r] = relu1(pre2[r]);
+    MCCNN_PHASE();
+}
+
 // One block's forward weights as the lane needs them for the 4x4x1 form (44 VGPRs), read straight from the flat
 // tensors (w1[nu][3], w2 / w3 [q][out][in]): rows i4 and 4 + i4 of every layer.
 struct BlockWeights {
@@ -174,20 +227,7 @@ __device__ __forceinline__ void load_block_weights(const ConvArgs& a, int q, int
 // Kernel MLP of one block from register-resident weights: identical chains (and bits) as mlp_block_mfma.
 __device__ __forceinline__ void mlp_block_regs(const BlockWeights& w, float d0, float d1, float d2, float* a1, float* a2, float* o) {
     float pre[8];
-    {
-        f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-        const float one = opaque_one();
-        lo = MFMA4(w.w1lo[0], d0, lo);
-        hi = MFMA4(w.w1hi[0], d0, hi);
-        lo = MFMA4(w.w1lo[1], d1, lo);
-        hi = MFMA4(w.w1hi[1], d1, hi);
-        lo = MFMA4(w.w1lo[2], d2, lo);
-        hi = MFMA4(w.w1hi[2], d2, hi);
-        lo = MFMA4(w.w1lo[3], one, lo);
-        hi = MFMA4(w.w1hi[3], one, hi);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pre[r] = lo[r]; pre[4 + r] = hi[r]; }
-    }
+    layer1_regs(w.w1lo, w.w1hi, d0, d1, d2, pre);
     MCCNN_PHASE();
 #pragma unroll
     for (int r = 0; r < 8; ++r) a1[r] = relu1(pre[r]);

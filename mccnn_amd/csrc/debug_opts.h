@@ -35,6 +35,9 @@
 //     plan_batch_sync (0)            1 = a synchronisation and a stderr line per launch of the plan batch
 //     caller_join_off (0)            fault injection: a geometry nobody joined does not order the caller's stream
 //     bwd_min_chunks (2)             64-edge chunks per wave of the edge-streaming backward passes at least
+//     f1_coop_min_chunks (3)         chunks per workgroup (whole chip in use) from which a one-input-feature backward pass takes the cooperative edge kernel
+//     f1_coop_off (0)                1 = never the cooperative edge kernel (seeds mccnn_debug_conv_impl, bit 2)
+//     f1_coop_force (0)              1 = the cooperative edge kernel whenever the block count is even (seeds mccnn_debug_conv_impl, bit 3)
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +51,7 @@ namespace mccnn {
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",      \
     "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",                                                       \
     "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks", \
+    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force",                                                                \
     /* Python side (mccnn_amd/_env.py) */                                                                                \
     "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",                          \
     "ecap_scale", "hier_pmode", "geo_trace"

@@ -161,7 +161,7 @@ GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int
     return L;
 }
 
-int read_mask() { return conv_impl_override().load(std::memory_order_relaxed); }
+int read_mask() { return conv_impl_override().load(std::memory_order_relaxed) & 3; }  // (bits 2 / 3 choose between the Fin = 1 backward edge kernels)
 
 bool env_flag(const char* name, bool dflt) {
     const char* v = getenv(name);
