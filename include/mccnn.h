@@ -206,6 +206,35 @@ int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_ba
                                       const int* centre_order, const int* start_idx, int e,
                                       int* packed, void* ws, size_t ws_bytes, mccnn_stream_t stream,
                                       int max_neighbors, unsigned seed);
+/* The search with a budget on the EDGES of its list (extension). max_edges = B > 0; max_neighbors =
+ * Ku >= 0 (0 = no cap of the caller's). With k_i the uncapped row lengths, kmax = max(max_i k_i, 1)
+ * and S(K) = sum_i min(k_i, K) in 64-bit integers, the search picks on the device
+ *     K* = max{ K : 1 <= K <= min(Ku, kmax), S(K) <= B }   if S(1) <= B,   K* = 1 otherwise
+ * and its output is byte for byte that of the capped pair at max_neighbors = K* (fill: sampled != 0,
+ * that of mccnn_find_neighbors_fill_sampled at K* and `seed`). E = S(K*) <= max(B, non-empty rows):
+ * every non-empty row keeps one hit, so a budget below m is a floor, not an error; a packed buffer
+ * of max(B, m) rows cannot overflow. count: count pass (the capped one, no clamp) -> selection (one
+ * launch up to 4096 centres, three above) -> prefix sum of min(k_i, K*); *cap_dev = K*, a
+ * device-accessible word the fill pass reads -- nothing returns to the host in between. Integer
+ * atomics only: the same inputs give the same K* and the same bytes in every run. Protocol of the
+ * capped pair (ws of mccnn_find_neighbors_budget_workspace_bytes untouched between the calls, e may
+ * be a guess). max_edges <= 0, max_neighbors < 0, cap_dev == NULL: MCCNN_E_BADARG; m == 0 writes
+ * total 0 and cap 1; m > 2^21: MCCNN_E_TOOLARGE. */
+size_t mccnn_find_neighbors_budget_workspace_bytes(int m, int n);
+int mccnn_find_neighbors_count_budget(const float* centres, const int* centre_batch_ids, int m,
+                                      const float* sorted_pts, int n, const int* cell_indexs,
+                                      const float* aabb_min, const float* aabb_max, int batch_size,
+                                      int num_cells, float radius, int scale_inv,
+                                      const int* centre_order, int* start_idx, int* total_dev,
+                                      void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                      int max_neighbors, int max_edges, int* cap_dev);
+int mccnn_find_neighbors_fill_budget(const float* centres, const int* centre_batch_ids, int m,
+                                     const float* sorted_pts, int n, const int* cell_indexs,
+                                     const float* aabb_min, const float* aabb_max, int batch_size,
+                                     int num_cells, float radius, int scale_inv,
+                                     const int* centre_order, const int* start_idx, int e,
+                                     int* packed, void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                     const int* cap_dev, int sampled, unsigned seed);
 /* inv[new_idx[i]] = i -- the visiting order above for same-level searches (sort_gpu.cu:332-345). */
 int mccnn_invert_permutation(const int* new_idx, int n, int* inv, mccnn_stream_t stream);
 

@@ -343,7 +343,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
-                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False, pointGrad=False):
+                 maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False, pointGrad=False,
+                 maxEdges=0):
         """pdfMode (extension): 'edge' (default) -- the reference's density, a Gaussian sum over the centre's row for every
         edge (compute_pdf); 'point' -- the density of every point over its OWN ball, computed once per (grid, KDEWindow)
         and shared by every list over that grid (compute_pdf_points + expand_pdf). A 'point' layer with usePDF takes the
@@ -367,9 +368,16 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         capNative_ may be reassigned between steps (followed by reset()).
         sampleSeed (extension): None, or an integer in [0, 2^32) -- the capped layers then draw a stratified sample of
         their over-full rows (find_neighbors(sampleSeed=)) instead of the canonical ranks. The attribute sampleSeed_ may be
-        reassigned between steps (typically to the step number, followed by reset()); layers without a cap ignore it."""
+        reassigned between steps (typically to the step number, followed by reset()); layers without a cap ignore it.
+        maxEdges (extension): the default budget B on the EDGES of every layer's neighbour list (find_neighbors(maxEdges=));
+        0 = none. The search picks the largest cap <= maxNeighbors whose list has at most B rows, on the device; the
+        budget is per list. A budgeted layer runs op by op, like a capped layer without capNative, whatever capNative_
+        says; chosenCaps_[keyNeighs] holds the device tensor with the cap its last search chose (never read back here).
+        The attribute maxEdges_ may be reassigned between steps (followed by reset())."""
         super().__init__()
         self.maxNeighbors_ = self.__check_cap__(maxNeighbors)
+        self.maxEdges_ = self.__check_budget__(maxEdges)
+        self.chosenCaps_ = {}       # keyNeighs -> int32 device tensor [1]: the cap of the list's last budgeted search
         self.sampleSeed_ = self.__check_seed__(sampleSeed)
         if not isinstance(capNative, bool):
             from .MCConvModule import InvalidArgumentError
@@ -473,6 +481,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         return maxNeighbors
 
     @staticmethod
+    def __check_budget__(maxEdges):
+        if not isinstance(maxEdges, int) or isinstance(maxEdges, bool) or not 0 <= maxEdges < 2 ** 31:
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("maxEdges must be an integer in [0, 2^31) (0 = no budget)")
+        return maxEdges
+
+    @staticmethod
     def __check_seed__(sampleSeed):
         if sampleSeed is not None and (not isinstance(sampleSeed, int) or isinstance(sampleSeed, bool)
                                        or not 0 <= sampleSeed < 2 ** 32):
@@ -487,26 +502,40 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             raise InvalidArgumentError("pdfMode must be 'edge' or 'point'")
         return pdfMode
 
-    def __layer_seed__(self, currCap, sampleSeed):
-        """The seed of a layer with cap currCap: its own (which needs a cap) or the builder's (capped layers only)."""
+    def __layer_seed__(self, currCap, sampleSeed, currBudget=0):
+        """The seed of a layer with cap currCap and budget currBudget: its own (which needs a cap or a budget) or the
+        builder's (capped and budgeted layers only)."""
         if sampleSeed is not None:
-            if currCap == 0:
+            if currCap == 0 and currBudget == 0:
                 from .MCConvModule import InvalidArgumentError
-                raise InvalidArgumentError("sampleSeed needs a cap (maxNeighbors > 0)")
+                raise InvalidArgumentError("sampleSeed needs a cap (maxNeighbors > 0) or a budget (maxEdges > 0)")
             return self.__check_seed__(sampleSeed)
-        return self.__check_seed__(self.sampleSeed_) if currCap > 0 else None
+        return self.__check_seed__(self.sampleSeed_) if (currCap > 0 or currBudget > 0) else None
 
     @staticmethod
-    def __search_args__(currCap, currSeed, keyNeighs):
+    def __search_args__(currCap, currSeed, keyNeighs, currBudget=0):
         """Keywords of the find_neighbors call of a geometry (none without a cap: a checker behind `ops=` need not know
         them). The op's seed is the layer's plus the CRC-32 of the geometry's neighbour key without the seed part, so that
         two layers over the same centres do not draw the same offsets."""
-        if currCap == 0:
+        if currBudget > 0:   # a budgeted search also returns the cap it chose (a device tensor: __take_search__)
+            kw = {"maxEdges": currBudget, "returnCap": True}
+            if currCap > 0:
+                kw["maxNeighbors"] = currCap
+        elif currCap == 0:
             return {}
-        if currSeed is None:
-            return {"maxNeighbors": currCap}
-        base = keyNeighs[:-len('|s' + str(currSeed))]
-        return {"maxNeighbors": currCap, "sampleSeed": (currSeed + zlib.crc32(base.encode())) & 0xffffffff}
+        else:
+            kw = {"maxNeighbors": currCap}
+        if currSeed is not None:
+            base = keyNeighs[:-len('|s' + str(currSeed))]
+            kw["sampleSeed"] = (currSeed + zlib.crc32(base.encode())) & 0xffffffff
+        return kw
+
+    def __take_search__(self, res, keyNeighs):
+        """(startIndexs, packedNeighs) of a find_neighbors result; the cap a budgeted search appends goes to chosenCaps_."""
+        res = tuple(res)
+        if len(res) > 2:
+            self.chosenCaps_[keyNeighs] = res[2]
+        return res[:2]
 
     def __geometry_defaults__(self, inPH, inLevel, outPH, outLevel, KDEWindow, relativeRadius, usePDF):
         """-> (KDEWindow, relativeRadius, usePDF, outPH, outLevel) with the builder's defaults filled in
@@ -517,14 +546,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 inPH if outPH is None else outPH, inLevel if outLevel is None else outLevel)
 
     def __compute_dic_keys__(self, inPointHierarchy, outPointHierarchy, inPointLevel, outPointLevel, convRadius,
-                             KDEWindow, relativeRadius, usePDF, maxNeighbors=0, sampleSeed=None):
+                             KDEWindow, relativeRadius, usePDF, maxNeighbors=0, sampleSeed=None, maxEdges=0):
         # MCConvBuilder.py:203-238 (the strings depend on names and numbers only: memoised -- six str() of floats per call)
         # maxNeighbors > 0 (extension): a capped list and its PDFs are other cache entries than the uncapped ones and those
         # of another cap; the grid is the same. Without a cap the strings are the reference's. sampleSeed (with a cap): the
-        # draw is part of the neighbour and PDF keys, after the cap.
+        # draw is part of the neighbour and PDF keys, after the cap. maxEdges > 0: '|e' + B after the cap and before the seed.
         memo = self.__dict__.setdefault("_keyMemo", {})
         k = (inPointHierarchy.hierarchyName_, outPointHierarchy.hierarchyName_, inPointLevel, outPointLevel, convRadius, KDEWindow,
-             relativeRadius, usePDF, maxNeighbors, sampleSeed)
+             relativeRadius, usePDF, maxNeighbors, sampleSeed) + ((maxEdges,) if maxEdges > 0 else ())
         try:
             hit = memo.get(k)
         except TypeError:   # (an unhashable argument: a tensor radius)
@@ -538,9 +567,12 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if maxNeighbors > 0:
             keyNeighs += '|' + str(maxNeighbors)
             keyPDF += '|' + str(maxNeighbors)
-            if sampleSeed is not None:
-                keyNeighs += '|s' + str(sampleSeed)
-                keyPDF += '|s' + str(sampleSeed)
+        if maxEdges > 0:
+            keyNeighs += '|e' + str(maxEdges)
+            keyPDF += '|e' + str(maxEdges)
+        if (maxNeighbors > 0 or maxEdges > 0) and sampleSeed is not None:
+            keyNeighs += '|s' + str(sampleSeed)
+            keyPDF += '|s' + str(sampleSeed)
         if k is not None and len(memo) < 4096:
             memo[k] = (keyGrid, keyNeighs, keyPDF)
         return keyGrid, keyNeighs, keyPDF
@@ -619,7 +651,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def prefetch_geometry(self, inPointHierarchy, inPointLevel, convRadius, outPointHierarchy=None, outPointLevel=None,
                           KDEWindow=None, relativeRadius=None, usePDF=None, transposed=False, maxNeighbors=None,
-                          sampleSeed=None, pdfMode=None):
+                          sampleSeed=None, pdfMode=None, maxEdges=None):
         """Extension (no counterpart in the reference): computes the grid, the neighbour list and the PDFs that
         create_convolution() with the same arguments looks up in the caches -- for the NEXT batch, on a side stream, and
         parks them until the next reset(). Geometry depends on the points only, not on the network, so in a training
@@ -642,6 +674,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geometry is prefetched op by op on the side stream, or -- with capNative_ -- by the native executor like an
         uncapped one.
         sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call).
+        maxEdges: the edge budget of that call (None = the builder's maxEdges_). A budgeted geometry is prefetched op by op
+        on the side stream, like a capped one without capNative_.
         pdfMode: the mode of that call (None = the builder's). The per-point density has a prefetched form on the native
         executor only: 'point' with usePDF raises unless pointNative_ is set, and then parks a native point geometry (where
         the native executor cannot take the levels nothing is started: create_convolution computes them itself)."""
@@ -653,17 +687,20 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             raise InvalidArgumentError("prefetch_geometry: pdfMode='point' has no prefetched form (its layers build their "
                                        "geometry themselves, op by op)")
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
-        if pointPDF and currCap > 0:
+        currBudget = self.maxEdges_ if maxEdges is None else self.__check_budget__(maxEdges)
+        if pointPDF and (currCap > 0 or currBudget > 0):
             from .MCConvModule import InvalidArgumentError
-            raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0)")
-        currSeed = self.__layer_seed__(currCap, sampleSeed)
+            raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0, maxEdges = 0: a "
+                                       "budget is a cap)")
+        currSeed = self.__layer_seed__(currCap, sampleSeed, currBudget)
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(inPointHierarchy, outPH, inPointLevel, outLevel, convRadius,
-                                                               currKDEWindow, currRelativeRadius, currUsePDF, currCap, currSeed)
+                                                               currKDEWindow, currRelativeRadius, currUsePDF, currCap, currSeed,
+                                                               currBudget)
         pts, bids = inPointHierarchy.points_[inPointLevel], inPointHierarchy.batchIds_[inPointLevel]
         mn, mx, B = inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, inPointHierarchy.batchSize_
         if not pts.is_cuda:
             return  # host tensors (a CPU checker behind `ops=`): nothing to overlap, create_convolution computes inline
-        if (currCap == 0 or self.capNative_) and self.__prefetch_native__(
+        if currBudget == 0 and (currCap == 0 or self.capNative_) and self.__prefetch_native__(
                 inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow, currRelativeRadius, currUsePDF,
                 keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed, point=pointPDF):
             return
@@ -700,14 +737,16 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             bg_prev = bg.mccnn_background_launches(1)
         try:
             self.__prefetch_on_side__(side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap, currSeed)
+                                      currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap, currSeed,
+                                      currBudget)
         finally:
             if bg is not None:
                 bg.mccnn_background_launches(bg_prev)
 
     def __prefetch_on_side__(self, side, grids, neighs, pdfs, keyGrid, keyNeighs, keyPDF, pts, bids, mn, mx, B, convRadius,
-                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap=0, currSeed=None):
-        capArgs = self.__search_args__(currCap, currSeed, keyNeighs)
+                             currRelativeRadius, currKDEWindow, currUsePDF, outPH, outLevel, transposed, currCap=0, currSeed=None,
+                             currBudget=0):
+        capArgs = self.__search_args__(currCap, currSeed, keyNeighs, currBudget)
         with torch.cuda.stream(side):
             if keyGrid not in grids and self.fuseSort_ and self.hipSurface_ and not pts.requires_grad:
                 _hip_ops = _hip_ops_mod()
@@ -722,7 +761,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 grids[keyGrid] = (sortPts, sortBatchs, cellIndexs, indexs)
             g = grids[keyGrid]
             deferred = None
-            if self.hipSurface_ and currCap == 0:  # the HIP op surface (not a checker handed in through `ops=`); the deferred op has no capped form
+            if self.hipSurface_ and currCap == 0 and currBudget == 0:  # the HIP op surface (not a checker handed in through `ops=`); the deferred op has no capped form
                 _hip_ops = _hip_ops_mod()
                 deferred = _hip_ops.find_neighbors_pdf_deferred
             if keyNeighs not in neighs and keyPDF not in pdfs and currUsePDF and deferred is not None:
@@ -737,8 +776,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 self.prefetchTransposed_[keyNeighs] = (keyGrid, keyPDF, outPH.points_[outLevel], mn, mx, B, convRadius,
                                                        currRelativeRadius)
             if keyNeighs not in neighs:
-                neighs[keyNeighs] = tuple(self.ops_.find_neighbors(outPH.points_[outLevel], outPH.batchIds_[outLevel], g[0],
-                                                                   g[2], mn, mx, convRadius, B, currRelativeRadius, **capArgs))
+                neighs[keyNeighs] = self.__take_search__(
+                    self.ops_.find_neighbors(outPH.points_[outLevel], outPH.batchIds_[outLevel], g[0], g[2], mn, mx, convRadius, B,
+                                             currRelativeRadius, **capArgs), keyNeighs)
             nb = neighs[keyNeighs]
             if keyPDF not in pdfs:
                 if currUsePDF:
@@ -748,6 +788,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                     pdfs[keyPDF] = torch.ones((nb[1].shape[0], 1), dtype=torch.float32, device=nb[1].device)
             event = torch.cuda.Event()
             event.record(side)
+        if currBudget > 0 and keyNeighs in self.chosenCaps_:   # (allocated on the side stream, read on the caller's)
+            self.chosenCaps_[keyNeighs].record_stream(torch.cuda.current_stream())
         self.prefetched_ = (grids, neighs, pdfs, event)
 
     def _trace(self, *rec):
@@ -1067,7 +1109,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     def create_convolution(self, convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                            outPointHierarchy=None, outPointLevel=None, multiFeatureConv=None, outNumFeatures=None,
                            KDEWindow=None, relativeRadius=None, usePDF=None, useAVG=None, maxNeighbors=None,
-                           sampleSeed=None, pdfMode=None):
+                           sampleSeed=None, pdfMode=None, maxEdges=None):
         # defaults: MCConvBuilder.py:299-325
         # pdfMode (extension; None = the builder's pdfMode_): 'point' with usePDF takes the density of every point over its
         # own ball (one compute_pdf_points per grid and window, cachePointPDFs_) and spreads it over the list's edges
@@ -1081,8 +1123,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # like one whose points require a gradient, unless the builder was made with capNative=True (capNative_): then it
         # runs through the native executor like an uncapped one, with the same bytes. sampleSeed (extension; None = the builder's sampleSeed_): the capped
         # search draws a stratified sample of the over-full rows; a seed of the layer's own needs a cap.
+        # maxEdges (extension; None = the builder's maxEdges_): a budget on the edges of this layer's list -- the search picks
+        # the cap itself (find_neighbors(maxEdges=)). A budgeted layer takes the op-by-op path below, whatever capNative_ says.
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
-        currSeed = self.__layer_seed__(currCap, sampleSeed)
+        currBudget = self.maxEdges_ if maxEdges is None else self.__check_budget__(maxEdges)
+        currSeed = self.__layer_seed__(currCap, sampleSeed, currBudget)
         currPDFMode = self.__check_pdf_mode__(self.pdfMode_ if pdfMode is None else pdfMode)
         currMultiFeatureConv = self.multiFeatureConvs_ if multiFeatureConv is None else multiFeatureConv
         currNumOutFeatures = inNumFeatures if outNumFeatures is None else outNumFeatures
@@ -1098,7 +1143,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
         keyGrid, keyNeighs, keyPDF = self.__compute_dic_keys__(
             inPointHierarchy, currOutPointHierarchy, inPointLevel, currOutPointLevel, convRadius, currKDEWindow,
-            currRelativeRadius, currUsePDF, currCap, currSeed)
+            currRelativeRadius, currUsePDF, currCap, currSeed, currBudget)
         _log("Convolution: %s (KDE: %s | MF: %s | Rel: %s | PDF: %s)" % (convName, currKDEWindow,
                                                                        currMultiFeatureConv, currRelativeRadius,
                                                                        currUsePDF))
@@ -1110,9 +1155,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         pointGradLayer = False
         if pointPDF:
             from .MCConvModule import InvalidArgumentError
-            if currCap > 0:
-                raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0): on a capped "
-                                           "row the per-point density is unbiased but far noisier than the per-edge one")
+            if currCap > 0 or currBudget > 0:
+                raise InvalidArgumentError("pdfMode='point' needs an uncapped neighbour list (maxNeighbors = 0, maxEdges = 0: a "
+                                           "budget is a cap): on a capped row the per-point density is unbiased but far "
+                                           "noisier than the per-edge one")
             if inPts.requires_grad or currOutPointHierarchy.points_[currOutPointLevel].requires_grad:
                 if not (self.pointGrad_ and self.hipSurface_):
                     raise InvalidArgumentError("pdfMode='point' is not differentiable with respect to the points: they must "
@@ -1121,7 +1167,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 pointGradLayer = True   # op by op below, whatever pointNative_ says
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
         if self.native_ and fused and (not pointPDF or (self.pointNative_ and not pointGradLayer)) \
-                and (currCap == 0 or self.capNative_):
+                and currBudget == 0 and (currCap == 0 or self.capNative_):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
@@ -1168,7 +1214,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # neighbours (MCConvBuilder.py:366-376)
         # (uncapped lists only: the deferred op has no capped form -- a capped layer that did not take the native executor
         # above runs find_neighbors + compute_pdf)
-        if fused and currCap == 0 and currUsePDF and not pointPDF and keyNeighs not in self.cacheNeighs_ \
+        if fused and currCap == 0 and currBudget == 0 and currUsePDF and not pointPDF and keyNeighs not in self.cacheNeighs_ \
                 and keyPDF not in self.cachePDFs_:
             # search + KDE enqueued back to back (list sizes from the last total of this shape), ONE wait for the edge
             # count at the end instead of a wait between the two ops; None on the first call of a shape
@@ -1186,10 +1232,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if keyNeighs in self.cacheNeighs_:
             currNeighTuple = self.cacheNeighs_[keyNeighs]
         else:
-            startIndexs, packedNeighs = self.ops_.find_neighbors(
+            startIndexs, packedNeighs = self.__take_search__(self.ops_.find_neighbors(
                 currOutPointHierarchy.points_[currOutPointLevel], currOutPointHierarchy.batchIds_[currOutPointLevel],
                 currGridTuple[0], currGridTuple[2], inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, convRadius,
-                inPointHierarchy.batchSize_, currRelativeRadius, **self.__search_args__(currCap, currSeed, keyNeighs))
+                inPointHierarchy.batchSize_, currRelativeRadius,
+                **self.__search_args__(currCap, currSeed, keyNeighs, currBudget)), keyNeighs)
             currNeighTuple = (startIndexs, packedNeighs)
             self.cacheNeighs_[keyNeighs] = currNeighTuple
             self._trace("find_neighbors", keyNeighs)

@@ -781,16 +781,21 @@ def transform_indexs(inIndexs, inNewPositions):
 
 
 def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radius, batchSize, scaleInv, maxNeighbors=0,
-                   sampleSeed=None):
+                   sampleSeed=None, maxEdges=0, returnCap=False):
     """FindNeighbors (MCConvModuleSrc:51, find_neighbors.cc:80-185) -> (startIndexs [M,1], packedNeighs [E,2]).
     Reads E back to the host to size the second output, like the reference (find_neighbors.cu:307-309).
     maxNeighbors (extension): K > 0 caps the neighbours per centre -- a row of k > K hits keeps the K hits at the canonical
     ranks floor(t * k / K), t = 0 .. K-1, a stride over the whole row; shorter rows are unchanged. The capped list is a
     subsequence of the uncapped one and the same bytes in every run. 0 = no cap (the reference's list).
-    sampleSeed (extension, needs a cap): an integer in [0, 2^32) draws a stratified sample instead -- slot t of a row of
+    sampleSeed (extension, needs a cap or a budget): an integer in [0, 2^32) draws a stratified sample instead -- slot t of a row of
     k > K hits holds the hit at rank floor(t * k / K) + off_t, off_t hashed from (seed, centre index, t) inside stratum t
     (neighbors.hip: sample_slot). Same startIndexs, still a subsequence in canonical order, the same bytes for the same
-    (inputs, K, seed); None = the canonical ranks above."""
+    (inputs, K, seed); None = the canonical ranks above.
+    maxEdges (extension): B > 0 bounds the EDGES of the list -- the search itself picks, on the device and with no read-back
+    of its own, the largest cap K* <= maxNeighbors (when given) whose list has at most B rows (at least 1: every non-empty
+    row keeps one hit, so E <= max(B, non-empty rows)); the outputs are byte for byte those of maxNeighbors=K* (and the same
+    sampleSeed). 0 = no budget. returnCap=True appends an int32 device tensor of one element holding K* (without a budget:
+    maxNeighbors); the op never reads it back."""
     op = "FindNeighborsOp"
     _req(radius > 0.0, op + " expects a positive radius")
     _req(batchSize > 0, op + " expects a positive batch size")
@@ -798,7 +803,10 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
          op + " expects maxNeighbors to be an integer >= 0 (0 = no cap)")
     _req(sampleSeed is None or (isinstance(sampleSeed, int) and not isinstance(sampleSeed, bool) and 0 <= sampleSeed < 2 ** 32),
          op + " expects sampleSeed to be None or an integer in [0, 2^32)")
-    _req(sampleSeed is None or maxNeighbors > 0, op + " expects a cap (maxNeighbors > 0) with a sampleSeed")
+    _req(isinstance(maxEdges, int) and not isinstance(maxEdges, bool) and 0 <= maxEdges < 2 ** 31,
+         op + " expects maxEdges to be an integer in [0, 2^31) (0 = no budget)")
+    _req(sampleSeed is None or maxNeighbors > 0 or maxEdges > 0,
+         op + " expects a cap (maxNeighbors > 0) or a budget (maxEdges > 0) with a sampleSeed")
     c, cb = _points_input(op, inPts.detach(), inBatchIds)
     p2 = _f32(inPts2.detach(), "points2")
     _check_points(p2, "points2", op)
@@ -811,7 +819,15 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     box, boxv = _host_mailbox()
     n2 = p2.shape[0]
     cap = int(maxNeighbors)
-    if cap > 0:   # the capped passes: entries of their own, a workspace that also holds the true row lengths
+    budget = int(maxEdges)
+    capT = None
+    if budget > 0:   # the budgeted passes: the cap is a device word the count call writes and the fill call reads
+        ws = _ws(lib.mccnn_find_neighbors_budget_workspace_bytes(m, n2), c.device)
+        capT = torch.empty(1, dtype=torch.int32, device=c.device)
+        tail = (cap, budget, ptr(capT))
+        ftail = (ptr(capT), int(sampleSeed is not None), int(sampleSeed or 0))
+        count_fn, fill_fn = lib.mccnn_find_neighbors_count_budget, lib.mccnn_find_neighbors_fill_budget
+    elif cap > 0:   # the capped passes: entries of their own, a workspace that also holds the true row lengths
         ws = _ws(lib.mccnn_find_neighbors_capped_workspace_bytes(m, n2), c.device)
         tail = ftail = (cap,)
         count_fn, fill_fn = lib.mccnn_find_neighbors_count_capped, lib.mccnn_find_neighbors_fill_capped
@@ -835,7 +851,12 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
     gkey = (c.device.index, m, n2, float(radius), int(batchSize), bool(scaleInv))
     if cap > 0:   # capped searches keep guesses of their own, per cap (the ratio table is keyed by gkey[3] and gkey[5])
         gkey = gkey[:5] + ((bool(scaleInv), cap),)
+    if budget > 0:   # ... and budgeted ones per (cap, budget)
+        gkey = gkey[:5] + ((bool(scaleInv), cap, budget),)
     guess = _edge_guess(_EDGE_GUESS, _EDGE_RATIO, gkey, m)
+    if budget > 0:   # max(B, m) rows cannot overflow: the fill always goes out before the total is read
+        bound = min(max(budget, m), m * (min(cap, n2) if cap > 0 else n2))   # (no list has more than m * min(Ku, n) rows)
+        guess = min(bound, guess) if guess > 0 else bound
     packed = None
     if guess > 0:
         buf = torch.empty((guess, 2), dtype=torch.int32, device=c.device)
@@ -849,6 +870,10 @@ def find_neighbors(inPts, inBatchIds, inPts2, cellIndexs, aabbMin, aabbMax, radi
         packed = torch.empty((e, 2), dtype=torch.int32, device=c.device)
         check(fill_fn(*args, ptr(start), e, ptr(packed), ptr(ws), ws.numel(), stream_handle(), *ftail), "find_neighbors(fill)")
     _remember_edges(_EDGE_GUESS, _EDGE_RATIO, gkey, m, e)
+    if returnCap:
+        if capT is None:
+            capT = torch.full((1,), cap, dtype=torch.int32, device=c.device)
+        return start, packed, capT
     return start, packed
 
 

@@ -57,6 +57,9 @@ SIGNATURES = {
     "mccnn_find_neighbors_count_capped": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp, _i]),
     "mccnn_find_neighbors_fill_capped": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "mccnn_find_neighbors_fill_sampled": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _i, C.c_uint]),
+    "mccnn_find_neighbors_budget_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_find_neighbors_count_budget": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _vp]),
+    "mccnn_find_neighbors_fill_budget": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _i, C.c_uint]),
     "mccnn_invert_permutation": (_i, [_vp, _i, _vp, _vp]),
     "mccnn_compute_pdf_workspace_bytes": (_sz, [_i, _i]),
     "mccnn_compute_pdf": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _f, _f, _i, _i, _vp, _vp, _sz, _vp]),

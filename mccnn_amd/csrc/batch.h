@@ -135,6 +135,13 @@ struct NeighSearch {
     int max_neighbors, sampled; unsigned seed;            // the cap: 0 = none; sampled: the draw of `seed`
 };
 int find_neighbors_chain(const NeighSearch& q, hipStream_t s);   // count (scan) fill, back to back
+// neigh_budget.hip: the edge budget of a search (mccnn_find_neighbors_count_budget). `region`: budget_region_bytes(m) behind
+// the capped workspace, one run of 8-byte words the count pass clears (budget_region_zero names them)
+size_t budget_region_bytes(int m);
+void budget_region_zero(void* region, int m, unsigned long long** words, int* count);
+int budget_select_scan(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, int* start_idx,
+                       int* total_dev, hipStream_t s);
+int launch_budget_empty(int* total_dev, int* cap_dev, hipStream_t s);
 bool neigh_batch_eligible(int m, int n);
 int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q);
 int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s);   // 0 count, 1 fill

@@ -454,6 +454,15 @@ __global__ __launch_bounds__(256) void neigh_window(NeighItem g, NeighScan ps, N
     neigh_window_body<MODE, LEAN, KIND != NEIGH_PLAIN, KIND == NEIGH_SAMPLED>((int)blockIdx.x, (int)gridDim.x, g, ps, cp);
 }
 
+// The fill pass of a search with an edge budget (mccnn_find_neighbors_fill_budget): the capped or the sampled body with
+// the cap read from the word the selection left on the device (neigh_budget.hip) -- one wave-uniform load in the prologue.
+// A kernel of its own: the instantiations above keep their arguments and their code.
+template <bool LEAN, bool SAMPLED>
+__global__ __launch_bounds__(256) void neigh_window_budget(NeighItem g, NeighCapItem cp, const int* __restrict__ capDev) {
+    cp.capK = __builtin_amdgcn_readfirstlane(*capDev);
+    neigh_window_body<1, LEAN, true, SAMPLED>((int)blockIdx.x, (int)gridDim.x, g, NeighScan{}, cp);
+}
+
 // One launch for the count (or the fill) pass of a BATCH of searches of one kind (mccnn_geometry_build_batch): the plain
 // loop of the background launches, the prefix sum of the counts a launch of its own in between (scan.hip's batch form).
 // The cap of item k travels beside it (NeighCapBatch).
@@ -1135,6 +1144,75 @@ int mccnn_find_neighbors_fill_sampled(const float* centres, const int* centre_ba
     q.sampled = 1;
     q.seed = seed;
     return find_neighbors_fill_impl(q, (hipStream_t)stream);
+}
+
+// The search with a budget on the edges of its list (max_edges = B > 0): count -> selection -> scan -> fill, nothing
+// returns to the host in between. The count pass is the capped one with no clamp (it leaves the uncapped row lengths in
+// `kfull` and clears what the selection and the scan need zero); neigh_budget.hip turns them into the cap K* (*cap_dev) and
+// the prefix sum of min(k, K*); the fill pass reads the cap from that word. Lists of up to 2 M centres (the chained scan).
+size_t mccnn_find_neighbors_budget_workspace_bytes(int m, int n) {
+    return mccnn_find_neighbors_capped_workspace_bytes(m, n) + budget_region_bytes(m);
+}
+int mccnn_find_neighbors_count_budget(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
+                                      int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
+                                      int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
+                                      int* start_idx, int* total_dev, void* ws, size_t ws_bytes, mccnn_stream_t stream,
+                                      int max_neighbors, int max_edges, int* cap_dev) {
+    if (max_edges <= 0 || max_neighbors < 0 || !cap_dev || !total_dev) return MCCNN_E_BADARG;
+    if (m < 0 || n < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f)) return MCCNN_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) return launch_budget_empty(total_dev, cap_dev, s);
+    if (!centres || !centre_batch_ids || !cell_indexs || !aabb_min || !aabb_max || !start_idx || (n > 0 && !sorted_pts)) return MCCNN_E_BADARG;
+    if ((long long)m > 2048LL * 1024) return MCCNN_E_TOOLARGE;
+    if (!ws || ws_bytes < mccnn_find_neighbors_budget_workspace_bytes(m, n)) return MCCNN_E_WORKSPACE;
+    MCCNN_NEIGH_SEARCH(q);
+    q.total_dev = total_dev;
+    q.max_neighbors = 0x7fffffff;   // the capped count pass, no clamp
+    NeighItem it;
+    NeighCapItem cap;
+    NeighWs w;
+    int rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    void* region = (char*)ws + mccnn_find_neighbors_capped_workspace_bytes(m, n);
+    budget_region_zero(region, m, &it.zeroWords, &it.numZero);
+    rc = launch_neigh(0, neigh_lean(), NEIGH_CAPPED, ceil_div(m, 4 * it.G), neigh_lds_pad(), s, it, NeighScan{}, cap);
+    if (rc) return rc;
+    return budget_select_scan(w.kfull, m, region, max_edges, max_neighbors, cap_dev, start_idx, total_dev, s);
+}
+
+int mccnn_find_neighbors_fill_budget(const float* centres, const int* centre_batch_ids, int m, const float* sorted_pts,
+                                     int n, const int* cell_indexs, const float* aabb_min, const float* aabb_max,
+                                     int batch_size, int num_cells, float radius, int scale_inv, const int* centre_order,
+                                     const int* start_idx, int e, int* packed, void* ws, size_t ws_bytes,
+                                     mccnn_stream_t stream, const int* cap_dev, int sampled, unsigned seed) {
+    if (!cap_dev || m < 0 || n < 0 || e < 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.0f)) return MCCNN_E_BADARG;
+    if (m == 0 || e == 0) return 0;
+    if (!centres || !centre_batch_ids || !sorted_pts || !cell_indexs || !aabb_min || !aabb_max || !start_idx || !packed) return MCCNN_E_BADARG;
+    if (!ws || ws_bytes < mccnn_find_neighbors_budget_workspace_bytes(m, n)) return MCCNN_E_WORKSPACE;
+    MCCNN_NEIGH_SEARCH(q);
+    q.capacity = e;
+    q.packed = packed;
+    q.max_neighbors = 1;   // (the capped workspace layout; the kernel takes the cap from *cap_dev)
+    q.sampled = sampled ? 1 : 0;
+    q.seed = seed;
+    NeighItem it;
+    NeighCapItem cap;
+    NeighWs w;
+    int rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    if (it.G == 16) it.G = MCCNN_NW_G;   // (as find_neighbors_fill_impl)
+    const int grid = ceil_div(m, 4 * it.G);
+    const size_t dyn = neigh_lds_pad();
+    hipStream_t s = (hipStream_t)stream;
+    if (neigh_lean()) {
+        if (sampled) neigh_window_budget<true, true><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
+        else neigh_window_budget<true, false><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
+    } else {
+        if (sampled) neigh_window_budget<false, true><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
+        else neigh_window_budget<false, false><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
+    }
+    MCCNN_LAUNCHED();
+    return 0;
 }
 #undef MCCNN_NEIGH_SEARCH
 
