@@ -677,6 +677,34 @@ int mccnn_geometry_build_point(mccnn_geometry_t* g, const float* pts, const int*
                                const mccnn_point_pdf* point);
 int mccnn_geometry_build_batch_point(const mccnn_geometry_request* requests, const mccnn_neighbor_cap* caps,
                                      const mccnn_point_pdf* points, int count, mccnn_stream_t stream);
+/* An edge budget in the geometry's chain (the passes of mccnn_find_neighbors_count_budget / _fill_budget, the same bytes):
+ * max_edges = B > 0 lets the search pick, on the device, the largest cap K* <= max_neighbors (0 = no cap of the caller's)
+ * whose list has at most B rows (at least 1 per non-empty centre); 0 = no budget: the entries below then ARE the point
+ * ones. The chain of one geometry: ... count (unclamped; it clears the budget region) -> selection (1 launch up to 4096
+ * centres, 3 above) -> clamped prefix sum -> fill with the cap read from the device word; lists of <= 4096 centres have no
+ * scan launch: their fill pass scans min(k, K*) itself (three search launches). cap->sampled is allowed with a cap or a
+ * budget. The list holds at most max(B, m) rows: an e_capacity of that size never overflows. The buffer is sized by
+ * mccnn_geometry_bytes_budget (the search keeps budget_region bytes behind the capped layout; with max_edges == 0 it equals
+ * mccnn_geometry_bytes_capped). max_edges < 0 or a budget together with a per-point density: MCCNN_E_BADARG; more than 2^21
+ * centres with a budget: MCCNN_E_TOOLARGE. A budgeted geometry may share the grid of any other geometry and the reverse.
+ * mccnn_geometry_build_batch_budget: budgets[k] belongs to requests[k]; budgets == NULL: none. A chunk (<= 16 requests) with
+ * budgeted requests adds at most 1 count + 3 + 1 selection + 1 scan + 2 fill launches to those of its other kinds; a batch
+ * without one issues the launches of mccnn_geometry_build_batch_point.
+ * mccnn_geometry_cap: the device word that holds K* once the build has run (read it in stream order behind the build); NULL
+ * for a geometry without a budget, whose cap is the max_neighbors the caller passed. */
+typedef struct mccnn_neighbor_budget { int max_edges; } mccnn_neighbor_budget;
+size_t mccnn_geometry_bytes_budget(int n, int m, int batch_size, int num_cells, int e_capacity, int with_grid, int max_neighbors,
+                                   int max_edges);
+int mccnn_geometry_build_budget(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                                const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max,
+                                int batch_size, int num_cells, float radius, int scale_inv, float window, int use_pdf,
+                                int e_capacity, const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes,
+                                int* total_host, mccnn_stream_t stream, const mccnn_neighbor_cap* cap,
+                                const mccnn_point_pdf* point, const mccnn_neighbor_budget* budget);
+int mccnn_geometry_build_batch_budget(const mccnn_geometry_request* requests, const mccnn_neighbor_cap* caps,
+                                      const mccnn_point_pdf* points, const mccnn_neighbor_budget* budgets, int count,
+                                      mccnn_stream_t stream);
+const int* mccnn_geometry_cap(const mccnn_geometry_t* g);
 /* E, or -1 while the count pass has not retired (wait_us: 0 = look once, < 0 = wait, > 0 = wait at most that long). */
 int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
 /* out[0..7]: device addresses of sortPts [n,3], sortBatchs [n], cellIndexs [B,nc,nc,nc,2], index_new_pos [n], its

@@ -344,7 +344,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
     def __init__(self, multiFeatureConvs=False, KDEWindow=0.25, relativeRadius=True, usePDF=True, useAVG=True,
                  decayLossCollection='weight_decay_loss', device=None, ops=None, fuseSort=None, native=None,
                  maxNeighbors=0, sampleSeed=None, capNative=False, pdfMode='edge', pointNative=False, pointGrad=False,
-                 maxEdges=0):
+                 maxEdges=0, budgetNative=False):
         """pdfMode (extension): 'edge' (default) -- the reference's density, a Gaussian sum over the centre's row for every
         edge (compute_pdf); 'point' -- the density of every point over its OWN ball, computed once per (grid, KDEWindow)
         and shared by every list over that grid (compute_pdf_points + expand_pdf). A 'point' layer with usePDF takes the
@@ -372,8 +372,14 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         maxEdges (extension): the default budget B on the EDGES of every layer's neighbour list (find_neighbors(maxEdges=));
         0 = none. The search picks the largest cap <= maxNeighbors whose list has at most B rows, on the device; the
         budget is per list. A budgeted layer runs op by op, like a capped layer without capNative, whatever capNative_
-        says; chosenCaps_[keyNeighs] holds the device tensor with the cap its last search chose (never read back here).
-        The attribute maxEdges_ may be reassigned between steps (followed by reset())."""
+        says, unless budgetNative is set; chosenCaps_[keyNeighs] holds the device tensor with the cap its last search chose
+        (never read back here). The attribute maxEdges_ may be reassigned between steps (followed by reset()).
+        budgetNative (extension, default False): True sends budgeted layers -- with or without a cap of the caller's, whatever
+        capNative_ says -- through the native step executor: one library call per geometry (mccnn_geometry_build_budget),
+        learned prefetch, prefetch_step, prefetch_geometry and the batch form included, with the bytes of the op-by-op path,
+        filed under the same '|e' cache keys. chosenCaps_[keyNeighs] is then a view of the geometry's own cap word
+        (Geometry.chosen_cap()), made when somebody looks and dropped with the geometry at reset(). The attribute
+        budgetNative_ may be reassigned between steps (followed by reset())."""
         super().__init__()
         self.maxNeighbors_ = self.__check_cap__(maxNeighbors)
         self.maxEdges_ = self.__check_budget__(maxEdges)
@@ -383,6 +389,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("capNative must be True or False")
         self.capNative_ = capNative
+        if not isinstance(budgetNative, bool):
+            from .MCConvModule import InvalidArgumentError
+            raise InvalidArgumentError("budgetNative must be True or False")
+        self.budgetNative_ = budgetNative
         if not isinstance(pointNative, bool):
             from .MCConvModule import InvalidArgumentError
             raise InvalidArgumentError("pointNative must be True or False")
@@ -530,6 +540,20 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             kw["sampleSeed"] = (currSeed + zlib.crc32(base.encode())) & 0xffffffff
         return kw
 
+    def __native_thinning__(self, currCap, currBudget):
+        """Whether a layer with this cap and budget may take the native step executor: a budgeted one under budgetNative_
+        (its cap needs no capNative_), a capped one under capNative_, an unthinned one always."""
+        if currBudget > 0:
+            return self.budgetNative_
+        return currCap == 0 or self.capNative_
+
+    @classmethod
+    def __native_search_args__(cls, currCap, currSeed, keyNeighs, currBudget=0):
+        """__search_args__ as native.build_geometry takes them (the geometry keeps the cap word itself: no returnCap)."""
+        kw = cls.__search_args__(currCap, currSeed, keyNeighs, currBudget)
+        kw.pop("returnCap", None)
+        return kw
+
     def __take_search__(self, res, keyNeighs):
         """(startIndexs, packedNeighs) of a find_neighbors result; the cap a budgeted search appends goes to chosenCaps_."""
         res = tuple(res)
@@ -611,6 +635,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 plan.append(ent[:7] + ((geo.have & 7) if geo is not None else 0, key) + ent[7:])
             state["geoPlan_"], state["geoSeen_"] = plan, {}
         state["cacheGeo_"], state["cacheGeoGrid_"] = {}, {}
+        if self.chosenCaps_:   # (views of native geometries' cap words go with the geometries; tensors of the op path stay)
+            for kN in [kN for kN, v in self.chosenCaps_.items() if isinstance(v, _LazyEntry)]:
+                del self.chosenCaps_[kN]
         if self.prefetchedGeo_:
             self.__install_prefetched_geometries__()
         pf, state["prefetched_"] = self.prefetched_, None
@@ -675,7 +702,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         uncapped one.
         sampleSeed: the seed of that call (None = the builder's sampleSeed_ at the time of THIS call).
         maxEdges: the edge budget of that call (None = the builder's maxEdges_). A budgeted geometry is prefetched op by op
-        on the side stream, like a capped one without capNative_.
+        on the side stream, like a capped one without capNative_, or -- with budgetNative_ -- by the native executor.
         pdfMode: the mode of that call (None = the builder's). The per-point density has a prefetched form on the native
         executor only: 'point' with usePDF raises unless pointNative_ is set, and then parks a native point geometry (where
         the native executor cannot take the levels nothing is started: create_convolution computes them itself)."""
@@ -700,9 +727,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         mn, mx, B = inPointHierarchy.aabbMin_, inPointHierarchy.aabbMax_, inPointHierarchy.batchSize_
         if not pts.is_cuda:
             return  # host tensors (a CPU checker behind `ops=`): nothing to overlap, create_convolution computes inline
-        if currBudget == 0 and (currCap == 0 or self.capNative_) and self.__prefetch_native__(
+        if self.__native_thinning__(currCap, currBudget) and self.__prefetch_native__(
                 inPointHierarchy, inPointLevel, convRadius, outPH, outLevel, currKDEWindow, currRelativeRadius, currUsePDF,
-                keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed, point=pointPDF):
+                keyGrid, keyNeighs, keyPDF, transposed, currCap=currCap, currSeed=currSeed, point=pointPDF,
+                currBudget=currBudget):
             return
         if pointPDF:
             return  # (no op-by-op prefetched form)
@@ -848,6 +876,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 self._trace("sort_points_step2", keyGrid)
         self.cacheNeighs_[keyNeighs] = _LazyEntry(geo, geo.neighbors)
         self.cachePDFs_[keyPDF] = _LazyEntry(geo, geo.pdfs)
+        if geo.budget > 0:   # (a budgeted search: the cap it chose, a view of the geometry's own word)
+            self.chosenCaps_[keyNeighs] = _LazyEntry(geo, geo.chosen_cap)
         if trace:
             self._trace("find_neighbors", keyNeighs)
         if point:
@@ -869,6 +899,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             self.cacheGeo_.pop(keyPDF, None)
             self.cachePDFs_.pop(keyPDF, None)
             self.cacheNeighs_.pop(keyNeighs, None)
+            if isinstance(self.chosenCaps_.get(keyNeighs), _LazyEntry):
+                self.chosenCaps_.pop(keyNeighs, None)
         if self.cacheGeoGrid_.get(keyGrid) is geo:
             self.cacheGeoGrid_.pop(keyGrid, None)
             self.cacheGrids_.pop(keyGrid, None)
@@ -878,19 +910,22 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __plan_entries__(self, ph, sampleSeed=None):
         """The geometries the last step used over a hierarchy of `ph`'s name whose levels `ph` has: (entry, keyGrid,
-        keyNeighs, keyPDF, search keywords, point mode) each, the keys computed for `ph`. The plan knows the cap of a capped layer, not
-        its seed: sampleSeed is the layers' seed of the step the geometries are for (part of the capped keys)."""
+        keyNeighs, keyPDF, search keywords, point mode, budget) each, the keys computed for `ph`. The plan knows the cap and the
+        budget of a layer, not its seed: sampleSeed is the layers' seed of the step the geometries are for (part of the capped
+        and budgeted keys)."""
         name, levels = ph.hierarchyName_, len(ph.points_)
         for ent in self.geoPlan_:
             if ent[0] != name or ent[1] >= levels or ent[2] >= levels:
                 continue
             cap = ent[9] if len(ent) > 9 else 0
-            seed = sampleSeed if cap > 0 else None
-            keys = self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6], cap, seed)
-            yield (ent,) + keys + (self.__search_args__(cap, seed, keys[1]), len(ent) > 10 and ent[10] == 'point')
+            budget = ent[11] if len(ent) > 11 else 0
+            seed = sampleSeed if (cap > 0 or budget > 0) else None
+            keys = self.__compute_dic_keys__(ph, ph, ent[1], ent[2], ent[3], ent[4], ent[5], ent[6], cap, seed, budget)
+            yield (ent,) + keys + (self.__native_search_args__(cap, seed, keys[1], budget), len(ent) > 10 and ent[10] == 'point',
+                                   budget)
 
     def __prefetch_native__(self, inPH, inLevel, convRadius, outPH, outLevel, KDEWindow, relativeRadius, usePDF, keyGrid,
-                            keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None, point=False):
+                            keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None, point=False, currBudget=0):
         """prefetch_geometry() on the native step executor: the geometry is ONE buffer, allocated on the CALLER's stream and
         written on a side stream that starts behind everything the caller's stream holds at this moment; the layers that
         use it order their stream behind its event. No reference counting decides anything: the buffer goes back to the
@@ -920,7 +955,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                      usePDF, owner, side=k, fork=fork, background=True,
                                      after=(inPH.prefetchFuture_ if inPH is outPH else None), pointPDF=point,
-                                     **self.__search_args__(currCap, currSeed, keyNeighs))
+                                     **self.__native_search_args__(currCap, currSeed, keyNeighs, currBudget))
         if owner is None:
             owners[keyGrid] = geo
         if pieces:   # row plans / transposed list the layers of the last step used: attached and issued by a helper thread
@@ -937,7 +972,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         step after it then finds its geometry built and runs its convolutions back to back. Returns the number of
         geometries started (0 on the first steps, while there is nothing to replay, and wherever the native path does
         not apply: nothing is lost, the next step builds what it needs itself).
-        sampleSeed: the seed the NEXT step's capped layers will run with (capNative_; None = the current sampleSeed_) -- the
+        sampleSeed: the seed the NEXT step's capped and budgeted layers will run with (capNative_ / budgetNative_; None = the current sampleSeed_) -- the
         geometries are filed under that seed's keys, so `cb.prefetch_step(ph_next, sampleSeed=step + 1)` followed by
         `cb.sampleSeed_ = step + 1; cb.reset()` finds them. One prefetched with another seed is never asked for and is
         dropped at the reset() after.
@@ -949,16 +984,16 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         _native = _native_mod()
         _native.begin_batch()   # the step's geometries go out together: one launch per kernel kind over all of them
         try:
-            for ent, keyGrid, keyNeighs, keyPDF, capArgs, point in self.__plan_entries__(pointHierarchy, seed):
+            for ent, keyGrid, keyNeighs, keyPDF, capArgs, point, budget in self.__plan_entries__(pointHierarchy, seed):
                 _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
                 if (keyPDF + '|pt' if point else keyPDF) in self.prefetchedGeo_:
                     continue
-                if (capArgs and not self.capNative_) or (point and not self.pointNative_):
+                if not self.__native_thinning__(ent[9] if len(ent) > 9 else 0, budget) or (point and not self.pointNative_):
                     continue
                 if self.__prefetch_native__(pointHierarchy, inLevel, radius, pointHierarchy, outLevel, window, rel, usePDF,
                                             keyGrid, keyNeighs, keyPDF, False, fork=(started == 0),
                                             pieces=(have if pieces else 0), currCap=(ent[9] if len(ent) > 9 else 0),
-                                            currSeed=(seed if len(ent) > 9 else None), point=point):
+                                            currSeed=(seed if len(ent) > 9 else None), point=point, currBudget=budget):
                     started += 1
         finally:
             _native.end_batch()
@@ -988,11 +1023,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         mn, mx, B = ph.aabbMin_, ph.aabbMax_, ph.batchSize_
         k = 0
         pieces = _env.debug("plan_prefetch", True)
-        for ent, keyGrid, keyNeighs, keyPDF, capArgs, point in self.__plan_entries__(ph, self.__check_seed__(self.sampleSeed_)):
+        for ent, keyGrid, keyNeighs, keyPDF, capArgs, point, budget in self.__plan_entries__(ph, self.__check_seed__(self.sampleSeed_)):
             _hname, inLevel, outLevel, radius, window, rel, usePDF, have = ent[:8]
             if (keyPDF + '|pt' if point else keyPDF) in self.cacheGeo_:
                 continue
-            if (capArgs and not self.capNative_) or (point and not self.pointNative_):
+            if not self.__native_thinning__(ent[9] if len(ent) > 9 else 0, budget) or (point and not self.pointNative_):
                 continue
             inputs = self.__native_inputs__(ph, inLevel, ph, outLevel)
             if inputs is None:
@@ -1009,12 +1044,13 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
 
     def __native_convolution__(self, convName, inPH, inLevel, inFeatures, inNumFeatures, convRadius, outPH, outLevel,
                                multiFeatureConv, numOutFeatures, KDEWindow, relativeRadius, usePDF, useAVG, keyGrid,
-                               keyNeighs, keyPDF, currCap=0, currSeed=None, point=False):
+                               keyNeighs, keyPDF, currCap=0, currSeed=None, point=False, currBudget=0):
         """create_convolution on the native step executor (mccnn_amd.native): the geometry of (keyGrid, keyNeighs, keyPDF)
         is ONE library call (no host wait), the layer one call per direction with the feature sort inside. Returns None
         when this call has to take the op-by-op path: a cache entry of that path exists already (prefetch_geometry), the
         level is empty, or the features are not rows the library reads in place. currCap / currSeed (capNative_): the
         layer's cap and seed -- the geometry's search is the capped one, with the seed the op would get (__search_args__).
+        currBudget (budgetNative_): the layer's edge budget -- the geometry's search picks the cap itself, on the device.
         point (pointNative_): the PDFs are the grid's per-point density expanded over the list; the geometry and its PDFs
         are filed under keyPDF + '|pt'."""
         keyGeo = keyPDF + '|pt' if point else keyPDF
@@ -1056,6 +1092,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             if inputs is None:
                 return None
             inPts, inBids, centres, cBids = inputs
+            if currBudget > 0 and centres.shape[0] > 2 ** 21:
+                return None   # (beyond the clamped scan: the op-by-op path reports it)
             mn, mx, B = inPH.aabbMin_, inPH.aabbMax_, inPH.batchSize_
             nc = _hip_ops._num_cells(mn, mx, B, convRadius, relativeRadius)
             owner = self.cacheGeoGrid_.get(keyGrid)
@@ -1065,7 +1103,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                     self.__unfile_geometry__(owner, keyGrid)
                     owner = None
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
-                                         usePDF, owner, pointPDF=point, **self.__search_args__(currCap, currSeed, keyNeighs))
+                                         usePDF, owner, pointPDF=point,
+                                         **self.__native_search_args__(currCap, currSeed, keyNeighs, currBudget))
             if owner is not None:   # (a shared grid: the layer sorts its rows only, as on a cache hit)
                 self._trace("sort_features", keyGrid)
             self.__file_geometry__(geo, keyGrid, keyNeighs, keyPDF, usePDF, True, point, KDEWindow)
@@ -1074,7 +1113,7 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         if inPH is outPH and keyGeo not in self.geoSeen_:
             # (the plan remembers a layer's cap and, behind it, its mode)
             self.geoSeen_[keyGeo] = (inPH.hierarchyName_, inLevel, outLevel, convRadius, KDEWindow, relativeRadius, usePDF) + \
-                ((0, 'point') if point else ((currCap,) if currCap > 0 else ()))
+                ((0, 'point') if point else ((currCap, 'edge', currBudget) if currBudget > 0 else ((currCap,) if currCap > 0 else ())))
         feats = inFeatures
         if _GEO_TRACE and feats.dim() == 2 and feats.shape[0] != geo.n:
             print("native conv %s: %d feature rows for a geometry over %d points (key %s, unverified %s, built from %s, level has %s)" % (
@@ -1124,7 +1163,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         # runs through the native executor like an uncapped one, with the same bytes. sampleSeed (extension; None = the builder's sampleSeed_): the capped
         # search draws a stratified sample of the over-full rows; a seed of the layer's own needs a cap.
         # maxEdges (extension; None = the builder's maxEdges_): a budget on the edges of this layer's list -- the search picks
-        # the cap itself (find_neighbors(maxEdges=)). A budgeted layer takes the op-by-op path below, whatever capNative_ says.
+        # the cap itself (find_neighbors(maxEdges=)). A budgeted layer takes the op-by-op path below, whatever capNative_ says,
+        # unless the builder was made with budgetNative=True (budgetNative_): then it runs through the native executor, with
+        # the same bytes, under the same '|e' keys.
         currCap = self.maxNeighbors_ if maxNeighbors is None else self.__check_cap__(maxNeighbors)
         currBudget = self.maxEdges_ if maxEdges is None else self.__check_budget__(maxEdges)
         currSeed = self.__layer_seed__(currCap, sampleSeed, currBudget)
@@ -1167,11 +1208,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                 pointGradLayer = True   # op by op below, whatever pointNative_ says
         fused = self.fuseSort_ and self.hipSurface_ and inPts.is_cuda and not inPts.requires_grad
         if self.native_ and fused and (not pointPDF or (self.pointNative_ and not pointGradLayer)) \
-                and currBudget == 0 and (currCap == 0 or self.capNative_):
+                and self.__native_thinning__(currCap, currBudget):
             out = self.__native_convolution__(convName, inPointHierarchy, inPointLevel, inFeatures, inNumFeatures, convRadius,
                                               currOutPointHierarchy, currOutPointLevel, currMultiFeatureConv,
                                               currNumOutFeatures, currKDEWindow, currRelativeRadius, currUsePDF, currUseAVG,
-                                              keyGrid, keyNeighs, keyPDF, currCap, currSeed, pointPDF)
+                                              keyGrid, keyNeighs, keyPDF, currCap, currSeed, pointPDF, currBudget)
             if out is not None:
                 return out
 

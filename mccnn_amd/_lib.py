@@ -114,6 +114,10 @@ SIGNATURES = {
     # ... and with a per-point density (mccnn_point_pdf: pdfMode='point')
     "mccnn_geometry_build_point": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mccnn_geometry_build_batch_point": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "mccnn_geometry_bytes_budget": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "mccnn_geometry_build_budget": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "mccnn_geometry_build_batch_budget": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "mccnn_geometry_cap": (_vp, [_vp]),
     "mccnn_geometry_edges": (_i, [_vp, _i]),
     "mccnn_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "mccnn_geometry_attach": (_i, [_vp, _i, _vp, _sz]),

@@ -24,13 +24,16 @@ struct NeighItem {
 };
 struct NeighBatch { NeighItem it[MCCNN_BATCH_MAX]; };
 // the cap of a search: beside NeighItem (in a batch: NeighCapBatch, item k of one belongs to item k of the other).
-// capK == 0: no cap; sampled: the fill pass draws the stratified sample of `seed` (neigh_sample.h)
-struct NeighCapItem { int* kfull; int capK; unsigned seed; int sampled; };
+// capK == 0: no cap; sampled: the fill pass draws the stratified sample of `seed` (neigh_sample.h). capDev (an edge budget;
+// nullptr: none): the device word the selection leaves the cap in -- the count pass of such a search runs unclamped (capK =
+// 0x7fffffff), its fill pass reads capK from the word
+struct NeighCapItem { int* kfull; const int* capDev; int capK; unsigned seed; int sampled; };
 struct NeighCapBatch { NeighCapItem it[MCCNN_BATCH_MAX]; };
 // the prefix sum of the counts inside the fill pass of a small list (single launches; all null in a batch)
 struct NeighScan { const int* scanCnt; int* startOut; int* totalDev; int* totalHost; };
 // the kind of a search's kernels: which of the three records above an instantiation reads
-enum { NEIGH_PLAIN = 0, NEIGH_CAPPED = 1, NEIGH_SAMPLED = 2 };
+// (the two budget kinds are fill passes of a batch only: the capped / sampled body with the cap read from NeighCapItem::capDev)
+enum { NEIGH_PLAIN = 0, NEIGH_CAPPED = 1, NEIGH_SAMPLED = 2, NEIGH_BUDGET = 3, NEIGH_BUDGET_SAMPLED = 4 };
 static_assert(sizeof(NeighBatch) + sizeof(NeighCapBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched search: < 4 KB");
 
 // one kernel-density estimate
@@ -133,6 +136,7 @@ struct NeighSearch {
     int* total_dev; int* total_host;                      // the edge total: device word, pinned host word (or nullptr)
     void* ws; size_t ws_bytes;
     int max_neighbors, sampled; unsigned seed;            // the cap: 0 = none; sampled: the draw of `seed`
+    int max_edges; int* cap_dev;                          // the edge budget: 0 = none; the device word its cap K* goes to
 };
 int find_neighbors_chain(const NeighSearch& q, hipStream_t s);   // count (scan) fill, back to back
 // neigh_budget.hip: the edge budget of a search (mccnn_find_neighbors_count_budget). `region`: budget_region_bytes(m) behind
@@ -141,9 +145,20 @@ size_t budget_region_bytes(int m);
 void budget_region_zero(void* region, int m, unsigned long long** words, int* count);
 int budget_select_scan(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, int* start_idx,
                        int* total_dev, hipStream_t s);
+int budget_select(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, hipStream_t s);
+int budget_scan(const int* kfull, int m, void* region, const int* cap_dev, int* start_idx, int* total_dev, int* total_host, hipStream_t s);
+// one budgeted search of a batch, between its count and its fill pass: the row lengths, the region the count pass cleared, the
+// budget and the caller's cap, and where the cap, the prefix sum and the edge total go
+struct BudgetItem {
+    const int* kfull; void* region; int m, max_edges, max_neighbors;
+    int* cap_dev; int* start_idx; int* total_dev; int* total_host;
+};
+int launch_budget_select_batch(const BudgetItem* items, int count, hipStream_t s);   // <= 1 + 3 launches
+int launch_budget_scan_batch(const BudgetItem* items, int count, hipStream_t s);     // 1 launch
 int launch_budget_empty(int* total_dev, int* cap_dev, hipStream_t s);
 bool neigh_batch_eligible(int m, int n);
-int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q);
+// (a budgeted search: `sc` is left alone -- its prefix sum is the clamped one -- and `bud` describes what runs between its passes)
+int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q, BudgetItem* bud = nullptr);
 int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s);   // 0 count, 1 fill
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,

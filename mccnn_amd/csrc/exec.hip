@@ -7,6 +7,9 @@
 //     the seed of a stratified sample) handed to the search -- the capped passes of find_neighbors in the same chain;
 //     mccnn_geometry_build_point / _build_batch_point: the same with the PDFs taken from a per-point density (pdfMode='point':
 //     mccnn_compute_pdf_points once per grid and window, its expansion over the list in the place of compute_pdf);
+//     mccnn_geometry_build_budget / _build_batch_budget: the same with an edge budget handed to the search, which then picks
+//     the cap itself on the device (the passes of mccnn_find_neighbors_count_budget / _fill_budget in the same chain; the cap
+//     stays in a word of the geometry's buffer: mccnn_geometry_cap);
 //   * mccnn_conv_forward / mccnn_conv_backward : the convolution of one layer over a geometry, INCLUDING the feature sort
 //     (sort_features / its gradient, MCConvModuleSrc:35-45), the choice of the kernel family (row-per-lane depth-wise,
 //     factored Fin = 1, edge streaming) and the row plans / transposed list a family needs, built on first use and kept
@@ -76,6 +79,8 @@ struct mccnn_geometry {
     float radius = 0.f, window = 0.f;
     int cap_k = 0, cap_sampled = 0;  // the search's cap (0 = none) and whether it draws the sample of cap_seed
     unsigned cap_seed = 0;
+    int max_edges = 0;               // the search's edge budget (0 = none): it picks the cap itself, into *cap_dev
+    int* cap_dev = nullptr;          // the device word that holds K* after the build (budgeted geometries; in the buffer)
     // the per-point density the PDFs are expanded from (the caller's buffers; nullptr: edge mode) and whether it is there already
     float* pp_density = nullptr;
     int* pp_counts = nullptr;
@@ -117,7 +122,7 @@ size_t cells_of(int B, int nc) { return (size_t)B * nc * nc * nc; }
 constexpr int MCCNN_ORDER_MIN_M = 16384;  // foreign centres get a visiting order of their own from this many on
 
 // byte offsets of the pieces of a geometry buffer; total_bytes == 0: the grid does not fit 32-bit keys
-GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int max_neighbors = 0) {
+GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int max_neighbors = 0, int max_edges = 0) {
     GeoLayout L;
     memset(&L, 0, sizeof(L));
     const size_t n1 = n > 0 ? n : 1, m1 = m > 0 ? m : 1, e1 = e_cap > 0 ? e_cap : 1;
@@ -153,7 +158,10 @@ GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int
     const size_t p = mccnn_compute_pdf_workspace_bytes(e_cap, 1);
     if (p > w) w = p;
     // (the capped search keeps m more words behind whatever stage sets the size: mccnn_find_neighbors_capped_workspace_bytes)
-    if (max_neighbors > 0) w = al(w) + (mccnn_find_neighbors_capped_workspace_bytes(m, n) - mccnn_find_neighbors_workspace_bytes(m, n));
+    // (the budgeted search keeps them too, and behind the capped layout the region of its selection and clamped scan:
+    // budget_region_bytes(m) -- mccnn_find_neighbors_budget_workspace_bytes)
+    if (max_edges > 0) w = al(w) + (mccnn_find_neighbors_budget_workspace_bytes(m, n) - mccnn_find_neighbors_workspace_bytes(m, n));
+    else if (max_neighbors > 0) w = al(w) + (mccnn_find_neighbors_capped_workspace_bytes(m, n) - mccnn_find_neighbors_workspace_bytes(m, n));
     L.ws = o;
     L.ws_bytes = al(w) + 256;
     o += L.ws_bytes;
@@ -321,36 +329,49 @@ size_t mccnn_geometry_bytes_capped(int n, int m, int batch_size, int num_cells, 
     return geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid != 0, max_neighbors).total_bytes;
 }
 
+size_t mccnn_geometry_bytes_budget(int n, int m, int batch_size, int num_cells, int e_capacity, int with_grid, int max_neighbors,
+                                   int max_edges) {
+    if (n < 0 || m < 0 || batch_size <= 0 || num_cells <= 0 || e_capacity < 0 || max_neighbors < 0 || max_edges < 0) return 0;
+    if (cells_of(batch_size, num_cells) > 0x7fffffffULL) return 0;
+    return geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid != 0, max_neighbors, max_edges).total_bytes;
+}
+
 }  // extern "C"
 namespace {
+constexpr size_t GEO_CAP_WORD = 64;   // the cap word of a budgeted geometry: in the 256 bytes of the edge total, behind it
 // Argument checks + the struct of a geometry over the caller's buffer (nothing is launched). `in_batch`: the grid owner may
 // be a geometry set up earlier in the same batch (not built yet).
 int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                    const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size, int num_cells,
                    float radius, int scale_inv, float window, int use_pdf, int e_capacity, const mccnn_geometry_t* grid_from,
                    void* buffer, size_t buffer_bytes, int* total_host, bool in_batch, const mccnn_neighbor_cap* cap,
-                   const mccnn_point_pdf* point) {
+                   const mccnn_point_pdf* point, const mccnn_neighbor_budget* budget) {
     if (!g || !pts || !batch_ids || !centres || !centre_batch_ids || !aabb_min || !aabb_max || !buffer || !total_host)
         return MCCNN_E_BADARG;
     if (n <= 0 || m <= 0 || batch_size <= 0 || num_cells <= 0 || !(radius > 0.f) || e_capacity <= 0) return MCCNN_E_BADARG;
     if (use_pdf && !(window > 0.f)) return MCCNN_E_BADARG;
-    if (cap && (cap->max_neighbors < 0 || (cap->sampled && cap->max_neighbors == 0))) return MCCNN_E_BADARG;
+    if (budget && budget->max_edges < 0) return MCCNN_E_BADARG;
+    const int max_edges = budget ? budget->max_edges : 0;
+    // (a sample needs a cap or a budget, as in the op)
+    if (cap && (cap->max_neighbors < 0 || (cap->sampled && cap->max_neighbors == 0 && max_edges == 0))) return MCCNN_E_BADARG;
     const int cap_k = cap ? cap->max_neighbors : 0;
     // a per-point density: both buffers, PDFs asked for, no cap (both null: edge mode)
     const bool pp = point && (point->density || point->counts);
-    if (pp && (!point->density || !point->counts || !use_pdf || cap_k > 0)) return MCCNN_E_BADARG;
+    if (pp && (!point->density || !point->counts || !use_pdf || cap_k > 0 || max_edges > 0)) return MCCNN_E_BADARG;
+    if (max_edges > 0 && (long long)m > 2048LL * 1024) return MCCNN_E_TOOLARGE;   // (the clamped scan is the chained one)
     if (grid_from && (grid_from->n != n || grid_from->nc != num_cells || grid_from->B != batch_size ||
                       !(grid_owner(grid_from)->built || (in_batch && grid_owner(grid_from)->s_pts))))
         return MCCNN_E_BADARG;
     const bool with_grid = grid_from == nullptr;
-    const GeoLayout L = geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid, cap_k);
+    const GeoLayout L = geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid, cap_k, max_edges);
     if (L.total_bytes == 0) return MCCNN_E_TOOLARGE;
     if (buffer_bytes < L.total_bytes || (((uintptr_t)buffer) & 255)) return MCCNN_E_WORKSPACE;
     *g = mccnn_geometry();
     g->pts = pts; g->bids = batch_ids; g->centres = centres; g->cbids = centre_batch_ids; g->mn = aabb_min; g->mx = aabb_max;
     g->n = n; g->m = m; g->B = batch_size; g->nc = num_cells; g->scale_inv = scale_inv ? 1 : 0; g->use_pdf = use_pdf ? 1 : 0;
     g->radius = radius; g->window = window;
-    g->cap_k = cap_k; g->cap_sampled = (cap && cap_k > 0 && cap->sampled) ? 1 : 0; g->cap_seed = g->cap_sampled ? cap->seed : 0u;
+    g->cap_k = cap_k; g->cap_sampled = (cap && (cap_k > 0 || max_edges > 0) && cap->sampled) ? 1 : 0; g->cap_seed = g->cap_sampled ? cap->seed : 0u;
+    g->max_edges = max_edges;
     if (pp) { g->pp_density = point->density; g->pp_counts = point->counts; g->pp_ready = point->ready != 0; }
     g->same_level = (centres == pts && m == n) ? 1 : 0;
     g->buf = (char*)buffer; g->bytes = buffer_bytes;
@@ -363,6 +384,7 @@ int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, 
     }
     g->start = (int*)(b + L.start); g->packed = (int*)(b + L.packed); g->pdfs = (float*)(b + L.pdfs);
     g->total_dev = (int*)(b + L.total);
+    if (max_edges > 0) g->cap_dev = (int*)(b + L.total + GEO_CAP_WORD);
     g->order_buf = (int*)(b + L.order);
     g->ws = b + L.ws; g->ws_bytes = L.ws_bytes;
     g->e_cap = e_capacity; g->e = -1; g->total_host = total_host;
@@ -400,6 +422,7 @@ NeighSearch geometry_search(const mccnn_geometry_t* g, const int* order) {
     q.total_dev = g->total_dev; q.total_host = const_cast<int*>((volatile int*)g->total_host);
     q.ws = g->ws; q.ws_bytes = g->ws_bytes;
     q.max_neighbors = g->cap_k; q.sampled = g->cap_sampled; q.seed = g->cap_seed;
+    q.max_edges = g->max_edges; q.cap_dev = g->cap_dev;
     return q;
 }
 
@@ -482,7 +505,8 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     ExpandBatch exB;
     SpanBatch spans;
     spans.count = 0;
-    int nGrid = 0, nPdf = 0, nPp = 0, nEx = 0;
+    BudgetItem budB[MCCNN_BATCH_MAX];
+    int nGrid = 0, nPdf = 0, nPp = 0, nEx = 0, nScan = 0, nBud = 0;
     int rc;
     for (int k = 0; k < count; ++k) {
         mccnn_geometry_t* g = gs[k];
@@ -526,7 +550,9 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
         mccnn_geometry_t* g = gs[k];
         const mccnn_geometry* go = grid_owner(g);
         const int* order = g->same_level ? go->inv_idx : g->order;
-        rc = neigh_batch_item(neighB.it[k], capB.it[k], scanN.it[k], geometry_search(g, order));
+        // (a budgeted geometry takes no item of the plain prefix sum: its scan is the clamped one, behind its selection)
+        if (g->max_edges > 0) rc = neigh_batch_item(neighB.it[k], capB.it[k], scanN.it[nScan], geometry_search(g, order), &budB[nBud++]);
+        else rc = neigh_batch_item(neighB.it[k], capB.it[k], scanN.it[nScan++], geometry_search(g, order));
         if (rc) return rc;
         if (g->pp_density) {
             if ((rc = geometry_expand_item(g, exB.it[nEx++]))) return rc;
@@ -536,7 +562,13 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
     }
     // (one launch per kind of search that is present: a chunk without a capped geometry makes the plain launches alone)
     if ((rc = launch_neigh_batch(neighB, capB, count, 0, s))) return rc;
-    if ((rc = launch_scan_batch(scanN, count, s))) return rc;
+    if ((rc = launch_scan_batch(scanN, nScan, s))) return rc;
+    // budgeted geometries of the chunk: selection (one launch over the small lists, three over the larger ones), then ONE
+    // clamped prefix sum; their fill passes are two kinds more of the fill launches below
+    if (nBud) {
+        if ((rc = launch_budget_select_batch(budB, nBud, s))) return rc;
+        if ((rc = launch_budget_scan_batch(budB, nBud, s))) return rc;
+    }
     if ((rc = launch_neigh_batch(neighB, capB, count, 1, s))) return rc;
     if (nEx && (rc = launch_expand_batch(exB, nEx, s))) return rc;
     if (nPdf && (rc = launch_pdf_batch(pdfB, nPdf, s))) return rc;
@@ -553,17 +585,31 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
 }  // namespace
 extern "C" {
 
-// (the uncapped entries are the capped ones with no cap, the capped ones the point ones with no point record)
+// (the uncapped entries are the capped ones with no cap, the capped ones the point ones with no point record, the point
+// ones the budget ones with no budget)
+int mccnn_geometry_build_budget(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
+                                const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
+                                int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
+                                const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
+                                mccnn_stream_t stream, const mccnn_neighbor_cap* cap, const mccnn_point_pdf* point,
+                                const mccnn_neighbor_budget* budget) {
+    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
+                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false, cap, point, budget);
+    if (rc) return rc;
+    return geometry_issue_single(g, stream);
+}
+
 int mccnn_geometry_build_point(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                                const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
                                int num_cells, float radius, int scale_inv, float window, int use_pdf, int e_capacity,
                                const mccnn_geometry_t* grid_from, void* buffer, size_t buffer_bytes, int* total_host,
                                mccnn_stream_t stream, const mccnn_neighbor_cap* cap, const mccnn_point_pdf* point) {
-    int rc = geometry_setup(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells, radius,
-                            scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host, false, cap, point);
-    if (rc) return rc;
-    return geometry_issue_single(g, stream);
+    return mccnn_geometry_build_budget(g, pts, batch_ids, n, centres, centre_batch_ids, m, aabb_min, aabb_max, batch_size, num_cells,
+                                       radius, scale_inv, window, use_pdf, e_capacity, grid_from, buffer, buffer_bytes, total_host,
+                                       stream, cap, point, nullptr);
 }
+
+const int* mccnn_geometry_cap(const mccnn_geometry_t* g) { return (g && g->built) ? g->cap_dev : nullptr; }
 
 int mccnn_geometry_build_capped(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
                                 const int* centre_batch_ids, int m, const float* aabb_min, const float* aabb_max, int batch_size,
@@ -603,12 +649,21 @@ int mccnn_geometry_build_batch_capped(const mccnn_geometry_request* req, const m
 // issued -- whichever chunk or chain each ends up in, the sweep goes out once and the stream orders the rest.
 int mccnn_geometry_build_batch_point(const mccnn_geometry_request* req, const mccnn_neighbor_cap* caps, const mccnn_point_pdf* points,
                                      int count, mccnn_stream_t stream) {
+    return mccnn_geometry_build_batch_budget(req, caps, points, nullptr, count, stream);
+}
+
+// budgets[k]: the edge budget of req[k] (budgets == NULL, or max_edges == 0: none). A chunk with budgeted requests adds, to the
+// launches of its other kinds, at most one capped count pass, the selection (one launch over its lists of up to 4096 centres,
+// three over its larger ones), one clamped prefix sum and two fill kinds; a chunk without one issues what it issued before.
+int mccnn_geometry_build_batch_budget(const mccnn_geometry_request* req, const mccnn_neighbor_cap* caps, const mccnn_point_pdf* points,
+                                      const mccnn_neighbor_budget* budgets, int count, mccnn_stream_t stream) {
     if (!req || count < 0) return MCCNN_E_BADARG;
     for (int k = 0; k < count; ++k) {
         const mccnn_geometry_request& r = req[k];
         int rc = geometry_setup(r.geometry, r.pts, r.batch_ids, r.n, r.centres, r.centre_batch_ids, r.m, r.aabb_min, r.aabb_max,
                                 r.batch_size, r.num_cells, r.radius, r.scale_inv, r.window, r.use_pdf, r.e_capacity, r.grid_from,
-                                r.buffer, r.buffer_bytes, r.total_host, true, caps ? &caps[k] : nullptr, points ? &points[k] : nullptr);
+                                r.buffer, r.buffer_bytes, r.total_host, true, caps ? &caps[k] : nullptr, points ? &points[k] : nullptr,
+                                budgets ? &budgets[k] : nullptr);
         if (rc) return rc;
     }
     if (points)

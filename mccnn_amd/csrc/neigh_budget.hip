@@ -95,8 +95,8 @@ __device__ __forceinline__ bool budget_step(int level, const uint32_t* hr, const
 }
 
 // All levels in one workgroup (no global atomics, no tickets)
-__global__ __launch_bounds__(256) void budget_select_small(const int* __restrict__ kfull, int m, unsigned long long budget, int Ku,
-                                                           int* __restrict__ capDev) {
+__device__ __forceinline__ void budget_select_small_body(const int* __restrict__ kfull, int m, unsigned long long budget, int Ku,
+                                                         int* __restrict__ capDev) {
     __shared__ uint32_t hr[MCCNN_NB_BUCKETS];
     __shared__ unsigned long long hs[MCCNN_NB_BUCKETS];
     __shared__ BudgetRange sR;
@@ -127,12 +127,26 @@ __global__ __launch_bounds__(256) void budget_select_small(const int* __restrict
         if (sDone) return;
     }
 }
+__global__ __launch_bounds__(256) void budget_select_small(const int* __restrict__ kfull, int m, unsigned long long budget, int Ku,
+                                                           int* __restrict__ capDev) {
+    budget_select_small_body(kfull, m, budget, Ku, capDev);
+}
+// The same for the small lists of a BATCH of searches (mccnn_geometry_build_batch_budget): one workgroup per list, the lists'
+// arguments by value in the kernel arguments
+struct BudgetSmallItem { const int* kfull; int* capDev; unsigned long long B; int m, Ku; };
+struct BudgetSmallBatch { BudgetSmallItem it[MCCNN_BATCH_MAX]; };
+__global__ __launch_bounds__(256) void budget_select_small_batch(BudgetSmallBatch sb) {
+    const BudgetSmallItem& g = sb.it[blockIdx.x];
+    budget_select_small_body(g.kfull, g.m, g.B, g.Ku, g.capDev);
+}
 
 // One level over the whole chip: per-workgroup histograms in LDS, merged into the level's global histogram with integer
 // atomics; the workgroup that draws the last ticket reads the merged histogram back and takes the scalar step.
+// (workgroup `blk` of the `nblk` that share the list: the single launch, and one list's share of a batch launch -- "last"
+// is the last of THIS list, its ticket and histograms are the list's own)
 template <int LEVEL>
-__global__ __launch_bounds__(256) void budget_select_level(const int* __restrict__ kfull, int m, BudgetWs w, unsigned long long budget,
-                                                           int Ku, int* __restrict__ capDev) {
+__device__ __forceinline__ void budget_select_level_body(const int* __restrict__ kfull, int m, const BudgetWs& w, unsigned long long budget,
+                                                         int Ku, int* __restrict__ capDev, const unsigned blk, const unsigned nblk) {
     __shared__ uint32_t hr[MCCNN_NB_BUCKETS];
     __shared__ unsigned long long hs[MCCNN_NB_BUCKETS];
     __shared__ uint32_t sMax;
@@ -146,7 +160,7 @@ __global__ __launch_bounds__(256) void budget_select_level(const int* __restrict
     for (int b = threadIdx.x; b < nb; b += 256) { hr[b] = 0u; hs[b] = 0ull; }
     if (threadIdx.x == 0) sMax = 0u;
     __syncthreads();
-    const uint32_t kmax = budget_hist(kfull, m, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256), r.lo, shift, nb, hr, hs);
+    const uint32_t kmax = budget_hist(kfull, m, (int)(blk * 256 + threadIdx.x), (int)(nblk * 256), r.lo, shift, nb, hr, hs);
     if (LEVEL == 0) atomicMax(&sMax, kmax);
     __syncthreads();
     for (int b = threadIdx.x; b < nb; b += 256) {
@@ -160,7 +174,7 @@ __global__ __launch_bounds__(256) void budget_select_level(const int* __restrict
     __threadfence();
     __syncthreads();
     if (threadIdx.x == 0)
-        sLast = __hip_atomic_fetch_add(w.misc + NB_TICKET + LEVEL, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
+        sLast = __hip_atomic_fetch_add(w.misc + NB_TICKET + LEVEL, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1u;
     __syncthreads();
     if (!sLast) return;
     __threadfence();
@@ -191,17 +205,34 @@ __global__ __launch_bounds__(256) void budget_select_level(const int* __restrict
         }
     }
 }
+template <int LEVEL>
+__global__ __launch_bounds__(256) void budget_select_level(const int* __restrict__ kfull, int m, BudgetWs w, unsigned long long budget,
+                                                           int Ku, int* __restrict__ capDev) {
+    budget_select_level_body<LEVEL>(kfull, m, w, budget, Ku, capDev, blockIdx.x, gridDim.x);
+}
+// One level of the larger lists of a batch: their workgroups share one grid (BatchBlocks), every list keeps its own region
+struct BudgetLevelItem { const int* kfull; int* capDev; BudgetWs w; unsigned long long B; int m, Ku; };
+struct BudgetLevelBatch { BudgetLevelItem it[MCCNN_BATCH_MAX]; };
+static_assert(sizeof(BudgetLevelBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched selection level: < 4 KB");
+template <int LEVEL>
+__global__ __launch_bounds__(256) void budget_select_level_batch(BudgetLevelBatch lb, BatchBlocks bb) {
+    int local, blocks;
+    const BudgetLevelItem& g = lb.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
+    budget_select_level_body<LEVEL>(g.kfull, g.m, g.w, g.B, g.Ku, g.capDev, (unsigned)local, (unsigned)blocks);
+}
 
 // scan_chained (scan.hip) over min(in[i], *capDev): the prefix sum of the capped row lengths; one tile or many (a single
 // tile is tile 0 of a chain of one). status: tiles + 1 words, zero on entry.
-__global__ __launch_bounds__(SCAN_THREADS) void scan_chained_clamp(const int* __restrict__ in, const int* __restrict__ capDev,
-                                                                   int* __restrict__ out, int n, unsigned long long* status,
-                                                                   int* __restrict__ total) {
+// (tile taken from the ticket behind the `nblk` status words of THIS array: the look-back never waits for a tile that is not
+// scheduled, in a launch of its own and as one array's share of a batch launch alike)
+__device__ __forceinline__ void scan_clamp_body(const int* __restrict__ in, const int* __restrict__ capDev, int* __restrict__ out, int n,
+                                                unsigned long long* status, int* __restrict__ total, int* __restrict__ total2,
+                                                const int nblk) {
     __shared__ int lds[4];
     __shared__ int sOff;
     __shared__ int sTile;
     if (threadIdx.x == 0)
-        sTile = (int)__hip_atomic_fetch_add(status + gridDim.x, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sTile = (int)__hip_atomic_fetch_add(status + nblk, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int cap = __builtin_amdgcn_readfirstlane(*capDev);
     __syncthreads();
     const int tile = sTile;
@@ -226,7 +257,24 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_chained_clamp(const int* __
         if (base + k < n) out[base + k] = run;
         run += v[k];
     }
-    if (tile == (int)gridDim.x - 1 && threadIdx.x == SCAN_THREADS - 1) *total = run;
+    if (tile == nblk - 1 && threadIdx.x == SCAN_THREADS - 1) {
+        *total = run;
+        if (total2) *total2 = run;   // (a geometry's pinned host word)
+    }
+}
+__global__ __launch_bounds__(SCAN_THREADS) void scan_chained_clamp(const int* __restrict__ in, const int* __restrict__ capDev,
+                                                                   int* __restrict__ out, int n, unsigned long long* status,
+                                                                   int* __restrict__ total, int* __restrict__ total2) {
+    scan_clamp_body(in, capDev, out, n, status, total, total2, (int)gridDim.x);
+}
+// ... of the budgeted lists of a batch: a launch of their own beside scan_chained_batch, which keeps its arguments and its
+// code. clamp[k]: the cap word of item k.
+struct ClampBatch { const int* cap[MCCNN_BATCH_MAX]; };
+__global__ __launch_bounds__(SCAN_THREADS) void scan_chained_clamp_batch(ScanBatch sb, ClampBatch cb, BatchBlocks bb) {
+    int local, blocks;
+    const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
+    const ScanItem& it = sb.it[k];
+    scan_clamp_body(it.in, cb.cap[k], it.out, it.n, it.status, it.total, it.total2, blocks);
 }
 
 // m == 0: an empty list and the floor of the cap
@@ -242,9 +290,8 @@ int launch_budget_empty(int* total_dev, int* cap_dev, hipStream_t s) {
     return 0;
 }
 
-// selection + prefix sum over the row lengths the count pass left (which also cleared `region`): 2 or 4 launches
-int budget_select_scan(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, int* start_idx,
-                       int* total_dev, hipStream_t s) {
+// the selection over the row lengths the count pass left (which also cleared `region`): 1 or 3 launches
+int budget_select(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, hipStream_t s) {
     const int tiles = ceil_div(m, SCAN_TILE);
     if (m <= 0 || tiles > 1024) return MCCNN_E_TOOLARGE;   // (the chained scan: up to 2 M centres)
     const BudgetWs w = budget_ws(region, m);
@@ -261,7 +308,83 @@ int budget_select_scan(const int* kfull, int m, void* region, int max_edges, int
         budget_select_level<2><<<blocks, 256, 0, s>>>(kfull, m, w, B, max_neighbors, cap_dev);
         MCCNN_LAUNCHED();
     }
-    scan_chained_clamp<<<tiles, SCAN_THREADS, 0, s>>>(kfull, cap_dev, start_idx, m, w.status, total_dev);
+    return 0;
+}
+// the prefix sum of min(kfull, *cap_dev) behind it: one launch
+int budget_scan(const int* kfull, int m, void* region, const int* cap_dev, int* start_idx, int* total_dev, int* total_host, hipStream_t s) {
+    const int tiles = ceil_div(m, SCAN_TILE);
+    if (m <= 0 || tiles > 1024) return MCCNN_E_TOOLARGE;
+    scan_chained_clamp<<<tiles, SCAN_THREADS, 0, s>>>(kfull, cap_dev, start_idx, m, budget_ws(region, m).status, total_dev, total_host);
+    MCCNN_LAUNCHED();
+    return 0;
+}
+// selection + prefix sum (mccnn_find_neighbors_count_budget): 2 or 4 launches
+int budget_select_scan(const int* kfull, int m, void* region, int max_edges, int max_neighbors, int* cap_dev, int* start_idx,
+                       int* total_dev, hipStream_t s) {
+    int rc = budget_select(kfull, m, region, max_edges, max_neighbors, cap_dev, s);
+    if (rc) return rc;
+    return budget_scan(kfull, m, region, cap_dev, start_idx, total_dev, nullptr, s);
+}
+
+// ---- batch form (exec.hip: a chunk of mccnn_geometry_build_batch_budget). The count pass of the chunk has left every item's
+// row lengths and cleared its region. Selection: ONE launch over the small items (one workgroup each) and three over the
+// larger ones (the levels; their workgroups share a grid) -- each only when items of its size class are present.
+int launch_budget_select_batch(const BudgetItem* items, int count, hipStream_t s) {
+    if (count < 0 || count > MCCNN_BATCH_MAX) return MCCNN_E_BADARG;
+    BudgetSmallBatch sb;
+    BudgetLevelBatch lb;
+    BatchBlocks bb;
+    int nS = 0, nL = 0, run = 0;
+    for (int k = 0; k < count; ++k) {
+        const BudgetItem& b = items[k];
+        if (b.m <= 0 || ceil_div(b.m, SCAN_TILE) > 1024) return MCCNN_E_TOOLARGE;
+        if (b.m <= MCCNN_NB_SMALL_M && small_kernels_on()) {
+            sb.it[nS++] = BudgetSmallItem{b.kfull, b.cap_dev, (unsigned long long)b.max_edges, b.m, b.max_neighbors};
+        } else {
+            lb.it[nL] = BudgetLevelItem{b.kfull, b.cap_dev, budget_ws(b.region, b.m), (unsigned long long)b.max_edges, b.m, b.max_neighbors};
+            bb.first[nL++] = run;
+            run += min(ceil_div(b.m, 4 * 256), MCCNN_NB_MAX_BLOCKS);
+        }
+    }
+    if (nS) {
+        for (int k = nS; k < MCCNN_BATCH_MAX; ++k) sb.it[k] = sb.it[0];   // (never addressed: defined bytes)
+        budget_select_small_batch<<<nS, 256, 0, s>>>(sb);
+        MCCNN_LAUNCHED();
+    }
+    if (nL) {
+        for (int k = nL; k < MCCNN_BATCH_MAX; ++k) lb.it[k] = lb.it[0];
+        for (int k = nL; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+        bb.count = nL;
+        budget_select_level_batch<0><<<run, 256, 0, s>>>(lb, bb);
+        MCCNN_LAUNCHED();
+        budget_select_level_batch<1><<<run, 256, 0, s>>>(lb, bb);
+        MCCNN_LAUNCHED();
+        budget_select_level_batch<2><<<run, 256, 0, s>>>(lb, bb);
+        MCCNN_LAUNCHED();
+    }
+    return 0;
+}
+// ... and the prefix sums of min(kfull, K*) of all of them: one launch
+int launch_budget_scan_batch(const BudgetItem* items, int count, hipStream_t s) {
+    if (count < 0 || count > MCCNN_BATCH_MAX) return MCCNN_E_BADARG;
+    if (count == 0) return 0;
+    ScanBatch sc;
+    ClampBatch cb;
+    BatchBlocks bb;
+    int run = 0;
+    for (int k = 0; k < count; ++k) {
+        const BudgetItem& b = items[k];
+        const int tiles = ceil_div(b.m, SCAN_TILE);
+        if (b.m <= 0 || tiles > 1024) return MCCNN_E_TOOLARGE;
+        sc.it[k] = ScanItem{b.kfull, b.start_idx, budget_ws(b.region, b.m).status, b.total_dev, b.total_host, b.m, tiles};
+        cb.cap[k] = b.cap_dev;
+        bb.first[k] = run;
+        run += tiles;
+    }
+    for (int k = count; k < MCCNN_BATCH_MAX; ++k) { sc.it[k] = sc.it[0]; cb.cap[k] = cb.cap[0]; }
+    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    bb.count = count;
+    scan_chained_clamp_batch<<<run, SCAN_THREADS, 0, s>>>(sc, cb, bb);
     MCCNN_LAUNCHED();
     return 0;
 }

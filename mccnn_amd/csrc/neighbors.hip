@@ -104,7 +104,9 @@ __device__ __forceinline__ int kept_slot(int r, int k, int cap, unsigned rowh) {
 // Called from neigh_window_body below and from nowhere else; the pointers are parameters because `__restrict__` holds for
 // parameters only -- bound to locals instead, the fill pass's mask, cell and point loads may alias its stores: 66 VGPRs
 // instead of 56 and 7 waves per SIMD instead of 8.)
-template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED>
+// CLAMP (the fill pass of a small list with an edge budget, scan mode): `scanCnt` holds the TRUE row lengths and the prefix
+// sum is that of min(scanCnt[i], capK) -- the clamp rides in the load, as in neigh_budget.hip's scan_chained_clamp.
+template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED, bool CLAMP = false>
 __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk, const float* __restrict__ centres, const int* __restrict__ cb, int m,
                                                     const float* __restrict__ pts, const int* __restrict__ cells,
                                                     const float* __restrict__ mn, const float* __restrict__ mx, int B, int nc,
@@ -120,6 +122,7 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
                                                     const unsigned sseed /* SAMPLED: the seed of the draw */) {
     constexpr bool FILL = MODE == 1;
     static_assert(!SAMPLED || (CAPPED && FILL), "the sample is a form of the capped fill pass");
+    static_assert(!CLAMP || (CAPPED && FILL), "the clamped prefix sum belongs to the capped fill pass");
     // the status words of the prefix sum that follows the count pass (scan.hip): cleared here, no launch of their own
     if (!FILL && blk == 0)
         for (int k = threadIdx.x; k < numZero; k += blockDim.x) zeroWords[k] = 0ull;
@@ -138,7 +141,8 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int idx = threadIdx.x * PER + k;
-            v[k] = idx < m ? scanCnt[idx] : 0;
+            if constexpr (CLAMP) v[k] = idx < m ? min(scanCnt[idx], capK) : 0;
+            else v[k] = idx < m ? scanCnt[idx] : 0;
             sum += v[k];
         }
         const int incl = wave_incl_scan(sum);
@@ -437,10 +441,10 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
 
 // The kernel's body over the records of batch.h: the search `g`, the in-fill prefix sum `ps` (all null in a batch) and the
 // cap `cp`, which only the CAPPED instantiations read. The one place that spells the statements' argument list.
-template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED>
+template <int MODE, bool LEAN, bool CAPPED, bool SAMPLED, bool CLAMP = false>
 __device__ __forceinline__ void neigh_window_body(const int blk, const int nblk, const NeighItem& g, const NeighScan& ps,
                                                     const NeighCapItem& cp) {
-    neigh_window_impl<MODE, LEAN, CAPPED, SAMPLED>(blk, nblk, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv,
+    neigh_window_impl<MODE, LEAN, CAPPED, SAMPLED, CLAMP>(blk, nblk, g.centres, g.cb, g.m, g.pts, g.cells, g.mn, g.mx, g.B, g.nc, g.radius, g.scaleInv,
                                                    g.order, g.cnt, g.masks, g.startIdx, g.packed, g.capacity, g.zeroWords, g.numZero, g.G,
                                                    g.Tabs, ps.scanCnt, ps.startOut, ps.totalDev, ps.totalHost, CAPPED ? cp.capK : 0,
                                                    CAPPED ? cp.kfull : nullptr, SAMPLED ? cp.seed : 0u);
@@ -462,6 +466,13 @@ __global__ __launch_bounds__(256) void neigh_window_budget(NeighItem g, NeighCap
     cp.capK = __builtin_amdgcn_readfirstlane(*capDev);
     neigh_window_body<1, LEAN, true, SAMPLED>((int)blockIdx.x, (int)gridDim.x, g, NeighScan{}, cp);
 }
+// ... of a list of at most MCCNN_NW_SCAN_M centres inside the native executor's chain (find_neighbors_chain): the prefix sum
+// of min(k, K*) rides in this pass (`ps`: the true row lengths in, start_idx and the totals out), no scan launch before it.
+template <bool LEAN, bool SAMPLED>
+__global__ __launch_bounds__(256) void neigh_window_budget_scan(NeighItem g, NeighScan ps, NeighCapItem cp, const int* __restrict__ capDev) {
+    cp.capK = __builtin_amdgcn_readfirstlane(*capDev);
+    neigh_window_body<1, LEAN, true, SAMPLED, true>((int)blockIdx.x, (int)gridDim.x, g, ps, cp);
+}
 
 // One launch for the count (or the fill) pass of a BATCH of searches of one kind (mccnn_geometry_build_batch): the plain
 // loop of the background launches, the prefix sum of the counts a launch of its own in between (scan.hip's batch form).
@@ -471,6 +482,16 @@ __global__ __launch_bounds__(256) void neigh_window_batch(NeighBatch nbt, NeighC
     int local, blocks;
     const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
     neigh_window_body<MODE, false, KIND != NEIGH_PLAIN, KIND == NEIGH_SAMPLED>(local, blocks, nbt.it[k], NeighScan{}, caps.it[k]);
+}
+// The fill pass of the BUDGETED searches of a batch (kinds NEIGH_BUDGET / NEIGH_BUDGET_SAMPLED): the capped / sampled body with
+// every item's cap read from its own device word -- one wave-uniform load in the prologue, as neigh_window_budget does.
+template <bool SAMPLED>
+__global__ __launch_bounds__(256) void neigh_window_batch_budget(NeighBatch nbt, NeighCapBatch caps, BatchBlocks bb) {
+    int local, blocks;
+    const int k = batch_item(bb, (int)blockIdx.x, local, blocks);
+    NeighCapItem cp = caps.it[k];
+    cp.capK = __builtin_amdgcn_readfirstlane(*cp.capDev);
+    neigh_window_body<1, false, true, SAMPLED>(local, blocks, nbt.it[k], NeighScan{}, cp);
 }
 
 __global__ __launch_bounds__(256) void invert_perm_k(const int* __restrict__ newIdx, int n, int* __restrict__ inv) {
@@ -985,7 +1006,7 @@ static int neigh_item(const NeighSearch& q, bool batch, NeighItem& it, NeighCapI
     it.numZero = batch ? ceil_div(q.m, 2048) + 1 : (int)(scan_status_bytes(q.m) / sizeof(unsigned long long));
     it.radius = q.radius;
     it.Tabs = q.scale_inv ? 0.0f : sqrt_threshold_host(q.radius);
-    cap.kfull = w.kfull; cap.capK = q.max_neighbors; cap.seed = q.seed; cap.sampled = q.sampled ? 1 : 0;
+    cap.kfull = w.kfull; cap.capDev = nullptr; cap.capK = q.max_neighbors; cap.seed = q.seed; cap.sampled = q.sampled ? 1 : 0;
     return 0;
 }
 static int neigh_kind(int max_neighbors, int sampled) { return max_neighbors > 0 ? (sampled ? NEIGH_SAMPLED : NEIGH_CAPPED) : NEIGH_PLAIN; }
@@ -1017,6 +1038,26 @@ static int launch_neigh_kind(int mode, int kind, int grid, size_t dyn, hipStream
     neigh_pick(mode, kind, [&](auto m, auto k) {
         neigh_window_batch<decltype(m)::value, decltype(k)::value><<<grid, 256, dyn, s>>>(nbt, caps, bb);   // (background launches: the plain loop)
     });
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+// The fill pass of a search with an edge budget: the cap comes from *cap_dev. scan (`ps` set): the pass clamps and scans the
+// true row lengths itself (lists of at most MCCNN_NW_SCAN_M centres inside find_neighbors_chain).
+static int launch_neigh_budget(bool lean, bool sampled, bool scan, int grid, size_t dyn, hipStream_t s, const NeighItem& it,
+                               const NeighScan& ps, const NeighCapItem& cap, const int* cap_dev) {
+    auto go = [&](auto l, auto sm) {
+        constexpr bool L = decltype(l)::value, S = decltype(sm)::value;
+        if (scan) neigh_window_budget_scan<L, S><<<grid, 256, dyn, s>>>(it, ps, cap, cap_dev);
+        else neigh_window_budget<L, S><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
+    };
+    if (lean) {
+        if (sampled) go(std::true_type{}, std::true_type{});
+        else go(std::true_type{}, std::false_type{});
+    } else {
+        if (sampled) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+    }
     MCCNN_LAUNCHED();
     return 0;
 }
@@ -1201,28 +1242,71 @@ int mccnn_find_neighbors_fill_budget(const float* centres, const int* centre_bat
     int rc = neigh_item(q, false, it, cap, w);
     if (rc) return rc;
     if (it.G == 16) it.G = MCCNN_NW_G;   // (as find_neighbors_fill_impl)
-    const int grid = ceil_div(m, 4 * it.G);
-    const size_t dyn = neigh_lds_pad();
-    hipStream_t s = (hipStream_t)stream;
-    if (neigh_lean()) {
-        if (sampled) neigh_window_budget<true, true><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
-        else neigh_window_budget<true, false><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
-    } else {
-        if (sampled) neigh_window_budget<false, true><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
-        else neigh_window_budget<false, false><<<grid, 256, dyn, s>>>(it, cap, cap_dev);
-    }
-    MCCNN_LAUNCHED();
-    return 0;
+    return launch_neigh_budget(neigh_lean(), sampled != 0, false, ceil_div(m, 4 * it.G), neigh_lds_pad(), (hipStream_t)stream, it,
+                               NeighScan{}, cap, cap_dev);
 }
 #undef MCCNN_NEIGH_SEARCH
 
 }  // extern "C"
 namespace mccnn {
+// the region of a budgeted search inside its workspace: behind the capped layout (mccnn_find_neighbors_budget_workspace_bytes)
+static void* neigh_budget_region(void* ws, int m, int n) { return (char*)ws + mccnn_find_neighbors_capped_workspace_bytes(m, n); }
+
+// The search of a native geometry's chain with an edge budget (max_edges = B > 0; the passes of
+// mccnn_find_neighbors_count_budget / _fill_budget, the same bytes):
+// unclamped capped count pass (clears the budget region) -> selection (K* into *cap_dev) -> prefix sum of min(k, K*) -> fill
+// pass with the cap read from the word. Lists of at most MCCNN_NW_SCAN_M centres lose the scan launch as the others do: their
+// fill pass clamps and scans the true row lengths itself (neigh_window_budget_scan).
+static int find_neighbors_chain_budget(const NeighSearch& q0, hipStream_t s) {
+    if (q0.max_neighbors < 0 || !q0.cap_dev || !q0.total_dev) return MCCNN_E_BADARG;
+    if (q0.m < 0 || q0.n < 0 || q0.capacity < 0 || q0.B <= 0 || q0.nc <= 0 || !(q0.radius > 0.0f)) return MCCNN_E_BADARG;
+    const int m = q0.m;
+    if (m == 0) {
+        int rc = launch_budget_empty(q0.total_dev, q0.cap_dev, s);
+        if (!rc && q0.total_host) rc = launch_zero_words(q0.total_host, 1, s);
+        return rc;
+    }
+    if (!q0.centres || !q0.cbids || !q0.cells || !q0.mn || !q0.mx || !q0.start_idx || (q0.n > 0 && !q0.pts)) return MCCNN_E_BADARG;
+    if ((long long)m > 2048LL * 1024) return MCCNN_E_TOOLARGE;
+    if (!q0.ws || q0.ws_bytes < mccnn_find_neighbors_budget_workspace_bytes(m, q0.n)) return MCCNN_E_WORKSPACE;
+    NeighSearch q = q0;
+    q.max_neighbors = 0x7fffffff;   // the capped count pass, no clamp
+    q.sampled = 0;
+    NeighItem it;
+    NeighCapItem cap;
+    NeighWs w;
+    int rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    void* region = neigh_budget_region(q.ws, m, q.n);
+    budget_region_zero(region, m, &it.zeroWords, &it.numZero);
+    rc = launch_neigh(0, neigh_lean(), NEIGH_CAPPED, ceil_div(m, 4 * it.G), neigh_lds_pad(), s, it, NeighScan{}, cap);
+    if (rc) return rc;
+    rc = budget_select(w.kfull, m, region, q0.max_edges, q0.max_neighbors, q0.cap_dev, s);
+    if (rc) return rc;
+    const bool small = m <= MCCNN_NW_SCAN_M && q0.capacity > 0 && q0.n > 0;
+    if (!small) {
+        rc = budget_scan(w.kfull, m, region, q0.cap_dev, q0.start_idx, q0.total_dev, q0.total_host, s);
+        if (rc || q0.capacity == 0 || q0.n == 0) return rc;
+    }
+    if (!q0.packed) return MCCNN_E_BADARG;
+    q.max_neighbors = 1;   // (the capped workspace layout; the kernel takes the cap from *cap_dev)
+    q.sampled = q0.sampled ? 1 : 0;
+    rc = neigh_item(q, false, it, cap, w);
+    if (rc) return rc;
+    if (it.G == 16) it.G = MCCNN_NW_G;   // (as find_neighbors_fill_impl)
+    size_t dyn = neigh_lds_pad();
+    if (small && dyn < (size_t)m * sizeof(int)) dyn = (size_t)m * sizeof(int);
+    const NeighScan ps = small ? NeighScan{w.kfull, q0.start_idx, q0.total_dev, q0.total_host} : NeighScan{};
+    return launch_neigh_budget(neigh_lean(), q.sampled != 0, small, ceil_div(m, 4 * it.G), dyn, s, it, ps, cap, q0.cap_dev);
+}
+
 // Both passes of a search back to back (the native executor's geometry chain). Lists of at most MCCNN_NW_SCAN_M centres:
 // count -> fill, the prefix sum of the counts rides in the fill pass (two launches); larger ones: count -> scan -> fill.
 // max_neighbors > 0: the capped passes over the capped workspace layout (the counts the fill pass scans are min(k, K));
-// sampled: the fill pass draws the stratified sample of `seed`.
+// sampled: the fill pass draws the stratified sample of `seed`. max_edges > 0: find_neighbors_chain_budget above.
 int find_neighbors_chain(const NeighSearch& q, hipStream_t s) {
+    if (q.max_edges < 0) return MCCNN_E_BADARG;
+    if (q.max_edges > 0) return find_neighbors_chain_budget(q, s);
     if (q.max_neighbors < 0 || (q.sampled && q.max_neighbors == 0)) return MCCNN_E_BADARG;
     const bool small = q.m > 0 && q.m <= MCCNN_NW_SCAN_M && q.capacity > 0 && q.n > 0;
     int rc = find_neighbors_count_impl(q, s, small);
@@ -1233,8 +1317,24 @@ int find_neighbors_chain(const NeighSearch& q, hipStream_t s) {
 // ---- host side of the batch form (mccnn_geometry_build_batch): one item per search / KDE, the workspace layout of the
 // single calls (neigh_ws); background settings (plain loop, centres per wave by the list's size)
 bool neigh_batch_eligible(int m, int n) { return m > 0 && n > 0 && (long long)m <= 2048LL * 1024; }
-int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q) {
+int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const NeighSearch& q, BudgetItem* bud) {
     if (!neigh_batch_eligible(q.m, q.n)) return MCCNN_E_TOOLARGE;
+    if (q.max_edges < 0 || (q.max_edges > 0 && (!bud || !q.cap_dev || q.max_neighbors < 0))) return MCCNN_E_BADARG;
+    if (q.max_edges > 0) {
+        // a budgeted item: the unclamped capped count pass, which clears the item's budget region (whose first tiles + 1 words
+        // are the status words of its clamped scan); the fill pass reads the cap from the word
+        if (q.ws_bytes < mccnn_find_neighbors_budget_workspace_bytes(q.m, q.n)) return MCCNN_E_WORKSPACE;
+        NeighSearch qc = q;
+        qc.max_neighbors = 0x7fffffff;
+        NeighWs w;
+        int rc = neigh_item(qc, true, it, cap, w);
+        if (rc) return rc;
+        cap.capDev = q.cap_dev;
+        void* region = neigh_budget_region(q.ws, q.m, q.n);
+        budget_region_zero(region, q.m, &it.zeroWords, &it.numZero);
+        *bud = BudgetItem{w.kfull, region, q.m, q.max_edges, q.max_neighbors, q.cap_dev, q.start_idx, q.total_dev, q.total_host};
+        return 0;
+    }
     if (q.max_neighbors < 0 || (q.sampled && q.max_neighbors == 0)) return MCCNN_E_BADARG;
     NeighWs w;
     int rc = neigh_item(q, true, it, cap, w);
@@ -1255,14 +1355,18 @@ int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int cou
     // kind that is present: a chunk without a capped item is the one plain launch over all its items.
     // (Items are independent searches over buffers of their own: their order inside a kind's launch does not matter. The
     // copies below are ~2.5 KB of host memory per kind and pass.)
-    for (int kind = NEIGH_PLAIN; kind <= NEIGH_SAMPLED; ++kind) {
+    // A budgeted item (capDev) joins the capped count launch -- its capK is 0x7fffffff there -- and one of the two budget
+    // kinds of the fill pass.
+    for (int kind = NEIGH_PLAIN; kind <= NEIGH_BUDGET_SAMPLED; ++kind) {
+        if (mode == 0 && kind > NEIGH_SAMPLED) break;
         NeighBatch sub;
         NeighCapBatch subc;
         int cnt = 0;
         for (int k = 0; k < count; ++k) {
             const NeighCapItem& c = caps.it[k];
             int kd = neigh_kind(c.capK, c.sampled);
-            if (mode == 0 && kd == NEIGH_SAMPLED) kd = NEIGH_CAPPED;
+            if (c.capDev) kd = c.sampled ? NEIGH_BUDGET_SAMPLED : NEIGH_BUDGET;
+            if (mode == 0 && kd != NEIGH_PLAIN) kd = NEIGH_CAPPED;
             if (kd != kind) continue;
             sub.it[cnt] = nbt.it[k];
             subc.it[cnt] = c;
@@ -1273,6 +1377,12 @@ int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int cou
         BatchBlocks bb;
         const int run = neigh_batch_blocks(sub, cnt, bb);
         if (run == 0) continue;
+        if (kind > NEIGH_SAMPLED) {
+            if (kind == NEIGH_BUDGET) neigh_window_batch_budget<false><<<run, 256, 24000, s>>>(sub, subc, bb);
+            else neigh_window_batch_budget<true><<<run, 256, 24000, s>>>(sub, subc, bb);
+            MCCNN_LAUNCHED();
+            continue;
+        }
         int rc = launch_neigh_kind(mode, kind, run, 24000, s, sub, subc, bb);   // (the LDS pad of background launches: neigh_lds_pad)
         if (rc) return rc;
     }

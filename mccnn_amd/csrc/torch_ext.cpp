@@ -562,6 +562,11 @@ struct Geo {
         check(mccnn_geometry_info(h, out), "geometry_info");
         return std::vector<int64_t>(out, out + 16);
     }
+    // device address of the word that holds the cap a budgeted search chose (0: the geometry has no budget)
+    int64_t cap_addr() {
+        wait_issued();
+        return (int64_t)(uintptr_t)mccnn_geometry_cap(h);
+    }
 };
 
 void check_dev(const Tensor& t, at::ScalarType dt, const char* name) {
@@ -584,6 +589,7 @@ struct BatchEntry {
     mccnn_geometry_request req;
     mccnn_neighbor_cap cap;   // of the request's search (max_neighbors 0: none)
     mccnn_point_pdf point;    // its per-point density (density null: edge mode)
+    mccnn_neighbor_budget budget{0};   // its edge budget (0: none)
     bool writes_point = false;   // this request computes the density: its event is recorded behind the batch
 };
 struct PieceEntry {   // row plans / transposed list of a batched geometry whose list is small: built as a batch as well
@@ -649,7 +655,9 @@ void end_geometry_batch() {
         std::vector<mccnn_geometry_request> reqs;
         std::vector<mccnn_neighbor_cap> caps;
         std::vector<mccnn_point_pdf> points;
-        bool any_cap = false, any_point = false;
+        std::vector<mccnn_neighbor_budget> budgets;
+        bool any_cap = false, any_point = false, any_budget = false;
+        budgets.reserve(entries->size());
         reqs.reserve(entries->size());
         caps.reserve(entries->size());
         points.reserve(entries->size());
@@ -661,12 +669,15 @@ void end_geometry_batch() {
             if (e.grid_from && !inside) e.grid_from->wait_issued_nothrow();
             reqs.push_back(e.req);
             caps.push_back(e.cap);
-            any_cap = any_cap || e.cap.max_neighbors > 0;
+            any_cap = any_cap || e.cap.max_neighbors > 0 || e.budget.max_edges > 0;   // (a budgeted request may carry a seed)
+            budgets.push_back(e.budget);
+            any_budget = any_budget || e.budget.max_edges > 0;
             points.push_back(e.point);
             any_point = any_point || e.point.density != nullptr;
         }
         const int prev = background ? mccnn_background_launches(1) : 0;
-        int rc = any_point ? mccnn_geometry_build_batch_point(reqs.data(), any_cap ? caps.data() : nullptr, points.data(), (int)reqs.size(), (void*)stream)
+        int rc = any_budget ? mccnn_geometry_build_batch_budget(reqs.data(), caps.data(), any_point ? points.data() : nullptr, budgets.data(), (int)reqs.size(), (void*)stream)
+               : any_point ? mccnn_geometry_build_batch_point(reqs.data(), any_cap ? caps.data() : nullptr, points.data(), (int)reqs.size(), (void*)stream)
                            : mccnn_geometry_build_batch_capped(reqs.data(), any_cap ? caps.data() : nullptr, (int)reqs.size(), (void*)stream);
         if (background) mccnn_background_launches(prev);
         for (BatchEntry& e : *entries) {
@@ -747,7 +758,8 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
                                     double window, bool use_pdf, int64_t capacity, std::shared_ptr<Geo> grid_from,
                                     int64_t side, bool fork, bool background, std::shared_ptr<HierFuture> after,
                                     int64_t max_neighbors, int64_t sample_seed /* < 0: none */, bool point_pdf,
-                                    std::shared_ptr<PointPdf> point_from /* the density of this grid and window, when it exists */) {
+                                    std::shared_ptr<PointPdf> point_from /* the density of this grid and window, when it exists */,
+                                    int64_t max_edges /* the edge budget of the search; 0: none */) {
     check_dev(pts, at::kFloat, "points");
     check_dev(centres, at::kFloat, "sample points");
     check_dev(bids, at::kInt, "batch ids");
@@ -758,8 +770,9 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     const int n = (int)pts.size(0), m = (int)centres.size(0);
     if (grid_from && grid_from->grid_owner) grid_from = grid_from->grid_owner;
     TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= 0x7fffffffLL, "geometry: maxNeighbors must be >= 0");
-    TORCH_CHECK(sample_seed < 0 || (max_neighbors > 0 && sample_seed <= 0xffffffffLL), "geometry: sampleSeed needs a cap and lies in [0, 2^32)");
-    TORCH_CHECK(!(point_pdf || point_from) || (use_pdf && max_neighbors == 0), "geometry: a per-point density needs usePDF and an uncapped list");
+    TORCH_CHECK(max_edges >= 0 && max_edges <= 0x7fffffffLL, "geometry: maxEdges must lie in [0, 2^31)");
+    TORCH_CHECK(sample_seed < 0 || ((max_neighbors > 0 || max_edges > 0) && sample_seed <= 0xffffffffLL), "geometry: sampleSeed needs a cap or a budget and lies in [0, 2^32)");
+    TORCH_CHECK(!(point_pdf || point_from) || (use_pdf && max_neighbors == 0 && max_edges == 0), "geometry: a per-point density needs usePDF and an uncapped list");
     TORCH_CHECK(!point_from || (point_from->density.defined() && point_from->density.size(0) == n), "geometry: the per-point density is of another grid");
     std::shared_ptr<PointPdf> pp = point_from;
     const bool pp_ready = pp != nullptr;
@@ -774,7 +787,8 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     };
     // the cap of the search (by value into the helper thread's job / the batch entry)
     const mccnn_neighbor_cap cap{(int)max_neighbors, sample_seed >= 0 ? 1 : 0, sample_seed >= 0 ? (unsigned)sample_seed : 0u};
-    const size_t bytes = mccnn_geometry_bytes_capped(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors);
+    const mccnn_neighbor_budget budget{(int)max_edges};
+    const size_t bytes = mccnn_geometry_bytes_budget(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors, budget.max_edges);
     TORCH_CHECK(bytes > 0, "geometry: batch_size * num_cells^3 does not fit 32-bit keys");
     auto g = std::make_shared<Geo>();
     g->h = mccnn_geometry_create();
@@ -899,19 +913,20 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
                                            grid_from ? grid_from->h : nullptr, bufp, bytes, slotp};
             e.cap = cap;
             e.point = point;
+            e.budget = budget;
             e.writes_point = writes_point;
             t_geo_batch.entries.push_back(std::move(e));
             g->plan_side = asked_side;   // the pieces built ahead keep the spread over the side streams the builds gave up
             return g;
         }
-        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev, cap, point, writes_point] {
+        Issuer::get().push([g, grid_from, p0, p1, p2, p3, p4, p5, bufp, slotp, n, m, iB, inc, icap, isi, ipdf, fr, fw, bytes, stream, background, dev, cap, point, writes_point, budget] {
             enter_device(dev);
             if (grid_from) grid_from->wait_issued_nothrow();
             // background: these launches run beside kernels a step waits for (the convolutions of the current batch) --
             // the search kernels then hold back (mccnn_background_launches, thread-local: set on THIS thread)
             const int prev = background ? mccnn_background_launches(1) : 0;
-            int rc = mccnn_geometry_build_point(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
-                                                grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream, &cap, &point);
+            int rc = mccnn_geometry_build_budget(g->h, p0, p1, n, p2, p3, m, p4, p5, iB, inc, fr, isi, fw, ipdf, icap,
+                                                 grid_from ? grid_from->h : nullptr, bufp, bytes, slotp, stream, &cap, &point, &budget);
             if (background) mccnn_background_launches(prev);
             if (writes_point) g->pp->mark(stream);
             if (rc == 0 && hipEventRecord(g->event, (hipStream_t)stream) != hipSuccess) rc = (int)hipErrorUnknown;
@@ -926,11 +941,11 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
         bool on; int prev;
         ~Restore() { if (on) mccnn_background_launches(prev); }
     } restore{background && g->side >= 0, prev_bg};
-    const int build_rc = mccnn_geometry_build_point(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
+    const int build_rc = mccnn_geometry_build_budget(g->h, pts.data_ptr<float>(), bids.data_ptr<int>(), n, centres.data_ptr<float>(),
                                                     cbids.data_ptr<int>(), m, mn.data_ptr<float>(), mx.data_ptr<float>(), (int)B, (int)nc,
                                                     (float)radius, scale_inv ? 1 : 0, (float)window, use_pdf ? 1 : 0, (int)capacity,
                                                     grid_from ? grid_from->h : nullptr, g->buf.data_ptr(), bytes,
-                                                    g->slot.data_ptr<int>(), stream, &cap, &point);
+                                                    g->slot.data_ptr<int>(), stream, &cap, &point, &budget);
     if (writes_point) pp->mark(stream);
     check(build_rc, "geometry_build");
     if (g->side >= 0) {
@@ -1659,7 +1674,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
         .def("prebuild", &Geo::prebuild, py::arg("what"), py::arg("avg"), py::arg("side"), py::arg("like"),
              py::call_guard<py::gil_scoped_release>())
         .def("edges", &Geo::edges, py::arg("wait_us") = -1, py::call_guard<py::gil_scoped_release>())
-        .def("info", &Geo::info, py::call_guard<py::gil_scoped_release>());
+        .def("info", &Geo::info, py::call_guard<py::gil_scoped_release>())
+        .def("cap_addr", &Geo::cap_addr, py::call_guard<py::gil_scoped_release>());
     py::class_<PointPdf, std::shared_ptr<PointPdf>>(mod, "PointPdf")
         .def_readonly("density", &PointPdf::density)
         .def_readonly("counts", &PointPdf::counts)
@@ -1670,7 +1686,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("window"), py::arg("use_pdf"), py::arg("capacity"), py::arg("grid_from").none(true),
             py::arg("side") = -1, py::arg("fork") = false, py::arg("background") = false,
             py::arg("after").none(true) = py::none(), py::arg("max_neighbors") = 0, py::arg("sample_seed") = -1,
-            py::arg("point_pdf") = false, py::arg("point_from").none(true) = py::none(),
+            py::arg("point_pdf") = false, py::arg("point_from").none(true) = py::none(), py::arg("max_edges") = 0,
             py::call_guard<py::gil_scoped_release>());
     mod.def("sampled_features", &sampled_features, py::call_guard<py::gil_scoped_release>());
     mod.def("begin_geometry_batch", &begin_geometry_batch);

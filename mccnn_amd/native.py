@@ -136,6 +136,11 @@ class _NeighborCap(C.Structure):
     _fields_ = [("max_neighbors", C.c_int), ("sampled", C.c_int), ("seed", C.c_uint)]
 
 
+class _NeighborBudget(C.Structure):
+    """mccnn_neighbor_budget (include/mccnn.h)"""
+    _fields_ = [("max_edges", C.c_int)]
+
+
 class _PointPdf(C.Structure):
     """mccnn_point_pdf (include/mccnn.h)"""
     _fields_ = [("density", C.c_void_p), ("counts", C.c_void_p), ("ready", C.c_int)]
@@ -159,6 +164,7 @@ class Geometry:
         self.gkey = None
         self.args = None
         self.cap = (0, None)    # (maxNeighbors, sampleSeed) of the search
+        self.budget = 0         # maxEdges of the search (0: none): the search picks the cap itself, chosen_cap()
         self.point = False      # the PDFs are expanded from the per-point density of (grid, window): pdfMode='point'
         self.window = None
         # a grid owner: window -> (density [n,1] f32, counts [n,1] i32, handle of the extension or None) of its sorted points --
@@ -200,9 +206,11 @@ class Geometry:
         inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF = self.args
         if self.cap[0] > 0:   # (a capped list never holds more)
             capacity = min(capacity, self.m * self.cap[0])
+        if self.budget > 0:   # (nor does a budgeted one hold more than max(B, m) rows)
+            capacity = min(capacity, max(self.budget, self.m))
         # (a per-point density does not depend on the list: the one that exists is expanded again, not computed again)
         _build_into(self, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity,
-                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1], pointPDF=self.point)
+                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1], pointPDF=self.point, maxEdges=self.budget)
         e = self.core.edges(-1) if self.core is not None else _lib.load().mccnn_geometry_edges(self.handle, -1)
         if e < 0 or e > self.e_cap:
             raise _lib.MCCNNError("geometry: rebuilt list still does not fit (%d > %d)" % (e, self.e_cap))
@@ -270,6 +278,23 @@ class Geometry:
         i = self._info()
         return self._view(self.buf, i[7], e * 4, torch.float32, (e, 1))
 
+    def chosen_cap(self):
+        """int32 [1] on the device: the cap the search ran with -- K*, the cap a budgeted search chose (a view of the
+        geometry's own word, written by the build; never read back here), or without a budget the caller's maxNeighbors.
+        Readable on the current stream."""
+        if self.budget <= 0:
+            return torch.full((1,), self.cap[0], dtype=torch.int32, device=self.buf.device)
+        # (no wait for the edge total: the selection runs before the fill pass, so a list that outgrows its buffer and is
+        # built again leaves the same K* in the word of either buffer, and the view keeps its buffer alive)
+        self._join()
+        if self.core is not None:
+            addr = int(self.core.cap_addr())
+        else:
+            addr = int(_lib.load().mccnn_geometry_cap(self.handle) or 0)
+        if not addr:
+            raise _lib.MCCNNError("geometry: no cap word (built without a budget)")
+        return self._view(self.buf, addr, 4, torch.int32, (1,))
+
     def point_density(self, window=None):
         """(density [n,1] f32, counts [n,1] i32) of the grid's sorted points at `window` (None: this geometry's own): the
         pair every point geometry over this grid and window shares -- the same tensors whichever of them is asked. Readable
@@ -284,9 +309,10 @@ class Geometry:
 
 
 def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity, grid_from,
-                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False):
+                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False, maxEdges=0):
     n, m = inPts.shape[0], centres.shape[0]
     g.cap = (int(maxNeighbors), None if sampleSeed is None else int(sampleSeed))   # (a rebuild repeats them: _rebuild)
+    g.budget = int(maxEdges)
     g.point, g.window = bool(pointPDF), float(window)
     pairs = (grid_from if grid_from is not None else g).pointPairs   # (the grid's owner keeps the densities)
     pair = pairs.get(g.window) if pointPDF else None
@@ -295,7 +321,7 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
         g.core = _EXT.build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, float(radius), bool(scaleInv), float(window),
                                      bool(usePDF), capacity, grid_from.core if grid_from is not None else None, side, fork,
                                      background, after, int(maxNeighbors), -1 if sampleSeed is None else int(sampleSeed),
-                                     bool(pointPDF), pair[2] if pair is not None else None)
+                                     bool(pointPDF), pair[2] if pair is not None else None, int(maxEdges))
         if pointPDF and pair is None:
             pp = g.core.point
             pairs[g.window] = (pp.density, pp.counts, pp)
@@ -308,7 +334,7 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     lib = _lib.load()
     dev = inPts.device
     with_grid = 0 if grid_from is not None else 1
-    nbytes = lib.mccnn_geometry_bytes_capped(n, m, B, nc, capacity, with_grid, int(maxNeighbors))
+    nbytes = lib.mccnn_geometry_bytes_budget(n, m, B, nc, capacity, with_grid, int(maxNeighbors), int(maxEdges))
     if nbytes == 0:
         raise _lib.MCCNNError("geometry: batch_size * num_cells^3 does not fit 32-bit keys")
     if g.handle is None:
@@ -330,10 +356,12 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
         if not ready:
             pair = (torch.empty((n, 1), dtype=torch.float32, device=dev), torch.empty((n, 1), dtype=torch.int32, device=dev), None)
         point = _PointPdf(pair[0].data_ptr(), pair[1].data_ptr(), 1 if ready else 0)
-    check(lib.mccnn_geometry_build_point(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B,
+    budget = _NeighborBudget(int(maxEdges))
+    check(lib.mccnn_geometry_build_budget(g.handle, ptr(inPts), ptr(inBids), n, ptr(centres), ptr(cbids), m, ptr(mn), ptr(mx), B,
                                          nc, float(radius), int(bool(scaleInv)), float(window), int(bool(usePDF)), capacity,
                                          grid_from.handle if grid_from is not None else None, g.buf.data_ptr(), nbytes,
-                                         g.slot.data_ptr(), stream_handle(), C.addressof(cap), C.addressof(point)), "geometry_build")
+                                         g.slot.data_ptr(), stream_handle(), C.addressof(cap), C.addressof(point), C.addressof(budget)),
+          "geometry_build")
     if pointPDF:
         pairs[g.window] = pair
 
@@ -356,7 +384,8 @@ def side_streams_available():
 
 
 def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, grid_from=None,
-                   side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False):
+                   side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False,
+                   maxEdges=0):
     """Enqueues grid + search + KDE of one convolution geometry; no host wait. nc: cells per axis
     (MCConvModule._num_cells). grid_from: a Geometry over the same points / radius whose grid is shared. side >= 0
     (torch extension only): the build runs on side stream `side` -- behind everything the current stream holds at the
@@ -370,18 +399,26 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     pointPDF (needs usePDF and no cap): the PDFs are the per-point density of (grid, window) expanded over the list --
     compute_pdf_points + expand_pdf of the op surface, the same bytes -- instead of the KDE of the list. The grid's owner keeps
     ONE (density, counts) pair per window (Geometry.point_density); the first build over a grid and window computes it
-    right behind the grid, every later one, whatever its centres and stream, only expands it."""
+    right behind the grid, every later one, whatever its centres and stream, only expands it.
+    maxEdges = B > 0 (with or without a cap of the caller's; not with pointPDF): the search picks, on the device, the largest
+    cap K* whose list has at most B rows (find_neighbors(maxEdges=), the same bytes) -- Geometry.chosen_cap() is the device
+    word it lands in. The list holds at most max(B, m) rows: the capacity is min(max(B, m), guess), and guesses of budgeted
+    shapes are kept apart from those of every other shape."""
     n, m = inPts.shape[0], centres.shape[0]
+    if isinstance(maxEdges, bool) or not isinstance(maxEdges, int) or not 0 <= maxEdges < 2 ** 31:
+        raise ValueError("build_geometry: maxEdges is an integer in [0, 2^31) (0 = no budget)")
     maxNeighbors = int(maxNeighbors)
-    if maxNeighbors < 0 or (sampleSeed is not None and (maxNeighbors == 0 or not 0 <= int(sampleSeed) < 2 ** 32)):
-        raise ValueError("build_geometry: maxNeighbors >= 0; sampleSeed needs a cap and lies in [0, 2^32)")
-    if pointPDF and (maxNeighbors > 0 or not usePDF):
-        raise ValueError("build_geometry: pointPDF needs usePDF and an uncapped list")
+    if maxNeighbors < 0 or (sampleSeed is not None and ((maxNeighbors == 0 and maxEdges == 0) or not 0 <= int(sampleSeed) < 2 ** 32)):
+        raise ValueError("build_geometry: maxNeighbors >= 0; sampleSeed needs a cap or a budget and lies in [0, 2^32)")
+    if pointPDF and (maxNeighbors > 0 or maxEdges > 0 or not usePDF):
+        raise ValueError("build_geometry: pointPDF needs usePDF and an uncapped list (no cap, no budget)")
     gkey = (inPts.device.index, n, m, float(radius), int(B), bool(scaleInv))
     if maxNeighbors > 0:
         # (capped totals never shrink the guess of an uncapped geometry of the shape, or the reverse: the cap is a seventh
         # element of the key, which _edge_guess / _remember_edges carry into the key of the edges-per-centre table)
         gkey = gkey + (maxNeighbors,)
+    if maxEdges > 0:   # (... and budgeted totals move the guesses of their own (cap, budget) alone)
+        gkey = gkey[:6] + ((maxNeighbors, maxEdges),)
     g = Geometry()
     g.gkey = gkey
     if grid_from is not None and grid_from.grid_owner is not None:
@@ -389,9 +426,11 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     capacity = _capacity_guess(gkey, m)
     if maxNeighbors > 0:
         capacity = max(1, min(m * maxNeighbors, capacity))
+    if maxEdges > 0:   # (at max(B, m) rows the list cannot overflow)
+        capacity = max(1, min(max(maxEdges, m), capacity))
     _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF,
                 capacity, grid_from, side if _EXT is not None else -1, fork, background,
-                after if _EXT is not None else None, maxNeighbors, sampleSeed, pointPDF)
+                after if _EXT is not None else None, maxNeighbors, sampleSeed, pointPDF, maxEdges)
     return g
 
 
