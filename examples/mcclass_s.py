@@ -26,10 +26,11 @@ class MCClassS(torch.nn.Module):
     whose sub-modules (the convolution builder and the dense helpers' variable store) register every variable under
     the reference's name, so `parameters()` / `state_dict()` / optimisers / DDP see the whole network."""
 
-    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None):
+    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k, numOutCat)
-        self.store = VariableStore(device)
+        # fused (extension): batch norm + ReLU + dropout of the dense glue as one library op (VariableStore.fused_)
+        self.store = VariableStore(device, fused=fused)
         self.ops = ops  # None = the HIP op surface; the parity tests pass the CPU checker's
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
@@ -83,10 +84,10 @@ class MCClassS(torch.nn.Module):
 class MCNormS(torch.nn.Module):
     """models/MCNormS.py create_network(): two same-level multi-feature convolutions (normal estimation)."""
 
-    def __init__(self, numInputFeatures, batchSize, k, device, ops=None):
+    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k)
-        self.store = VariableStore(device)
+        self.store = VariableStore(device, fused=fused)
         self.ops = ops
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
@@ -149,6 +150,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--points", type=int, default=1024)
+    ap.add_argument("--fused-glue", action="store_true",
+                    help="batch norm + ReLU + dropout of the dense layers as one library op (VariableStore(fused=True))")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
@@ -156,7 +159,7 @@ def main():
     # one process per GPU: run the backward pass on the calling thread -- the autograd engine's per-device worker thread
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
-    net = MCClassS(1, args.batch, 16, 4, device)
+    net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \
         (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
     P, Bi, F, y = make_batch()

@@ -810,6 +810,35 @@ int mccnn_batch_sample(const float* store_pts, const float* store_normals, int s
                        const mccnn_batch_slot* slots_host, int num_slots, int out_rows, float* out_pts,
                        int* out_batch_ids, int* out_src, int* counts, int* status, mccnn_stream_t stream);
 
+/* THE DENSE GLUE AS ONE OP (extension, ABI 18; bn_act.hip): y = drop(act(bn(x))) over an [n, c] float32 row-major
+ * contiguous tensor, n >= 1, c >= 1 -- what the reference's batch_norm_RELU_drop_out and the batch norms of its MLPs
+ * compute (utils/MCNetworkUtils.py:20-144).
+ *   training: mean_c = (1/n) sum_i x[i,c], var_c = (1/n) sum_i (x[i,c] - mean_c)^2 (biased, for the normalisation AND the
+ *             moving average), rstd_c = 1 / sqrt(var_c + eps); moving = moving * momentum + stat * (1 - momentum), in
+ *             place. eval (training == 0): mean, var = the moving statistics, nothing is updated, no dropout.
+ *   xhat = (x - mean) * rstd; pre = xhat * gamma + beta; act = relu ? max(pre, 0) : pre; backward gate: pre > 0.
+ *   dropout (training): element (i, j) is kept iff (uint64) h < keep_threshold, h = mix(row_hash(seed, i) + (uint32) j)
+ *             (csrc/bn_drop.h), keep_threshold = floor(keepProb * 2^32) computed by the caller in double; 2^32 = no
+ *             dropout. Kept values are multiplied by keep_scale (1.0f / (float) keepProb). No stored mask: the backward
+ *             recomputes it from (seed, i, j).
+ *   backward (training form): g = dy * mask * keep_scale * gate, dbeta = sum_i g, dgamma = sum_i g * xhat,
+ *             dx = gamma * rstd * (g - dbeta / n - xhat * dgamma / n); dx == NULL: not wanted (same dgamma, dbeta bytes).
+ * saved = [mean; rstd], [2, c], written by the training forward and read by the backward. Launches: n <= 256 one forward,
+ * one backward; otherwise two and two; eval one. No atomics, no memset, a fixed merge order: the same inputs and seed
+ * give the same bytes. ws of mccnn_bn_act_workspace_bytes(n, c) bytes (0 for n <= 256 and for eval; ws may then be NULL).
+ * n < 1, c < 1, keep_threshold == 0 or > 2^32, a NULL required pointer: MCCNN_E_BADARG; a missing or short workspace:
+ * MCCNN_E_WORKSPACE; both before anything is launched. */
+size_t mccnn_bn_act_workspace_bytes(int n, int c);
+int mccnn_bn_act_fwd(const float* x, int n, int c, const float* gamma, const float* beta,
+                     float* moving_mean, float* moving_var, float momentum, float eps,
+                     int training, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                     float* y, float* saved /* [2,c]; may be NULL when !training */,
+                     void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float* gamma, const float* beta,
+                     const float* saved, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                     float* dx /* NULL: not wanted */, float* dgamma, float* dbeta,
+                     void* ws, size_t ws_bytes, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

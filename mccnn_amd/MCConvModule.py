@@ -1648,3 +1648,87 @@ def spatial_conv(inPts, inFeatures, inBatchIds, inPDFs, inSamplePts, neighStartI
     return _SpatialConv.apply(inPts, inFeatures, inBatchIds, inPDFs, inSamplePts, neighStartIndexs, packedNeighs,
                               aabbMin, aabbMax, weights1, biases1, weights2, biases2, weightsOut, biasesOut,
                               numOutFeatures, combin, batchSize, radius, scaleInv, avg, sortIndex, _trusted, featIndex)
+
+
+# ---------------------------------------------------------------------------------------------
+# The dense glue between two convolutions as one op (extension; csrc/bn_act.hip, include/mccnn.h "THE DENSE GLUE AS ONE
+# OP"): y = drop(act(bn(x))) with the moving statistics updated in place. The dropout mask is counter-based
+# (csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream.
+BN_DROP_ALL = 1 << 32   # keep threshold of "no dropout"
+
+
+def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed):
+    """Checks of bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale)."""
+    _req(keepProb is None or (isinstance(keepProb, (int, float)) and not isinstance(keepProb, bool) and 0.0 < keepProb <= 1.0),
+         "bn_relu_dropout expects keepProb in (0, 1] (or None)")
+    _req(isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < (1 << 32),
+         "bn_relu_dropout expects a seed in [0, 2^32)")
+    for t, name in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32, "bn_relu_dropout: %s must be a float32 tensor" % name)
+        _req(t.is_contiguous(), "bn_relu_dropout: %s must be contiguous" % name)
+    _req(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "bn_relu_dropout expects x with dimensions (n, c), n, c >= 1")
+    _req(x.shape[0] * x.shape[1] < (1 << 62) and max(x.shape) < (1 << 31), "bn_relu_dropout: x too large")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(t.dim() == 1 and t.shape[0] == x.shape[1], "bn_relu_dropout: %s must have shape (c,)" % name)
+        _req(t.device == x.device, "bn_relu_dropout: %s is on another device than x" % name)
+    _req(x.is_cuda, "bn_relu_dropout: x must be a CUDA tensor")
+    if keepProb is None:
+        return BN_DROP_ALL, 1.0
+    kp = float(keepProb)
+    thr = int(kp * 4294967296.0)   # floor(keepProb * 2^32) in double
+    _req(thr >= 1, "bn_relu_dropout: keepProb keeps nothing")
+    return thr, float(_np.float32(1.0) / _np.float32(kp))   # 1.0f / (float) keepProb
+
+
+class _BnReluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon):
+        lib = _lib.load()
+        n, c = x.shape
+        y = torch.empty_like(x)
+        saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+        xd, gd, bd = x.detach(), gamma.detach(), beta.detach()
+        check(lib.mccnn_bn_act_fwd(ptr(xd), n, c, ptr(gd), ptr(bd), ptr(movingMean), ptr(movingVar), momentum, epsilon, 1,
+                                   int(relu), thr, scale, seed, ptr(y), ptr(saved), ptr(ws), ws.numel(), stream_handle()),
+              "bn_relu_dropout")
+        ctx.save_for_backward(xd, gd, bd, saved)
+        ctx.attrs = (int(relu), thr, scale, seed)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gamma, beta, saved = ctx.saved_tensors
+        relu, thr, scale, seed = ctx.attrs
+        lib = _lib.load()
+        n, c = x.shape
+        gy = gy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+        check(lib.mccnn_bn_act_bwd(ptr(x), ptr(gy), n, c, ptr(gamma), ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx),
+                                   ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_grad")
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None, None)
+
+
+def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
+                    epsilon=1e-3):
+    """y = drop(act(bn(x))) over an [n, c] float32 contiguous tensor in one library op; differentiable (once) with respect
+    to x, gamma and beta. training: batch statistics (biased variance), movingMean / movingVar updated in place as
+    moving * momentum + stat * (1 - momentum), dropout with keep probability keepProb (None: none) from the counter-based
+    mask of `seed`. Eval: the moving statistics, no dropout, and no gradients -- an input that requires one raises."""
+    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed)
+    if training:
+        return _BnReluDropout.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
+                                    float(epsilon))
+    _req(not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
+         "bn_relu_dropout: the eval form has no gradients")
+    lib = _lib.load()
+    n, c = x.shape
+    y = torch.empty_like(x)
+    check(lib.mccnn_bn_act_fwd(ptr(x), n, c, ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar), float(momentum),
+                               float(epsilon), 0, int(bool(relu)), BN_DROP_ALL, 1.0, seed, ptr(y), None, None, 0,
+                               stream_handle()), "bn_relu_dropout")
+    return y

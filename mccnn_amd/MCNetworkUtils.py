@@ -7,6 +7,11 @@ tf.layers.batch_normalization's defaults (momentum 0.99, epsilon 1e-3, gamma/bet
 cloud-per-GPU while the reference normalises over the WHOLE batch (utils/MCNetworkUtils.py:140) -- synchronises its
 statistics across ranks with one small all-reduce when torch.distributed is initialised (point counts differ per rank,
 so sums and counts are reduced, not means).
+
+VariableStore(fused=True) (extension, opt-in): batch norm + ReLU + dropout of a block run as ONE library op
+(MCConvModule.bn_relu_dropout, csrc/bn_act.hip) where its conditions hold (_fused_glue); everywhere else, and always
+with fused off, the code below is what runs. Names, shapes, initialisers and state_dict are the same either way; the
+dropout mask of the fused op is counter-based (seed dropSeed_ + dropCalls_), not torch's random stream.
 """
 import math
 
@@ -20,10 +25,13 @@ class VariableStore(torch.nn.Module):
     names (`Reduce_1_weights`, `Final_Logits_BN_h1/gamma`, ...). Variables are created on first use (tf.get_variable),
     so load_state_dict() also accepts names that do not exist yet."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, fused=False):
         super().__init__()
         self.device = device
         self.collections_ = {}
+        self.fused_ = bool(fused)   # the dense glue as one library op where it applies (may be reassigned at any time)
+        self.dropSeed_ = 0          # a fused call that drops uses the seed (dropSeed_ + dropCalls_) mod 2^32 ...
+        self.dropCalls_ = 0         # ... and increments this counter
 
     @property
     def variables_(self):
@@ -153,6 +161,77 @@ def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsil
     return (inputs - mean) * torch.rsqrt(var + epsilon) * gamma + beta
 
 
+_FUSED_OP = False   # native.bn_relu_drop once the library has loaded; None when it does not
+
+
+def _fused_op():
+    global _FUSED_OP
+    if _FUSED_OP is False:
+        try:
+            from . import _lib, native
+            _lib.load()
+            _FUSED_OP = native.bn_relu_drop
+        except (ImportError, OSError, AttributeError, RuntimeError):
+            _FUSED_OP = None
+    return _FUSED_OP
+
+
+def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True):
+    """drop(act(batch_normalization(inputs))) as one library op, or None where the fused form does not apply (the caller
+    then runs the torch code): the store's switch is off, the input is not a contiguous float32 [n, c] tensor on a HIP
+    device, the library does not load, training statistics are synchronised across ranks, or an eval call wants
+    gradients. keepProb: the keep probability of a dropout that applies (None: none)."""
+    if not getattr(st, "fused_", False):
+        return None
+    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
+            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+        return None
+    if training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return None
+    if keepProb is not None and not 0.0 < keepProb <= 1.0:
+        return None
+    op = _fused_op()
+    if op is None:
+        return None
+    c = inputs.shape[1]
+    dev = inputs.device
+    gamma = st.get_variable(name + "/gamma", (c,), _ones, dev)
+    beta = st.get_variable(name + "/beta", (c,), _zeros, dev)
+    mov_mean = st.get_buffer(name + "/moving_mean", (c,), 0.0, dev)
+    mov_var = st.get_buffer(name + "/moving_variance", (c,), 1.0, dev)
+    if not training and torch.is_grad_enabled() and (inputs.requires_grad or gamma.requires_grad or beta.requires_grad):
+        return None
+    if not all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+               for t in (gamma, beta, mov_mean, mov_var)):
+        return None
+    seed = 0
+    if training and keepProb is not None:
+        seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
+        st.dropCalls_ += 1
+    else:
+        keepProb = None
+    return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon)
+
+
+def _keep_prob(useDropOut, keepProb):
+    """The keep probability of a block's dropout as a float, None when the block has none."""
+    if not useDropOut or keepProb is None or keepProb is False:
+        return None
+    return float(keepProb)
+
+
+def _bn_relu_drop(st, inputs, training, name, useDropOut, keepProb):
+    """relu(batch_normalization(inputs)) [+ dropout]: the fused op where it applies, the torch code otherwise."""
+    if getattr(st, "fused_", False):
+        y = _fused_glue(st, inputs, training, name, True, _keep_prob(useDropOut, keepProb))
+        if y is not None:
+            return y
+    y = torch.relu(batch_normalization(inputs, training, name, st))
+    if useDropOut:
+        y = _dropout(y, keepProb, training)
+    return y
+
+
 def _dropout(x, keepProb, training=True):
     if keepProb is None or keepProb is False:
         return x
@@ -165,21 +244,18 @@ def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOu
     st = store or _DEFAULT_STORE
     dev = features.device
     if useInitBN:
-        features = batch_normalization(features, isTraining, layerName + "_BN_Init", st)
+        y = _fused_glue(st, features, isTraining, layerName + "_BN_Init", False)
+        features = y if y is not None else batch_normalization(features, isTraining, layerName + "_BN_Init", st)
     w = st.get_variable(layerName + '_weights1', (numInputFeatures, hidden1_units),
                         _fan_avg_uniform(numInputFeatures, hidden1_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases1', (hidden1_units,), _zeros, dev)
-    hidden1 = torch.relu(batch_normalization(features @ w + b, isTraining, layerName + "_BN_h1", st))
-    if useDropOut:
-        hidden1 = _dropout(hidden1, keepProb, isTraining)
+    hidden1 = _bn_relu_drop(st, features @ w + b, isTraining, layerName + "_BN_h1", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights2', (hidden1_units, hidden2_units),
                         _glorot_uniform(hidden1_units, hidden2_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases2', (hidden2_units,), _zeros, dev)
-    hidden2 = torch.relu(batch_normalization(hidden1 @ w + b, isTraining, layerName + "_BN_h2", st))
-    if useDropOut:
-        hidden2 = _dropout(hidden2, keepProb, isTraining)
+    hidden2 = _bn_relu_drop(st, hidden1 @ w + b, isTraining, layerName + "_BN_h2", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights3', (hidden2_units, numOutFeatures),
                         _fan_avg_uniform(hidden2_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
@@ -196,9 +272,7 @@ def MLP_1_hidden(features, numInputFeatures, hidden_units, numOutFeatures, layer
                         _fan_avg_uniform(numInputFeatures, hidden_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases1', (hidden_units,), _zeros, dev)
-    hidden = torch.relu(batch_normalization(features @ w + b, isTraining, layerName + "_BN_h", st))
-    if useDropOut:
-        hidden = _dropout(hidden, keepProb, isTraining)
+    hidden = _bn_relu_drop(st, features @ w + b, isTraining, layerName + "_BN_h", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights2', (hidden_units, numOutFeatures),
                         _fan_avg_uniform(hidden_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
@@ -219,7 +293,4 @@ def conv_1x1(layerName, inputs, numInputs, numOutFeatures, store=None):
 def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, keepProb, store=None):
     """utils/MCNetworkUtils.py:129-144."""
     st = store or _DEFAULT_STORE
-    x = torch.relu(batch_normalization(inFeatures, isTraining, layerName + "_BN", st))
-    if usedDropOut:
-        x = _dropout(x, keepProb, isTraining)
-    return x
+    return _bn_relu_drop(st, inFeatures, isTraining, layerName + "_BN", usedDropOut, keepProb)

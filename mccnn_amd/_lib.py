@@ -131,6 +131,10 @@ SIGNATURES = {
     "mccnn_batch_sample_chunk": (_i, []),
     "mccnn_batch_max_passes": (_i, []),
     "mccnn_batch_sample": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the dense glue as one op (bn_act.hip)
+    "mccnn_bn_act_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_bn_act_fwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_bn_act_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -1342,6 +1342,91 @@ Tensor sampled_features(const Tensor& idx, const Tensor& feats) {
     return out;
 }
 
+// ---- the dense glue as one op (mccnn_bn_act_fwd / _bwd): y = drop(act(bn(x))), the C++ form of
+// MCConvModule.bn_relu_dropout -- the same library calls with the same arguments, so the same bytes; the autograd node is
+// here, so a block costs the host one Python -> C++ call forward and none backward.
+struct BnActBackward : public torch::autograd::Node {
+    Tensor x_, gamma_, beta_, saved;
+    uint32_t versions[3] = {0, 0, 0};
+    int relu = 1;
+    unsigned long long thr = 0;
+    float scale = 1.f;
+    unsigned seed = 0;
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        TORCH_CHECK(x_.defined() && saved.defined(), "bn_relu_drop: backward through a graph whose buffers have been freed (retain_graph=True?)");
+        Tensor gy = grads[0];
+        TORCH_CHECK(!(at::GradMode::is_enabled() && gy.defined() && gy.requires_grad()),
+                    "bn_relu_drop is differentiable once: no double backward");
+        {
+            const Tensor* in[3] = {&x_, &gamma_, &beta_};
+            for (int k = 0; k < 3; ++k)
+                TORCH_CHECK(in[k]->_version() == versions[k],
+                            "one of the variables needed for gradient computation has been modified by an inplace operation "
+                            "(bn_relu_drop input ", k, ")");
+        }
+        const DevGuard device_guard((int)x_.device().index());
+        const int n = (int)x_.size(0), c = (int)x_.size(1);
+        if (!gy.defined()) gy = at::zeros_like(x_);
+        if (!gy.is_contiguous()) gy = gy.contiguous();
+        const bool want_dx = task_should_compute_output(0);
+        Tensor dx;
+        if (want_dx) dx = at::empty_like(x_);
+        Tensor dgb = at::empty({2, (int64_t)c}, x_.options());
+        void* st = cur_stream(x_);
+        Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(n, c), x_, st);
+        check(mccnn_bn_act_bwd(x_.data_ptr<float>(), gy.data_ptr<float>(), n, c, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
+                               saved.data_ptr<float>(), relu, thr, scale, seed, want_dx ? dx.data_ptr<float>() : nullptr,
+                               dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
+              "bn_relu_dropout_grad");
+        torch::autograd::variable_list out(3);
+        out[0] = dx;
+        if (task_should_compute_output(1)) out[1] = dgb.select(0, 0);
+        if (task_should_compute_output(2)) out[2] = dgb.select(0, 1);
+        return out;
+    }
+    void release_variables() override { x_.reset(); gamma_.reset(); beta_.reset(); saved.reset(); }
+};
+
+Tensor bn_relu_drop(const Tensor& x, const Tensor& gamma, const Tensor& beta, const Tensor& mov_mean, const Tensor& mov_var,
+                    bool training, bool relu, unsigned long long thr, double scale, unsigned seed, double momentum, double eps) {
+    check_dev(x, at::kFloat, "x");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31),
+                "bn_relu_drop expects x with dimensions (n, c), n, c >= 1");
+    for (const Tensor* t : {&gamma, &beta, &mov_mean, &mov_var}) {
+        check_dev(*t, at::kFloat, "per-column tensor");
+        TORCH_CHECK(t->dim() == 1 && t->size(0) == x.size(1) && t->device() == x.device(), "bn_relu_drop: per-column tensors must have shape (c,)");
+    }
+    const DevGuard device_guard((int)x.device().index());
+    const int n = (int)x.size(0), c = (int)x.size(1);
+    const bool need_grad = at::GradMode::is_enabled() && (x.requires_grad() || gamma.requires_grad() || beta.requires_grad());
+    TORCH_CHECK(training || !need_grad, "bn_relu_drop: the eval form has no gradients");
+    Tensor y, saved;
+    {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        y = at::empty_like(x);
+        if (training) saved = at::empty({2, (int64_t)c}, x.options());
+        void* st = cur_stream(x);
+        const size_t wsb = training ? mccnn_bn_act_workspace_bytes(n, c) : 0;
+        Tensor& ws = scratch(wsb, x, st);
+        check(mccnn_bn_act_fwd(x.data_ptr<float>(), n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
+                               mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
+                               training ? thr : 0x100000000ull, training ? (float)scale : 1.f, seed, y.data_ptr<float>(),
+                               training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+              "bn_relu_dropout");
+    }
+    if (need_grad) {
+        auto node = std::shared_ptr<BnActBackward>(new BnActBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(x, gamma, beta));
+        node->x_ = x; node->gamma_ = gamma; node->beta_ = beta;
+        node->versions[0] = x._version(); node->versions[1] = gamma._version(); node->versions[2] = beta._version();
+        node->saved = saved;
+        node->relu = relu ? 1 : 0; node->thr = thr; node->scale = (float)scale; node->seed = seed;
+        torch::autograd::set_history(y, node);
+    }
+    return y;
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -1696,6 +1781,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("conv", &conv, py::arg("geometry"), py::arg("feats"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
             py::arg("w3"), py::arg("b3"), py::arg("fout"), py::arg("combin"), py::arg("avg"), py::arg("deterministic") = false,
             py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_relu_drop", &bn_relu_drop, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
+            py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
+            py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")
