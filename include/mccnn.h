@@ -705,6 +705,25 @@ int mccnn_geometry_build_batch_budget(const mccnn_geometry_request* requests, co
                                       const mccnn_point_pdf* points, const mccnn_neighbor_budget* budgets, int count,
                                       mccnn_stream_t stream);
 const int* mccnn_geometry_cap(const mccnn_geometry_t* g);
+/* PER-EDGE RECORDS FROM THE KDE (extension, ABI 19). The convolution kernels read one 16-byte record per edge, (delta =
+ * (p_j - c_i) / R, 1 / (pdf K)) -- mccnn_edge_records. The KDE of a geometry's build has every input of it at hand (the row's
+ * centre is uniform over a wave there, K is the row length, the PDF is produced on the spot), so a build that was ASKED for
+ * records leaves them beside the PDFs: the same bytes as mccnn_edge_records over the finished list, for the price of one more
+ * pass per row inside the KDE kernel instead of a kernel of gathers and divisions per layer.
+ * mccnn_geometry_want_records(g, avg): call on the handle BEFORE its build (single or batch); avg = the `avg` flag of the
+ *   layers that will read the records (0 / 1), -1 takes the request back. The records live BEHIND the geometry's own pieces in
+ *   the build's buffer: hand the build mccnn_geometry_bytes*(...) + mccnn_geometry_records_bytes(e_capacity) bytes. A buffer
+ *   without that room, use_pdf = 0, a per-point density or MCCNN_DEBUG=kde_records=0 leave the request without effect: the
+ *   geometry is built as without it and the layers evaluate their records themselves.
+ * mccnn_geometry_records: the `avg` the geometry's records hold (0 / 1) and their device address (e_capacity records, E
+ *   valid), or -1 and NULL when it has none. Records a row plan's build evaluated into an attached buffer are reported too.
+ * mccnn_conv_uses_records: 1 when a layer of this shape and `avg` can read the geometry's records -- a combin layer with one
+ *   input feature on the factored kernels, records of that `avg` present. Such a layer passes flags bit 2 to
+ *   mccnn_conv_prepare / _forward / _backward. */
+size_t mccnn_geometry_records_bytes(int e_capacity);
+int mccnn_geometry_want_records(mccnn_geometry_t* g, int avg);
+int mccnn_geometry_records(const mccnn_geometry_t* g, const void** records);
+int mccnn_conv_uses_records(const mccnn_geometry_t* g, int num_in_feats, int num_out_feats, int combin, int avg);
 /* E, or -1 while the count pass has not retired (wait_us: 0 = look once, < 0 = wait, > 0 = wait at most that long). */
 int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
 /* out[0..7]: device addresses of sortPts [n,3], sortBatchs [n], cellIndexs [B,nc,nc,nc,2], index_new_pos [n], its
@@ -739,7 +758,11 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
  * (MCConvModuleSrc:35-45,70-81). feats [n, num_in_feats] and feat_grad are rows of the UNSORTED points (f32, or bf16
  * with bf16 != 0: depth-wise layers, num_in_feats % 8 == 0); out [m, combin ? num_out_feats : num_in_feats].
  * flags: bit 0 = keep the forward state for the backward pass, bit 1 = deterministic feature gradient of combin layers
- * with 2..4 input features (gathered through the transposed list instead of float atomics).
+ * with 2..4 input features (gathered through the transposed list instead of float atomics), bit 2 = the layer reads the
+ * geometry's per-edge records (only where mccnn_conv_uses_records says 1, and in all three calls of the layer alike): the
+ * forward pass neither evaluates nor stores records, `saved` holds the sorted rows and the per-centre sums alone (16 bytes per
+ * edge less), and the backward pass reads the same records (or evaluates them afresh, should a row plan of the other `avg`
+ * have replaced them in between).
  * prepare (forward or backward): waits for E, then reports need_mask / need_bytes[k] (pieces to attach first, bit k),
  * the scratch bytes of the call and -- forward -- the bytes of `saved`, which the caller keeps from forward to
  * backward (sorted feature rows + forward state). The kernel family is chosen as the Python op surface chooses it

@@ -422,6 +422,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         self.geoPrefetch_ = _env.flag("GEO_PREFETCH")
         self.geoSeen_ = {}
         self.geoPlan_ = []
+        # lists whose layers read per-edge records (one-input-feature combin layers): (hierarchy name, levels, radius, window,
+        # radius mode, usePDF) -> the layers' useAVG. Learned from the layers as they run, kept across reset(): a geometry built
+        # for such a list -- inline, by prefetch_geometry() or by prefetch_step() -- asks its KDE for the records
+        # (native.build_geometry(recordsAvg=)), so that the layer neither evaluates nor keeps its own
+        self.recSeen_ = {}
         self.prefetchedGeo_ = {}    # prefetch_geometry() on the native path: keyPDF [+ '|pt'] -> (Geometry, keyGrid, keyNeighs, usePDF, transposed, point, KDEWindow, keyPDF)
         self.multiFeatureConvs_ = multiFeatureConvs
         self.KDEWindow_ = KDEWindow
@@ -924,6 +929,11 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             yield (ent,) + keys + (self.__native_search_args__(cap, seed, keys[1], budget), len(ent) > 10 and ent[10] == 'point',
                                    budget)
 
+    @staticmethod
+    def __rec_key__(inPH, inLevel, outPH, outLevel, convRadius, KDEWindow, relativeRadius, usePDF):
+        return (inPH.hierarchyName_, outPH.hierarchyName_, inLevel, outLevel, float(convRadius), None if KDEWindow is None else float(KDEWindow),
+                bool(relativeRadius), bool(usePDF))
+
     def __prefetch_native__(self, inPH, inLevel, convRadius, outPH, outLevel, KDEWindow, relativeRadius, usePDF, keyGrid,
                             keyNeighs, keyPDF, transposed, fork=True, pieces=0, currCap=0, currSeed=None, point=False, currBudget=0):
         """prefetch_geometry() on the native step executor: the geometry is ONE buffer, allocated on the CALLER's stream and
@@ -955,6 +965,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                      usePDF, owner, side=k, fork=fork, background=True,
                                      after=(inPH.prefetchFuture_ if inPH is outPH else None), pointPDF=point,
+                                     recordsAvg=self.recSeen_.get(self.__rec_key__(inPH, inLevel, outPH, outLevel, convRadius,
+                                                                                   KDEWindow, relativeRadius, usePDF)),
                                      **self.__native_search_args__(currCap, currSeed, keyNeighs, currBudget))
         if owner is None:
             owners[keyGrid] = geo
@@ -1036,7 +1048,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             nc = _hip_ops._num_cells(mn, mx, B, radius, rel)
             owner = self.cacheGeoGrid_.get(keyGrid)
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, radius, rel, window, usePDF, owner,
-                                         side=k, fork=(k == 0), after=ph.prefetchFuture_, pointPDF=point, **capArgs)
+                                         side=k, fork=(k == 0), after=ph.prefetchFuture_, pointPDF=point,
+                                         recordsAvg=self.recSeen_.get(self.__rec_key__(ph, inLevel, ph, outLevel, radius, window, rel,
+                                                                                       usePDF)), **capArgs)
             k += 1
             if have and pieces and geo.e_cap <= _PLAN_PREFETCH_MAX_E:
                 geo.prebuild_async(have, self.useAVG_)
@@ -1056,6 +1070,9 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
         keyGeo = keyPDF + '|pt' if point else keyPDF
         _native = _native_mod()
         _hip_ops = _hip_ops_mod()
+        if inNumFeatures == 1 and multiFeatureConv and usePDF and not point:
+            # this layer reads per-edge records: the geometries of this list are asked for them from here on
+            self.recSeen_[self.__rec_key__(inPH, inLevel, outPH, outLevel, convRadius, KDEWindow, relativeRadius, usePDF)] = bool(useAVG)
         # (a step with a handful of geometries gains nothing: the hops between the streams cost what the overlap saves --
         # measured: BASELINE cfg1, three lists, 0.93 -> 0.97 ms; cfg2, seven, 2.59 -> 2.18)
         if (not self.cacheGeo_ and self.geoPrefetch_ and len(self.geoPlan_) >= _GEO_PREFETCH_MIN and inPH is outPH and self.prefetched_ is None
@@ -1104,6 +1121,8 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
                     owner = None
             geo = _native.build_geometry(inPts, inBids, centres, cBids, mn, mx, B, nc, convRadius, relativeRadius, KDEWindow,
                                          usePDF, owner, pointPDF=point,
+                                         recordsAvg=self.recSeen_.get(self.__rec_key__(inPH, inLevel, outPH, outLevel, convRadius,
+                                                                                       KDEWindow, relativeRadius, usePDF)),
                                          **self.__native_search_args__(currCap, currSeed, keyNeighs, currBudget))
             if owner is not None:   # (a shared grid: the layer sorts its rows only, as on a cache hit)
                 self._trace("sort_features", keyGrid)

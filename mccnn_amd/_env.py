@@ -27,6 +27,7 @@ MCCNN_DEBUG that is not in it is reported once on stderr instead of being silent
     geo_trace (0)                 1 = a stderr line wherever the native path hands a convolution to the op-by-op one
     rows_min_degree (16)          (shared with the library, csrc/debug_opts.h)
     unsorted_max_points (32768)   (shared with the library, csrc/debug_opts.h)
+    kde_records (1)               0 = no geometry is asked for per-edge records (shared with the library, csrc/debug_opts.h)
 
 (MCCNN_LIB_NAME / MCCNN_EXTRA_FLAGS belong to mccnn_amd.build: A/B builds of the library.)"""
 import os
@@ -38,7 +39,7 @@ KNOWN_KEYS = (
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",
     "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",
     "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks",
-    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force",
+    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force", "kde_records",
     # Python side
     "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",
     "ecap_scale", "hier_pmode", "geo_trace")

@@ -118,6 +118,10 @@ SIGNATURES = {
     "mccnn_geometry_build_budget": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _i, _f, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mccnn_geometry_build_batch_budget": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "mccnn_geometry_cap": (_vp, [_vp]),
+    "mccnn_geometry_records_bytes": (_sz, [_i]),
+    "mccnn_geometry_want_records": (_i, [_vp, _i]),
+    "mccnn_geometry_records": (_i, [_vp, _vp]),
+    "mccnn_conv_uses_records": (_i, [_vp, _i, _i, _i, _i]),
     "mccnn_geometry_edges": (_i, [_vp, _i]),
     "mccnn_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "mccnn_geometry_attach": (_i, [_vp, _i, _vp, _sz]),

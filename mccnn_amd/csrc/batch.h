@@ -42,8 +42,12 @@ struct PdfItem {
     const int* eDev;
     int m, e, B, scaleInv, rowsPerWave;
     float window, radius;
+    // the per-edge records of the convolution kernels, written beside the PDFs (rec == nullptr: PDFs alone): the centres the
+    // rows belong to, the records in edge order, and whether their weight carries the row length (the layers' `avg`)
+    const float* centres; float4* rec; int avg;
 };
 struct PdfBatch { PdfItem it[MCCNN_BATCH_MAX]; };
+static_assert(sizeof(PdfBatch) + sizeof(BatchBlocks) < 4096, "the kernel arguments of a batched KDE: < 4 KB");
 // one per-point density sweep (pdf_points.hip): the sorted points of a grid, its cell table and boxes -> density, counts
 struct PointPdfItem {
     const float* pts; const int* bids; const int* cells; const float* mn; const float* mx; float* density; int* counts;
@@ -162,7 +166,8 @@ int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const Neigh
 int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s);   // 0 count, 1 fill
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,
-                    float radius, int scale_inv, float* pdfs);
+                    float radius, int scale_inv, float* pdfs, const float* centres = nullptr, void* rec = nullptr, int avg = 0);
+int launch_pdf(const PdfItem& it, hipStream_t s);   // one list: 4 or 16 waves per workgroup by its row count
 int launch_pdf_batch(const PdfBatch& pb, int count, hipStream_t s);
 // pdf_points.hip: the per-point density and its expansion as items (single launches take the same records)
 int point_pdf_item(PointPdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, int n, const int* cell_indexs,

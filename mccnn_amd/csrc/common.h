@@ -200,6 +200,26 @@ __device__ __forceinline__ int xcd_contiguous(int b, int n) {
 // every kernel clamps a batch id before it indexes a per-cloud table (mccnn_check_batch_ids reports invalid ids)
 __device__ __forceinline__ int clamp_batch(int b, int B) { return max(0, min(b, B - 1)); }
 
+// Correctly rounded x / R from y = RN(1 / R) in three instructions (Markstein): q = RN(x y) is within one ulp,
+// r = x - q R is exact in an fma, RN(q + r y) is the correctly rounded quotient. The reference divides
+// (spatial_conv.cu:155-158); the quotient feeds layer 1 of the kernel MLP, whose pre-activations have to be
+// bit-identical (conv_mfma.h). Spelled with fma builtins: the library is compiled with -ffp-contract=off.
+__device__ __forceinline__ float div_exact(float x, float R, float invR) {
+    const float q = x * invR;
+    const float r = __builtin_fmaf(-q, R, x);
+    return __builtin_fmaf(r, invR, q);
+}
+
+// The per-edge record of the convolution kernels from its inputs: (delta0, delta1, delta2, 1 / (pdf K)) -- delta =
+// (point - centre) / R correctly rounded (spatial_conv.cu:155-158), invR = RN(1 / R), K = the centre's neighbour count when
+// the layer averages, else 1 (spatial_conv.cu:160-166). ONE spelling for every kernel that produces records (the
+// convolutions' own record kernels, the KDE that leaves them with the PDFs): the same bits wherever a record comes from.
+__device__ __forceinline__ float4 edge_record_of(float px, float py, float pz, float cx, float cy, float cz, float R, float invR,
+                                                 float pdf, float K) {
+    return make_float4(div_exact(px - cx, R, invR), div_exact(py - cy, R, invR), div_exact(pz - cz, R, invR),
+                       __builtin_amdgcn_rcpf(pdf * K));
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // wave64 inclusive scan (int)

@@ -1280,7 +1280,8 @@ static int conv_fwd_impl(const float* sorted_pts, const float* sorted_feats, con
                          const float* w2, const float* b2, const float* w3, const float* b3, int n, int m, int e,
                          int num_in_feats, int num_out_feats, int combin, int batch_size, float radius,
                          int scale_inv, int avg, float* out, void* state, void* ws, size_t ws_bytes,
-                         mccnn_stream_t stream, int bf16) {
+                         mccnn_stream_t stream, int bf16, const float4* rec_in = nullptr) {
+    // (rec_in: Fin = 1 combin layers only -- conv_fwd_rec; `state` then is (A, S) alone, without the record region)
     ConvArgs a;
     int rc = fill_args(a, sorted_pts, sorted_feats, sorted_batch_ids, pdfs, samples, start_idx, packed, aabb_min,
                        aabb_max, w1, b1, w2, b2, w3, b3, n, m, e, num_in_feats, num_out_feats, combin, batch_size,
@@ -1291,9 +1292,10 @@ static int conv_fwd_impl(const float* sorted_pts, const float* sorted_feats, con
     hipStream_t s = (hipStream_t)stream;
     bool vec = !combin && (a.Fin % 8 == 0) && ((((uintptr_t)sorted_feats) & 15) == 0);
     if (bf16 && !bf16_shape_ok(a, combin, sorted_feats, out)) return MCCNN_E_SHAPE;
-    float4* recOut = state ? reinterpret_cast<float4*>(state) : nullptr;
+    float4* recOut = (state && !rec_in) ? reinterpret_cast<float4*>(state) : nullptr;
     if (e > 0 && f1_shape(num_in_feats, num_out_feats, combin))
-        return f1_forward(a, out, recOut, state ? (char*)state + state_record_bytes(e) : nullptr, ws, ws_bytes, s);
+        return f1_forward(a, out, recOut, rec_in, state ? (char*)state + (rec_in ? 0 : state_record_bytes(e)) : nullptr, ws, ws_bytes, s);
+    if (rec_in && !f1_shape(num_in_feats, num_out_feats, combin)) return MCCNN_E_SHAPE;
     if (use_mfma(a, combin != 0) && e > 0) {
         if (combin || a.nb <= MCCNN_TILE_FWD) return launch_conv_stream<false>(a, combin != 0, vec, bf16 != 0, out, nullptr, nullptr, s, recOut);
         int tiles, per;
@@ -1437,7 +1439,8 @@ static int conv_bwd_impl(const float* sorted_pts, const float* sorted_feats, con
                          int n, int m, int e, int num_in_feats, int num_out_feats, int combin, int batch_size,
                          float radius, int scale_inv, int avg, const void* state, const int* start_t,
                          const int* perm_t, float* feat_grad, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
-                         void* ws, size_t ws_bytes, mccnn_stream_t stream, int bf16) {
+                         void* ws, size_t ws_bytes, mccnn_stream_t stream, int bf16, const float4* rec_in = nullptr,
+                         bool state_as_only = false /* conv_bwd_rec: `state` is (A, S) alone */) {
     ConvArgs a;
     int rc = fill_args(a, sorted_pts, sorted_feats, sorted_batch_ids, pdfs, samples, start_idx, packed, aabb_min,
                        aabb_max, w1, b1, w2, b2, w3, b3, n, m, e, num_in_feats, num_out_feats, combin, batch_size,
@@ -1483,10 +1486,12 @@ static int conv_bwd_impl(const float* sorted_pts, const float* sorted_feats, con
     }
     if (m == 0 || e == 0) return 0;
     if (!out_grad) return MCCNN_E_BADARG;
-    const float4* recIn = state ? reinterpret_cast<const float4*>(state) : nullptr;
+    // the records of the list: the caller's (a geometry's own, exec.hip), or those the forward call left in `state`
+    const float4* recIn = rec_in ? rec_in : ((state && !state_as_only) ? reinterpret_cast<const float4*>(state) : nullptr);
     if (mfma && f1_shape(num_in_feats, num_out_feats, combin))
-        return f1_backward(a, out_grad, recIn, state ? (const char*)state + state_record_bytes(e) : nullptr, feat_grad, dw1, db1,
-                           dw2, db2, dw3, db3, ws, ws_bytes, s);
+        return f1_backward(a, out_grad, recIn, state ? (const char*)state + (state_as_only ? 0 : state_record_bytes(e)) : nullptr, feat_grad,
+                           dw1, db1, dw2, db2, dw3, db3, ws, ws_bytes, s);
+    // (a Fin = 1 layer too wide for the MFMA sweep's LDS: the kernels below use neither the state nor, without rec_in, records)
     if (mfma) {
         if (!ws || ws_bytes < mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, num_in_feats, num_out_feats, combin))
             return MCCNN_E_WORKSPACE;
@@ -1611,3 +1616,32 @@ int mccnn_spatial_conv_bwd_bf16(const float* sorted_pts, const void* sorted_feat
 }
 
 }  // extern "C"
+
+// The float32 convolution with the per-edge records of the list handed in (exec.hip: a geometry whose KDE left them).
+// Fin = 1 combin layers only (any other shape: MCCNN_E_SHAPE). The forward pass reads them instead of evaluating and storing
+// them, and `state` is (A, S) alone: f1_state_bytes, no record region. The backward pass reads them instead of the forward
+// call's copy; rec_in == nullptr there: the records are evaluated afresh (f1_edge_records), the state still (A, S) alone.
+namespace mccnn {
+int conv_fwd_rec(const float* sorted_pts, const float* sorted_feats, const int* sorted_batch_ids, const float* pdfs, const float* samples,
+                 const int* start_idx, const int* packed, const float* aabb_min, const float* aabb_max, const float* w1, const float* b1,
+                 const float* w2, const float* b2, const float* w3, const float* b3, int n, int m, int e, int num_in_feats,
+                 int num_out_feats, int combin, int batch_size, float radius, int scale_inv, int avg, float* out, void* state, void* ws,
+                 size_t ws_bytes, mccnn_stream_t stream, const void* rec_in) {
+    return conv_fwd_impl(sorted_pts, sorted_feats, sorted_batch_ids, pdfs, samples, start_idx, packed, aabb_min, aabb_max, w1, b1, w2, b2,
+                         w3, b3, n, m, e, num_in_feats, num_out_feats, combin, batch_size, radius, scale_inv, avg, out, state, ws, ws_bytes,
+                         stream, 0, reinterpret_cast<const float4*>(rec_in));
+}
+bool conv_f1_shape(int num_in_feats, int num_out_feats, int combin) { return f1_shape(num_in_feats, num_out_feats, combin); }
+size_t conv_f1_state_bytes(int m, int num_out_feats) { return f1_state_bytes(m, (num_out_feats + 7) / 8); }
+int conv_bwd_rec(const float* sorted_pts, const float* sorted_feats, const int* sorted_batch_ids, const float* pdfs, const float* samples,
+                 const int* start_idx, const int* packed, const float* aabb_min, const float* aabb_max, const float* w1, const float* b1,
+                 const float* w2, const float* b2, const float* w3, const float* b3, const float* out_grad, int n, int m, int e,
+                 int num_in_feats, int num_out_feats, int combin, int batch_size, float radius, int scale_inv, int avg, const void* state,
+                 const int* start_t, const int* perm_t, float* feat_grad, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                 float* db3, void* ws, size_t ws_bytes, mccnn_stream_t stream, const void* rec_in) {
+    return conv_bwd_impl(sorted_pts, sorted_feats, sorted_batch_ids, pdfs, samples, start_idx, packed, aabb_min, aabb_max, w1, b1, w2, b2,
+                         w3, b3, out_grad, n, m, e, num_in_feats, num_out_feats, combin, batch_size, radius, scale_inv, avg, state, start_t,
+                         perm_t, feat_grad, dw1, db1, dw2, db2, dw3, db3, ws, ws_bytes, stream, 0, reinterpret_cast<const float4*>(rec_in),
+                         true);
+}
+}  // namespace mccnn

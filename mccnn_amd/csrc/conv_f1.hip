@@ -33,9 +33,14 @@ __device__ __forceinline__ float wave_seg_scan1(float v, float m1, float m2, flo
 // Forward, edge pass: A_i = sum_e s_e a2_e (nb*8 floats per centre), S_i = sum_e s_e. Same streaming structure as
 // conv_stream (conv.hip): edge-balanced centre-aligned slices, chunks of 64 consecutive edges, wave-wide segmented
 // scan with carry, the last lane of a centre stores its finished sums.
+// RECIN: the per-edge records exist already (recIn: the geometry's, left by its KDE -- neighbors.hip): an edge costs ONE
+// 16-byte load where the other form loads its PDF, gathers point, centre, batch id and row bounds, divides three times and
+// stores the record for the backward pass. Same delta and weight bits (edge_record_of), same slices, scans and tails: the
+// same output bits.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void f1_fwd_edges(ConvArgs a, float* __restrict__ A, float* __restrict__ S,
-                                                    int numWaves, float4* __restrict__ recOut) {
+template <bool RECIN>
+__global__ __launch_bounds__(256, RECIN ? 7 : 1) void f1_fwd_edges(ConvArgs a, float* __restrict__ A, float* __restrict__ S,
+                                                    int numWaves, float4* __restrict__ recOut, const float4* __restrict__ recIn) {
     extern __shared__ float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i4 = lane & 3;
     const int rowA = a.nb * 8;
@@ -65,26 +70,42 @@ __global__ __launch_bounds__(256) void f1_fwd_edges(ConvArgs a, float* __restric
     float carryS = 0.f;
     int2 prN = make_int2(0, cA);
     float pdfN = 1.0f;
-    if (eBeg + lane < eEnd) { prN = a.packed[eBeg + lane]; pdfN = a.pdfs[eBeg + lane]; }
+    float4 recN = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (eBeg + lane < eEnd) {
+        prN = a.packed[eBeg + lane];
+        if (RECIN) recN = recIn[eBeg + lane];
+        else pdfN = a.pdfs[eBeg + lane];
+    }
     for (int base = eBeg; base < eEnd; base += 64) {
         const int t = base + lane;
         const int nIn = min(64, eEnd - base);
         const bool in = lane < nIn;
         const int2 pr = prN;
         const float pdf = pdfN;
-        if (t + 64 < eEnd) { prN = a.packed[t + 64]; pdfN = a.pdfs[t + 64]; }
+        const float4 rcd = recN;
+        if (t + 64 < eEnd) {
+            prN = a.packed[t + 64];
+            if (RECIN) recN = recIn[t + 64];
+            else pdfN = a.pdfs[t + 64];
+        }
         const int ci = pr.y, j = pr.x;
-        float invR = a.invRadius;
-        if (a.scaleInv) invR = 1.0f / (a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B)));
-        const float* pp = a.pts + (size_t)j * 3;
-        const float* cc = a.samples + (size_t)ci * 3;
-        const float R = a.scaleInv ? a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B)) : a.radius;
-        const float d0 = div_exact(pp[0] - cc[0], R, invR), d1 = div_exact(pp[1] - cc[1], R, invR), d2 = div_exact(pp[2] - cc[2], R, invR);
-        float K = 1.0f;
-        if (a.avg) K = (float)(((ci + 1 < a.m) ? a.start[ci + 1] : a.e) - a.start[ci]);
-        const float inv = in ? __builtin_amdgcn_rcpf(pdf * K) : 0.0f;
+        float d0, d1, d2, inv;
+        if (RECIN) {
+            d0 = rcd.x; d1 = rcd.y; d2 = rcd.z;
+            inv = in ? rcd.w : 0.0f;
+        } else {
+            float invR = a.invRadius;
+            if (a.scaleInv) invR = 1.0f / (a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B)));
+            const float* pp = a.pts + (size_t)j * 3;
+            const float* cc = a.samples + (size_t)ci * 3;
+            const float R = a.scaleInv ? a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B)) : a.radius;
+            d0 = div_exact(pp[0] - cc[0], R, invR); d1 = div_exact(pp[1] - cc[1], R, invR); d2 = div_exact(pp[2] - cc[2], R, invR);
+            float K = 1.0f;
+            if (a.avg) K = (float)(((ci + 1 < a.m) ? a.start[ci + 1] : a.e) - a.start[ci]);
+            inv = in ? __builtin_amdgcn_rcpf(pdf * K) : 0.0f;
+        }
         const float s = in ? a.feats[j] * inv : 0.0f;
-        if (recOut && in) recOut[t] = make_float4(d0, d1, d2, inv);  // the record f1_edge_records would compute (same bits)
+        if (!RECIN && recOut && in) recOut[t] = make_float4(d0, d1, d2, inv);  // the record f1_edge_records would compute (same bits)
         const int key = in ? ci + 1 : 0;
         const int cLast = __builtin_amdgcn_readlane(ci, nIn - 1);
         const int rowEnd = (cLast + 1 < a.m) ? a.start[cLast + 1] : a.e;
@@ -173,8 +194,10 @@ __device__ __forceinline__ void load_l12(const float* __restrict__ wq, int i4, L
 #else
 #define X4_PHASE() MCCNN_PHASE()
 #endif
+// RECIN (see f1_fwd_edges): the lane's four records are 64 contiguous bytes, four 16-byte loads; no record stage in LDS.
+template <bool RECIN>
 __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a, float* __restrict__ A, float* __restrict__ S,
-                                                     int numWaves, float4* __restrict__ recOut) {
+                                                     int numWaves, float4* __restrict__ recOut, const float4* __restrict__ recIn) {
     extern __shared__ float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i4 = lane & 3;
     const int rowA = a.nb * 8;
@@ -213,11 +236,13 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
     // are ~12 us and the prologue 5 us; kernel MLP 63 us, segmented sums 18 us.)
     int2 prN[4];
     float pdfN[4];
+    float4 recN[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int t = min(eBeg + 4 * lane + u, a.e - 1);
         prN[u] = a.packed[t];
-        pdfN[u] = a.pdfs[t];
+        if (RECIN) recN[u] = recIn[t];
+        else pdfN[u] = a.pdfs[t];
     }
     for (int base = eBeg; base < eEnd; base += 256) {
         const int lastPos = min(base + 256, eEnd) - 1;  // the last edge of this iteration
@@ -229,27 +254,34 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
             const int t = base + 4 * lane + u;
             in[u] = t < eEnd;
             const int2 pr = prN[u];
-            const float pdf = pdfN[u];
             const int j = pr.x;
             ci[u] = pr.y;
-            float invR = a.invRadius, R = a.radius;
-            if (a.scaleInv) {
-                R = a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B));
-                invR = 1.0f / R;
+            float inv;
+            if (RECIN) {
+                const float4 rcd = recN[u];
+                d0[u] = rcd.x; d1[u] = rcd.y; d2[u] = rcd.z;
+                inv = in[u] ? rcd.w : 0.0f;
+            } else {
+                const float pdf = pdfN[u];
+                float invR = a.invRadius, R = a.radius;
+                if (a.scaleInv) {
+                    R = a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[j], a.B));
+                    invR = 1.0f / R;
+                }
+                const float* pp = a.pts + (size_t)j * 3;
+                const float* cc = a.samples + (size_t)pr.y * 3;
+                d0[u] = div_exact(pp[0] - cc[0], R, invR);
+                d1[u] = div_exact(pp[1] - cc[1], R, invR);
+                d2[u] = div_exact(pp[2] - cc[2], R, invR);
+                float K = 1.0f;
+                if (a.avg) K = (float)(((pr.y + 1 < a.m) ? a.start[pr.y + 1] : a.e) - a.start[pr.y]);
+                inv = in[u] ? __builtin_amdgcn_rcpf(pdf * K) : 0.0f;
             }
-            const float* pp = a.pts + (size_t)j * 3;
-            const float* cc = a.samples + (size_t)pr.y * 3;
-            d0[u] = div_exact(pp[0] - cc[0], R, invR);
-            d1[u] = div_exact(pp[1] - cc[1], R, invR);
-            d2[u] = div_exact(pp[2] - cc[2], R, invR);
-            float K = 1.0f;
-            if (a.avg) K = (float)(((pr.y + 1 < a.m) ? a.start[pr.y + 1] : a.e) - a.start[pr.y]);
-            const float inv = in[u] ? __builtin_amdgcn_rcpf(pdf * K) : 0.0f;
             sE[u] = in[u] ? a.feats[j] * inv : 0.0f;
-            if (recOut) recStage[4 * lane + u] = make_float4(d0[u], d1[u], d2[u], inv);  // the record f1_edge_records would compute
+            if (!RECIN && recOut) recStage[4 * lane + u] = make_float4(d0[u], d1[u], d2[u], inv);  // the record f1_edge_records would compute
             key[u] = in[u] ? pr.y + 1 : 0;
         }
-        if (recOut) {
+        if (!RECIN && recOut) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int t = base + 64 * k + lane;
@@ -261,7 +293,8 @@ __global__ __launch_bounds__(256, MCCNN_F1_X4_OCC) void f1_fwd_edges4(ConvArgs a
             for (int u = 0; u < 4; ++u) {
                 const int t = min(base + 256 + 4 * lane + u, a.e - 1);
                 prN[u] = a.packed[t];
-                pdfN[u] = a.pdfs[t];
+                if (RECIN) recN[u] = recIn[t];
+                else pdfN[u] = a.pdfs[t];
             }
         }
         // the centre of the last edge: does its row go on behind this iteration?
@@ -441,8 +474,7 @@ __global__ __launch_bounds__(256) void f1_edge_records(ConvArgs a, float4* __res
     int e1 = (pr.y < a.m - 1) ? a.start[pr.y + 1] : a.e;
     float K = a.avg ? (float)(e1 - e0) : 1.0f;
     const float R = a.scaleInv ? a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[pr.x], a.B)) : a.radius;
-    rec[t] = make_float4(div_exact(p[0] - c[0], R, invR), div_exact(p[1] - c[1], R, invR), div_exact(p[2] - c[2], R, invR),
-                         __builtin_amdgcn_rcpf(a.pdfs[t] * K));
+    rec[t] = edge_record_of(p[0], p[1], p[2], c[0], c[1], c[2], R, invR, a.pdfs[t], K);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -933,41 +965,47 @@ static void f1_state_split(void* state, int m, int nb, float*& A, float*& S) {
     S = (float*)((char*)state + align_up((size_t)m * nb * 8 * sizeof(float)));
 }
 
-static int f1_run_edges(const ConvArgs& a, float* A, float* S, float4* recOut, hipStream_t s) {
+// recIn: the records of the list, computed already (the RECIN kernels: nothing is written to recOut)
+static int f1_run_edges(const ConvArgs& a, float* A, float* S, float4* recOut, const float4* recIn, hipStream_t s) {
     const size_t lds = ((size_t)a.nb * MCCNN_WQ_FWD + 4 * (size_t)a.nb * 8) * sizeof(float);
     // long lists: four edges per lane (one scan per 256 edges); short ones keep 64-edge chunks (more waves to spread)
     if (a.e >= g_f1_x4_min_edges.load(std::memory_order_relaxed)) {
-        const size_t lds4 = lds + 4 * 256 * sizeof(float4);  // + the record stage of the four waves
-        const int perCU4 = cached_blocks_per_cu(reinterpret_cast<const void*>(f1_fwd_edges4), lds4);
+        const size_t ldsStage = lds + 4 * 256 * sizeof(float4);  // + the record stage of the four waves
+        const size_t lds4 = recIn ? lds : ldsStage;
+        // (the slices decide the summation order of a centre's edges: the RECIN form takes the slice count of the other form,
+        // whatever its own occupancy, so that both give the same output bits)
+        const int perCU4 = cached_blocks_per_cu(reinterpret_cast<const void*>(f1_fwd_edges4<false>), ldsStage);
         const long long iters = ((long long)a.e + 255) / 256;
         static const int wpc = debug_int("f1_x4_waves_per_cu", 0);
         long long W4 = (long long)num_cus() * (wpc > 0 ? wpc : perCU4 * 4);
         if (W4 > (iters + 1) / 2) W4 = (iters + 1) / 2;
         if (W4 < 1) W4 = 1;
-        f1_fwd_edges4<<<(int)((W4 + 3) / 4), 256, lds4, s>>>(a, A, S, (int)W4, recOut);
+        if (recIn) f1_fwd_edges4<true><<<(int)((W4 + 3) / 4), 256, lds4, s>>>(a, A, S, (int)W4, nullptr, recIn);
+        else f1_fwd_edges4<false><<<(int)((W4 + 3) / 4), 256, lds4, s>>>(a, A, S, (int)W4, recOut, nullptr);
         MCCNN_LAUNCHED();
         return 0;
     }
-    const int perCU = cached_blocks_per_cu(reinterpret_cast<const void*>(f1_fwd_edges), lds);
+    const int perCU = cached_blocks_per_cu(reinterpret_cast<const void*>(f1_fwd_edges<false>), lds);   // (one slice count: see above)
     const long long chunks = ((long long)a.e + 63) / 64;
     long long W = (long long)num_cus() * perCU * 4;
     if (W > (chunks + 1) / 2) W = (chunks + 1) / 2;
     if (W < 1) W = 1;
-    f1_fwd_edges<<<(int)((W + 3) / 4), 256, lds, s>>>(a, A, S, (int)W, recOut);
+    if (recIn) f1_fwd_edges<true><<<(int)((W + 3) / 4), 256, lds, s>>>(a, A, S, (int)W, nullptr, recIn);
+    else f1_fwd_edges<false><<<(int)((W + 3) / 4), 256, lds, s>>>(a, A, S, (int)W, recOut, nullptr);
     MCCNN_LAUNCHED();
     return 0;
 }
 
 size_t f1_fwd_workspace_bytes(int m, int nb) { return f1_state_bytes(m, nb) + 256; }
 
-int f1_forward(const ConvArgs& a, float* out, float4* rec_out, void* state, void* ws, size_t ws_bytes, hipStream_t s) {
+int f1_forward(const ConvArgs& a, float* out, float4* rec_out, const float4* rec_in, void* state, void* ws, size_t ws_bytes, hipStream_t s) {
     if (!state) {
         if (!ws || ws_bytes < f1_fwd_workspace_bytes(a.m, a.nb)) return MCCNN_E_WORKSPACE;
         state = ws;
     }
     float *A, *S;
     f1_state_split(state, a.m, a.nb, A, S);
-    int rc = f1_run_edges(a, A, S, rec_out, s);
+    int rc = f1_run_edges(a, A, S, rec_in ? nullptr : rec_out, rec_in, s);
     if (rc) return rc;
     f1_fwd_centres<<<ceil_div((long long)a.m * a.nb, 256), 256, (size_t)a.nb * 72 * sizeof(float), s>>>(a, A, S, out);
     MCCNN_LAUNCHED();
@@ -1018,7 +1056,7 @@ int f1_backward(const ConvArgs& a, const float* out_grad, const float4* rec_in, 
         f1_state_split(const_cast<void*>(state), a.m, a.nb, A, S);
     } else {
         f1_state_split(own, a.m, a.nb, A, S);
-        int rc = f1_run_edges(a, A, S, nullptr, s);
+        int rc = f1_run_edges(a, A, S, nullptr, rec_in, s);
         if (rc) return rc;
     }
     f1_bwd_centres<<<ceil_div((long long)wavesC * (a.nb + 1), 4), 256, 0, s>>>(a, out_grad, A, S, cPerWave, wavesC, G, gb, pc, feat_grad);

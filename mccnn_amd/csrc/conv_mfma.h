@@ -304,18 +304,11 @@ __device__ __forceinline__ uint4 f32x8_to_bf16(const float* c) {
     return make_uint4(f32x2_to_bf16(c[0], c[1]), f32x2_to_bf16(c[2], c[3]), f32x2_to_bf16(c[4], c[5]), f32x2_to_bf16(c[6], c[7]));
 }
 
-// Correctly rounded x / R from y = RN(1 / R) in three instructions (Markstein): q = RN(x y) is within one ulp,
-// r = x - q R is exact in an fma, RN(q + r y) is the correctly rounded quotient. The reference divides
-// (spatial_conv.cu:155-158); the quotient feeds layer 1, whose pre-activations have to be
-// bit-identical (see above). Spelled with fma builtins: the library is compiled with -ffp-contract=off.
-__device__ __forceinline__ float div_exact(float x, float R, float invR) {
-    const float q = x * invR;
-    const float r = __builtin_fmaf(-q, R, x);
-    return __builtin_fmaf(r, invR, q);
-}
+// (div_exact, the correctly rounded x / R of the records: common.h)
 
 // The record of edge t: (delta0, delta1, delta2, 1 / (pdf K)) -- delta = (point - centre) / R correctly rounded
 // (spatial_conv.cu:155-158), K = the centre's neighbour count when the layer averages (spatial_conv.cu:160-166).
+// (the arithmetic: edge_record_of, common.h)
 __device__ __forceinline__ float4 edge_record(const ConvArgs& a, int t) {
     const int2 pr = a.packed[t];
     float invR = a.invRadius;
@@ -326,8 +319,7 @@ __device__ __forceinline__ float4 edge_record(const ConvArgs& a, int t) {
     const int e1 = (pr.y < a.m - 1) ? a.start[pr.y + 1] : a.e;
     const float K = a.avg ? (float)(e1 - e0) : 1.0f;
     const float R = a.scaleInv ? a.radius * max_extent(a.mn, a.mx, clamp_batch(a.bids[pr.x], a.B)) : a.radius;
-    return make_float4(div_exact(p[0] - c[0], R, invR), div_exact(p[1] - c[1], R, invR), div_exact(p[2] - c[2], R, invR),
-                       __builtin_amdgcn_rcpf(a.pdfs[t] * K));
+    return edge_record_of(p[0], p[1], p[2], c[0], c[1], c[2], R, invR, a.pdfs[t], K);
 }
 
 // smallest c in [0, m] with S(c) >= t, S(c) = start[c] (c < m), S(m) = e. 64-ary: three dependent loads for m < 2^18.
@@ -494,7 +486,8 @@ std::atomic<int>& conv_impl_override();
 size_t f1_state_bytes(int m, int nb);
 size_t f1_fwd_workspace_bytes(int m, int nb);
 size_t f1_bwd_workspace_bytes(int m, int e, int nb);
-int f1_forward(const ConvArgs& a, float* out, float4* rec_out, void* state, void* ws, size_t ws_bytes, hipStream_t s);
+// rec_in: the records of the list, computed already (the geometry's: exec.hip) -- read instead of evaluated, rec_out untouched
+int f1_forward(const ConvArgs& a, float* out, float4* rec_out, const float4* rec_in, void* state, void* ws, size_t ws_bytes, hipStream_t s);
 int f1_backward(const ConvArgs& a, const float* out_grad, const float4* rec_in, const void* state, float* feat_grad, float* dw1, float* db1,
                 float* dw2, float* db2, float* dw3, float* db3, void* ws, size_t ws_bytes, hipStream_t s);
 

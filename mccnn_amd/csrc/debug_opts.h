@@ -38,6 +38,7 @@
 //     f1_coop_min_chunks (3)         chunks per workgroup (whole chip in use) from which a one-input-feature backward pass takes the cooperative edge kernel
 //     f1_coop_off (0)                1 = never the cooperative edge kernel (seeds mccnn_debug_conv_impl, bit 2)
 //     f1_coop_force (0)              1 = the cooperative edge kernel whenever the block count is even (seeds mccnn_debug_conv_impl, bit 3)
+//     kde_records (1)                0 = the KDE of a geometry writes no per-edge records (the layers evaluate their own); shared with the Python side
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -51,7 +52,7 @@ namespace mccnn {
     "rows_min_degree", "unsorted_max_points", "force_valu", "no_f1", "f1_x4_min_e", "f1_x4_waves_per_cu", "nw_lean",      \
     "nw_lds_pad", "scan_bg_tiles", "issue_thread", "job_delay_us",                                                       \
     "hier_trace", "geo_own_pool", "trace_terminate", "aabb_one_max", "plan_batch_sync", "caller_join_off", "bwd_min_chunks", \
-    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force",                                                                \
+    "f1_coop_min_chunks", "f1_coop_off", "f1_coop_force", "kde_records",                                                 \
     /* Python side (mccnn_amd/_env.py) */                                                                                \
     "fuse_sort", "native_prefetch", "plan_prefetch", "plan_prefetch_max_e", "geo_prefetch_min",                          \
     "ecap_scale", "hier_pmode", "geo_trace"

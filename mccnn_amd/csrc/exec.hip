@@ -27,6 +27,20 @@
 
 namespace mccnn {
 std::atomic<int>& conv_impl_override();  // conv.hip (mccnn_debug_conv_impl)
+// conv.hip: the factored Fin = 1 layer with the per-edge records handed in (`state`: (A, S) alone, no record region)
+bool conv_f1_shape(int num_in_feats, int num_out_feats, int combin);
+size_t conv_f1_state_bytes(int m, int num_out_feats);
+int conv_fwd_rec(const float* sorted_pts, const float* sorted_feats, const int* sorted_batch_ids, const float* pdfs, const float* samples,
+                 const int* start_idx, const int* packed, const float* aabb_min, const float* aabb_max, const float* w1, const float* b1,
+                 const float* w2, const float* b2, const float* w3, const float* b3, int n, int m, int e, int num_in_feats,
+                 int num_out_feats, int combin, int batch_size, float radius, int scale_inv, int avg, float* out, void* state, void* ws,
+                 size_t ws_bytes, mccnn_stream_t stream, const void* rec_in);
+int conv_bwd_rec(const float* sorted_pts, const float* sorted_feats, const int* sorted_batch_ids, const float* pdfs, const float* samples,
+                 const int* start_idx, const int* packed, const float* aabb_min, const float* aabb_max, const float* w1, const float* b1,
+                 const float* w2, const float* b2, const float* w3, const float* b3, const float* out_grad, int n, int m, int e,
+                 int num_in_feats, int num_out_feats, int combin, int batch_size, float radius, int scale_inv, int avg, const void* state,
+                 const int* start_t, const int* perm_t, float* feat_grad, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                 float* db3, void* ws, size_t ws_bytes, mccnn_stream_t stream, const void* rec_in);
 // grid.hip: the grid build as one chain of four launches, the visiting order of foreign centres as three; what each wants
 // cleared before its first kernel is a span the caller may clear together with others (one launch per geometry)
 ClearSpan grid_head_span(int n, int batch_size, int num_cells, void* ws, size_t ws_bytes);
@@ -108,6 +122,9 @@ struct mccnn_geometry {
     char* rec_buf = nullptr;         // per-edge records (16 B per edge) in edge order
     size_t rec_bytes = 0;
     int rec_avg = -1;
+    // asked for BEFORE the build (mccnn_geometry_want_records; survives geometry_setup): the KDE of the build leaves the
+    // records of layers with this `avg` behind the geometry's own pieces, in the same buffer (-1: not asked for)
+    int rec_want = -1;
 };
 
 namespace {
@@ -167,6 +184,14 @@ GeoLayout geo_layout(int n, int m, int B, int nc, int e_cap, bool with_grid, int
     o += L.ws_bytes;
     L.total_bytes = o;
     return L;
+}
+
+// MCCNN_DEBUG=kde_records=0: the KDE writes PDFs alone, whatever was asked for (A/B against the records computed by the layers)
+bool kde_records_on() { static const bool on = debug_int("kde_records", 1) != 0; return on; }
+size_t kde_records_bytes(int e_cap) { return al((size_t)(e_cap > 0 ? e_cap : 1) * 16); }
+// the build of g writes records: asked for, a buffer to hold them, and PDFs that come from the KDE of the list
+bool kde_writes_records(const mccnn_geometry* g) {
+    return g->rec_want >= 0 && g->rec_buf && g->use_pdf && !g->pp_density && kde_records_on();
 }
 
 int read_mask() { return conv_impl_override().load(std::memory_order_relaxed) & 3; }  // (bits 2 / 3 choose between the Fin = 1 backward edge kernels)
@@ -366,7 +391,9 @@ int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, 
     const GeoLayout L = geo_layout(n, m, batch_size, num_cells, e_capacity, with_grid, cap_k, max_edges);
     if (L.total_bytes == 0) return MCCNN_E_TOOLARGE;
     if (buffer_bytes < L.total_bytes || (((uintptr_t)buffer) & 255)) return MCCNN_E_WORKSPACE;
+    const int rec_want = g->rec_want;
     *g = mccnn_geometry();
+    g->rec_want = rec_want;
     g->pts = pts; g->bids = batch_ids; g->centres = centres; g->cbids = centre_batch_ids; g->mn = aabb_min; g->mx = aabb_max;
     g->n = n; g->m = m; g->B = batch_size; g->nc = num_cells; g->scale_inv = scale_inv ? 1 : 0; g->use_pdf = use_pdf ? 1 : 0;
     g->radius = radius; g->window = window;
@@ -388,6 +415,11 @@ int geometry_setup(mccnn_geometry_t* g, const float* pts, const int* batch_ids, 
     g->order_buf = (int*)(b + L.order);
     g->ws = b + L.ws; g->ws_bytes = L.ws_bytes;
     g->e_cap = e_capacity; g->e = -1; g->total_host = total_host;
+    // records asked for: behind the geometry's own pieces, when the caller's buffer has the room (mccnn_geometry_records_bytes)
+    if (rec_want >= 0 && buffer_bytes >= L.total_bytes + kde_records_bytes(e_capacity)) {
+        g->rec_buf = b + L.total_bytes;
+        g->rec_bytes = kde_records_bytes(e_capacity);
+    }
     *total_host = -1;  // armed: the prefix sum of the count pass overwrites it
     return 0;
 }
@@ -476,6 +508,12 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
         ExpandItem it;
         if ((rc = geometry_expand_item(g, it))) return rc;
         if ((rc = launch_expand_dn(it, s))) return rc;
+    } else if (kde_writes_records(g)) {   // the KDE of mccnn_compute_pdf_dn, with the records of the list beside its PDFs
+        PdfItem it;
+        pdf_batch_item(it, go->s_pts, go->s_bids, g->start, m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, batch_size, g->window,
+                       g->radius, g->scale_inv, g->pdfs, g->centres, g->rec_buf, g->rec_want);
+        rc = launch_pdf(it, s);
+        if (rc) return rc;
     } else if (g->use_pdf) {
         rc = mccnn_compute_pdf_dn(go->s_pts, go->s_bids, g->start, m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, batch_size,
                                   g->window, g->radius, g->scale_inv, g->pdfs, g->ws, g->ws_bytes, stream);
@@ -485,6 +523,7 @@ int geometry_issue_single(mccnn_geometry_t* g, mccnn_stream_t stream) {
         if (rc) return rc;
     }
     g->built = true;
+    if (kde_writes_records(g)) g->rec_avg = g->rec_want;
     return 0;
 }
 
@@ -556,9 +595,12 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
         if (rc) return rc;
         if (g->pp_density) {
             if ((rc = geometry_expand_item(g, exB.it[nEx++]))) return rc;
-        } else if (g->use_pdf)
+        } else if (g->use_pdf) {
+            const bool kr = kde_writes_records(g);
             pdf_batch_item(pdfB.it[nPdf++], go->s_pts, go->s_bids, g->start, g->m, g->packed, g->e_cap, g->total_dev, g->mn, g->mx, g->B,
-                           g->window, g->radius, g->scale_inv, g->pdfs);
+                           g->window, g->radius, g->scale_inv, g->pdfs, kr ? g->centres : nullptr, kr ? g->rec_buf : nullptr,
+                           kr ? g->rec_want : 0);
+        }
     }
     // (one launch per kind of search that is present: a chunk without a capped geometry makes the plain launches alone)
     if ((rc = launch_neigh_batch(neighB, capB, count, 0, s))) return rc;
@@ -579,11 +621,32 @@ int geometry_issue_chunk(mccnn_geometry_t* const* gs, int count, mccnn_stream_t 
             if (rc) return rc;
         }
         g->built = true;
+        if (kde_writes_records(g)) g->rec_avg = g->rec_want;
     }
     return 0;
 }
 }  // namespace
 extern "C" {
+
+size_t mccnn_geometry_records_bytes(int e_capacity) { return e_capacity < 0 ? 0 : kde_records_bytes(e_capacity); }
+
+int mccnn_geometry_want_records(mccnn_geometry_t* g, int avg) {
+    if (!g || avg < -1) return MCCNN_E_BADARG;
+    g->rec_want = avg < 0 ? -1 : (avg ? 1 : 0);
+    return 0;
+}
+
+int mccnn_geometry_records(const mccnn_geometry_t* g, const void** records) {
+    if (records) *records = nullptr;
+    if (!g || !g->built || !g->rec_buf || g->rec_avg < 0) return -1;
+    if (records) *records = g->rec_buf;
+    return g->rec_avg;
+}
+
+int mccnn_conv_uses_records(const mccnn_geometry_t* g, int num_in_feats, int num_out_feats, int combin, int avg) {
+    if (!g || !g->built || !g->rec_buf || g->rec_avg < 0) return 0;
+    return (g->rec_avg == (avg ? 1 : 0) && conv_f1_shape(num_in_feats, num_out_feats, combin)) ? 1 : 0;
+}
 
 // (the uncapped entries are the capped ones with no cap, the capped ones the point ones with no point record, the point
 // ones the budget ones with no budget)
@@ -1076,7 +1139,9 @@ static int requirements(mccnn_geometry* g, const Shape& s, const void* feats, in
         } else if (!s.bf16) {
             const size_t w = mccnn_spatial_conv_fwd_workspace_bytes(m, e, s.fin, s.fout, s.combin);
             if (w > ws) ws = w;
-            if (flags & 1) saved += al(mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin));
+            // (flags bit 2: a Fin = 1 layer that reads the geometry's records keeps (A, S) alone)
+            if ((flags & 1) && (flags & 4) && conv_f1_shape(s.fin, s.fout, s.combin)) saved += al(m > 0 && e > 0 ? conv_f1_state_bytes(m, s.fout) : 0);
+            else if (flags & 1) saved += al(mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin));
         }
     } else {
         const bool rows_bwd = f.rows_bwd && m > 0;
@@ -1182,6 +1247,17 @@ int mccnn_conv_forward(mccnn_geometry_t* g, const void* feats, int num_in_feats,
                                            b1, w2, b2, w3, b3, n, m, e, s.fin, g->B, g->radius, g->scale_inv, avg, out, ws, ws_bytes,
                                            stream);
     void* state = nullptr;
+    if (flags & 4) {
+        // the records of this list exist (the geometry's KDE left them): read, not evaluated, and not kept a second time
+        if (!mccnn_conv_uses_records(g, s.fin, s.fout, s.combin, avg) || g->rec_bytes < (size_t)e * 16) return MCCNN_E_BADARG;
+        if ((flags & 1) && m > 0 && e > 0) {
+            if (!saved || saved_bytes < sv_off + conv_f1_state_bytes(m, s.fout)) return MCCNN_E_WORKSPACE;
+            state = sv + sv_off;
+        }
+        return conv_fwd_rec(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1, b1,
+                            w2, b2, w3, b3, n, m, e, s.fin, s.fout, s.combin, g->B, g->radius, g->scale_inv, avg, (float*)out, state, ws,
+                            ws_bytes, stream, g->rec_buf);
+    }
     if (flags & 1) {
         const size_t sb = mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin);
         if (sb) {
@@ -1283,6 +1359,16 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
         rc = mccnn_spatial_conv_bwd_bf16(go->s_pts, rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1,
                                          b1, w2, b2, w3, b3, out_grad, n, m, e, s.fin, g->B, g->radius, g->scale_inv, avg, st, pt,
                                          fg, dw1, db1, dw2, db2, dw3, db3, w, wb, stream);
+    } else if (flags & 4) {
+        // the forward call read the geometry's records and kept (A, S) alone; the records are read again where they still
+        // are the ones of this `avg` (a layer with the other flag may have rebuilt them for a row plan: evaluated afresh then)
+        if (!conv_f1_shape(s.fin, s.fout, s.combin) || f.unsorted || f.rows_fwd) return MCCNN_E_BADARG;
+        const void* state = nullptr;
+        if ((flags & 1) && m > 0 && e > 0 && saved && saved_bytes >= sv_off + conv_f1_state_bytes(m, s.fout)) state = sv + sv_off;
+        const bool have = mccnn_conv_uses_records(g, s.fin, s.fout, s.combin, avg) && g->rec_bytes >= (size_t)e * 16;
+        rc = conv_bwd_rec(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1, b1,
+                          w2, b2, w3, b3, (const float*)out_grad, n, m, e, s.fin, s.fout, s.combin, g->B, g->radius, g->scale_inv, avg,
+                          state, st, pt, (float*)fg, dw1, db1, dw2, db2, dw3, db3, w, wb, stream, have ? g->rec_buf : nullptr);
     } else {
         const void* state = nullptr;
         if (flags & 1) {

@@ -643,9 +643,13 @@ __device__ __forceinline__ PdfPoint pdf_gather(const float* __restrict__ pts, in
 // average, some with > 1 000 -- alone set the kernel's time: 597 us on BASELINE cfg2 Pool_1).
 // (force-inlined: through a non-inlined call the LDS planes arrive as a generic pointer and every pair step became a
 // FLAT load with a full wait -- 0.58 T pair terms/s on BASELINE cfg2 Pool_1 against 3.2 T on the tile path)
+// rec != nullptr: the record of every edge beside its PDF (the lane holds the edge's point already) -- centre (cx, cy, cz),
+// R / invR and K as the convolution kernels take them (edge_record_of, common.h).
 __device__ __forceinline__ void pdf_row_long(const float* __restrict__ pts, const int2* __restrict__ rowpk, int k, int rowStart,
                                           int lane, float s, float scale, float* __restrict__ P,
-                                          float* __restrict__ pdfs, int aBegin, int aStep) {
+                                          float* __restrict__ pdfs, int aBegin, int aStep, float4* __restrict__ rec = nullptr,
+                                          float cx = 0.f, float cy = 0.f, float cz = 0.f, float R = 1.f, float invR = 1.f,
+                                          float K = 1.f) {
     float4* __restrict__ P4 = reinterpret_cast<float4*>(P);
     const float cc = (-0.5f * 1.44269504088896f) * (s * s);
     for (int a0 = aBegin; a0 < k; a0 += aStep) {
@@ -670,15 +674,32 @@ __device__ __forceinline__ void pdf_row_long(const float* __restrict__ pts, cons
                 acc += __builtin_amdgcn_exp2f(cc * fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
             }
         }
-        if (a < k) pdfs[rowStart + a] = acc * scale;
+        if (a < k) {
+            const float pdf = acc * scale;
+            pdfs[rowStart + a] = pdf;
+            if (rec) rec[rowStart + a] = edge_record_of(me.x, me.y, me.z, cx, cy, cz, R, invR, pdf, K);
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
 struct PdfLongRow { int rowStart, k; float s, scale; };
-template <int WAVES>  // 4: lists of many rows (4 rows per wave); 16: lists of few rows (one row per wave)
+struct PdfLongRec { int row; float R; };   // what the records of a long row need beside PdfLongRow: its centre and radius
+// REC: the instantiation that can leave the per-edge records of the convolution kernels beside the PDFs (PdfItem::rec; a
+// null pointer there leaves the PDFs alone, as the REC = false instantiation does -- the code of before the records).
+//   A record is (delta = (p_j - c_i) / R, 1 / (pdf K)): the row's centre is wave-uniform here (three scalar loads per ROW
+//   where the convolution gathers three values per EDGE), K is the row length, R the radius the window was scaled with, and
+//   the point is in the lane's registers from staging. The PDFs of a tile row come out 16 lanes at a time (one column block
+//   J per pass); every 16-lane group holds the finished sum after the two row swaps, so group J & 3 keeps the value of
+//   point 16 J + (lane & 15) = 64 (J >> 2) + lane in a register, and ONE pass per 64 points behind the J loop, lanes =
+//   points, writes the records as contiguous 16-byte stores.
+template <int WAVES, bool REC>  // 4: lists of many rows (4 rows per wave); 16: lists of few rows (one row per wave)
 __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem& g) {
+    static_assert(!REC || MCCNN_PDF_CAP <= 192, "a lane keeps the PDFs of at most three of its row's points for the records");
+    const float* __restrict__ centres = g.centres;
+    float4* __restrict__ rec = REC ? g.rec : nullptr;
+    const float Kavg = g.avg ? 1.0f : 0.0f;
     const float* __restrict__ pts = g.pts;
     const int* __restrict__ bids = g.bids;
     const int2* __restrict__ packed = g.packed;
@@ -693,6 +714,7 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
     __shared__ __attribute__((aligned(16))) float planes[WAVES][5 * MCCNN_PDF_CAP];  // per wave: ux, uy, uz, q, ones
     // rows longer than the planes: set aside here and walked by ALL waves of the workgroup afterwards (pdf_row_long)
     __shared__ PdfLongRow longRows[WAVES * MCCNN_PDF_ROWS];
+    __shared__ PdfLongRec longRec[REC ? WAVES * MCCNN_PDF_ROWS : 1];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // wave-uniform: rows, tile counts and loops live in SGPRs
     __shared__ int anyLong;
     for (int t = threadIdx.x; t < WAVES * MCCNN_PDF_ROWS; t += WAVES * 64) longRows[t].k = 0;
@@ -761,8 +783,15 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
             s = (float)(1.0 / (double)((radius * max_extent(mn, mx, b0)) * window));
         }
         const float scale = norm * __builtin_amdgcn_rcpf((float)k);  // 1 ulp: this mode is not the bit-exact one
+        // the radius of the records: the one the convolution kernels divide by (the row's cloud: its first neighbour's)
+        float Rr = radius;
+        if (REC && rec && scaleInv) Rr = radius * max_extent(mn, mx, clamp_batch(__builtin_amdgcn_readfirstlane(bme), B));
         if (k > MCCNN_PDF_CAP) {
-            if (lane == 0) { longRows[wave * MCCNN_PDF_ROWS + rr] = PdfLongRow{rowStart, k, s, scale}; anyLong = 1; }
+            if (lane == 0) {
+                longRows[wave * MCCNN_PDF_ROWS + rr] = PdfLongRow{rowStart, k, s, scale};
+                if (REC) longRec[wave * MCCNN_PDF_ROWS + rr] = PdfLongRec{r0 + rr, Rr};
+                anyLong = 1;
+            }
             continue;
         }
         const int T = (k + 15) >> 4;
@@ -784,6 +813,7 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float pdf0 = 0.f, pdf1 = 0.f, pdf2 = 0.f;   // (REC) the PDFs of points lane, lane + 64, lane + 128
         for (int J = 0; J < T; ++J) {
             const float bop = pb[16 * J] * bscale;
             float acc0 = 0.f, acc1 = 0.f;
@@ -819,7 +849,27 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
                 acc = lo + hi;
             }
             const int a = 16 * J + mm;
-            if (c == 0 && a < k) pdfs[rowStart + a] = acc * scale;
+            const float pdf = acc * scale;
+            if (c == 0 && a < k) pdfs[rowStart + a] = pdf;
+            if (REC && c == (J & 3)) {
+                if ((J >> 2) == 0) pdf0 = pdf;
+                else if ((J >> 2) == 1) pdf1 = pdf;
+                else pdf2 = pdf;
+            }
+        }
+        if (REC && rec) {
+            const float* __restrict__ cp = centres + (size_t)(r0 + rr) * 3;
+            const float cx = cp[0], cy = cp[1], cz = cp[2];
+            const float invRr = 1.0f / Rr;
+            const float K = Kavg != 0.f ? (float)k : 1.0f;
+            for (int t = 0; 64 * t < k; ++t) {
+                const int a = 64 * t + lane;
+                if (a < k) {
+                    const PdfPoint p = (t == 0) ? me : pdf_gather(pts, rowpk[a].x);
+                    const float pdf = (t == 0) ? pdf0 : (t == 1) ? pdf1 : pdf2;
+                    rec[rowStart + a] = edge_record_of(p.x, p.y, p.z, cx, cy, cz, Rr, invRr, pdf, K);
+                }
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -841,6 +891,15 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
             const int2* __restrict__ rowpk = packed + lr.rowStart;
             const PdfPoint o = pdf_gather(pts, rowpk[0].x);  // the row's first point: every difference is within 2 R of it
             const float sp = lr.s * 0.84932180f;
+            float cxL = 0.f, cyL = 0.f, czL = 0.f, RL = 1.f, invRL = 1.f, KL = 1.f;
+            if (REC && rec) {
+                const PdfLongRec lq = longRec[t];
+                const float* __restrict__ cp = centres + (size_t)lq.row * 3;
+                cxL = cp[0]; cyL = cp[1]; czL = cp[2];
+                RL = lq.R;
+                invRL = 1.0f / RL;
+                KL = Kavg != 0.f ? (float)k : 1.0f;
+            }
             __syncthreads();  // the planes are free (the waves' own rows, the previous long row)
             for (int a = threadIdx.x; a < 16 * T; a += WAVES * 64) {
                 const PdfPoint q = pdf_gather(pts, rowpk[min(a, k - 1)].x);
@@ -885,7 +944,14 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
                     acc = lo + hi;
                 }
                 const int a = 16 * J + mm;
-                if (c == 0 && a < k) pdfs[lr.rowStart + a] = acc * lr.scale;
+                if (c == 0 && a < k) {
+                    const float pdf = acc * lr.scale;
+                    pdfs[lr.rowStart + a] = pdf;
+                    if (REC && rec) {   // (rare rows: the point is gathered again, 16 lanes per store)
+                        const PdfPoint p = pdf_gather(pts, rowpk[a].x);
+                        rec[lr.rowStart + a] = edge_record_of(p.x, p.y, p.z, cxL, cyL, czL, RL, invRL, pdf, KL);
+                    }
+                }
             }
             continue;
         }
@@ -893,23 +959,36 @@ __device__ __forceinline__ void pdf_rows_mfma_body(const int blk, const PdfItem&
         // subtract-first loop with the row streamed through each wave's own planes
         __syncthreads();
         const int blocks = (lr.k + 63) >> 6;
-        for (int b = (wave - item % WAVES + WAVES) % WAVES; b < blocks; b += WAVES)
-            pdf_row_long(pts, packed + lr.rowStart, lr.k, lr.rowStart, lane, lr.s, lr.scale, P, pdfs, b * 64, 1 << 30);
+        if (REC && rec) {
+            const PdfLongRec lq = longRec[t];
+            const float* __restrict__ cp = centres + (size_t)lq.row * 3;
+            const float cx = cp[0], cy = cp[1], cz = cp[2];
+            const float invRL = 1.0f / lq.R;
+            const float KL = Kavg != 0.f ? (float)lr.k : 1.0f;
+            for (int b = (wave - item % WAVES + WAVES) % WAVES; b < blocks; b += WAVES)
+                pdf_row_long(pts, packed + lr.rowStart, lr.k, lr.rowStart, lane, lr.s, lr.scale, P, pdfs, b * 64, 1 << 30, rec, cx, cy, cz,
+                             lq.R, invRL, KL);
+        } else {
+            for (int b = (wave - item % WAVES + WAVES) % WAVES; b < blocks; b += WAVES)
+                pdf_row_long(pts, packed + lr.rowStart, lr.k, lr.rowStart, lane, lr.s, lr.scale, P, pdfs, b * 64, 1 << 30);
+        }
         item += blocks;
     }
 }
 
-template <int WAVES>
+template <int WAVES, bool REC>
 __global__ __launch_bounds__(WAVES * 64) void pdf_rows_mfma(PdfItem g) {
-    pdf_rows_mfma_body<WAVES>((int)blockIdx.x, g);
+    pdf_rows_mfma_body<WAVES, REC>((int)blockIdx.x, g);
 }
 
 // One launch for the KDE of a BATCH of lists (mccnn_geometry_build_batch): 16 waves per workgroup for every list (the
 // pooled planes of long rows), rows per wave by the list's size.
+// (REC: at least one list of the batch gets its records; the others carry a null pointer)
+template <bool REC>
 __global__ __launch_bounds__(1024) void pdf_rows_mfma_batch(PdfBatch pb, BatchBlocks bb) {
     int local, blocks;
     const PdfItem& g = pb.it[batch_item(bb, (int)blockIdx.x, local, blocks)];
-    pdf_rows_mfma_body<16>(local, g);
+    pdf_rows_mfma_body<16, REC>(local, g);
 }
 
 }  // namespace mccnn
@@ -1390,9 +1469,23 @@ int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int cou
 }
 void pdf_batch_item(PdfItem& it, const float* sorted_pts, const int* sorted_batch_ids, const int* start_idx, int m, const int* packed,
                     int e_capacity, const int* e_dev, const float* aabb_min, const float* aabb_max, int batch_size, float window,
-                    float radius, int scale_inv, float* pdfs) {
+                    float radius, int scale_inv, float* pdfs, const float* centres, void* rec, int avg) {
     it = PdfItem{sorted_pts, sorted_batch_ids, reinterpret_cast<const int2*>(packed), start_idx, aabb_min, aabb_max, pdfs, e_dev,
-                 m, e_capacity, batch_size, scale_inv, m >= 16384 ? MCCNN_PDF_ROWS : 1, window, radius};
+                 m, e_capacity, batch_size, scale_inv, m >= 16384 ? MCCNN_PDF_ROWS : 1, window, radius,
+                 centres, (centres && rec) ? reinterpret_cast<float4*>(rec) : nullptr, avg ? 1 : 0};
+}
+int launch_pdf(const PdfItem& it, hipStream_t s) {
+    static_assert(MCCNN_PDF_ROWS > 1, "rowsPerWave > 1 tells the list of many rows (4 waves per workgroup) from the one of few");
+    if (it.m <= 0 || it.e <= 0) return 0;
+    if (it.rowsPerWave > 1) {
+        if (it.rec) pdf_rows_mfma<4, true><<<ceil_div(it.m, 4 * it.rowsPerWave), 256, 0, s>>>(it);
+        else pdf_rows_mfma<4, false><<<ceil_div(it.m, 4 * it.rowsPerWave), 256, 0, s>>>(it);
+    } else {
+        if (it.rec) pdf_rows_mfma<16, true><<<ceil_div(it.m, 16), 1024, 0, s>>>(it);
+        else pdf_rows_mfma<16, false><<<ceil_div(it.m, 16), 1024, 0, s>>>(it);
+    }
+    MCCNN_LAUNCHED();
+    return 0;
 }
 int launch_pdf_batch(const PdfBatch& pb, int count, hipStream_t s) {
     BatchBlocks bb;
@@ -1401,7 +1494,10 @@ int launch_pdf_batch(const PdfBatch& pb, int count, hipStream_t s) {
     for (int k = 0; k < count; ++k) { bb.first[k] = run; run += ceil_div(pb.it[k].m, 16 * pb.it[k].rowsPerWave); }
     for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
     if (run == 0) return 0;
-    pdf_rows_mfma_batch<<<run, 1024, 0, s>>>(pb, bb);
+    bool anyRec = false;
+    for (int k = 0; k < count; ++k) anyRec = anyRec || pb.it[k].rec != nullptr;
+    if (anyRec) pdf_rows_mfma_batch<true><<<run, 1024, 0, s>>>(pb, bb);
+    else pdf_rows_mfma_batch<false><<<run, 1024, 0, s>>>(pb, bb);
     MCCNN_LAUNCHED();
     return 0;
 }
@@ -1450,9 +1546,7 @@ static int compute_pdf_impl(const float* sorted_pts, const int* sorted_batch_ids
             PdfItem it;
             pdf_batch_item(it, sorted_pts, sorted_batch_ids, start_idx, m, packed, e, e_dev, aabb_min, aabb_max, batch_size, window, radius,
                            scale_inv, pdfs);
-            static_assert(MCCNN_PDF_ROWS > 1, "rowsPerWave > 1 tells the list of many rows (4 waves per workgroup) from the one of few");
-            if (it.rowsPerWave > 1) pdf_rows_mfma<4><<<ceil_div(m, 4 * it.rowsPerWave), 256, 0, s>>>(it);
-            else pdf_rows_mfma<16><<<ceil_div(m, 16), 1024, 0, s>>>(it);
+            return launch_pdf(it, s);
         }
     }
     MCCNN_LAUNCHED();

@@ -759,7 +759,8 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
                                     int64_t side, bool fork, bool background, std::shared_ptr<HierFuture> after,
                                     int64_t max_neighbors, int64_t sample_seed /* < 0: none */, bool point_pdf,
                                     std::shared_ptr<PointPdf> point_from /* the density of this grid and window, when it exists */,
-                                    int64_t max_edges /* the edge budget of the search; 0: none */) {
+                                    int64_t max_edges /* the edge budget of the search; 0: none */,
+                                    int64_t records_avg /* >= 0: the KDE leaves the per-edge records of layers with this `avg`; -1: none */) {
     check_dev(pts, at::kFloat, "points");
     check_dev(centres, at::kFloat, "sample points");
     check_dev(bids, at::kInt, "batch ids");
@@ -788,11 +789,20 @@ std::shared_ptr<Geo> build_geometry(const Tensor& pts, const Tensor& bids, const
     // the cap of the search (by value into the helper thread's job / the batch entry)
     const mccnn_neighbor_cap cap{(int)max_neighbors, sample_seed >= 0 ? 1 : 0, sample_seed >= 0 ? (unsigned)sample_seed : 0u};
     const mccnn_neighbor_budget budget{(int)max_edges};
-    const size_t bytes = mccnn_geometry_bytes_budget(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors, budget.max_edges);
+    size_t bytes = mccnn_geometry_bytes_budget(n, m, (int)B, (int)nc, (int)capacity, grid_from ? 0 : 1, cap.max_neighbors, budget.max_edges);
     TORCH_CHECK(bytes > 0, "geometry: batch_size * num_cells^3 does not fit 32-bit keys");
+    // per-edge records from the build's KDE (mccnn_geometry_want_records): behind the geometry's own pieces, in the same
+    // buffer -- no block, event or stream ordering of their own
+    static const bool kde_records = mccnn::debug_int("kde_records", 1) != 0;
+    const bool want_records = records_avg >= 0 && kde_records && use_pdf && !point_pdf && !point_from;
+    if (want_records) bytes += mccnn_geometry_records_bytes((int)capacity);
     auto g = std::make_shared<Geo>();
     g->h = mccnn_geometry_create();
     TORCH_CHECK(g->h, "mccnn_geometry_create failed");
+    if (want_records) {
+        check(mccnn_geometry_want_records(g->h, records_avg ? 1 : 0), "geometry_want_records");
+        g->have |= 8;   // (the record buffer is there: a row plan built ahead attaches none of its own)
+    }
     g->slot = take_slot();
     g->keep = {pts, bids, centres, cbids, mn, mx};
     g->grid_owner = grid_from;
@@ -1173,6 +1183,8 @@ Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats, const Tensor& w1, con
         at::AutoDispatchBelowADInplaceOrView guard;
         geo->join(cur_stream(feats), geo->pre_avg != L.avg);
         if (geo->grid_owner) geo->grid_owner->join(cur_stream(feats));
+        // bit 2: the geometry holds the per-edge records of this layer (its KDE wrote them): read in both passes, kept by neither
+        if (L.fin == 1 && L.combin && mccnn_conv_uses_records(geo->h, L.fin, L.fout, L.combin, L.avg)) L.flags |= 4;
         long long wsb = 0, svb = 0;
         prepare(*geo, feats, L, 0, L.flags, wsb, svb);
         {
@@ -1760,7 +1772,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
              py::call_guard<py::gil_scoped_release>())
         .def("edges", &Geo::edges, py::arg("wait_us") = -1, py::call_guard<py::gil_scoped_release>())
         .def("info", &Geo::info, py::call_guard<py::gil_scoped_release>())
-        .def("cap_addr", &Geo::cap_addr, py::call_guard<py::gil_scoped_release>());
+        .def("cap_addr", &Geo::cap_addr, py::call_guard<py::gil_scoped_release>())
+        // (avg of the per-edge records the geometry holds or -1, their device address or 0)
+        .def("records", [](Geo& g) {
+            g.wait_issued();
+            const void* p = nullptr;
+            const int avg = mccnn_geometry_records(g.h, &p);
+            return std::make_pair(avg, (int64_t)(uintptr_t)p);
+        }, py::call_guard<py::gil_scoped_release>());
     py::class_<PointPdf, std::shared_ptr<PointPdf>>(mod, "PointPdf")
         .def_readonly("density", &PointPdf::density)
         .def_readonly("counts", &PointPdf::counts)
@@ -1772,7 +1791,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("side") = -1, py::arg("fork") = false, py::arg("background") = false,
             py::arg("after").none(true) = py::none(), py::arg("max_neighbors") = 0, py::arg("sample_seed") = -1,
             py::arg("point_pdf") = false, py::arg("point_from").none(true) = py::none(), py::arg("max_edges") = 0,
-            py::call_guard<py::gil_scoped_release>());
+            py::arg("records_avg") = -1, py::call_guard<py::gil_scoped_release>());
     mod.def("sampled_features", &sampled_features, py::call_guard<py::gil_scoped_release>());
     mod.def("begin_geometry_batch", &begin_geometry_batch);
     mod.def("end_geometry_batch", &end_geometry_batch, py::call_guard<py::gil_scoped_release>());

@@ -119,6 +119,7 @@ def _poll_parked():
         _PARKED_LOCK.release()
 
 
+_KDE_RECORDS = _env.debug("kde_records", True)   # (0: no geometry is asked for per-edge records -- A/B)
 _ECAP_SCALE = _env.debug("ecap_scale", 1.0)   # (debugging: generous / starved capacity guesses)
 
 
@@ -167,6 +168,7 @@ class Geometry:
         self.budget = 0         # maxEdges of the search (0: none): the search picks the cap itself, chosen_cap()
         self.point = False      # the PDFs are expanded from the per-point density of (grid, window): pdfMode='point'
         self.window = None
+        self.recordsAvg = None  # the `avg` of the per-edge records the build's KDE was asked to leave (None: not asked)
         # a grid owner: window -> (density [n,1] f32, counts [n,1] i32, handle of the extension or None) of its sorted points --
         # ONE pair per window, shared by every geometry over this grid (alive as long as the owner is)
         self.pointPairs = {}
@@ -210,7 +212,8 @@ class Geometry:
             capacity = min(capacity, max(self.budget, self.m))
         # (a per-point density does not depend on the list: the one that exists is expanded again, not computed again)
         _build_into(self, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity,
-                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1], pointPDF=self.point, maxEdges=self.budget)
+                    self.grid_owner, maxNeighbors=self.cap[0], sampleSeed=self.cap[1], pointPDF=self.point, maxEdges=self.budget,
+                    recordsAvg=self.recordsAvg)
         e = self.core.edges(-1) if self.core is not None else _lib.load().mccnn_geometry_edges(self.handle, -1)
         if e < 0 or e > self.e_cap:
             raise _lib.MCCNNError("geometry: rebuilt list still does not fit (%d > %d)" % (e, self.e_cap))
@@ -278,6 +281,24 @@ class Geometry:
         i = self._info()
         return self._view(self.buf, i[7], e * 4, torch.float32, (e, 1))
 
+    def records(self):
+        """(avg, records [E,4] f32) -- the per-edge records (delta, 1 / (pdf K)) the geometry holds, in edge order, and the
+        `avg` flag they were made for; None when it holds none (not asked for, or MCCNN_DEBUG=kde_records=0)."""
+        e = self.edges()
+        self._join()
+        if self.core is not None:
+            avg, addr = self.core.records()
+        else:
+            p = C.c_void_p(0)
+            avg = _lib.load().mccnn_geometry_records(self.handle, C.byref(p))
+            addr = p.value or 0
+        if avg < 0 or not addr:
+            return None
+        off = addr - self.buf.data_ptr()
+        if off < 0 or off + e * 16 > self.buf.numel():
+            return None   # (records in an attached buffer of a row plan, not the build's own)
+        return int(avg), self._view(self.buf, addr, e * 16, torch.float32, (e, 4))
+
     def chosen_cap(self):
         """int32 [1] on the device: the cap the search ran with -- K*, the cap a budgeted search chose (a view of the
         geometry's own word, written by the build; never read back here), or without a budget the caller's maxNeighbors.
@@ -309,8 +330,13 @@ class Geometry:
 
 
 def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, capacity, grid_from,
-                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False, maxEdges=0):
+                side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False, maxEdges=0,
+                recordsAvg=None):
     n, m = inPts.shape[0], centres.shape[0]
+    # per-edge records from the build's KDE: only lists whose PDFs come from it (MCCNN_DEBUG=kde_records=0: never)
+    if recordsAvg is not None and not (_KDE_RECORDS and usePDF and not pointPDF):
+        recordsAvg = None
+    g.recordsAvg = None if recordsAvg is None else int(bool(recordsAvg))
     g.cap = (int(maxNeighbors), None if sampleSeed is None else int(sampleSeed))   # (a rebuild repeats them: _rebuild)
     g.budget = int(maxEdges)
     g.point, g.window = bool(pointPDF), float(window)
@@ -321,7 +347,8 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
         g.core = _EXT.build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, float(radius), bool(scaleInv), float(window),
                                      bool(usePDF), capacity, grid_from.core if grid_from is not None else None, side, fork,
                                      background, after, int(maxNeighbors), -1 if sampleSeed is None else int(sampleSeed),
-                                     bool(pointPDF), pair[2] if pair is not None else None, int(maxEdges))
+                                     bool(pointPDF), pair[2] if pair is not None else None, int(maxEdges),
+                                     -1 if g.recordsAvg is None else g.recordsAvg)
         if pointPDF and pair is None:
             pp = g.core.point
             pairs[g.window] = (pp.density, pp.counts, pp)
@@ -343,6 +370,9 @@ def _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
             raise MemoryError("mccnn_geometry_create")
     if g.slot is None:
         g.slot = _slot()
+    check(lib.mccnn_geometry_want_records(g.handle, -1 if g.recordsAvg is None else g.recordsAvg), "geometry_want_records")
+    if g.recordsAvg is not None:   # (behind the geometry's own pieces, in the same buffer)
+        nbytes += lib.mccnn_geometry_records_bytes(capacity)
     g.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     g.attached = []
     g.keep = (inPts, inBids, centres, cbids, mn, mx)
@@ -385,7 +415,7 @@ def side_streams_available():
 
 def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF, grid_from=None,
                    side=-1, fork=False, background=False, after=None, maxNeighbors=0, sampleSeed=None, pointPDF=False,
-                   maxEdges=0):
+                   maxEdges=0, recordsAvg=None):
     """Enqueues grid + search + KDE of one convolution geometry; no host wait. nc: cells per axis
     (MCConvModule._num_cells). grid_from: a Geometry over the same points / radius whose grid is shared. side >= 0
     (torch extension only): the build runs on side stream `side` -- behind everything the current stream holds at the
@@ -403,7 +433,11 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
     maxEdges = B > 0 (with or without a cap of the caller's; not with pointPDF): the search picks, on the device, the largest
     cap K* whose list has at most B rows (find_neighbors(maxEdges=), the same bytes) -- Geometry.chosen_cap() is the device
     word it lands in. The list holds at most max(B, m) rows: the capacity is min(max(B, m), guess), and guesses of budgeted
-    shapes are kept apart from those of every other shape."""
+    shapes are kept apart from those of every other shape.
+    recordsAvg (None: no): the KDE of the build also leaves the per-edge records (delta, 1 / (pdf K)) the convolution kernels
+    read, for layers whose useAVG is this flag -- behind the geometry's pieces, in its buffer (16 bytes per edge of the
+    capacity). A one-input-feature combin layer over the geometry then reads them in both passes and neither evaluates nor
+    keeps records of its own (mccnn_geometry_want_records). Without effect on lists without a KDE (usePDF=False, pointPDF)."""
     n, m = inPts.shape[0], centres.shape[0]
     if isinstance(maxEdges, bool) or not isinstance(maxEdges, int) or not 0 <= maxEdges < 2 ** 31:
         raise ValueError("build_geometry: maxEdges is an integer in [0, 2^31) (0 = no budget)")
@@ -430,7 +464,7 @@ def build_geometry(inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleIn
         capacity = max(1, min(max(maxEdges, m), capacity))
     _build_into(g, inPts, inBids, centres, cbids, mn, mx, B, nc, radius, scaleInv, window, usePDF,
                 capacity, grid_from, side if _EXT is not None else -1, fork, background,
-                after if _EXT is not None else None, maxNeighbors, sampleSeed, pointPDF, maxEdges)
+                after if _EXT is not None else None, maxNeighbors, sampleSeed, pointPDF, maxEdges, recordsAvg)
     return g
 
 
@@ -483,9 +517,11 @@ class _Conv(torch.autograd.Function):
         flags = (1 if need_grad else 0) | (2 if deterministic else 0)
         combin = 1 if combin else 0
         avg = 1 if avg else 0
+        if fin == 1 and combin and lib.mccnn_conv_uses_records(geo.handle, fin, fout, combin, avg):
+            flags |= 4   # the geometry holds this layer's per-edge records: read in both passes, kept by neither
         dev = feats.device
         out = torch.empty((geo.m, fout if combin else fin), dtype=feats.dtype, device=dev)
-        skey = (flags & 1, fin, fout, combin, bf16, geo.n, geo.m)
+        skey = (flags & 5, fin, fout, combin, bf16, geo.n, geo.m)
         wsb, svb = _SIZES.get(skey, (0, -1))
         if svb < 0:
             wsb, svb = _prepare(geo, feats, fin, fout, combin, bf16, 0, flags)
