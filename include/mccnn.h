@@ -338,7 +338,14 @@ int mccnn_poisson_sampling_fill(const float* sorted_pts, int n, const int* cell_
  * needs again: one 16-byte record (delta, 1 / (pdf K)) per edge and, for combin layers with one
  * input feature, the per-centre sums of the factored algorithm; handing the same buffer to
  * mccnn_spatial_conv_bwd saves it its pre-pass over the edges (and, for those layers, one more).
- * NULL is always allowed (the reference op has no such output: SpatialConvGrad then recomputes). */
+ * NULL is always allowed (the reference op has no such output: SpatialConvGrad then recomputes).
+ * Shapes: the six MLP tensors hold 8 * ceil(neurons / 8) neurons, neurons = num_in_feats *
+ * num_out_feats (combin; the padded count must be a multiple of num_in_feats, spatial_conv.cc:290) or
+ * num_in_feats (depth-wise, num_out_feats == num_in_feats). A depth-wise layer may have ANY width:
+ * the reference's op wrapper asks for num_in_feats % 8 == 0 (spatial_conv.cc:292-296), its kernels do
+ * not, and neither do these -- the last block's neurons beyond num_in_feats are padding. Feature rows,
+ * outputs and out-gradients need 4-byte alignment only (16-byte aligned rows of a multiple of 8
+ * features take the vector kernels). MCCNN_E_SHAPE otherwise. */
 size_t mccnn_spatial_conv_state_bytes(int m, int e, int num_in_feats, int num_out_feats, int combin);
 size_t mccnn_spatial_conv_fwd_workspace_bytes(int m, int e, int num_in_feats, int num_out_feats,
                                               int combin);

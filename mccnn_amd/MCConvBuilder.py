@@ -1145,12 +1145,10 @@ class ConvolutionBuilder(_PlainState, torch.nn.Module):
             return None
         if not feats.is_contiguous():
             feats = feats.contiguous()
-        # the op's shape rules (spatial_conv.cc:290-296)
+        # the op's shape rule (spatial_conv.cc:290; a depth-wise layer may have any width, see MCConvModule._conv_checks)
         neurons = inNumFeatures * numOutFeatures if multiFeatureConv else inNumFeatures
-        if ((neurons + 7) // 8 * 8) % inNumFeatures != 0:
+        if multiFeatureConv and ((neurons + 7) // 8 * 8) % inNumFeatures != 0:
             raise _hip_ops.InvalidArgumentError("SpatialConvOp expects a number of output neurons multiple of the number of features.")
-        if not multiFeatureConv and inNumFeatures % 8 != 0:
-            raise _hip_ops.InvalidArgumentError("SpatialConvOp expects the same number of features in the input and the output")
         lay = self.layers_.get(convName)
         spec = (inNumFeatures, numOutFeatures, bool(multiFeatureConv))
         if lay is None or lay[0] != spec:

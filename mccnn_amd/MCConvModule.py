@@ -52,6 +52,16 @@ def _rows32(t):
     return t.view(torch.float32) if t.dtype == torch.bfloat16 else t
 
 
+def _bf16_rows_aligned(t):
+    """bf16 rows on a 16-byte boundary: the bf16 kernels move 16-byte pieces (csrc/conv.hip bf16_shape_ok, the row kernels'
+    rows_shape_ok) and the row permutations see the rows as 32-bit words, so a contiguous bf16 tensor that starts anywhere
+    else (a view into a larger buffer) is copied into an allocation of its own. f32 tensors pass through: their kernels have
+    scalar forms for that."""
+    if t.dtype == torch.bfloat16 and (t.data_ptr() & 15) != 0:
+        return t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def _like_rows(words, ref):
     """Undo _rows32 for a result tensor."""
     return words.view(torch.bfloat16) if ref.dtype == torch.bfloat16 else words
@@ -1387,9 +1397,13 @@ def _conv_checks(op, pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2
     _req(w3.dim() == 2 and w3.shape[0] == bs and b3.dim() == 1 and w3.shape[1] == b3.shape[0],
          op + " expects a correct output layer")
     fin = feats.shape[1]
-    _req(w3.shape[1] % fin == 0, op + " expects a number of output neurons multiple of the number of features.")
-    if not combin:
-        _req(w3.shape[1] == fin, op + " expects the same number of features in the input and the output")
+    _req(fin > 0, op + " expects features with at least one component")
+    if combin:
+        _req(w3.shape[1] % fin == 0, op + " expects a number of output neurons multiple of the number of features.")
+    else:
+        # (the reference's op also asks for numFeatures output neurons, i.e. numFeatures % 8 == 0, spatial_conv.cc:292-296;
+        # extension: a depth-wise layer of any width, its last block padded like a combining layer's -- the rule below)
+        _req(numOutFeatures == fin, op + " expects the same number of features in the input and the output")
     neurons = fin * numOutFeatures if combin else fin
     nb = (neurons + bs - 1) // bs
     _req(w1.shape[1] == nb * bs and w3.shape[1] == nb * bs, op + " expects %d neurons per layer" % (nb * bs))
@@ -1402,7 +1416,7 @@ class _SpatialConv(torch.autograd.Function):
                 aabbMax, weights1, biases1, weights2, biases2, weightsOut, biasesOut, numOutFeatures, combin,
                 batchSize, radius, scaleInv, avg, sortIndex=None, trusted=False, featIndex=None):
         op = "SpatialConvOp"
-        feats = _feat(inFeatures, "features")
+        feats = _bf16_rows_aligned(_feat(inFeatures, "features"))
         bf16 = feats.dtype == torch.bfloat16
         # the kernel-MLP tensors may arrive in the shapes the builder STORES them in ([numBlocks, bs, bs] / [numBlocks, bs],
         # MCConvBuilder.py:407-419) -- the same memory as the [bs, numBlocks*bs] / [numBlocks*bs] operands of the op, so the
@@ -1459,8 +1473,8 @@ class _SpatialConv(torch.autograd.Function):
             _req(feats.dim() == 2 and feats.shape[0] == n,
                  op + " expects as feature inputs the following dimensions (numPoints, numFeatures)")
             # the two shape rules that depend on the CALLER's layer shape (spatial_conv.cc:290-296)
-            _req(w3.shape[1] % fin == 0, op + " expects a number of output neurons multiple of the number of features.")
-            _req(combin or w3.shape[1] == fin, op + " expects the same number of features in the input and the output")
+            _req(not combin or w3.shape[1] % fin == 0, op + " expects a number of output neurons multiple of the number of features.")
+            _req(combin or w3.shape[1] == (fin + 7) // 8 * 8, op + " expects the same number of features in the input and the output")
         else:
             n, m, e, fin = _conv_checks(op, pts, feats, bids, pdfs, smp, st, pk, mn, mx, w1, b1, w2, b2, w3, b3,
                                         numOutFeatures, combin, batchSize, radius)
@@ -1536,6 +1550,7 @@ class _SpatialConv(torch.autograd.Function):
         og = _feat(outGrad, "out_features_grad")
         if bf16 and og.dtype != torch.bfloat16:
             og = og.to(torch.bfloat16)
+        og = _bf16_rows_aligned(og)   # (a misaligned f32 out-gradient stays where it is: the scalar streaming kernels below)
         lib = _lib.load()
         n, fin = feats.shape
         m, e = smp.shape[0], pk.shape[0]

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void conv_stream(ConvArgs a, float* __restrict
     if (cA >= cB) return;
     const int eBeg = a.start[cA];
     const int eEnd = (cB < a.m) ? a.start[cB] : a.e;
-    const bool vecOut = (!COMBIN || FEAT == 1) && (outF & 3) == 0;
+    const bool vecOut = (!COMBIN || FEAT == 1) && (outF & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;  // (column tiles start at multiples of 32 bytes)
     constexpr bool BF = FEAT == 4;  // bf16 rows: `a.feats` and `out` hold 2-byte elements
     const unsigned short* feats16 = reinterpret_cast<const unsigned short*>(a.feats);
     unsigned short* out16 = reinterpret_cast<unsigned short*>(out);
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256, (COMBIN && FEAT != 1) ? MCCNN_BWD_OCC_COMBIN :
                 for (int n = 0; n < 8; ++n) { g[n] = act ? gg[n] : 0.f; ff[n] = f8[n]; }
             } else if (FEAT == 1) {
                 float f = a.feats[j];
-                if (numOuts == 8 && (outF & 3) == 0) {
+                if (numOuts == 8 && (outF & 3) == 0 && (reinterpret_cast<uintptr_t>(outGrad) & 15) == 0) {
                     const float4* gp = reinterpret_cast<const float4*>(grow + q * 8);
                     float4 ga = gp[0], gb = gp[1];
                     float gg[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
@@ -1117,7 +1117,10 @@ static int fill_args(ConvArgs& a, const float* sorted_pts, const float* sorted_f
     if (neurons > (1 << 24)) return MCCNN_E_TOOLARGE;
     a.neuronsOut = (int)neurons;
     a.nb = (a.neuronsOut + 7) / 8;
-    if ((a.nb * 8) % Fin != 0) return MCCNN_E_SHAPE;    // spatial_conv.cc:290
+    // spatial_conv.cc:290, combining layers. (The op wrapper of the reference also asks a depth-wise layer for as many
+    // output neurons as features, spatial_conv.cc:292-296, i.e. Fin % 8 == 0; its kernels and these do not need that:
+    // neuron nu reads feature nu and writes column nu, the last block's neurons beyond Fin are padding -- any width runs.)
+    if (combin && (a.nb * 8) % Fin != 0) return MCCNN_E_SHAPE;
     a.outF = combin ? Fout : Fin;
     a.pts = sorted_pts; a.feats = sorted_feats; a.bids = sorted_batch_ids; a.pdfs = pdfs; a.samples = samples;
     a.start = start_idx; a.packed = reinterpret_cast<const int2*>(packed); a.mn = aabb_min; a.mx = aabb_max;

@@ -452,7 +452,7 @@ __global__ __launch_bounds__(256) void f1_fwd_centres(ConvArgs a, const float* _
         o[n] = acc;
     }
     float* dst = out + (size_t)i * a.outF + q * 8;
-    if ((a.outF & 3) == 0 && q * 8 + 8 <= a.outF) {
+    if ((a.outF & 3) == 0 && q * 8 + 8 <= a.outF && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {  // (rows of a multiple of 4 floats from a 16-byte aligned base)
         reinterpret_cast<float4*>(dst)[0] = make_float4(o[0], o[1], o[2], o[3]);
         reinterpret_cast<float4*>(dst)[1] = make_float4(o[4], o[5], o[6], o[7]);
     } else {
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(256) void f1_bwd_centres(ConvArgs a, const float* _
             const float* row = outGrad + (size_t)i * a.outF;
             float gbv = 0.f;
             int f = 0;
-            if ((a.outF & 3) == 0) {
+            if ((a.outF & 3) == 0 && (reinterpret_cast<uintptr_t>(outGrad) & 15) == 0) {  // (a caller's pointer: 16-byte loads only from an aligned base)
                 for (; f + 4 <= a.outF; f += 4) {
                     const float4 gg = *reinterpret_cast<const float4*>(row + f);
                     gbv = fmaf(gg.x, a.b3[f], gbv);
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(256) void f1_bwd_centres(ConvArgs a, const float* _
         return;
     }
     const int rowA = a.nb * 8;
-    const bool vec = (a.outF & 3) == 0 && q * 8 + 8 <= a.outF;
+    const bool vec = (a.outF & 3) == 0 && q * 8 + 8 <= a.outF && (reinterpret_cast<uintptr_t>(outGrad) & 15) == 0;
     float wq[64];  // W3[8][8] of this block: wave-uniform -> scalar registers
 #pragma unroll
     for (int r = 0; r < 64; ++r) wq[r] = a.w3[q * 64 + r];

@@ -1086,6 +1086,7 @@ struct ConvBackward : public torch::autograd::Node {
     // what it guards against, an input modified in place since the forward pass, is checked here directly)
     Tensor feats_, w1_, b1_, w2_, b2_, w3_, b3_;
     uint32_t versions[7] = {0, 0, 0, 0, 0, 0, 0};
+    Tensor rows_;   // bf16 rows that did not start on a 16-byte boundary: the aligned copy the forward pass read (conv())
     Tensor saved;
     Layer L;
 
@@ -1093,7 +1094,7 @@ struct ConvBackward : public torch::autograd::Node {
         const Tick tick_all(T_BWD);
         TORCH_CHECK(geo && feats_.defined(), "MC convolution: backward through a graph whose buffers have been freed (retain_graph=True?)");
         const DevGuard device_guard((int)geo->buf.device().index());
-        const Tensor &feats = feats_, &w1 = w1_, &b1 = b1_, &w2 = w2_, &b2 = b2_, &w3 = w3_, &b3 = b3_;
+        const Tensor &feats = rows_.defined() ? rows_ : feats_, &w1 = w1_, &b1 = b1_, &w2 = w2_, &b2 = b2_, &w3 = w3_, &b3 = b3_;
         {
             const Tensor* in[7] = {&feats_, &w1_, &b1_, &w2_, &b2_, &w3_, &b3_};
             for (int k = 0; k < 7; ++k)
@@ -1105,6 +1106,9 @@ struct ConvBackward : public torch::autograd::Node {
         if (!og.defined()) og = at::zeros({geo->m, L.combin ? L.fout : L.fin}, feats.options());
         if (!og.is_contiguous()) og = og.contiguous();
         if (og.scalar_type() != feats.scalar_type()) og = og.to(feats.scalar_type());
+        // (bf16 rows: the kernels move 16-byte pieces; an out-gradient that starts anywhere else -- a view into a larger
+        // buffer -- is copied into an allocation of its own. f32 rows stay where they are: scalar kernels exist for them)
+        if (L.bf16 && (reinterpret_cast<uintptr_t>(og.data_ptr()) & 15) != 0) og = og.clone(at::MemoryFormat::Contiguous);
         int flags = L.flags;
         // several layers share this neighbour list: its transposed form is built once and the feature gradient of combin
         // layers with 2..4 input features is gathered through it in a fixed order (bit-reproducible) instead of added
@@ -1152,6 +1156,7 @@ struct ConvBackward : public torch::autograd::Node {
 
     void release_variables() override {
         feats_.reset(); w1_.reset(); b1_.reset(); w2_.reset(); b2_.reset(); w3_.reset(); b3_.reset();
+        rows_.reset();
         saved.reset();
         geo.reset();
     }
@@ -1160,27 +1165,33 @@ struct ConvBackward : public torch::autograd::Node {
 // One MC convolution over `geo` (SpatialConv with sort_features folded in, MCConvModuleSrc:35-45,70-81): feats are the
 // rows of the UNSORTED input points ([n, Fin] f32, or bf16 for depth-wise layers); the kernel-MLP tensors in any shape
 // over the reference's flat layout.
-Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats_in, const Tensor& w1, const Tensor& b1, const Tensor& w2,
             const Tensor& b2, const Tensor& w3, const Tensor& b3, int64_t fout, bool combin, bool avg, bool deterministic) {
     TORCH_CHECK(geo && geo->h, "conv: no geometry");
-    const DevGuard device_guard((int)feats.device().index());
-    TORCH_CHECK(feats.defined() && feats.is_cuda() && feats.dim() == 2 && feats.size(0) == geo->n && feats.is_contiguous(),
+    const DevGuard device_guard((int)feats_in.device().index());
+    TORCH_CHECK(feats_in.defined() && feats_in.is_cuda() && feats_in.dim() == 2 && feats_in.size(0) == geo->n && feats_in.is_contiguous(),
                 "SpatialConvOp expects as feature inputs the following dimensions (numPoints, numFeatures)");
-    const bool bf = feats.scalar_type() == at::kBFloat16;
-    TORCH_CHECK(bf || feats.scalar_type() == at::kFloat, "features must be float32 or bfloat16");
+    const bool bf = feats_in.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(bf || feats_in.scalar_type() == at::kFloat, "features must be float32 or bfloat16");
     for (const Tensor* t : {&w1, &b1, &w2, &b2, &w3, &b3}) check_dev(*t, at::kFloat, "kernel-MLP tensor");
     Layer L;
-    L.fin = (int)feats.size(1); L.fout = (int)fout; L.combin = combin ? 1 : 0; L.avg = avg ? 1 : 0; L.bf16 = bf ? 1 : 0;
+    L.fin = (int)feats_in.size(1); L.fout = (int)fout; L.combin = combin ? 1 : 0; L.avg = avg ? 1 : 0; L.bf16 = bf ? 1 : 0;
     const bool need_grad = at::GradMode::is_enabled() &&
-                           (feats.requires_grad() || w1.requires_grad() || b1.requires_grad() || w2.requires_grad() ||
+                           (feats_in.requires_grad() || w1.requires_grad() || b1.requires_grad() || w2.requires_grad() ||
                             b2.requires_grad() || w3.requires_grad() || b3.requires_grad());
     // bit 1: the caller asks for bit-reproducible feature gradients (combin layers with 2..4 input features gather them
     // through the transposed list instead of adding them with float atomics)
     L.flags = (need_grad ? 1 : 0) | (deterministic ? 2 : 0);
     Tensor out, saved;
+    // bf16 rows that do not start on a 16-byte boundary (a view into a larger buffer): the bf16 kernels move 16-byte pieces
+    // and the permutes see the rows as 32-bit words, so such rows are copied into an allocation of their own, which both
+    // passes read. f32 rows stay where they are: the executor leaves the in-place mode and the vector kernels by itself.
+    Tensor rows_copy;
     const Tick tick_all(T_FWD);
     {
         at::AutoDispatchBelowADInplaceOrView guard;
+        if (bf && (reinterpret_cast<uintptr_t>(feats_in.data_ptr()) & 15) != 0) rows_copy = feats_in.detach().clone(at::MemoryFormat::Contiguous);
+        const Tensor& feats = rows_copy.defined() ? rows_copy : feats_in;
         geo->join(cur_stream(feats), geo->pre_avg != L.avg);
         if (geo->grid_owner) geo->grid_owner->join(cur_stream(feats));
         // bit 2: the geometry holds the per-edge records of this layer (its KDE wrote them): read in both passes, kept by neither
@@ -1203,11 +1214,12 @@ Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats, const Tensor& w1, con
     }
     if (need_grad) {
         auto node = std::shared_ptr<ConvBackward>(new ConvBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(feats, w1, b1, w2, b2, w3, b3));
+        node->set_next_edges(torch::autograd::collect_next_edges(feats_in, w1, b1, w2, b2, w3, b3));
         node->geo = geo;
-        node->feats_ = feats; node->w1_ = w1; node->b1_ = b1; node->w2_ = w2; node->b2_ = b2; node->w3_ = w3; node->b3_ = b3;
+        node->rows_ = rows_copy;
+        node->feats_ = feats_in; node->w1_ = w1; node->b1_ = b1; node->w2_ = w2; node->b2_ = b2; node->w3_ = w3; node->b3_ = b3;
         {
-            const Tensor* in[7] = {&feats, &w1, &b1, &w2, &b2, &w3, &b3};
+            const Tensor* in[7] = {&feats_in, &w1, &b1, &w2, &b2, &w3, &b3};
             for (int k = 0; k < 7; ++k) node->versions[k] = in[k]->_version();
         }
         node->saved = saved;

@@ -15,7 +15,7 @@ import torch
 
 from . import _env, _lib
 from ._lib import check, ptr, stream_handle
-from .MCConvModule import _edge_guess, _remember_edges, _ws
+from .MCConvModule import _edge_guess, _remember_edges, _ws, _bf16_rows_aligned
 
 
 def _load_ext():
@@ -514,6 +514,7 @@ class _Conv(torch.autograd.Function):
         bf16 = 1 if feats.dtype == torch.bfloat16 else 0
         need_grad = feats.requires_grad or w1.requires_grad or w3.requires_grad or w2.requires_grad or b1.requires_grad \
             or b2.requires_grad or b3.requires_grad
+        feats = _bf16_rows_aligned(feats)   # (no-op for f32 rows and aligned bf16 rows; both passes read the same tensor)
         flags = (1 if need_grad else 0) | (2 if deterministic else 0)
         combin = 1 if combin else 0
         avg = 1 if avg else 0
@@ -569,6 +570,7 @@ class _Conv(torch.autograd.Function):
         og = outGrad if outGrad.is_contiguous() else outGrad.contiguous()
         if og.dtype != feats.dtype:
             og = og.to(feats.dtype)
+        og = _bf16_rows_aligned(og)
         dev = feats.device
         fg = torch.empty_like(feats)
         # the six MLP gradients: consecutive slices of ONE buffer in the order the builder creates the variables (a

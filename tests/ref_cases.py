@@ -86,6 +86,9 @@ CASES = [
     _c("1to13_noavg_abs", 1, 13, True, False, False, 0.12),
     _c("1to64_nostate", 1, 64, True, True, True, 0.15, nostate=True),
     _c("dw32_bf16rows", 32, 32, False, True, True, 0.15, bf16=True),
+    # depth-wise widths that are no multiple of 8: the scalar instantiations of the HIP streaming kernels
+    _c("dw12_padded", 12, 12, False, True, True, 0.15),
+    _c("dw4_noavg_abs", 4, 4, False, False, False, 0.12),
 ]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 #: the smallest cases, whose reference outputs are kept as fixtures tests/golden/ref_<name>.npz

@@ -56,6 +56,33 @@ def test_binding_covers_header_and_loads(lib_path):
     assert lib.mccnn_spatial_conv_bwd_workspace_bytes(1000, 1000, 50000, 1, 64, 1) > 50000 * 16
 
 
+def test_bf16_convolution_entries_refuse_rows_off_the_16_byte_grid(lib_path):
+    """The bf16 kernels move 16-byte pieces of the feature / gradient rows, so the two bf16 entry points answer
+    MCCNN_E_SHAPE for a row pointer that is not 16-byte aligned (csrc/conv.hip bf16_shape_ok) -- before anything is
+    launched or read, which is why made-up addresses and no GPU do here. (The Python ops and the torch extension copy such
+    rows into an allocation of their own instead of handing them on: tests/test_gpu_conv_alignment.py.)"""
+    from mccnn_amd import _lib
+    lib = _lib.load()
+    E_SHAPE = -5
+    assert b"shape" in lib.mccnn_error_string(E_SHAPE).lower()
+    A = 0x7f0000000000          # a made-up, 16-byte aligned address: never dereferenced by the calls below
+    p = [A + 0x10000 * k for k in range(32)]
+    n = m = 64
+    e, fin = 256, 16
+
+    def fwd(feats, out):
+        return lib.mccnn_spatial_conv_fwd_bf16(p[0], feats, *p[2:15], n, m, e, fin, 1, 0.1, 0, 1, out, p[16], 1 << 20, None)
+
+    def bwd(feats, og, fg):
+        return lib.mccnn_spatial_conv_bwd_bf16(p[0], feats, *p[2:15], og, n, m, e, fin, 1, 0.1, 0, 1, p[17], p[18], fg,
+                                               *p[20:26], p[16], 1 << 20, None)
+
+    for d in (2, 4, 8):
+        assert fwd(p[1] + d, p[15]) == E_SHAPE and fwd(p[1], p[15] + d) == E_SHAPE
+        assert bwd(p[1] + d, p[19], p[26]) == E_SHAPE and bwd(p[1], p[19] + d, p[26]) == E_SHAPE
+        assert bwd(p[1], p[19], p[26] + d) == E_SHAPE
+
+
 def _code_objects(lib_path, tmp_path):
     """llvm-objdump --offloading EXTRACTS the bundles next to its input: work on a copy in a scratch directory.
     -> (objdump's text, paths of the extracted gfx950 code objects)"""

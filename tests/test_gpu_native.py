@@ -32,6 +32,9 @@ LAYERS = [  # name, lin, lout, fin, fout, combin, radius, bf16
     ("Up_dw", 1, 0, 16, 16, False, 0.3, False),         # same grid as Conv_l1, centres of level 0
     ("Conv_bf16", 0, 0, 16, 16, False, 0.12, True),
     ("Conv_2to5", 0, 0, 2, 5, True, 0.12, False),       # combin with padded neurons (10 -> 16)
+    # depth-wise, 12 features: Fin % 8 != 0, so neither the row kernels nor the vector streaming kernels (exec.hip
+    # rows_shape, conv.hip vec / vecD) -- rows of 12 words through the executor's permutes and the scalar streaming path
+    ("Conv_dw12", 0, 0, 12, 12, False, 0.12, False),
 ]
 
 
@@ -176,20 +179,40 @@ def test_native_room_layers_against_the_oracle(mc, oracle_omp):
 
 
 def test_native_path_keeps_the_ops_shape_rules(mc):
-    """spatial_conv.cc:290-296: the output neurons must be a multiple of the input features, and a depth-wise layer needs
-    exactly numInFeatures neurons (numInFeatures % 8 == 0) -- the native path raises like the op does."""
+    """spatial_conv.cc:290: the (padded) output neurons of a combining layer must be a multiple of the input features -- the
+    native path raises like the op does. A depth-wise layer may have any width (the reference's op wrapper asks for
+    numInFeatures % 8 == 0, spatial_conv.cc:292-296; its kernels, the oracle and the HIP kernels pad the last block): both
+    paths compute it, to the same values."""
     import torch
     from mccnn_amd.MCConvBuilder import PointHierarchy, ConvolutionBuilder
     from mccnn_amd.MCConvModule import InvalidArgumentError
     pts, bids = make_cloud(500, 1, 3, "uniform", False)
     P, Bi = _t(pts), _t(bids)
     ph = PointHierarchy(P, torch.ones((len(pts), 1), device="cuda"), Bi, [], "PH", 1, True)
-    for fin, fout, combin in ((4, 4, False), (3, 5, True)):
-        for native in (True, False):
-            cb = ConvolutionBuilder(relativeRadius=True, native=native)
-            F = torch.rand((len(pts), fin), device="cuda")
-            with pytest.raises(InvalidArgumentError):
-                cb.create_convolution("C", ph, 0, F, fin, 0.2, outNumFeatures=fout, multiFeatureConv=combin)
+    for native in (True, False):
+        cb = ConvolutionBuilder(relativeRadius=True, native=native)
+        F = torch.rand((len(pts), 3), device="cuda")
+        with pytest.raises(InvalidArgumentError):
+            cb.create_convolution("C", ph, 0, F, 3, 0.2, outNumFeatures=5, multiFeatureConv=True)
+        with pytest.raises(RuntimeError):   # a depth-wise layer keeps its width (MCConvBuilder.py:328-333)
+            cb.create_convolution("D", ph, 0, torch.rand((len(pts), 4), device="cuda"), 4, 0.2, outNumFeatures=8, multiFeatureConv=False)
+    outs, sd = [], None
+    F4 = torch.rand((len(pts), 4), device="cuda")
+    for native in (False, True):
+        torch.manual_seed(5)
+        cb = ConvolutionBuilder(relativeRadius=True, native=native)
+        if sd is not None:
+            cb.load_state_dict(sd)
+        cb.reset()
+        f = F4.clone().requires_grad_(True)
+        out = cb.create_convolution("C", ph, 0, f, 4, 0.2, outNumFeatures=4, multiFeatureConv=False)
+        assert bool(cb.cacheGeo_) == native and out.shape == (len(pts), 4)
+        (fg,) = torch.autograd.grad(out, f, torch.ones_like(out))
+        outs.append((out.detach(), fg))
+        sd = {k: v.detach().clone() for k, v in cb.state_dict().items()}
+        assert dict(cb.named_parameters())["C_weights3"].shape == (1, 8, 8)   # one block, four padded neurons
+    _close(outs[1][0], outs[0][0], 2e-5, "dw4 out")
+    _close(outs[1][1], outs[0][1], 2e-5, "dw4 featGrad")
 
 
 def test_learned_geometry_prefetch_on_side_streams(mc):

@@ -166,6 +166,19 @@ CONV_CASES = [
     ("1to256_combin", 1, 256, True, True, True, 0.15),  # nb = 32 through the factored path
     ("1to13_combin_padded_noavg_abs", 1, 13, True, False, False, 0.12),  # factored Fin=1 path, 3 padded neurons
     ("1to64_combin_nostate", 1, 64, True, True, True, 0.15),  # backward without the forward's state: recomputed
+    # Depth-wise layers whose width is no multiple of 8: launch_conv_stream / conv_bwd_impl compute vec = !combin &&
+    # Fin % 8 == 0 && (pointers 16-byte aligned), the row kernels ask Fin % 8 == 0 too (_rows_shape), so Fin % 8 != 0 =>
+    # vec == vecD == false => conv_stream<false, 0, false> (forward), conv_stream<false, 0, true> (feature gradient over
+    # the transposed list) and conv_bwd_mfma<false, 0, coop> (parameter gradients; coop at >= 4 blocks per tile): the
+    # scalar gathers with the incremental fin bookkeeping, the guarded store of a half-padded block, zero_rows with a
+    # width that is no whole block, tile_args' clipped neuronsOut.
+    ("dw1", 1, 1, False, True, True, 0.15),  # nb = 1 with 7 padded neurons; depth-wise, so NOT the factored Fin = 1 path
+    ("dw3", 3, 3, False, True, True, 0.15),  # outF & 3 != 0: scalar stores only
+    ("dw4_noavg_abs", 4, 4, False, False, False, 0.12),  # vecOut is true and the block is half padding: the next row's hazard
+    ("dw12", 12, 12, False, True, True, 0.15),  # nb = 2: a whole block stored as two float4, a half block scalar; 48-byte rows
+    ("dw20_noavg_abs", 20, 20, False, False, False, 0.12),
+    ("dw28", 28, 28, False, True, True, 0.15),  # nb = 4: the cooperative backward kernel with 4 padded neurons
+    ("dw524_column_tiles_padded", 524, 524, False, True, True, 0.3),  # nb = 66: two fwd / two bwd tiles of 33 blocks, the last block half padded
 ]
 
 
@@ -182,6 +195,10 @@ def test_spatial_conv_fwd_bwd(mc, oracle, case):
     g = run_chain(mc, _wrap, _unwrap, pts, bids, feats, B, radius, scaleInv, fout=fout, combin=combin)
     for k in INT_KEYS:
         assert np.array_equal(g[k], o[k]), k
+    if not combin and fin % 8 != 0:
+        # the scalar depth-wise kernels: rows longer than a wave's 64-edge chunk (carry across chunks), several waves
+        deg = np.diff(np.append(o["startIndexs"].reshape(-1), len(o["packedNeighs"])))
+        assert deg.max() > 64 and len(o["packedNeighs"]) > 4 * 64
     w = o["mlp"]
     outF = fout if combin else fin
     og = (2 * np.random.default_rng(11).random((len(pts), outF)) - 1).astype(np.float32)
@@ -239,10 +256,13 @@ def test_spatial_conv_fwd_bwd(mc, oracle, case):
     assert np.all(dw3[neurons * 8:] == 0)
 
 
-@pytest.mark.parametrize("fin,fout,combin", [(1, 16, True), (3, 8, True), (16, 16, False)], ids=["f1", "combin", "dw"])
+@pytest.mark.parametrize("fin,fout,combin", [(1, 16, True), (3, 8, True), (16, 16, False), (4, 4, False), (12, 12, False)],
+                         ids=["f1", "combin", "dw", "dw4", "dw12"])
 def test_conv_centres_without_neighbours(mc, oracle, fin, fout, combin):
     """Ragged neighbour lists: centres far from every point (empty rows at the start, in the middle and at the end
-    of the list) give zero output rows and take no part in the gradients; one centre owns a very long row."""
+    of the list) give zero output rows and take no part in the gradients; one centre owns a very long row. dw4 / dw12:
+    the scalar streaming kernels (Fin % 8 != 0), whose zero_rows clears a width that is no whole block. The output
+    buffers are taken from memory that held NaNs, so a row or a padded column nobody writes shows."""
     import torch
     B, radius = 1, 0.2
     pts, bids = make_cloud(1200, B, 33, "clustered", True)
@@ -269,13 +289,22 @@ def test_conv_centres_without_neighbours(mc, oracle, fin, fout, combin):
     h = g["_handles"]
     tw = {k: _wrap(v).requires_grad_(True) for k, v in w.items()}
     sF = h["sF"].detach().clone().requires_grad_(True)
-    out = mc.spatial_conv(h["sP"], sF, h["sB"], _wrap(o["pdfs"]), h["C"], h["start"], h["packed"], h["mn"], h["mx"],
+    pdfs, ogT = _wrap(o["pdfs"]), _wrap(og)
+    # poison the blocks the op's torch.empty() calls are about to receive
+    junk = [torch.full((len(centres), outF), float("nan"), device="cuda"), torch.full((len(pts), fin), float("nan"), device="cuda")]
+    torch.cuda.synchronize()
+    del junk
+    out = mc.spatial_conv(h["sP"], sF, h["sB"], pdfs, h["C"], h["start"], h["packed"], h["mn"], h["mx"],
                           tw["w1"], tw["w2"], tw["w3"], tw["b1"], tw["b2"], tw["b3"], fout, combin, B, radius, False, True)
     got = _unwrap(out)
-    assert np.all(got[deg == 0] == 0)
+    assert np.isfinite(got).all() and np.all(got[deg == 0] == 0)
     assert_close(got, ref, RTOL, "spatial_conv")
-    out.backward(_wrap(og))
+    junk = [torch.full((len(pts), fin), float("nan"), device="cuda"), torch.full((len(centres), outF), float("nan"), device="cuda")]
     torch.cuda.synchronize()
+    del junk
+    out.backward(ogT)
+    torch.cuda.synchronize()
+    assert np.isfinite(_unwrap(sF.grad)).all()
     gg = [sF.grad, tw["w1"].grad, tw["b1"].grad, tw["w2"].grad, tw["b2"].grad, tw["w3"].grad, tw["b3"].grad]
     for nm, a, b in zip(["featGrad", "dw1", "db1", "dw2", "db2", "dw3", "db3"], gg, rg):
         assert_close(_unwrap(a), b, RTOL, nm)

@@ -48,6 +48,7 @@ CASES = [  # combin, fin, fout, bf16, scaleInv, avg
     (False, 16, 16, False, True, True),   # row kernels
     (False, 64, 64, False, False, False),
     (False, 32, 32, True, True, True),    # bf16 rows
+    (False, 12, 12, False, True, True),   # depth-wise, Fin % 8 != 0: one whole block and one half padded
 ]
 
 
