@@ -26,9 +26,13 @@ class MCClassS(torch.nn.Module):
     whose sub-modules (the convolution builder and the dense helpers' variable store) register every variable under
     the reference's name, so `parameters()` / `state_dict()` / optimisers / DDP see the whole network."""
 
-    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False):
+    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k, numOutCat)
+        # rows (extension): torch.bfloat16 keeps the input rows of the depth-wise Conv_2 and Conv_3 in bf16 (they gather
+        # half the bytes). The glue blocks around them are the casts -- with fused=True one library op each, f32 statistics
+        # either way; the 1x1 matmuls and the MLP stay f32. None: every call is the f32 network's.
+        self.rows = rows
         # fused (extension): batch norm + ReLU + dropout of the dense glue as one library op (VariableStore.fused_)
         self.store = VariableStore(device, fused=fused)
         self.ops = ops  # None = the HIP op surface; the parity tests pass the CPU checker's
@@ -64,17 +68,23 @@ class MCClassS(torch.nn.Module):
             inNumFeatures=numInputFeatures, outNumFeatures=k, convRadius=0.2, multiFeatureConv=True)
         convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_In_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv, st)
         convFeatures1 = conv_1x1("Reduce_1", convFeatures1, k, k * 2, st)
-        convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_Out_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv, st)
+        toRows = {} if self.rows is None else {"outDtype": self.rows}          # into a depth-wise layer
+        toDense = {} if self.rows is None else {"outDtype": torch.float32}     # out of one, into a matmul
+        convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_Out_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv, st,
+                                                 **toRows)
         convFeatures2 = mConvBuilder.create_convolution(
             convName="Conv_2", inPointHierarchy=mPointHierarchy, inPointLevel=1, outPointLevel=2,
             inFeatures=convFeatures1, inNumFeatures=k * 2, convRadius=0.8)
-        convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_In_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st)
+        convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_In_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st,
+                                                 **toDense)
         convFeatures2 = conv_1x1("Reduce_2", convFeatures2, k * 2, k * 4, st)
-        convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_Out_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st)
+        convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_Out_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st,
+                                                 **toRows)
         convFeatures3 = mConvBuilder.create_convolution(
             convName="Conv_3", inPointHierarchy=mPointHierarchy, inPointLevel=2, outPointLevel=3,
             inFeatures=convFeatures2, inNumFeatures=k * 4, convRadius=math.sqrt(3.0) + 0.1)
-        finalInput = batch_norm_RELU_drop_out("BNRELUDROP_final", convFeatures3, isTraining, useConvDropOut, keepProbConv, st)
+        finalInput = batch_norm_RELU_drop_out("BNRELUDROP_final", convFeatures3, isTraining, useConvDropOut, keepProbConv, st,
+                                              **toDense)
         finalLogits = MLP_2_hidden(finalInput, k * 4, k * 2, k, numOutCat, "Final_Logits", keepProbFull, isTraining,
                                    useDropOutFull, store=st)
         self.lastHierarchy = mPointHierarchy
@@ -152,6 +162,8 @@ def main():
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--fused-glue", action="store_true",
                     help="batch norm + ReLU + dropout of the dense layers as one library op (VariableStore(fused=True))")
+    ap.add_argument("--bf16-rows", action="store_true",
+                    help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
@@ -159,7 +171,7 @@ def main():
     # one process per GPU: run the backward pass on the calling thread -- the autograd engine's per-device worker thread
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
-    net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue)
+    net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \
         (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
     P, Bi, F, y = make_batch()

@@ -868,6 +868,26 @@ int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float*
                      const float* saved, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
                      float* dx /* NULL: not wanted */, float* dgamma, float* dbeta,
                      void* ws, size_t ws_bytes, mccnn_stream_t stream);
+/* ... ON bf16 ROWS (extension, ABI 20): the same op with x and y each float32 (flag 0) or bfloat16 storage (flag 1),
+ * independently -- so the op is also the cast between a layer that keeps f32 rows and one that keeps bf16 rows. dy has
+ * y's type and dx has x's. gamma, beta, the moving statistics, saved, dgamma, dbeta, the workspace and every intermediate
+ * stay f32: bf16 is widened exactly on load, a bf16 result is rounded to nearest even at the store, everything in between
+ * is the arithmetic above, operand for operand; the backward recomputes xhat, the gate and the mask from x, saved and the
+ * seed and never reads y. For f32 x the statistics, saved and (before the rounding) y are the bytes of mccnn_bn_act_fwd,
+ * whatever y's type; for bf16 x they are the same bytes for both types of y. Same launch counts, the same workspace size.
+ * bf16 rows move as 32-bit words: an odd c with a bf16 operand, or a bf16 pointer off a 4-byte boundary, is MCCNN_E_SHAPE;
+ * a flag outside {0, 1} MCCNN_E_BADARG; both before anything is launched. 16-byte pieces (8 bf16 columns per access) need
+ * c % 8 == 0 and 16-byte aligned row pointers, which the entries look at themselves; other rows move as pairs. With both
+ * flags 0 these ARE mccnn_bn_act_fwd / _bwd. */
+int mccnn_bn_act_fwd_rows(const void* x, int x_bf16, int n, int c, const float* gamma, const float* beta,
+                          float* moving_mean, float* moving_var, float momentum, float eps,
+                          int training, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                          void* y, int y_bf16, float* saved /* [2,c]; may be NULL when !training */,
+                          void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, const float* gamma,
+                          const float* beta, const float* saved, int relu, unsigned long long keep_threshold,
+                          float keep_scale, unsigned seed, void* dx /* x's type; NULL: not wanted */, float* dgamma,
+                          float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream);
 
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature

@@ -1672,17 +1672,25 @@ def spatial_conv(inPts, inFeatures, inBatchIds, inPDFs, inSamplePts, neighStartI
 BN_DROP_ALL = 1 << 32   # keep threshold of "no dropout"
 
 
-def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed):
-    """Checks of bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale)."""
+def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
+    """Checks of bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale). x: float32 or
+    bfloat16 rows; outDtype: None (x's type), torch.float32 or torch.bfloat16; everything per column is float32."""
     _req(keepProb is None or (isinstance(keepProb, (int, float)) and not isinstance(keepProb, bool) and 0.0 < keepProb <= 1.0),
          "bn_relu_dropout expects keepProb in (0, 1] (or None)")
     _req(isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < (1 << 32),
          "bn_relu_dropout expects a seed in [0, 2^32)")
+    _req(outDtype is None or outDtype in (torch.float32, torch.bfloat16),
+         "bn_relu_dropout: outDtype must be None, torch.float32 or torch.bfloat16")
+    _req(isinstance(x, torch.Tensor) and x.dtype in (torch.float32, torch.bfloat16),
+         "bn_relu_dropout: x must be a float32 (or bfloat16 storage) tensor")
     for t, name in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
-        _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32, "bn_relu_dropout: %s must be a float32 tensor" % name)
+        _req(isinstance(t, torch.Tensor) and (t is x or t.dtype == torch.float32),
+             "bn_relu_dropout: %s must be a float32 tensor" % name)
         _req(t.is_contiguous(), "bn_relu_dropout: %s must be contiguous" % name)
     _req(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "bn_relu_dropout expects x with dimensions (n, c), n, c >= 1")
     _req(x.shape[0] * x.shape[1] < (1 << 62) and max(x.shape) < (1 << 31), "bn_relu_dropout: x too large")
+    _req(x.shape[1] % 2 == 0 or (x.dtype == torch.float32 and outDtype in (None, torch.float32)),
+         "bn_relu_dropout: bfloat16 rows need an even number of columns")
     for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
         _req(t.dim() == 1 and t.shape[0] == x.shape[1], "bn_relu_dropout: %s must have shape (c,)" % name)
         _req(t.device == x.device, "bn_relu_dropout: %s is on another device than x" % name)
@@ -1695,55 +1703,74 @@ def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed):
     return thr, float(_np.float32(1.0) / _np.float32(kp))   # 1.0f / (float) keepProb
 
 
+def _bn_act_fwd(lib, x, gamma, beta, movingMean, movingVar, momentum, epsilon, training, relu, thr, scale, seed, y, saved, ws):
+    """The forward library call: the float32 entry for float32 rows both ways, as before; the typed one otherwise."""
+    wsn = 0 if ws is None else ws.numel()
+    if x.dtype == torch.float32 and y.dtype == torch.float32:
+        check(lib.mccnn_bn_act_fwd(ptr(x), x.shape[0], x.shape[1], ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar),
+                                   momentum, epsilon, training, relu, thr, scale, seed, ptr(y), ptr(saved), ptr(ws), wsn,
+                                   stream_handle()), "bn_relu_dropout")
+    else:
+        check(lib.mccnn_bn_act_fwd_rows(ptr(x), int(x.dtype == torch.bfloat16), x.shape[0], x.shape[1], ptr(gamma), ptr(beta),
+                                        ptr(movingMean), ptr(movingVar), momentum, epsilon, training, relu, thr, scale, seed,
+                                        ptr(y), int(y.dtype == torch.bfloat16), ptr(saved), ptr(ws), wsn, stream_handle()),
+              "bn_relu_dropout")
+
+
 class _BnReluDropout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon):
+    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype=None):
         lib = _lib.load()
         n, c = x.shape
-        y = torch.empty_like(x)
+        xd, gd, bd = _bf16_rows_aligned(x.detach()), gamma.detach(), beta.detach()
+        y = torch.empty((n, c), dtype=outDtype or x.dtype, device=x.device)
         saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
         ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
-        xd, gd, bd = x.detach(), gamma.detach(), beta.detach()
-        check(lib.mccnn_bn_act_fwd(ptr(xd), n, c, ptr(gd), ptr(bd), ptr(movingMean), ptr(movingVar), momentum, epsilon, 1,
-                                   int(relu), thr, scale, seed, ptr(y), ptr(saved), ptr(ws), ws.numel(), stream_handle()),
-              "bn_relu_dropout")
+        _bn_act_fwd(lib, xd, gd, bd, movingMean, movingVar, momentum, epsilon, 1, int(relu), thr, scale, seed, y, saved, ws)
         ctx.save_for_backward(xd, gd, bd, saved)
-        ctx.attrs = (int(relu), thr, scale, seed)
+        ctx.attrs = (int(relu), thr, scale, seed, y.dtype)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         x, gamma, beta, saved = ctx.saved_tensors
-        relu, thr, scale, seed = ctx.attrs
+        relu, thr, scale, seed, ydt = ctx.attrs
         lib = _lib.load()
         n, c = x.shape
-        gy = gy.contiguous()
+        gy = _bf16_rows_aligned(gy.to(ydt).contiguous())   # (dy has y's type; .to is a no-op when autograd hands that over)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
         ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
-        check(lib.mccnn_bn_act_bwd(ptr(x), ptr(gy), n, c, ptr(gamma), ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx),
-                                   ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_grad")
+        if x.dtype == torch.float32 and ydt == torch.float32:
+            check(lib.mccnn_bn_act_bwd(ptr(x), ptr(gy), n, c, ptr(gamma), ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx),
+                                       ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_grad")
+        else:
+            check(lib.mccnn_bn_act_bwd_rows(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(ydt == torch.bfloat16), n, c,
+                                            ptr(gamma), ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx), ptr(dgb[0]),
+                                            ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_grad")
         return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
-                    epsilon=1e-3):
+                    epsilon=1e-3, outDtype=None):
     """y = drop(act(bn(x))) over an [n, c] float32 contiguous tensor in one library op; differentiable (once) with respect
     to x, gamma and beta. training: batch statistics (biased variance), movingMean / movingVar updated in place as
     moving * momentum + stat * (1 - momentum), dropout with keep probability keepProb (None: none) from the counter-based
-    mask of `seed`. Eval: the moving statistics, no dropout, and no gradients -- an input that requires one raises."""
-    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed)
+    mask of `seed`. Eval: the moving statistics, no dropout, and no gradients -- an input that requires one raises.
+    x may also be bfloat16 rows (an even c), and outDtype names y's type (None: x's; torch.float32; torch.bfloat16), so the
+    op is also the cast between layers that keep different row types: bf16 is widened exactly, the statistics and all
+    arithmetic are float32 as for float32 rows, a bf16 y is rounded to nearest even at the store. x.grad has x's type,
+    gamma.grad and beta.grad are float32."""
+    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
     if training:
         return _BnReluDropout.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
-                                    float(epsilon))
+                                    float(epsilon), outDtype)
     _req(not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
          "bn_relu_dropout: the eval form has no gradients")
     lib = _lib.load()
-    n, c = x.shape
-    y = torch.empty_like(x)
-    check(lib.mccnn_bn_act_fwd(ptr(x), n, c, ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar), float(momentum),
-                               float(epsilon), 0, int(bool(relu)), BN_DROP_ALL, 1.0, seed, ptr(y), None, None, 0,
-                               stream_handle()), "bn_relu_dropout")
+    y = torch.empty(x.shape, dtype=outDtype or x.dtype, device=x.device)
+    _bn_act_fwd(lib, _bf16_rows_aligned(x.detach()), gamma, beta, movingMean, movingVar, float(momentum), float(epsilon), 0,
+                int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
     return y

@@ -176,15 +176,20 @@ def _fused_op():
     return _FUSED_OP
 
 
-def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True):
+def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
     """drop(act(batch_normalization(inputs))) as one library op, or None where the fused form does not apply (the caller
-    then runs the torch code): the store's switch is off, the input is not a contiguous float32 [n, c] tensor on a HIP
-    device, the library does not load, training statistics are synchronised across ranks, or an eval call wants
-    gradients. keepProb: the keep probability of a dropout that applies (None: none)."""
+    then runs the torch code): the store's switch is off, the input is not a contiguous float32 (or bfloat16 with an even
+    c) [n, c] tensor on a HIP device, the library does not load, training statistics are synchronised across ranks, or an
+    eval call wants gradients. keepProb: the keep probability of a dropout that applies (None: none). outDtype: the
+    result's type (None: the input's; torch.float32; torch.bfloat16, which needs an even c as well)."""
     if not getattr(st, "fused_", False):
         return None
-    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
+    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype in (torch.float32, torch.bfloat16) and inputs.dim() == 2
             and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+        return None
+    if outDtype not in (None, torch.float32, torch.bfloat16):
+        return None
+    if inputs.shape[1] % 2 != 0 and (inputs.dtype == torch.bfloat16 or outDtype == torch.bfloat16):
         return None
     if training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         return None
@@ -210,7 +215,9 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
         st.dropCalls_ += 1
     else:
         keepProb = None
-    return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon)
+    if outDtype is None:
+        return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon)
+    return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon, outDtype)
 
 
 def _keep_prob(useDropOut, keepProb):
@@ -220,15 +227,18 @@ def _keep_prob(useDropOut, keepProb):
     return float(keepProb)
 
 
-def _bn_relu_drop(st, inputs, training, name, useDropOut, keepProb):
-    """relu(batch_normalization(inputs)) [+ dropout]: the fused op where it applies, the torch code otherwise."""
+def _bn_relu_drop(st, inputs, training, name, useDropOut, keepProb, outDtype=None):
+    """relu(batch_normalization(inputs)) [+ dropout]: the fused op where it applies, the torch code otherwise (followed by
+    a cast where another type than its result's was asked for)."""
     if getattr(st, "fused_", False):
-        y = _fused_glue(st, inputs, training, name, True, _keep_prob(useDropOut, keepProb))
+        y = _fused_glue(st, inputs, training, name, True, _keep_prob(useDropOut, keepProb), outDtype=outDtype)
         if y is not None:
             return y
     y = torch.relu(batch_normalization(inputs, training, name, st))
     if useDropOut:
         y = _dropout(y, keepProb, training)
+    if outDtype is not None and y.dtype != outDtype:
+        y = y.to(outDtype)
     return y
 
 
@@ -290,7 +300,9 @@ def conv_1x1(layerName, inputs, numInputs, numOutFeatures, store=None):
     return inputs @ w + b
 
 
-def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, keepProb, store=None):
-    """utils/MCNetworkUtils.py:129-144."""
+def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, keepProb, store=None, outDtype=None):
+    """utils/MCNetworkUtils.py:129-144. outDtype (extension): the result's type, torch.float32 or torch.bfloat16 (None: as
+    computed) -- with a fused store the one library op reads float32 or bfloat16 rows and writes either, so the block is
+    also the cast between layers that keep different row types."""
     st = store or _DEFAULT_STORE
-    return _bn_relu_drop(st, inFeatures, isTraining, layerName + "_BN", usedDropOut, keepProb)
+    return _bn_relu_drop(st, inFeatures, isTraining, layerName + "_BN", usedDropOut, keepProb, outDtype)

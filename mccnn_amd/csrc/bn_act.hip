@@ -1,8 +1,13 @@
-// The dense glue between two MC convolutions as one op (mccnn_bn_act_fwd / _bwd): y = drop(act(bn(x))) over an [n, c]
-// float32 row-major tensor, batch statistics over the rows.
+// The dense glue between two MC convolutions as one op (mccnn_bn_act_fwd / _bwd and their typed forms _fwd_rows /
+// _bwd_rows): y = drop(act(bn(x))) over an [n, c] row-major tensor, batch statistics over the rows. x (and dx) and y (and
+// dy) are float32 or bfloat16 storage, independently: bf16 is widened exactly on load and rounded to nearest even at the
+// store, everything in between is f32 and the same for every type (XT, YT below change loads and stores only).
 //
-// A workgroup of 256 threads owns a tile of up to 32 columns and a slab of rows: tw threads across (4 columns each when
-// c % 4 == 0 and the row pointers are 16-byte aligned, one column each otherwise), 256 / tw row lanes down.
+// A workgroup of 256 threads owns a tile of 128 bytes of a row of x and a slab of rows: tw threads across, 256 / tw row
+// lanes down. f32 x: up to 32 columns, 4 per thread when c % 4 == 0 and the row pointers allow (x, f32 y / dy / dx on 16
+// bytes, bf16 y / dy on 8), one per thread otherwise. bf16 x: up to 64 columns, 8 per thread (one 16-byte piece) when
+// c % 8 == 0 and every row pointer is on 16 bytes, a pair (one 32-bit word) otherwise. tw is at most 8 in the wide forms
+// and 32 in the narrow ones, whatever the type.
 //   forward, training   launch 1: per slab and column a partial (count, mean, M2) -- per thread sums shifted by the slab's
 //                                 first row (no cancellation when |mean| >> std), merged across the row lanes by Chan's
 //                                 rule in a fixed tree through LDS.
@@ -21,10 +26,15 @@
 namespace mccnn {
 
 constexpr int kBnThreads = 256;
-constexpr int kBnTileCols = 32;     // columns of a workgroup: 128 bytes of a row
+constexpr int kBnTileCols = 64;     // most columns of a workgroup: 128 bytes of a row of x (32 f32, 64 bf16)
 constexpr int kBnSmallRows = 256;   // up to here: the one-launch form
 constexpr int kBnSlabRows = 128;    // rows of a slab ...
 constexpr int kBnMaxSlabs = 64;     // ... until there would be more slabs than this: then the slabs grow
+
+// rows of a thread whose loads are in flight together in the streaming loops of the forward. 8 columns per thread (bf16 x)
+// come with half the workgroups of the f32 layout for the same c, each moving up to twice the bytes: they keep more ahead
+template <int VEC>
+constexpr int kBnRowsAhead = VEC == 8 ? 8 : 4;
 
 struct BnPlan {
     int vec, tw_log, tiles, slab_rows, slabs;
@@ -34,10 +44,12 @@ inline int bn_slab_rows(int n) {
     if (ceil_div(n, kBnSlabRows) <= kBnMaxSlabs) return kBnSlabRows;
     return ceil_div(ceil_div(n, kBnMaxSlabs), 32) * 32;
 }
-inline BnPlan bn_plan(int n, int c, bool aligned16) {
+// aligned: every row pointer allows the wide form (bn_rows_aligned); x_bf16: the thread layout follows x's type
+inline BnPlan bn_plan(int n, int c, bool aligned, int x_bf16 = 0) {
     BnPlan p;
-    p.vec = (c % 4 == 0 && aligned16) ? 4 : 1;
-    const int units = c / p.vec, most = kBnTileCols / p.vec;
+    if (x_bf16) p.vec = (c % 8 == 0 && aligned) ? 8 : 2;
+    else p.vec = (c % 4 == 0 && aligned) ? 4 : 1;
+    const int units = c / p.vec, most = (x_bf16 ? 64 : 32) / p.vec;
     p.tw_log = 0;
     while ((1 << p.tw_log) < most && (1 << p.tw_log) < units) ++p.tw_log;
     p.tiles = ceil_div(units, 1 << p.tw_log);
@@ -47,9 +59,9 @@ inline BnPlan bn_plan(int n, int c, bool aligned16) {
 }
 
 struct BnArgs {
-    const float* x;
-    const float* dy;
-    float* out;          // y (forward) or dx (backward)
+    const void* x;       // XT
+    const void* dy;      // YT
+    void* out;           // y (forward, YT) or dx (backward, XT)
     const float* gamma;
     const float* beta;
     float* mov_mean;
@@ -76,26 +88,108 @@ __device__ __forceinline__ BnCoord bn_coord(const BnArgs& a) {
     t.ry = t.tid >> a.tw_log;
     t.R = kBnThreads >> a.tw_log;
     const long long col = ((long long)blockIdx.x * (1 << a.tw_log) + t.cx) * VEC;
-    t.ok = col < (long long)a.c;    // (VEC == 4: c % 4 == 0, so all four columns are inside)
+    t.ok = col < (long long)a.c;    // (c % VEC == 0, so all VEC columns are inside)
     t.col = t.ok ? (int)col : 0;
     return t;
 }
 
+// VEC f32 values of the library's own memory (LDS, the slab partials): p is on VEC * 4 bytes, 16 at the most
 template <int VEC>
 __device__ __forceinline__ void bn_ld(const float* __restrict__ p, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 8) {
+        const float4 q = reinterpret_cast<const float4*>(p)[0], r = reinterpret_cast<const float4*>(p)[1];
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; v[4] = r.x; v[5] = r.y; v[6] = r.z; v[7] = r.w;
+    } else if constexpr (VEC == 4) {
         const float4 q = *reinterpret_cast<const float4*>(p);
         v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else if constexpr (VEC == 2) {
+        const float2 q = *reinterpret_cast<const float2*>(p);
+        v[0] = q.x; v[1] = q.y;
     } else {
         v[0] = *p;
     }
 }
 template <int VEC>
 __device__ __forceinline__ void bn_st(float* __restrict__ p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 8) {
+        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+    } else if constexpr (VEC == 4) {
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (VEC == 2) {
+        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
     } else {
         *p = v[0];
+    }
+}
+
+// The element types of a caller's rows: float, or bf16 storage (bn_bf16: 16 bits, widened exactly / rounded to nearest even)
+typedef uint16_t bn_bf16;
+
+// VEC elements at element offset `at` of a caller's tensor: bn_ld_raw moves them as they are stored (bn_raw_words 32-bit
+// words; one bf16 alone sits in the low half of a word), bn_widen makes f32 of them (bf16: exactly), bn_ldr is both. The
+// plan has looked at the pointers: VEC 8 and 4 only where every access below is aligned (f32: 16 bytes; bf16: 16 for VEC 8,
+// 8 for VEC 4); a pair of f32 moves as two words (an f32 pointer promises 4 bytes), a pair of bf16 as one (the entries
+// refuse a bf16 pointer off a 4-byte boundary)
+template <int VEC, typename T>
+constexpr int bn_raw_words() { return VEC * (int)sizeof(T) >= 4 ? VEC * (int)sizeof(T) / 4 : 1; }
+template <int VEC, typename T>
+__device__ __forceinline__ void bn_ld_raw(const void* __restrict__ base, size_t at, uint32_t (&w)[bn_raw_words<VEC, T>()]) {
+    const T* p = static_cast<const T*>(base) + at;
+    constexpr int W = bn_raw_words<VEC, T>();
+    if constexpr (sizeof(T) == 2 && VEC == 1) {
+        w[0] = *p;
+    } else if constexpr (W >= 4) {
+#pragma unroll
+        for (int i = 0; i < W / 4; ++i) {
+            const uint4 u = reinterpret_cast<const uint4*>(p)[i];
+            w[4 * i] = u.x; w[4 * i + 1] = u.y; w[4 * i + 2] = u.z; w[4 * i + 3] = u.w;
+        }
+    } else if constexpr (W == 2 && sizeof(T) == 2) {
+        const uint2 u = *reinterpret_cast<const uint2*>(p);
+        w[0] = u.x; w[1] = u.y;
+    } else {
+#pragma unroll
+        for (int i = 0; i < W; ++i) w[i] = reinterpret_cast<const uint32_t*>(p)[i];
+    }
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void bn_widen(const uint32_t (&w)[bn_raw_words<VEC, T>()], float (&v)[VEC]) {
+    if constexpr (sizeof(T) == 4) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) v[k] = __uint_as_float(w[k]);
+    } else if constexpr (VEC == 8) {
+        bf16x8_to_f32(make_uint4(w[0], w[1], w[2], w[3]), v);
+    } else if constexpr (VEC == 1) {
+        v[0] = __uint_as_float(w[0] << 16);
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC / 2; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+    }
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void bn_ldr(const void* __restrict__ base, size_t at, float (&v)[VEC]) {
+    uint32_t w[bn_raw_words<VEC, T>()];
+    bn_ld_raw<VEC, T>(base, at, w);
+    bn_widen<VEC, T>(w, v);
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void bn_str(void* __restrict__ base, size_t at, const float (&v)[VEC]) {
+    if constexpr (sizeof(T) == 4) {
+        float* p = static_cast<float*>(base) + at;
+        if constexpr (VEC == 2) { p[0] = v[0]; p[1] = v[1]; }
+        else bn_st<VEC>(p, v);
+    } else {
+        bn_bf16* p = static_cast<bn_bf16*>(base) + at;
+        if constexpr (VEC == 8) {
+            *reinterpret_cast<uint4*>(p) = f32x8_to_bf16(v);
+        } else if constexpr (VEC == 4) {
+            *reinterpret_cast<uint2*>(p) = make_uint2(f32x2_to_bf16(v[0], v[1]), f32x2_to_bf16(v[2], v[3]));
+        } else if constexpr (VEC == 2) {
+            *reinterpret_cast<unsigned*>(p) = f32x2_to_bf16(v[0], v[1]);
+        } else {
+            *p = (bn_bf16)(f32x2_to_bf16(v[0], 0.f) & 0xffffu);
+        }
     }
 }
 
@@ -173,7 +267,7 @@ __device__ __forceinline__ void bn_tree_sum(const BnArgs& a, const BnCoord& t, f
 }
 
 // (count, mean, M2) of rows [row0, row1) of the thread's columns, merged over the row lanes
-template <int VEC>
+template <int VEC, typename XT>
 __device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t, int row0, int row1, float& cnt,
                                               float (&mean)[VEC], float (&m2)[VEC], float* lds) {
     float s1[VEC], s2[VEC], K[VEC];
@@ -181,11 +275,11 @@ __device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t,
     for (int k = 0; k < VEC; ++k) { s1[k] = 0.f; s2[k] = 0.f; K[k] = 0.f; }
     int rows = 0;
     if (t.ok && row0 < row1) {
-        bn_ld<VEC>(a.x + (size_t)row0 * a.c + t.col, K);   // the shift: the slab's first row
-#pragma unroll 4
+        bn_ldr<VEC, XT>(a.x, (size_t)row0 * a.c + t.col, K);   // the shift: the slab's first row
+#pragma unroll kBnRowsAhead<VEC>
         for (int r = row0 + t.ry; r < row1; r += t.R) {
             float v[VEC];
-            bn_ld<VEC>(a.x + (size_t)r * a.c + t.col, v);
+            bn_ldr<VEC, XT>(a.x, (size_t)r * a.c + t.col, v);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float d = v[k] - K[k];
@@ -249,39 +343,50 @@ __device__ __forceinline__ void bn_finish_stats(const BnArgs& a, const BnCoord& 
     __syncthreads();
 }
 
-template <int VEC>
+template <int VEC, typename XT, typename YT>
 __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t, int row0, int row1, const float (&mean)[VEC],
                                               const float (&rstd)[VEC], bool drop) {
     if (!t.ok) return;   // (no barrier follows)
     float g[VEC], b[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { g[k] = a.gamma[t.col + k]; b[k] = a.beta[t.col + k]; }
-#pragma unroll 4
-    for (int r = row0 + t.ry; r < row1; r += t.R) {
-        float v[VEC], o[VEC];
-        bn_ld<VEC>(a.x + (size_t)r * a.c + t.col, v);
-        const uint32_t rh = drop ? bn_drop_row(a.seed, r) : 0u;
+    // the loads of U rows go out before the first row is used and stored: y may be x's memory for all the compiler knows,
+    // so behind a row's store it would hold the next row's load back, one memory latency per row
+    constexpr int U = kBnRowsAhead<VEC>;
+    for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
+        uint32_t wx[U][bn_raw_words<VEC, XT>()];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            const float xh = (v[k] - mean[k]) * rstd[k];
-            const float pre = xh * g[k] + b[k];
-            float act = a.relu ? (pre > 0.f ? pre : 0.f) : pre;
-            if (drop) act = bn_drop_keep(rh, (uint32_t)(t.col + k), a.T) ? act * a.keep_scale : 0.f;
-            o[k] = act;
+        for (int u = 0; u < U; ++u)
+            if (r + u * t.R < row1) bn_ld_raw<VEC, XT>(a.x, (size_t)(r + u * t.R) * a.c + t.col, wx[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long ru = r + u * t.R;
+            if (ru >= row1) break;
+            float v[VEC], o[VEC];
+            bn_widen<VEC, XT>(wx[u], v);
+            const uint32_t rh = drop ? bn_drop_row(a.seed, (int)ru) : 0u;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float xh = (v[k] - mean[k]) * rstd[k];
+                const float pre = xh * g[k] + b[k];
+                float act = a.relu ? (pre > 0.f ? pre : 0.f) : pre;
+                if (drop) act = bn_drop_keep(rh, (uint32_t)(t.col + k), a.T) ? act * a.keep_scale : 0.f;
+                o[k] = act;
+            }
+            bn_str<VEC, YT>(a.out, (size_t)ru * a.c + t.col, o);
         }
-        bn_st<VEC>(a.out + (size_t)r * a.c + t.col, o);
     }
 }
 
 // forward, training, launch 1
-template <int VEC>
+template <int VEC, typename XT>
 __global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
     const BnCoord t = bn_coord<VEC>(a);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float cnt, mean[VEC], m2[VEC];
-    bn_slab_stats<VEC>(a, t, row0, row1, cnt, mean, m2, lds);
+    bn_slab_stats<VEC, XT>(a, t, row0, row1, cnt, mean, m2, lds);
     if (t.ry == 0 && t.ok) {
         const size_t plane = (size_t)a.slabs * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
@@ -295,7 +400,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a) {
 }
 
 // MODE 0: forward, training, launch 2 (partials from launch 1); 1: the one-launch form (n <= 256); 2: eval
-template <int VEC, int MODE>
+template <int VEC, typename XT, typename YT, int MODE>
 __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
     __shared__ float sm[2][kBnTileCols];
@@ -309,15 +414,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
             mean[k] = t.ok ? a.mov_mean[t.col + k] : 0.f;
             rstd[k] = t.ok ? 1.0f / sqrtf(a.mov_var[t.col + k] + a.eps) : 0.f;
         }
-        bn_apply_rows<VEC>(a, t, row0, row1, mean, rstd, false);
+        bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, false);
     } else {
         float cnt, m2[VEC];
         if constexpr (MODE == 0) bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
-        else bn_slab_stats<VEC>(a, t, 0, a.n, cnt, mean, m2, lds);
+        else bn_slab_stats<VEC, XT>(a, t, 0, a.n, cnt, mean, m2, lds);
         bn_finish_stats<VEC>(a, t, mean, m2, slab == 0, sm);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
-        bn_apply_rows<VEC>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll);
+        bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll);
     }
 }
 
@@ -338,13 +443,11 @@ __device__ __forceinline__ BnCols<VEC> bn_cols(const BnArgs& a, const BnCoord& t
     }
     return q;
 }
-// g = dy * mask * scale * gate and xhat of row r of the thread's columns (the forward's arithmetic, operand for operand)
+// g = dy * mask * scale * gate and xhat of row r of the thread's columns from its x (v) and dy (d): the forward's
+// arithmetic, operand for operand
 template <int VEC>
 __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int r, bool drop,
-                                            float (&g)[VEC], float (&xh)[VEC]) {
-    float v[VEC], d[VEC];
-    bn_ld<VEC>(a.x + (size_t)r * a.c + t.col, v);
-    bn_ld<VEC>(a.dy + (size_t)r * a.c + t.col, d);
+                                            const float (&v)[VEC], const float (&d)[VEC], float (&g)[VEC], float (&xh)[VEC]) {
     const uint32_t rh = drop ? bn_drop_row(a.seed, r) : 0u;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -356,21 +459,47 @@ __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, c
         g[k] = w;
     }
 }
-template <int VEC>
+// f(r, g, xh) over rows row0 + ry, + R, ... below row1, in that order. The loads of U rows are issued before the first of
+// them is used: behind the (uniform) relu and dropout branches of a row the compiler would otherwise hold the next row's
+// loads back, one memory latency per row.
+template <int VEC, typename XT, typename YT, typename F>
+__device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
+                                             bool drop, F&& f) {
+    constexpr int U = 4;
+    for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
+        uint32_t wx[U][bn_raw_words<VEC, XT>()], wd[U][bn_raw_words<VEC, YT>()];   // (as stored: widened where they are used)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long ru = r + u * t.R;
+            if (ru < row1) {
+                bn_ld_raw<VEC, XT>(a.x, (size_t)ru * a.c + t.col, wx[u]);
+                bn_ld_raw<VEC, YT>(a.dy, (size_t)ru * a.c + t.col, wd[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long ru = r + u * t.R;
+            if (ru < row1) {
+                float v[VEC], d[VEC], g[VEC], xh[VEC];
+                bn_widen<VEC, XT>(wx[u], v);
+                bn_widen<VEC, YT>(wd[u], d);
+                bn_row_grad<VEC>(a, t, q, (int)ru, drop, v, d, g, xh);
+                f((int)ru, g, xh);
+            }
+        }
+    }
+}
+template <int VEC, typename XT, typename YT>
 __device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
                                              float (&sg)[VEC], float (&sx)[VEC], float (&sh)[VEC], float* lds) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
     const bool drop = a.T < kBnDropAll;
-    if (t.ok) {
-#pragma unroll 4
-        for (int r = row0 + t.ry; r < row1; r += t.R) {
-            float g[VEC], xh[VEC];
-            bn_row_grad<VEC>(a, t, q, r, drop, g, xh);
+    if (t.ok)
+        bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int, const float (&g)[VEC], const float (&xh)[VEC]) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) { sg[k] = sg[k] + g[k]; sx[k] = sx[k] + g[k] * xh[k]; sh[k] = sh[k] + xh[k]; }
-        }
-    }
+        });
     bn_tree_sum<VEC>(a, t, sg, sx, sh, lds);
 }
 
@@ -378,7 +507,7 @@ __device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, 
 // saved f32 mean it is -n * (mean's rounding error) * rstd, and launch 2 takes that shift out of xhat again -- on a column
 // of few rows with |mean| >> std (var + eps barely above var) dx is the small remainder of cancelling terms, and the
 // shift alone would cost it more than 1e-4
-template <int VEC>
+template <int VEC, typename XT, typename YT>
 __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
     const BnCoord t = bn_coord<VEC>(a);
@@ -386,7 +515,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float sg[VEC], sx[VEC], sh[VEC];
-    bn_slab_sums<VEC>(a, t, q, row0, row1, sg, sx, sh, lds);
+    bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds);
     if (t.ry == 0 && t.ok) {
         const size_t plane = (size_t)a.slabs * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
@@ -398,7 +527,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
 
 // backward, launch 2 (SMALL = 0: partials from launch 1, merged per workgroup) or the one-launch form (SMALL = 1): dgamma and
 // dbeta from slab 0, dx when wanted (without it the grid is one slab deep: the merge alone, in the same order)
-template <int VEC, int SMALL>
+template <int VEC, typename XT, typename YT, int SMALL>
 __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
     __shared__ float sm[3][kBnTileCols];
@@ -408,7 +537,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float sg[VEC], sx[VEC], sh[VEC];
     if constexpr (SMALL) {
-        bn_slab_sums<VEC>(a, t, q, 0, a.n, sg, sx, sh, lds);
+        bn_slab_sums<VEC, XT, YT>(a, t, q, 0, a.n, sg, sx, sh, lds);
     } else {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
@@ -451,17 +580,56 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
         mh[k] = sm[2][t.cx * VEC + k];
         gr[k] = q.g[k] * q.rstd[k];
     }
-#pragma unroll 4
-    for (int r = row0 + t.ry; r < row1; r += t.R) {
-        float g[VEC], xh[VEC], o[VEC];
-        bn_row_grad<VEC>(a, t, q, r, drop, g, xh);
+    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
+        float o[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
-        bn_st<VEC>(a.out + (size_t)r * a.c + t.col, o);
-    }
+        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
+    });
 }
 
+// a caller's row pointer allows the wide form: f32 x -> 4 columns per thread (f32 rows move as 16 bytes, bf16 rows as 8),
+// bf16 x -> 8 columns per thread (16 bytes of bf16, two 16-byte pieces of f32)
+inline bool bn_rows_aligned(const void* p, int bf16, int x_bf16) {
+    return ((uintptr_t)p & ((bf16 && !x_bf16) ? 7u : 15u)) == 0;
+}
 inline bool bn_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// odd c or a pointer off a 32-bit word with bf16 storage: bf16 rows move as 32-bit words
+inline bool bn_bf16_ok(const void* p, int bf16, int c) { return !bf16 || (c % 2 == 0 && ((uintptr_t)p & 3u) == 0); }
+
+// one kernel family over (columns per thread, x's type, y's / dy's type): L::go<VEC, XT, YT> launches it; 0 or the launch's
+// hipError_t
+template <typename L>
+inline int bn_launch(int vec, int x_bf16, int y_bf16, dim3 grid, hipStream_t st, const BnArgs& a) {
+    if (!x_bf16) {
+        if (!y_bf16) { if (vec == 4) L::template go<4, float, float>(grid, st, a); else L::template go<1, float, float>(grid, st, a); }
+        else { if (vec == 4) L::template go<4, float, bn_bf16>(grid, st, a); else L::template go<1, float, bn_bf16>(grid, st, a); }
+    } else {
+        if (!y_bf16) { if (vec == 8) L::template go<8, bn_bf16, float>(grid, st, a); else L::template go<2, bn_bf16, float>(grid, st, a); }
+        else { if (vec == 8) L::template go<8, bn_bf16, bn_bf16>(grid, st, a); else L::template go<2, bn_bf16, bn_bf16>(grid, st, a); }
+    }
+    MCCNN_LAUNCHED();
+    return 0;
+}
+struct BnStatsL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_stats_k<VEC, XT><<<grid, kBnThreads, 0, st>>>(a); }
+};
+template <int MODE>
+struct BnApplyL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_apply_k<VEC, XT, YT, MODE><<<grid, kBnThreads, 0, st>>>(a); }
+};
+struct BnBwdSumsL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_sums_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
+};
+template <int SMALL>
+struct BnBwdDxL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_dx_k<VEC, XT, YT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
+};
 
 }  // namespace mccnn
 
@@ -474,17 +642,20 @@ size_t mccnn_bn_act_workspace_bytes(int n, int c) {
     return align_up((size_t)3 * (size_t)ceil_div(n, bn_slab_rows(n)) * (size_t)c * sizeof(float));
 }
 
-int mccnn_bn_act_fwd(const float* x, int n, int c, const float* gamma, const float* beta, float* moving_mean,
-                     float* moving_var, float momentum, float eps, int training, int relu,
-                     unsigned long long keep_threshold, float keep_scale, unsigned seed, float* y, float* saved, void* ws,
-                     size_t ws_bytes, mccnn_stream_t stream) {
+int mccnn_bn_act_fwd_rows(const void* x, int x_bf16, int n, int c, const float* gamma, const float* beta, float* moving_mean,
+                          float* moving_var, float momentum, float eps, int training, int relu,
+                          unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16,
+                          float* saved, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
     if (n < 1 || c < 1) return MCCNN_E_BADARG;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !gamma || !beta || !moving_mean || !moving_var || !y) return MCCNN_E_BADARG;
     if (training && !saved) return MCCNN_E_BADARG;
+    if ((x_bf16 | y_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(y, y_bf16, c)) return MCCNN_E_SHAPE;
     const size_t need = training ? mccnn_bn_act_workspace_bytes(n, c) : 0;
     if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_aligned16(x) && bn_aligned16(y) && (!need || bn_aligned16(ws)));
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(y, y_bf16, x_bf16) && (!need || bn_aligned16(ws)),
+                             x_bf16);
     BnArgs a = {};
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
     a.part = (float*)ws;
@@ -494,35 +665,28 @@ int mccnn_bn_act_fwd(const float* x, int n, int c, const float* gamma, const flo
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
     if (!training) {
-        if (p.vec == 4) bn_apply_k<4, 2><<<grid, kBnThreads, 0, st>>>(a);
-        else bn_apply_k<1, 2><<<grid, kBnThreads, 0, st>>>(a);
-        MCCNN_LAUNCHED();
-        return 0;
+        return bn_launch<BnApplyL<2>>(p.vec, x_bf16, y_bf16, grid, st, a);
     }
     if (n <= kBnSmallRows) {
-        if (p.vec == 4) bn_apply_k<4, 1><<<grid, kBnThreads, 0, st>>>(a);
-        else bn_apply_k<1, 1><<<grid, kBnThreads, 0, st>>>(a);
-        MCCNN_LAUNCHED();
-        return 0;
+        return bn_launch<BnApplyL<1>>(p.vec, x_bf16, y_bf16, grid, st, a);
     }
-    if (p.vec == 4) bn_stats_k<4><<<grid, kBnThreads, 0, st>>>(a);
-    else bn_stats_k<1><<<grid, kBnThreads, 0, st>>>(a);
-    MCCNN_LAUNCHED();
-    if (p.vec == 4) bn_apply_k<4, 0><<<grid, kBnThreads, 0, st>>>(a);
-    else bn_apply_k<1, 0><<<grid, kBnThreads, 0, st>>>(a);
-    MCCNN_LAUNCHED();
-    return 0;
+    if (const int e = bn_launch<BnStatsL>(p.vec, x_bf16, 0, grid, st, a)) return e;
+    return bn_launch<BnApplyL<0>>(p.vec, x_bf16, y_bf16, grid, st, a);
 }
 
-int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float* gamma, const float* beta,
-                     const float* saved, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
-                     float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, const float* gamma,
+                          const float* beta, const float* saved, int relu, unsigned long long keep_threshold, float keep_scale,
+                          unsigned seed, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                          mccnn_stream_t stream) {
     if (n < 1 || c < 1) return MCCNN_E_BADARG;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
+    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
     const size_t need = mccnn_bn_act_workspace_bytes(n, c);
     if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_aligned16(x) && bn_aligned16(dy) && (!dx || bn_aligned16(dx)) && (!need || bn_aligned16(ws)));
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
+                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)) && (!need || bn_aligned16(ws)), x_bf16);
     BnArgs a = {};
     a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
     a.part = (float*)ws; a.dgamma = dgamma; a.dbeta = dbeta;
@@ -532,19 +696,27 @@ int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float*
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
     if (n <= kBnSmallRows) {
-        if (p.vec == 4) bn_bwd_dx_k<4, 1><<<grid, kBnThreads, 0, st>>>(a);
-        else bn_bwd_dx_k<1, 1><<<grid, kBnThreads, 0, st>>>(a);
-        MCCNN_LAUNCHED();
-        return 0;
+        return bn_launch<BnBwdDxL<1>>(p.vec, x_bf16, dy_bf16, grid, st, a);
     }
-    if (p.vec == 4) bn_bwd_sums_k<4><<<grid, kBnThreads, 0, st>>>(a);
-    else bn_bwd_sums_k<1><<<grid, kBnThreads, 0, st>>>(a);
-    MCCNN_LAUNCHED();
+    if (const int e = bn_launch<BnBwdSumsL>(p.vec, x_bf16, dy_bf16, grid, st, a)) return e;
     const dim3 grid2((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u);
-    if (p.vec == 4) bn_bwd_dx_k<4, 0><<<grid2, kBnThreads, 0, st>>>(a);
-    else bn_bwd_dx_k<1, 0><<<grid2, kBnThreads, 0, st>>>(a);
-    MCCNN_LAUNCHED();
-    return 0;
+    return bn_launch<BnBwdDxL<0>>(p.vec, x_bf16, dy_bf16, grid2, st, a);
+}
+
+// the float32 entries (ABI 18): the typed ones with both flags zero -- the same plan, kernels, launches and bytes
+int mccnn_bn_act_fwd(const float* x, int n, int c, const float* gamma, const float* beta, float* moving_mean,
+                     float* moving_var, float momentum, float eps, int training, int relu,
+                     unsigned long long keep_threshold, float keep_scale, unsigned seed, float* y, float* saved, void* ws,
+                     size_t ws_bytes, mccnn_stream_t stream) {
+    return mccnn_bn_act_fwd_rows(x, 0, n, c, gamma, beta, moving_mean, moving_var, momentum, eps, training, relu, keep_threshold,
+                                 keep_scale, seed, y, 0, saved, ws, ws_bytes, stream);
+}
+
+int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float* gamma, const float* beta,
+                     const float* saved, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                     float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+    return mccnn_bn_act_bwd_rows(x, 0, dy, 0, n, c, gamma, beta, saved, relu, keep_threshold, keep_scale, seed, dx, dgamma, dbeta,
+                                 ws, ws_bytes, stream);
 }
 
 }  // extern "C"

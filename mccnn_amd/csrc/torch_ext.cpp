@@ -1368,9 +1368,17 @@ Tensor sampled_features(const Tensor& idx, const Tensor& feats) {
 
 // ---- the dense glue as one op (mccnn_bn_act_fwd / _bwd): y = drop(act(bn(x))), the C++ form of
 // MCConvModule.bn_relu_dropout -- the same library calls with the same arguments, so the same bytes; the autograd node is
-// here, so a block costs the host one Python -> C++ call forward and none backward.
+// here, so a block costs the host one Python -> C++ call forward and none backward. x and y are each f32 or bf16 rows
+// (mccnn_bn_act_fwd_rows / _bwd_rows; f32 both ways goes through the float32 entries as before): dy has y's type, dx x's.
+// bf16 rows that do not start on a 16-byte boundary are copied where they enter, as the convolutions do.
+inline bool is_bf16(const Tensor& t) { return t.scalar_type() == at::kBFloat16; }
+inline Tensor bf16_rows_aligned(const Tensor& t) {
+    if (is_bf16(t) && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) != 0) return t.detach().clone(at::MemoryFormat::Contiguous);
+    return t;
+}
 struct BnActBackward : public torch::autograd::Node {
     Tensor x_, gamma_, beta_, saved;
+    bool y_bf16 = false;
     uint32_t versions[3] = {0, 0, 0};
     int relu = 1;
     unsigned long long thr = 0;
@@ -1391,18 +1399,29 @@ struct BnActBackward : public torch::autograd::Node {
         }
         const DevGuard device_guard((int)x_.device().index());
         const int n = (int)x_.size(0), c = (int)x_.size(1);
-        if (!gy.defined()) gy = at::zeros_like(x_);
+        const at::ScalarType yt = y_bf16 ? at::kBFloat16 : at::kFloat;
+        if (!gy.defined()) gy = at::zeros(x_.sizes(), x_.options().dtype(yt));
+        if (gy.scalar_type() != yt) gy = gy.to(yt);
         if (!gy.is_contiguous()) gy = gy.contiguous();
+        gy = bf16_rows_aligned(gy);
+        const bool x_bf16 = is_bf16(x_);
         const bool want_dx = task_should_compute_output(0);
         Tensor dx;
         if (want_dx) dx = at::empty_like(x_);
-        Tensor dgb = at::empty({2, (int64_t)c}, x_.options());
+        Tensor dgb = at::empty({2, (int64_t)c}, gamma_.options());
         void* st = cur_stream(x_);
         Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(n, c), x_, st);
-        check(mccnn_bn_act_bwd(x_.data_ptr<float>(), gy.data_ptr<float>(), n, c, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
-                               saved.data_ptr<float>(), relu, thr, scale, seed, want_dx ? dx.data_ptr<float>() : nullptr,
-                               dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
-              "bn_relu_dropout_grad");
+        if (!x_bf16 && !y_bf16)
+            check(mccnn_bn_act_bwd(x_.data_ptr<float>(), gy.data_ptr<float>(), n, c, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
+                                   saved.data_ptr<float>(), relu, thr, scale, seed, want_dx ? dx.data_ptr<float>() : nullptr,
+                                   dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
+                  "bn_relu_dropout_grad");
+        else
+            check(mccnn_bn_act_bwd_rows(x_.data_ptr(), x_bf16 ? 1 : 0, gy.data_ptr(), y_bf16 ? 1 : 0, n, c, gamma_.data_ptr<float>(),
+                                        beta_.data_ptr<float>(), saved.data_ptr<float>(), relu, thr, scale, seed,
+                                        want_dx ? dx.data_ptr() : nullptr, dgb.data_ptr<float>(), dgb.data_ptr<float>() + c,
+                                        ws.data_ptr(), (size_t)ws.numel(), st),
+                  "bn_relu_dropout_grad");
         torch::autograd::variable_list out(3);
         out[0] = dx;
         if (task_should_compute_output(1)) out[1] = dgb.select(0, 0);
@@ -1412,9 +1431,16 @@ struct BnActBackward : public torch::autograd::Node {
     void release_variables() override { x_.reset(); gamma_.reset(); beta_.reset(); saved.reset(); }
 };
 
-Tensor bn_relu_drop(const Tensor& x, const Tensor& gamma, const Tensor& beta, const Tensor& mov_mean, const Tensor& mov_var,
-                    bool training, bool relu, unsigned long long thr, double scale, unsigned seed, double momentum, double eps) {
-    check_dev(x, at::kFloat, "x");
+// out_type: -1 x's type, 0 float32, 1 bfloat16
+Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta, const Tensor& mov_mean, const Tensor& mov_var,
+                    bool training, bool relu, unsigned long long thr, double scale, unsigned seed, double momentum, double eps,
+                    int out_type) {
+    TORCH_CHECK(x_in.defined() && (x_in.scalar_type() == at::kFloat || is_bf16(x_in)), "bn_relu_drop: x must be float32 or bfloat16");
+    check_dev(x_in, x_in.scalar_type(), "x");
+    TORCH_CHECK(out_type >= -1 && out_type <= 1, "bn_relu_drop: out_type must be -1 (x's type), 0 (float32) or 1 (bfloat16)");
+    const bool x_bf16 = is_bf16(x_in), y_bf16 = out_type < 0 ? x_bf16 : out_type == 1;
+    TORCH_CHECK(!(x_bf16 || y_bf16) || (x_in.dim() == 2 && x_in.size(1) % 2 == 0), "bn_relu_drop: bfloat16 rows need an even number of columns");
+    const Tensor x = bf16_rows_aligned(x_in);
     TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31),
                 "bn_relu_drop expects x with dimensions (n, c), n, c >= 1");
     for (const Tensor* t : {&gamma, &beta, &mov_mean, &mov_var}) {
@@ -1423,26 +1449,34 @@ Tensor bn_relu_drop(const Tensor& x, const Tensor& gamma, const Tensor& beta, co
     }
     const DevGuard device_guard((int)x.device().index());
     const int n = (int)x.size(0), c = (int)x.size(1);
-    const bool need_grad = at::GradMode::is_enabled() && (x.requires_grad() || gamma.requires_grad() || beta.requires_grad());
+    const bool need_grad = at::GradMode::is_enabled() && (x_in.requires_grad() || gamma.requires_grad() || beta.requires_grad());
     TORCH_CHECK(training || !need_grad, "bn_relu_drop: the eval form has no gradients");
     Tensor y, saved;
     {
         at::AutoDispatchBelowADInplaceOrView guard;
-        y = at::empty_like(x);
-        if (training) saved = at::empty({2, (int64_t)c}, x.options());
+        y = at::empty(x.sizes(), x.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
+        if (training) saved = at::empty({2, (int64_t)c}, gamma.options());
         void* st = cur_stream(x);
         const size_t wsb = training ? mccnn_bn_act_workspace_bytes(n, c) : 0;
         Tensor& ws = scratch(wsb, x, st);
-        check(mccnn_bn_act_fwd(x.data_ptr<float>(), n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
-                               mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
-                               training ? thr : 0x100000000ull, training ? (float)scale : 1.f, seed, y.data_ptr<float>(),
-                               training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
-              "bn_relu_dropout");
+        if (!x_bf16 && !y_bf16)
+            check(mccnn_bn_act_fwd(x.data_ptr<float>(), n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
+                                   mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
+                                   training ? thr : 0x100000000ull, training ? (float)scale : 1.f, seed, y.data_ptr<float>(),
+                                   training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+                  "bn_relu_dropout");
+        else
+            check(mccnn_bn_act_fwd_rows(x.data_ptr(), x_bf16 ? 1 : 0, n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                                        mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum, (float)eps,
+                                        training ? 1 : 0, relu ? 1 : 0, training ? thr : 0x100000000ull,
+                                        training ? (float)scale : 1.f, seed, y.data_ptr(), y_bf16 ? 1 : 0,
+                                        training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+                  "bn_relu_dropout");
     }
     if (need_grad) {
         auto node = std::shared_ptr<BnActBackward>(new BnActBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(x, gamma, beta));
-        node->x_ = x; node->gamma_ = gamma; node->beta_ = beta;
+        node->set_next_edges(torch::autograd::collect_next_edges(x_in, gamma, beta));
+        node->x_ = x; node->gamma_ = gamma; node->beta_ = beta; node->y_bf16 = y_bf16;   // (x: the aligned copy where one was made)
         node->versions[0] = x._version(); node->versions[1] = gamma._version(); node->versions[2] = beta._version();
         node->saved = saved;
         node->relu = relu ? 1 : 0; node->thr = thr; node->scale = (float)scale; node->seed = seed;
@@ -1814,7 +1848,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::call_guard<py::gil_scoped_release>());
     mod.def("bn_relu_drop", &bn_relu_drop, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
             py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
-            py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::call_guard<py::gil_scoped_release>());
+            py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1, py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

@@ -626,15 +626,17 @@ def conv(geo, feats, w1, b1, w2, b2, w3, b3, numOutFeatures, combin, avg, determ
 
 
 def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
-                 epsilon=1e-3):
+                 epsilon=1e-3, outDtype=None):
     """The dense glue as one op, y = drop(act(bn(x))) (MCConvModule.bn_relu_dropout: its definition, checks and errors):
     one Python -> C++ call forward and an autograd node on the C++ side when the extension is loaded, the ctypes op
-    otherwise -- the same library calls either way, so the same bytes."""
+    otherwise -- the same library calls either way, so the same bytes. x: float32 or bfloat16 rows; outDtype: y's type
+    (None: x's)."""
     from . import MCConvModule as M
     if _EXT is None:
-        return M.bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum, epsilon)
-    thr, scale = M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed)
+        return M.bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum, epsilon,
+                                 outDtype)
+    thr, scale = M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
     M._req(training or not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
            "bn_relu_dropout: the eval form has no gradients")
     return _EXT.bn_relu_drop(x, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
-                             float(momentum), float(epsilon))
+                             float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
