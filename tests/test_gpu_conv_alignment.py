@@ -42,7 +42,8 @@ import numpy as np
 import pytest
 
 from tests import ref_cases as rc
-from tests.helpers import make_cloud, make_mlp, conv_nb, run_chain, assert_float_close
+from tests.combin_cases import off, pooling_cloud   # (shared with tests/test_gpu_combin_lattice.py)
+from tests.helpers import make_mlp, conv_nb, run_chain, assert_float_close
 
 pytestmark = pytest.mark.gpu
 
@@ -85,19 +86,6 @@ def _t(x):
     return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
-def off(a, nbytes):
-    """A contiguous [rows, F] view holding a's values that starts `nbytes` behind a fresh (16-byte aligned) allocation."""
-    import torch
-    k, r = divmod(nbytes, a.element_size())
-    assert r == 0
-    buf = torch.empty(a.numel() + 16, dtype=a.dtype, device=a.device)
-    assert buf.data_ptr() % 16 == 0
-    v = buf[k:k + a.numel()].view(a.shape)
-    v.copy_(a)
-    assert v.is_contiguous() and v.data_ptr() % 16 == nbytes
-    return v
-
-
 _GEO = {}
 
 
@@ -107,16 +95,8 @@ def _geometry(oracle):
     and for bf16-rounded inputs -- computed once."""
     if _GEO:
         return _GEO
-    pts, _ = make_cloud(1450, 1, 33, "clustered", True)   # (ragged: 885 points)
-    rng = np.random.default_rng(3)
-    lonely = (-5.0 - 3.0 * rng.random((24, 3))).astype(np.float32)      # points no centre reaches
-    pts = np.concatenate([pts[:400], lonely[:12], pts[400:], lonely[12:]]).astype(np.float32)
+    pts, bids, centres, cb, rng = pooling_cloud()
     n = len(pts)
-    bids = np.zeros((n, 1), np.int32)
-    far = np.array([[9.0, 9.0, 9.0]], np.float32)
-    near = pts[np.sort(rng.choice(np.nonzero(pts[:, 0] > -1.0)[0], 294, replace=False))]
-    centres = np.concatenate([far, far + 1, near[:150], far + 2, far + 3, near[150:], far + 4, far + 5]).astype(np.float32)
-    cb = np.zeros((len(centres), 1), np.int32)
     feats = (2 * rng.random((n, FIN)) - 1).astype(np.float32)           # rows of the UNSORTED points
     og = (2 * np.random.default_rng(5).random((len(centres), FIN)) - 1).astype(np.float32)
     w = make_mlp(conv_nb(FIN, FIN, False), 7)
