@@ -18,7 +18,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mccnn_amd.MCConvBuilder import PointHierarchy, ConvolutionBuilder
-from mccnn_amd.MCNetworkUtils import (MLP_2_hidden, batch_norm_RELU_drop_out, conv_1x1, VariableStore)
+from mccnn_amd.MCNetworkUtils import (MLP_2_hidden, batch_norm_RELU_drop_out, conv_1x1, conv_1x1_batch_norm_RELU_drop_out,
+                                      VariableStore)
 
 
 class MCClassS(torch.nn.Module):
@@ -26,7 +27,7 @@ class MCClassS(torch.nn.Module):
     whose sub-modules (the convolution builder and the dense helpers' variable store) register every variable under
     the reference's name, so `parameters()` / `state_dict()` / optimisers / DDP see the whole network."""
 
-    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None):
+    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None, fusedLinear=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k, numOutCat)
         # rows (extension): torch.bfloat16 keeps the input rows of the depth-wise Conv_2 and Conv_3 in bf16 (they gather
@@ -34,7 +35,10 @@ class MCClassS(torch.nn.Module):
         # either way; the 1x1 matmuls and the MLP stay f32. None: every call is the f32 network's.
         self.rows = rows
         # fused (extension): batch norm + ReLU + dropout of the dense glue as one library op (VariableStore.fused_)
-        self.store = VariableStore(device, fused=fused)
+        # fusedLinear (extension): Reduce_k + Reduce_k_Out_BN and the hidden layers of the MLP as one library op each
+        # (VariableStore.fusedLinear_, conv_1x1_batch_norm_RELU_drop_out)
+        self.fusedLinear = bool(fusedLinear)
+        self.store = VariableStore(device, fused=fused, fusedLinear=fusedLinear)
         self.ops = ops  # None = the HIP op surface; the parity tests pass the CPU checker's
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
@@ -67,19 +71,27 @@ class MCClassS(torch.nn.Module):
             convName="Conv_1", inPointHierarchy=mPointHierarchy, inPointLevel=0, outPointLevel=1, inFeatures=features,
             inNumFeatures=numInputFeatures, outNumFeatures=k, convRadius=0.2, multiFeatureConv=True)
         convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_In_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv, st)
-        convFeatures1 = conv_1x1("Reduce_1", convFeatures1, k, k * 2, st)
         toRows = {} if self.rows is None else {"outDtype": self.rows}          # into a depth-wise layer
         toDense = {} if self.rows is None else {"outDtype": torch.float32}     # out of one, into a matmul
-        convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_Out_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv, st,
-                                                 **toRows)
+        if self.fusedLinear:
+            convFeatures1 = conv_1x1_batch_norm_RELU_drop_out("Reduce_1", "Reduce_1_Out_BN", convFeatures1, k, k * 2, isTraining,
+                                                              useConvDropOut, keepProbConv, st, **toRows)
+        else:
+            convFeatures1 = conv_1x1("Reduce_1", convFeatures1, k, k * 2, st)
+            convFeatures1 = batch_norm_RELU_drop_out("Reduce_1_Out_BN", convFeatures1, isTraining, useConvDropOut, keepProbConv,
+                                                     st, **toRows)
         convFeatures2 = mConvBuilder.create_convolution(
             convName="Conv_2", inPointHierarchy=mPointHierarchy, inPointLevel=1, outPointLevel=2,
             inFeatures=convFeatures1, inNumFeatures=k * 2, convRadius=0.8)
         convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_In_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st,
                                                  **toDense)
-        convFeatures2 = conv_1x1("Reduce_2", convFeatures2, k * 2, k * 4, st)
-        convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_Out_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv, st,
-                                                 **toRows)
+        if self.fusedLinear:
+            convFeatures2 = conv_1x1_batch_norm_RELU_drop_out("Reduce_2", "Reduce_2_Out_BN", convFeatures2, k * 2, k * 4, isTraining,
+                                                              useConvDropOut, keepProbConv, st, **toRows)
+        else:
+            convFeatures2 = conv_1x1("Reduce_2", convFeatures2, k * 2, k * 4, st)
+            convFeatures2 = batch_norm_RELU_drop_out("Reduce_2_Out_BN", convFeatures2, isTraining, useConvDropOut, keepProbConv,
+                                                     st, **toRows)
         convFeatures3 = mConvBuilder.create_convolution(
             convName="Conv_3", inPointHierarchy=mPointHierarchy, inPointLevel=2, outPointLevel=3,
             inFeatures=convFeatures2, inNumFeatures=k * 4, convRadius=math.sqrt(3.0) + 0.1)
@@ -162,6 +174,9 @@ def main():
     ap.add_argument("--points", type=int, default=1024)
     ap.add_argument("--fused-glue", action="store_true",
                     help="batch norm + ReLU + dropout of the dense layers as one library op (VariableStore(fused=True))")
+    ap.add_argument("--fused-linear", action="store_true",
+                    help="Reduce_k + Reduce_k_Out_BN and the hidden layers of the MLP as one library op each "
+                         "(VariableStore(fusedLinear=True))")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()
@@ -171,7 +186,8 @@ def main():
     # one process per GPU: run the backward pass on the calling thread -- the autograd engine's per-device worker thread
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
-    net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None)
+    net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None,
+                   fusedLinear=args.fused_linear)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \
         (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
     P, Bi, F, y = make_batch()

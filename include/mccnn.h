@@ -889,6 +889,45 @@ int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16
                           float keep_scale, unsigned seed, void* dx /* x's type; NULL: not wanted */, float* dgamma,
                           float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream);
 
+/* A LINEAR LAYER AND THE DENSE GLUE BEHIND IT AS ONE OP (extension, ABI 21; linear_bn.hip):
+ *   z = x w + b,  y = drop(act(bn(z)))
+ * x [n, cin], w [cin, cout] (as the store holds *_weights), z [n, cout] float32 row-major contiguous; b, gamma, beta and
+ * the moving statistics [cout] float32; n, cin, cout >= 1 with no divisibility rule. bn, act and drop are THE DENSE GLUE AS
+ * ONE OP above, applied to z (biased variance, moving statistics updated in place when training, gate pre > 0, the
+ * counter-based mask of (seed, i, j)). y is float32 (y_bf16 == 0) or bfloat16 storage (1; an even cout and y on 4 bytes,
+ * otherwise MCCNN_E_SHAPE), rounded to nearest even at the store; dy has y's type. z is accumulated in f32 on the f32-input
+ * matrix cores -- one fmaf chain over k = 0 .. cin - 1 per element, then + b -- and row i of z does not depend on the other
+ * rows of the call. x moves in 16-byte pieces when cin % 4 == 0 and x is on 16 bytes, as single floats otherwise: the
+ * same bytes either way.
+ *   training: writes z (the backward reads it), saved = [mean; rstd; remainder] [3, cout], the moving statistics and y. Two launches:
+ *             the matmul, whose epilogue also leaves the per-slab statistics of z in ws, and the kernel that merges and
+ *             applies them; one launch up to 256 rows. Inside, a mean is carried as an exact value of its column plus a
+ *             remainder of the size of the std, so xhat keeps f32 precision on columns with |mean| >> std; saved holds
+ *             the mean rounded to f32 once, rstd, and what the exact mean has over the rounded one -- forward and
+ *             backward both normalise as ((z - mean) - remainder) * rstd, so their gates agree bit for bit.
+ *   eval:     the moving statistics, no dropout, nothing updated; z and saved may be NULL, nothing is stored but y. One
+ *             launch.
+ *   backward: dz = bn_act's backward over z (into ws), dw = x^T dz, db = sum_i dz[i,:] (the cancelling sum it is: batch
+ *             norm removes the bias), dx = dz w^T, dx == NULL: not wanted (same bytes for everything else). At most five
+ *             launches, four up to 256 rows.
+ * No atomics, no memset, fixed merge orders: the same inputs and seed give the same bytes. ws of
+ * mccnn_linear_bn_act_workspace_bytes(n, cin, cout) bytes serves both directions (the training forward uses the front of
+ * it, none up to 256 rows; eval none: ws may then be NULL). n, cin or cout < 1, keep_threshold == 0 or > 2^32, a type flag
+ * outside {0, 1}, a NULL required pointer: MCCNN_E_BADARG; more than 65535 tiles of 64 rows, or cin * cout past 2^31:
+ * MCCNN_E_TOOLARGE; a missing or short workspace: MCCNN_E_WORKSPACE; all before anything is launched. */
+size_t mccnn_linear_bn_act_workspace_bytes(int n, int cin, int cout);
+int mccnn_linear_bn_act_fwd(const float* x, const float* w, const float* b, int n, int cin, int cout, const float* gamma,
+                            const float* beta, float* moving_mean, float* moving_var, float momentum, float eps,
+                            int training, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                            float* z /* [n,cout]; may be NULL when !training */, void* y, int y_bf16,
+                            float* saved /* [3,cout]; may be NULL when !training */,
+                            void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_linear_bn_act_bwd(const float* x, const float* w, const float* z, const void* dy, int dy_bf16, int n, int cin,
+                            int cout, const float* gamma, const float* beta, const float* saved, int relu,
+                            unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                            float* dx /* NULL: not wanted */, float* dw, float* db, float* dgamma, float* dbeta,
+                            void* ws, size_t ws_bytes, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

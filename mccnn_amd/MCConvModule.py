@@ -1774,3 +1774,101 @@ def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, 
     _bn_act_fwd(lib, _bf16_rows_aligned(x.detach()), gamma, beta, movingMean, movingVar, float(momentum), float(epsilon), 0,
                 int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# A linear layer and the dense glue behind it as one op (extension; csrc/linear_bn.hip, include/mccnn.h "A LINEAR LAYER AND
+# THE DENSE GLUE BEHIND IT AS ONE OP"): z = x @ w + b, y = drop(act(bn(z))).
+def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
+    """Checks of linear_bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale)."""
+    _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "linear_bn_relu_dropout: x must be a float32 tensor")
+    _req(isinstance(w, torch.Tensor) and w.dtype == torch.float32, "linear_bn_relu_dropout: w must be a float32 tensor")
+    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
+         "linear_bn_relu_dropout expects x (n, cin) and w (cin, cout), n, cin, cout >= 1")
+    _req(x.is_contiguous() and w.is_contiguous(), "linear_bn_relu_dropout: x and w must be contiguous")
+    _req(w.device == x.device, "linear_bn_relu_dropout: w is on another device than x")
+    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
+         and b.shape[0] == w.shape[1] and b.device == x.device, "linear_bn_relu_dropout: b must be a float32 (cout,) tensor on x's device")
+    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "linear_bn_relu_dropout: x too large")
+    _req(keepProb is None or (isinstance(keepProb, (int, float)) and not isinstance(keepProb, bool) and 0.0 < keepProb <= 1.0),
+         "linear_bn_relu_dropout expects keepProb in (0, 1] (or None)")
+    _req(isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < (1 << 32),
+         "linear_bn_relu_dropout expects a seed in [0, 2^32)")
+    _req(outDtype is None or outDtype in (torch.float32, torch.bfloat16),
+         "linear_bn_relu_dropout: outDtype must be None, torch.float32 or torch.bfloat16")
+    _req(outDtype != torch.bfloat16 or w.shape[1] % 2 == 0, "linear_bn_relu_dropout: bfloat16 rows need an even number of columns")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
+             and t.shape[0] == w.shape[1] and t.device == x.device,
+             "linear_bn_relu_dropout: %s must be a contiguous float32 (cout,) tensor on x's device" % name)
+    _req(x.is_cuda, "linear_bn_relu_dropout: x must be a CUDA tensor")
+    if keepProb is None:
+        return BN_DROP_ALL, 1.0
+    kp = float(keepProb)
+    thr = int(kp * 4294967296.0)   # floor(keepProb * 2^32) in double
+    _req(thr >= 1, "linear_bn_relu_dropout: keepProb keeps nothing")
+    return thr, float(_np.float32(1.0) / _np.float32(kp))   # 1.0f / (float) keepProb
+
+
+class _LinearBnReluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype=None):
+        lib = _lib.load()
+        n, cin = x.shape
+        cout = w.shape[1]
+        xd, wd, bd, gd, bed = x.detach(), w.detach(), b.detach(), gamma.detach(), beta.detach()
+        z = torch.empty((n, cout), dtype=torch.float32, device=x.device)
+        y = torch.empty((n, cout), dtype=outDtype or torch.float32, device=x.device)
+        saved = torch.empty((3, cout), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_linear_bn_act_workspace_bytes(n, cin, cout), x.device)
+        check(lib.mccnn_linear_bn_act_fwd(ptr(xd), ptr(wd), ptr(bd), n, cin, cout, ptr(gd), ptr(bed), ptr(movingMean), ptr(movingVar),
+                                          momentum, epsilon, 1, int(relu), thr, scale, seed, ptr(z), ptr(y),
+                                          int(y.dtype == torch.bfloat16), ptr(saved), ptr(ws), ws.numel(), stream_handle()),
+              "linear_bn_relu_dropout")
+        ctx.save_for_backward(xd, wd, gd, bed, z, saved)
+        ctx.attrs = (int(relu), thr, scale, seed, y.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, gamma, beta, z, saved = ctx.saved_tensors
+        relu, thr, scale, seed, ydt = ctx.attrs
+        lib = _lib.load()
+        n, cin = x.shape
+        cout = w.shape[1]
+        gy = gy.to(ydt).contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w)
+        dv = torch.empty((3, cout), dtype=torch.float32, device=x.device)   # db, dgamma, dbeta
+        ws = _ws(lib.mccnn_linear_bn_act_workspace_bytes(n, cin, cout), x.device)
+        check(lib.mccnn_linear_bn_act_bwd(ptr(x), ptr(w), ptr(z), ptr(gy), int(ydt == torch.bfloat16), n, cin, cout, ptr(gamma),
+                                          ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx), ptr(dw), ptr(dv[0]), ptr(dv[1]),
+                                          ptr(dv[2]), ptr(ws), ws.numel(), stream_handle()), "linear_bn_relu_dropout_grad")
+        need = ctx.needs_input_grad
+        return (dx, dw if need[1] else None, dv[0] if need[2] else None, dv[1] if need[3] else None,
+                dv[2] if need[4] else None) + (None,) * 9
+
+
+def linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0,
+                           momentum=0.99, epsilon=1e-3, outDtype=None):
+    """y = drop(act(bn(x @ w + b))) in one library op: x (n, cin) and w (cin, cout) float32 contiguous, everything per
+    column float32 (cout,). bn, act and drop are bn_relu_dropout's, applied to z = x @ w + b (batch statistics and the
+    moving ones updated in place when training; the counter-based mask of `seed`); differentiable (once) with respect to
+    x, w, b, gamma and beta. outDtype: y's type, None / torch.float32 or torch.bfloat16 (an even cout). Eval: the moving
+    statistics, no dropout, and no gradients -- an input that requires one raises."""
+    thr, scale = _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    if training:
+        return _LinearBnReluDropout.apply(x, w, b, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed,
+                                          float(momentum), float(epsilon), outDtype)
+    _req(not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
+         "linear_bn_relu_dropout: the eval form has no gradients")
+    lib = _lib.load()
+    n, cin = x.shape
+    cout = w.shape[1]
+    y = torch.empty((n, cout), dtype=outDtype or torch.float32, device=x.device)
+    check(lib.mccnn_linear_bn_act_fwd(ptr(x.detach()), ptr(w.detach()), ptr(b.detach()), n, cin, cout, ptr(gamma.detach()),
+                                      ptr(beta.detach()), ptr(movingMean), ptr(movingVar), float(momentum), float(epsilon), 0,
+                                      int(bool(relu)), BN_DROP_ALL, 1.0, seed, None, ptr(y), int(y.dtype == torch.bfloat16), None,
+                                      None, 0, stream_handle()), "linear_bn_relu_dropout")
+    return y

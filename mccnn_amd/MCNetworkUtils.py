@@ -12,6 +12,13 @@ VariableStore(fused=True) (extension, opt-in): batch norm + ReLU + dropout of a 
 (MCConvModule.bn_relu_dropout, csrc/bn_act.hip) where its conditions hold (_fused_glue); everywhere else, and always
 with fused off, the code below is what runs. Names, shapes, initialisers and state_dict are the same either way; the
 dropout mask of the fused op is counter-based (seed dropSeed_ + dropCalls_), not torch's random stream.
+
+VariableStore(fusedLinear=True) (extension, opt-in): a linear layer with such a block behind it -- conv_1x1 followed by
+batch_norm_RELU_drop_out (conv_1x1_batch_norm_RELU_drop_out) and the hidden layers of the MLPs -- runs as ONE library op
+(MCConvModule.linear_bn_relu_dropout, csrc/linear_bn.hip) where its conditions hold (_fused_linear); everywhere else the
+matmul and the block run as before. Names, shapes, initialisers, creation order and state_dict are the same either way,
+and a call that drops takes its seed from dropSeed_ / dropCalls_ as the fused glue does: with `fused` on as well, the
+masks of a network do not depend on this switch.
 """
 import math
 
@@ -25,11 +32,12 @@ class VariableStore(torch.nn.Module):
     names (`Reduce_1_weights`, `Final_Logits_BN_h1/gamma`, ...). Variables are created on first use (tf.get_variable),
     so load_state_dict() also accepts names that do not exist yet."""
 
-    def __init__(self, device=None, fused=False):
+    def __init__(self, device=None, fused=False, fusedLinear=False):
         super().__init__()
         self.device = device
         self.collections_ = {}
         self.fused_ = bool(fused)   # the dense glue as one library op where it applies (may be reassigned at any time)
+        self.fusedLinear_ = bool(fusedLinear)   # linear layer + glue as one library op where it applies (reassignable too)
         self.dropSeed_ = 0          # a fused call that drops uses the seed (dropSeed_ + dropCalls_) mod 2^32 ...
         self.dropCalls_ = 0         # ... and increments this counter
 
@@ -242,6 +250,75 @@ def _bn_relu_drop(st, inputs, training, name, useDropOut, keepProb, outDtype=Non
     return y
 
 
+_FUSED_LINEAR_OP = False   # native.linear_bn_relu_drop once the library has loaded; None when it does not
+
+
+def _fused_linear_op():
+    global _FUSED_LINEAR_OP
+    if _FUSED_LINEAR_OP is False:
+        try:
+            from . import _lib, native
+            _lib.load()
+            _FUSED_LINEAR_OP = native.linear_bn_relu_drop
+        except (ImportError, OSError, AttributeError, RuntimeError):
+            _FUSED_LINEAR_OP = None
+    return _FUSED_LINEAR_OP
+
+
+def _fused_linear(st, inputs, w, b, training, name, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
+    """drop(relu(batch_normalization(inputs @ w + b))) as one library op, or None where that form does not apply (the
+    caller then runs the matmul and the block as before): the store's switch is off, inputs is not a contiguous float32
+    [n, cin] tensor on a HIP device (w and b likewise), the library does not load, training statistics are synchronised
+    across ranks, or an eval call wants gradients. The variables of the block are created as batch_normalization creates
+    them, and a call that drops takes its seed as _fused_glue does."""
+    if not getattr(st, "fusedLinear_", False):
+        return None
+    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
+            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+        return None
+    if not (w.dim() == 2 and w.shape[0] == inputs.shape[1] and w.shape[1] >= 1 and b.dim() == 1 and b.shape[0] == w.shape[1]):
+        return None
+    if outDtype not in (None, torch.float32, torch.bfloat16):
+        return None
+    if w.shape[1] % 2 != 0 and outDtype == torch.bfloat16:
+        return None
+    if training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return None
+    if keepProb is not None and not 0.0 < keepProb <= 1.0:
+        return None
+    op = _fused_linear_op()
+    if op is None:
+        return None
+    c = w.shape[1]
+    dev = inputs.device
+    gamma = st.get_variable(name + "/gamma", (c,), _ones, dev)
+    beta = st.get_variable(name + "/beta", (c,), _zeros, dev)
+    mov_mean = st.get_buffer(name + "/moving_mean", (c,), 0.0, dev)
+    mov_var = st.get_buffer(name + "/moving_variance", (c,), 1.0, dev)
+    if not training and torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, w, b, gamma, beta)):
+        return None
+    if not all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
+               for t in (w, b, gamma, beta, mov_mean, mov_var)):
+        return None
+    seed = 0
+    if training and keepProb is not None:
+        seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
+        st.dropCalls_ += 1
+    else:
+        keepProb = None
+    return op(inputs, w, b, gamma, beta, mov_mean, mov_var, bool(training), True, keepProb, seed, momentum, epsilon, outDtype)
+
+
+def _linear_bn_relu_drop(st, inputs, w, b, training, name, useDropOut, keepProb, outDtype=None):
+    """_bn_relu_drop(inputs @ w + b): as one library op where the store's fusedLinear_ says so and it applies, the matmul
+    and the block otherwise."""
+    if getattr(st, "fusedLinear_", False):
+        y = _fused_linear(st, inputs, w, b, training, name, _keep_prob(useDropOut, keepProb), outDtype=outDtype)
+        if y is not None:
+            return y
+    return _bn_relu_drop(st, inputs @ w + b, training, name, useDropOut, keepProb, outDtype)
+
+
 def _dropout(x, keepProb, training=True):
     if keepProb is None or keepProb is False:
         return x
@@ -260,12 +337,12 @@ def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOu
                         _fan_avg_uniform(numInputFeatures, hidden1_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases1', (hidden1_units,), _zeros, dev)
-    hidden1 = _bn_relu_drop(st, features @ w + b, isTraining, layerName + "_BN_h1", useDropOut, keepProb)
+    hidden1 = _linear_bn_relu_drop(st, features, w, b, isTraining, layerName + "_BN_h1", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights2', (hidden1_units, hidden2_units),
                         _glorot_uniform(hidden1_units, hidden2_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases2', (hidden2_units,), _zeros, dev)
-    hidden2 = _bn_relu_drop(st, hidden1 @ w + b, isTraining, layerName + "_BN_h2", useDropOut, keepProb)
+    hidden2 = _linear_bn_relu_drop(st, hidden1, w, b, isTraining, layerName + "_BN_h2", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights3', (hidden2_units, numOutFeatures),
                         _fan_avg_uniform(hidden2_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
@@ -282,7 +359,7 @@ def MLP_1_hidden(features, numInputFeatures, hidden_units, numOutFeatures, layer
                         _fan_avg_uniform(numInputFeatures, hidden_units), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases1', (hidden_units,), _zeros, dev)
-    hidden = _bn_relu_drop(st, features @ w + b, isTraining, layerName + "_BN_h", useDropOut, keepProb)
+    hidden = _linear_bn_relu_drop(st, features, w, b, isTraining, layerName + "_BN_h", useDropOut, keepProb)
     w = st.get_variable(layerName + '_weights2', (hidden_units, numOutFeatures),
                         _fan_avg_uniform(hidden_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
@@ -306,3 +383,21 @@ def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, kee
     also the cast between layers that keep different row types."""
     st = store or _DEFAULT_STORE
     return _bn_relu_drop(st, inFeatures, isTraining, layerName + "_BN", usedDropOut, keepProb, outDtype)
+
+
+def conv_1x1_batch_norm_RELU_drop_out(layerName, bnLayerName, inputs, numInputs, numOutFeatures, isTraining, usedDropOut,
+                                      keepProb, store=None, outDtype=None):
+    """batch_norm_RELU_drop_out(bnLayerName, conv_1x1(layerName, inputs, numInputs, numOutFeatures), isTraining,
+    usedDropOut, keepProb, outDtype=outDtype) (extension): the same variables, created in the same order from the same
+    initialisers; one library op where the store's fusedLinear_ is set and the op applies, the two helpers otherwise."""
+    st = store or _DEFAULT_STORE
+    if getattr(st, "fusedLinear_", False):
+        dev = inputs.device
+        w = st.get_variable(layerName + '_weights', (numInputs, numOutFeatures), _fan_avg_uniform(numInputs, numOutFeatures), dev)
+        st.add_to_collection('weight_decay_loss', w)
+        b = st.get_variable(layerName + '_biases', (numOutFeatures,), _zeros, dev)
+        y = _fused_linear(st, inputs, w, b, isTraining, bnLayerName + "_BN", _keep_prob(usedDropOut, keepProb), outDtype=outDtype)
+        if y is not None:
+            return y
+    return batch_norm_RELU_drop_out(bnLayerName, conv_1x1(layerName, inputs, numInputs, numOutFeatures, st), isTraining,
+                                    usedDropOut, keepProb, st, outDtype)

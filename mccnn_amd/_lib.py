@@ -144,6 +144,12 @@ SIGNATURES = {
                                    _sz, _vp]),
     "mccnn_bn_act_bwd_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    # a linear layer and the dense glue behind it as one op (linear_bn.hip)
+    "mccnn_linear_bn_act_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mccnn_linear_bn_act_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_ulonglong, _f, C.c_uint, _vp,
+                                     _vp, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_linear_bn_act_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _sz, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -22,6 +22,7 @@
 // same bytes. The gate is pre > 0 (torch's relu'), not the >= 0 of the convolution kernels.
 #include "common.h"
 #include "bn_drop.h"
+#include "bn_act.h"
 
 namespace mccnn {
 
@@ -39,7 +40,7 @@ constexpr int kBnRowsAhead = VEC == 8 ? 8 : 4;
 struct BnPlan {
     int vec, tw_log, tiles, slab_rows, slabs;
 };
-inline int bn_slab_rows(int n) {
+int bn_slab_rows(int n) {
     if (n <= kBnSmallRows) return n;
     if (ceil_div(n, kBnSlabRows) <= kBnMaxSlabs) return kBnSlabRows;
     return ceil_div(ceil_div(n, kBnMaxSlabs), 32) * 32;
@@ -67,6 +68,7 @@ struct BnArgs {
     float* mov_mean;
     float* mov_var;
     float* saved;        // [2, c]: written by the forward, read by the backward
+    const float* shift;  // backward, linear_bn.hip only: per column what the exact mean has over saved's (NULL: nothing)
     float* part;         // the slab partials: planes of [slabs, c]
     float* dgamma;
     float* dbeta;
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
 // ---- backward ----------------------------------------------------------------------------------------------------------
 template <int VEC>
 struct BnCols {
-    float mean[VEC], rstd[VEC], g[VEC], b[VEC];
+    float mean[VEC], rstd[VEC], g[VEC], b[VEC], c[VEC];
 };
 template <int VEC>
 __device__ __forceinline__ BnCols<VEC> bn_cols(const BnArgs& a, const BnCoord& t) {
@@ -440,6 +442,7 @@ __device__ __forceinline__ BnCols<VEC> bn_cols(const BnArgs& a, const BnCoord& t
         q.rstd[k] = t.ok ? a.saved[(size_t)a.c + t.col + k] : 0.f;
         q.g[k] = t.ok ? a.gamma[t.col + k] : 0.f;
         q.b[k] = t.ok ? a.beta[t.col + k] : 0.f;
+        q.c[k] = (t.ok && a.shift) ? a.shift[t.col + k] : 0.f;
     }
     return q;
 }
@@ -451,7 +454,7 @@ __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, c
     const uint32_t rh = drop ? bn_drop_row(a.seed, r) : 0u;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-        xh[k] = (v[k] - q.mean[k]) * q.rstd[k];
+        xh[k] = ((v[k] - q.mean[k]) - q.c[k]) * q.rstd[k];   // (c = 0 without a shift: x - 0 is x, bit for bit)
         const float pre = xh[k] * q.g[k] + q.b[k];
         float w = d[k];
         if (drop) w = bn_drop_keep(rh, (uint32_t)(t.col + k), a.T) ? w * a.keep_scale : 0.f;
@@ -635,6 +638,37 @@ struct BnBwdDxL {
 
 using namespace mccnn;
 
+// The backward behind mccnn_bn_act_bwd_rows. shift (linear_bn.hip; NULL otherwise): [c], what the exact mean of a column has
+// over saved's f32 one -- xhat is then ((x - mean) - shift) * rstd, the arithmetic of that file's forward
+int mccnn::bn_act_bwd_impl(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, const float* gamma,
+                           const float* beta, const float* saved, const float* shift, int relu, unsigned long long keep_threshold,
+                           float keep_scale, unsigned seed, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                           mccnn_stream_t stream) {
+    if (n < 1 || c < 1) return MCCNN_E_BADARG;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!x || !dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
+    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
+    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
+    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
+                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)) && (!need || bn_aligned16(ws)), x_bf16);
+    BnArgs a = {};
+    a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
+    a.part = (float*)ws; a.dgamma = dgamma; a.dbeta = dbeta; a.shift = shift;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
+    a.want_dx = dx ? 1 : 0;
+    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
+    if (n <= kBnSmallRows) {
+        return bn_launch<BnBwdDxL<1>>(p.vec, x_bf16, dy_bf16, grid, st, a);
+    }
+    if (const int e = bn_launch<BnBwdSumsL>(p.vec, x_bf16, dy_bf16, grid, st, a)) return e;
+    const dim3 grid2((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u);
+    return bn_launch<BnBwdDxL<0>>(p.vec, x_bf16, dy_bf16, grid2, st, a);
+}
+
 extern "C" {
 
 size_t mccnn_bn_act_workspace_bytes(int n, int c) {
@@ -678,29 +712,8 @@ int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16
                           const float* beta, const float* saved, int relu, unsigned long long keep_threshold, float keep_scale,
                           unsigned seed, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                           mccnn_stream_t stream) {
-    if (n < 1 || c < 1) return MCCNN_E_BADARG;
-    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
-    if (!x || !dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
-    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
-    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
-    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
-                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)) && (!need || bn_aligned16(ws)), x_bf16);
-    BnArgs a = {};
-    a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
-    a.part = (float*)ws; a.dgamma = dgamma; a.dbeta = dbeta;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
-    a.want_dx = dx ? 1 : 0;
-    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
-    if (n <= kBnSmallRows) {
-        return bn_launch<BnBwdDxL<1>>(p.vec, x_bf16, dy_bf16, grid, st, a);
-    }
-    if (const int e = bn_launch<BnBwdSumsL>(p.vec, x_bf16, dy_bf16, grid, st, a)) return e;
-    const dim3 grid2((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u);
-    return bn_launch<BnBwdDxL<0>>(p.vec, x_bf16, dy_bf16, grid2, st, a);
+    return bn_act_bwd_impl(x, x_bf16, dy, dy_bf16, n, c, gamma, beta, saved, nullptr, relu, keep_threshold, keep_scale, seed, dx,
+                           dgamma, dbeta, ws, ws_bytes, stream);
 }
 
 // the float32 entries (ABI 18): the typed ones with both flags zero -- the same plan, kernels, launches and bytes

@@ -1485,6 +1485,114 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
     return y;
 }
 
+// ---- a linear layer and the dense glue behind it as one op (mccnn_linear_bn_act_fwd / _bwd): y = drop(act(bn(x w + b))), the
+// C++ form of MCConvModule.linear_bn_relu_dropout -- the same library calls with the same arguments, so the same bytes.
+// x, w, z and everything per column are f32; y (and dy) f32 or bf16.
+struct LinearBnBackward : public torch::autograd::Node {
+    Tensor x_, w_, gamma_, beta_, z, saved;
+    bool y_bf16 = false;
+    uint32_t versions[4] = {0, 0, 0, 0};
+    int relu = 1;
+    unsigned long long thr = 0;
+    float scale = 1.f;
+    unsigned seed = 0;
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        TORCH_CHECK(x_.defined() && z.defined() && saved.defined(),
+                    "linear_bn_relu_drop: backward through a graph whose buffers have been freed (retain_graph=True?)");
+        Tensor gy = grads[0];
+        TORCH_CHECK(!(at::GradMode::is_enabled() && gy.defined() && gy.requires_grad()),
+                    "linear_bn_relu_drop is differentiable once: no double backward");
+        {
+            const Tensor* in[4] = {&x_, &w_, &gamma_, &beta_};
+            for (int k = 0; k < 4; ++k)
+                TORCH_CHECK(in[k]->_version() == versions[k],
+                            "one of the variables needed for gradient computation has been modified by an inplace operation "
+                            "(linear_bn_relu_drop input ", k, ")");
+        }
+        const DevGuard device_guard((int)x_.device().index());
+        const int n = (int)x_.size(0), cin = (int)x_.size(1), cout = (int)w_.size(1);
+        const at::ScalarType yt = y_bf16 ? at::kBFloat16 : at::kFloat;
+        if (!gy.defined()) gy = at::zeros(z.sizes(), z.options().dtype(yt));
+        if (gy.scalar_type() != yt) gy = gy.to(yt);
+        if (!gy.is_contiguous()) gy = gy.contiguous();
+        const bool want_dx = task_should_compute_output(0);
+        Tensor dx;
+        if (want_dx) dx = at::empty_like(x_);
+        Tensor dw = at::empty_like(w_);
+        Tensor dv = at::empty({3, (int64_t)cout}, gamma_.options());   // db, dgamma, dbeta
+        void* st = cur_stream(x_);
+        Tensor& ws = scratch(mccnn_linear_bn_act_workspace_bytes(n, cin, cout), x_, st);
+        check(mccnn_linear_bn_act_bwd(x_.data_ptr<float>(), w_.data_ptr<float>(), z.data_ptr<float>(), gy.data_ptr(), y_bf16 ? 1 : 0, n,
+                                      cin, cout, gamma_.data_ptr<float>(), beta_.data_ptr<float>(), saved.data_ptr<float>(), relu, thr,
+                                      scale, seed, want_dx ? dx.data_ptr<float>() : nullptr, dw.data_ptr<float>(), dv.data_ptr<float>(),
+                                      dv.data_ptr<float>() + cout, dv.data_ptr<float>() + 2 * (size_t)cout, ws.data_ptr(),
+                                      (size_t)ws.numel(), st),
+              "linear_bn_relu_dropout_grad");
+        torch::autograd::variable_list out(5);
+        out[0] = dx;
+        if (task_should_compute_output(1)) out[1] = dw;
+        if (task_should_compute_output(2)) out[2] = dv.select(0, 0);
+        if (task_should_compute_output(3)) out[3] = dv.select(0, 1);
+        if (task_should_compute_output(4)) out[4] = dv.select(0, 2);
+        return out;
+    }
+    void release_variables() override { x_.reset(); w_.reset(); gamma_.reset(); beta_.reset(); z.reset(); saved.reset(); }
+};
+
+// out_type: -1 or 0 float32, 1 bfloat16
+Tensor linear_bn_relu_drop(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& gamma, const Tensor& beta,
+                           const Tensor& mov_mean, const Tensor& mov_var, bool training, bool relu, unsigned long long thr,
+                           double scale, unsigned seed, double momentum, double eps, int out_type) {
+    check_dev(x, at::kFloat, "x");
+    check_dev(w, at::kFloat, "w");
+    TORCH_CHECK(out_type >= -1 && out_type <= 1, "linear_bn_relu_drop: out_type must be -1 / 0 (float32) or 1 (bfloat16)");
+    const bool y_bf16 = out_type == 1;
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && w.size(1) >= 1 && w.size(0) == x.size(1) &&
+                    x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31) && w.size(1) < (1ll << 31) && w.device() == x.device(),
+                "linear_bn_relu_drop expects x (n, cin) and w (cin, cout), n, cin, cout >= 1");
+    TORCH_CHECK(!y_bf16 || w.size(1) % 2 == 0, "linear_bn_relu_drop: bfloat16 rows need an even number of columns");
+    for (const Tensor* t : {&b, &gamma, &beta, &mov_mean, &mov_var}) {
+        check_dev(*t, at::kFloat, "per-column tensor");
+        TORCH_CHECK(t->dim() == 1 && t->size(0) == w.size(1) && t->device() == x.device(),
+                    "linear_bn_relu_drop: per-column tensors must have shape (cout,)");
+    }
+    const DevGuard device_guard((int)x.device().index());
+    const int n = (int)x.size(0), cin = (int)x.size(1), cout = (int)w.size(1);
+    const bool need_grad = at::GradMode::is_enabled() &&
+                           (x.requires_grad() || w.requires_grad() || b.requires_grad() || gamma.requires_grad() || beta.requires_grad());
+    TORCH_CHECK(training || !need_grad, "linear_bn_relu_drop: the eval form has no gradients");
+    Tensor y, z, saved;
+    {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        y = at::empty({(int64_t)n, (int64_t)cout}, x.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
+        if (training) {
+            z = at::empty({(int64_t)n, (int64_t)cout}, x.options());
+            saved = at::empty({3, (int64_t)cout}, gamma.options());
+        }
+        void* st = cur_stream(x);
+        Tensor& ws = scratch(training ? mccnn_linear_bn_act_workspace_bytes(n, cin, cout) : 0, x, st);
+        check(mccnn_linear_bn_act_fwd(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(), n, cin, cout, gamma.data_ptr<float>(),
+                                      beta.data_ptr<float>(), mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum,
+                                      (float)eps, training ? 1 : 0, relu ? 1 : 0, training ? thr : 0x100000000ull,
+                                      training ? (float)scale : 1.f, seed, training ? z.data_ptr<float>() : nullptr, y.data_ptr(),
+                                      y_bf16 ? 1 : 0, training ? saved.data_ptr<float>() : nullptr, training ? ws.data_ptr() : nullptr,
+                                      training ? (size_t)ws.numel() : 0, st),
+              "linear_bn_relu_dropout");
+    }
+    if (need_grad) {
+        auto node = std::shared_ptr<LinearBnBackward>(new LinearBnBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(x, w, b, gamma, beta));
+        node->x_ = x; node->w_ = w; node->gamma_ = gamma; node->beta_ = beta; node->y_bf16 = y_bf16;
+        node->versions[0] = x._version(); node->versions[1] = w._version(); node->versions[2] = gamma._version();
+        node->versions[3] = beta._version();
+        node->z = z; node->saved = saved;
+        node->relu = relu ? 1 : 0; node->thr = thr; node->scale = (float)scale; node->seed = seed;
+        torch::autograd::set_history(y, node);
+    }
+    return y;
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -1849,6 +1957,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("bn_relu_drop", &bn_relu_drop, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
             py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
             py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1, py::call_guard<py::gil_scoped_release>());
+    mod.def("linear_bn_relu_drop", &linear_bn_relu_drop, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("gamma"), py::arg("beta"),
+            py::arg("moving_mean"), py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"),
+            py::arg("keep_scale"), py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1,
+            py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

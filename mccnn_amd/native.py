@@ -640,3 +640,20 @@ def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, kee
            "bn_relu_dropout: the eval form has no gradients")
     return _EXT.bn_relu_drop(x, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
                              float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
+
+
+def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
+                        epsilon=1e-3, outDtype=None):
+    """A linear layer and the dense glue behind it as one op, y = drop(act(bn(x @ w + b)))
+    (MCConvModule.linear_bn_relu_dropout: its definition, checks and errors): one Python -> C++ call forward and an
+    autograd node on the C++ side when the extension is loaded, the ctypes op otherwise -- the same library calls either
+    way, so the same bytes."""
+    from . import MCConvModule as M
+    if _EXT is None:
+        return M.linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum,
+                                        epsilon, outDtype)
+    thr, scale = M._linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    M._req(training or not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
+           "linear_bn_relu_dropout: the eval form has no gradients")
+    return _EXT.linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
+                                    float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
