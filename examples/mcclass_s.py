@@ -27,7 +27,8 @@ class MCClassS(torch.nn.Module):
     whose sub-modules (the convolution builder and the dense helpers' variable store) register every variable under
     the reference's name, so `parameters()` / `state_dict()` / optimisers / DDP see the whole network."""
 
-    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None, fusedLinear=False):
+    def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None, fusedLinear=False,
+                 fusedSync=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k, numOutCat)
         # rows (extension): torch.bfloat16 keeps the input rows of the depth-wise Conv_2 and Conv_3 in bf16 (they gather
@@ -38,7 +39,9 @@ class MCClassS(torch.nn.Module):
         # fusedLinear (extension): Reduce_k + Reduce_k_Out_BN and the hidden layers of the MLP as one library op each
         # (VariableStore.fusedLinear_, conv_1x1_batch_norm_RELU_drop_out)
         self.fusedLinear = bool(fusedLinear)
-        self.store = VariableStore(device, fused=fused, fusedLinear=fusedLinear)
+        # fusedSync (extension): with fused, the glue stays a library op when its statistics run across ranks
+        # (VariableStore.fusedSync_)
+        self.store = VariableStore(device, fused=fused, fusedLinear=fusedLinear, fusedSync=fusedSync)
         self.ops = ops  # None = the HIP op surface; the parity tests pass the CPU checker's
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
@@ -106,10 +109,10 @@ class MCClassS(torch.nn.Module):
 class MCNormS(torch.nn.Module):
     """models/MCNormS.py create_network(): two same-level multi-feature convolutions (normal estimation)."""
 
-    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False):
+    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False, fusedSync=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k)
-        self.store = VariableStore(device, fused=fused)
+        self.store = VariableStore(device, fused=fused, fusedSync=fusedSync)
         self.ops = ops
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 

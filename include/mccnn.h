@@ -888,6 +888,53 @@ int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16
                           const float* beta, const float* saved, int relu, unsigned long long keep_threshold,
                           float keep_scale, unsigned seed, void* dx /* x's type; NULL: not wanted */, float* dgamma,
                           float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream);
+/* ... WITH BATCH STATISTICS ACROSS RANKS (extension, ABI 22; bn_act.hip): the training form of the same op when the rows of
+ * a batch are sharded over the `world` ranks of a process group. n, mean and var of the definition above are those of the
+ * concatenation of the ranks' rows in rank order (N rows); the op is cut in two where the caller's collective goes, forward
+ * and backward. Typed like the _rows entries (x / dx and y / dy each float32 or bfloat16 storage, the same alignment and
+ * even-c rules); n is THIS rank's row count, n >= 1 on every rank, and may differ between ranks.
+ *   forward:   mccnn_bn_sync_stats  -> [gather parts] -> mccnn_bn_sync_apply
+ *   backward:  mccnn_bn_sync_bwd_sums -> [gather parts_b] -> mccnn_bn_sync_bwd_dx
+ * parts, parts_b: [world, 3, c] float32 (moved as single floats: 4-byte alignment). A stats / sums stage writes this rank's
+ * row -- (count, mean, M2) per column, the slab partials of the plain op merged in its fixed order, resp. (sum g,
+ * sum g * xhat, sum xhat) -- and +0.0f into EVERY other row: nothing needs a memset, and an all-reduce(SUM) of the tensor is
+ * an exact gather (so is an all-gather of the rows). The stage behind the collective reads all rows.
+ *   apply:     every workgroup merges the rows of its columns by Chan's rule in rank order 0 .. world - 1 (once, ahead of
+ *              its rows), var = M2 / N; saved = [mean; rstd] and the moving statistics take the global mean and biased
+ *              variance; meta = int32[2] = (rowBase, N), rowBase = the rows of the lower ranks. The rest is the plain op's.
+ *   dropout:   the mask of local row i is that of GLOBAL row rowBase + i: with one seed on all ranks the shards reproduce
+ *              the mask of the unsharded batch.
+ *   bwd_sums:  g, xhat, gate and mask recomputed as the plain backward does (mask at global rows; meta and saved are the
+ *              forward's). dbeta = this rank's sum g, dgamma = this rank's sum g * xhat: adding them up over the ranks is
+ *              the caller's gradient all-reduce.
+ *   bwd_dx:    sums the rows of parts_b in rank order: dx = gamma * rstd * (g - Sg / N - (xhat - mh) * (Sgx - mh Sg) / N),
+ *              mh = Sh / N the mean of xhat (the saved f32 mean's rounding error; the correction of the plain backward).
+ *              dgamma != NULL: rewritten as this rank's sum g * (xhat - mh) -- the plain op's dgamma once the ranks' are
+ *              added. dx == NULL: not wanted (dgamma is then required).
+ * Launches: stats and bwd_sums two each, one for n <= 256; apply and bwd_dx one each. No atomics, no tickets, fixed merge
+ * orders: the same inputs and seed give the same bytes, and from the same gathered parts every rank computes the same
+ * bytes of saved and of the moving statistics. world == 1 is allowed (the plain op's y). ws: mccnn_bn_act_workspace_bytes(n, c)
+ * for stats and bwd_sums. n, c or world < 1, rank outside [0, world), keep_threshold == 0 or > 2^32, a type flag outside
+ * {0, 1}, a NULL required pointer: MCCNN_E_BADARG; n > 2^24 (counts travel as f32): MCCNN_E_TOOLARGE; a missing or short
+ * workspace: MCCNN_E_WORKSPACE; the bf16 rules: MCCNN_E_SHAPE; all before anything is launched. N must stay below 2^31.
+ * Not covered: a split form of mccnn_linear_bn_act_*, overlapping the collective with other work, ranks without rows,
+ * statistics in anything but f32. */
+int mccnn_bn_sync_stats(const void* x, int x_bf16, int n, int c, int rank, int world, float* parts /* [world,3,c] */,
+                        void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_sync_apply(const void* x, int x_bf16, int n, int c, int rank, int world, const float* parts /* gathered */,
+                        const float* gamma, const float* beta, float* moving_mean, float* moving_var, float momentum,
+                        float eps, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                        void* y, int y_bf16, float* saved /* [2,c] */, int* meta /* [2] */, mccnn_stream_t stream);
+int mccnn_bn_sync_bwd_sums(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
+                           const float* gamma, const float* beta, const float* saved, const int* meta, int relu,
+                           unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                           float* parts_b /* [world,3,c] */, float* dgamma, float* dbeta,
+                           void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_sync_bwd_dx(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
+                         const float* gamma, const float* beta, const float* parts_b /* gathered */, const float* saved,
+                         const int* meta, int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                         void* dx /* x's type; NULL: not wanted */, float* dgamma /* NULL: left as bwd_sums wrote it */,
+                         mccnn_stream_t stream);
 
 /* A LINEAR LAYER AND THE DENSE GLUE BEHIND IT AS ONE OP (extension, ABI 21; linear_bn.hip):
  *   z = x w + b,  y = drop(act(bn(z)))

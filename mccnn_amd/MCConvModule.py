@@ -1777,6 +1777,114 @@ def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, 
 
 
 # ---------------------------------------------------------------------------------------------
+# ... with batch statistics across the ranks of a process group (include/mccnn.h "... WITH BATCH STATISTICS ACROSS RANKS"):
+# the library op cut in two where the collective goes -- stats, gather, apply forward; sums, gather, dx backward. The
+# collective is torch.distributed's (mccnn_amd.dist.gather_rows), so the autograd node is Python's, over four stage calls:
+# the ctypes ones below, or the extension's (native.bn_relu_drop_sync) -- the same library calls, so the same bytes.
+def _bn_sync_stats(x, rank, world, parts):
+    lib = _lib.load()
+    n, c = x.shape
+    ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+    check(lib.mccnn_bn_sync_stats(ptr(x), int(x.dtype == torch.bfloat16), n, c, rank, world, ptr(parts), ptr(ws), ws.numel(),
+                                  stream_handle()), "bn_relu_dropout_sync")
+
+
+def _bn_sync_apply(x, rank, world, parts, gamma, beta, movingMean, movingVar, momentum, epsilon, relu, thr, scale, seed, y, saved,
+                   meta):
+    lib = _lib.load()
+    check(lib.mccnn_bn_sync_apply(ptr(x), int(x.dtype == torch.bfloat16), x.shape[0], x.shape[1], rank, world, ptr(parts), ptr(gamma),
+                                  ptr(beta), ptr(movingMean), ptr(movingVar), momentum, epsilon, int(relu), thr, scale, seed, ptr(y),
+                                  int(y.dtype == torch.bfloat16), ptr(saved), ptr(meta), stream_handle()), "bn_relu_dropout_sync")
+
+
+def _bn_sync_bwd_sums(x, gy, rank, world, gamma, beta, saved, meta, relu, thr, scale, seed, partsB, dgb):
+    lib = _lib.load()
+    n, c = x.shape
+    ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+    check(lib.mccnn_bn_sync_bwd_sums(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(gy.dtype == torch.bfloat16), n, c, rank,
+                                     world, ptr(gamma), ptr(beta), ptr(saved), ptr(meta), int(relu), thr, scale, seed, ptr(partsB),
+                                     ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_sync_grad")
+
+
+def _bn_sync_bwd_dx(x, gy, rank, world, gamma, beta, partsB, saved, meta, relu, thr, scale, seed, dx, dgb):
+    lib = _lib.load()
+    check(lib.mccnn_bn_sync_bwd_dx(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(gy.dtype == torch.bfloat16), x.shape[0],
+                                   x.shape[1], rank, world, ptr(gamma), ptr(beta), ptr(partsB), ptr(saved), ptr(meta), int(relu), thr,
+                                   scale, seed, ptr(dx), ptr(dgb[0]), stream_handle()), "bn_relu_dropout_sync_grad")
+
+
+_BN_SYNC_STAGES = (_bn_sync_stats, _bn_sync_apply, _bn_sync_bwd_sums, _bn_sync_bwd_dx)
+
+
+def _bn_sync_place(group):
+    """(rank, world) of this process in `group` (None: the default group); (0, 1) without a process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
+
+
+class _BnReluDropoutSync(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype, group, stages):
+        from .dist import gather_rows
+        rank, world = _bn_sync_place(group)
+        n, c = x.shape
+        xd, gd, bd = _bf16_rows_aligned(x.detach()), gamma.detach(), beta.detach()
+        parts = torch.empty((world, 3 * c), dtype=torch.float32, device=x.device)
+        stages[0](xd, rank, world, parts)
+        parts = gather_rows(parts, group)
+        y = torch.empty((n, c), dtype=outDtype or x.dtype, device=x.device)
+        saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        meta = torch.empty((2,), dtype=torch.int32, device=x.device)
+        stages[1](xd, rank, world, parts, gd, bd, movingMean, movingVar, momentum, epsilon, relu, thr, scale, seed, y, saved, meta)
+        ctx.save_for_backward(xd, gd, bd, saved, meta)
+        ctx.attrs = (relu, thr, scale, seed, y.dtype, group, stages, rank, world)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from .dist import gather_rows
+        x, gamma, beta, saved, meta = ctx.saved_tensors
+        relu, thr, scale, seed, ydt, group, stages, rank, world = ctx.attrs
+        c = x.shape[1]
+        gy = _bf16_rows_aligned(gy.to(ydt).contiguous())
+        partsB = torch.empty((world, 3 * c), dtype=torch.float32, device=x.device)
+        dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        stages[2](x, gy, rank, world, gamma, beta, saved, meta, relu, thr, scale, seed, partsB, dgb)
+        partsB = gather_rows(partsB, group)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        stages[3](x, gy, rank, world, gamma, beta, partsB, saved, meta, relu, thr, scale, seed, dx, dgb)
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
+def _bn_relu_dropout_sync(stages, x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype, group):
+    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    if group is not None:
+        import torch.distributed as dist
+        _req(dist.is_available() and isinstance(group, dist.ProcessGroup), "bn_relu_dropout_sync: group must be a process group (or None)")
+    _req(x.shape[0] <= (1 << 24), "bn_relu_dropout: x too large")   # counts travel as float32
+    return _BnReluDropoutSync.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
+                                    float(epsilon), outDtype, group, stages)
+
+
+def bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb=None, seed=0, momentum=0.99, epsilon=1e-3,
+                         outDtype=None, group=None):
+    """The training form of bn_relu_dropout (its definition, types, checks and errors) with the batch statistics over the
+    rows of ALL ranks of `group` (None: the default process group; without one, this process alone): n, mean and var are
+    those of the ranks' rows concatenated in rank order, and the dropout mask of a row is the mask of its global index, so
+    with the same seed on every rank the shards reproduce the unsharded batch. Every rank of the group calls it, with at
+    least one row; row counts may differ. Two collectives of 3c floats per rank, one forward and one backward
+    (mccnn_amd.dist.gather_rows). movingMean / movingVar get the same bytes on every rank. x.grad is the gradient of the
+    SUM of the ranks' losses; gamma.grad and beta.grad are this rank's share, to be added up by the caller's gradient
+    all-reduce as for every other parameter. Differentiable once."""
+    return _bn_relu_dropout_sync(_BN_SYNC_STAGES, x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon,
+                                 outDtype, group)
+
+
+# ---------------------------------------------------------------------------------------------
 # A linear layer and the dense glue behind it as one op (extension; csrc/linear_bn.hip, include/mccnn.h "A LINEAR LAYER AND
 # THE DENSE GLUE BEHIND IT AS ONE OP"): z = x @ w + b, y = drop(act(bn(z))).
 def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):

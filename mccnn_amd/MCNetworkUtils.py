@@ -13,6 +13,12 @@ VariableStore(fused=True) (extension, opt-in): batch norm + ReLU + dropout of a 
 with fused off, the code below is what runs. Names, shapes, initialisers and state_dict are the same either way; the
 dropout mask of the fused op is counter-based (seed dropSeed_ + dropCalls_), not torch's random stream.
 
+VariableStore(fused=True, fusedSync=True) (extension, opt-in): the one case `fused` leaves to the torch code below -- training
+statistics synchronised across the ranks of a process group -- runs as a library op too (MCConvModule.bn_relu_dropout_sync:
+the op cut in two around one gather of 3c floats per rank, forward and backward). Same names, shapes and state_dict; the
+mask of a row is that of its index in the whole batch, so with one dropSeed_ on all ranks the shards drop what a single
+process would. fusedLinear leaves that case to the matmul followed by this op.
+
 VariableStore(fusedLinear=True) (extension, opt-in): a linear layer with such a block behind it -- conv_1x1 followed by
 batch_norm_RELU_drop_out (conv_1x1_batch_norm_RELU_drop_out) and the hidden layers of the MLPs -- runs as ONE library op
 (MCConvModule.linear_bn_relu_dropout, csrc/linear_bn.hip) where its conditions hold (_fused_linear); everywhere else the
@@ -32,12 +38,14 @@ class VariableStore(torch.nn.Module):
     names (`Reduce_1_weights`, `Final_Logits_BN_h1/gamma`, ...). Variables are created on first use (tf.get_variable),
     so load_state_dict() also accepts names that do not exist yet."""
 
-    def __init__(self, device=None, fused=False, fusedLinear=False):
+    def __init__(self, device=None, fused=False, fusedLinear=False, fusedSync=False):
         super().__init__()
         self.device = device
         self.collections_ = {}
         self.fused_ = bool(fused)   # the dense glue as one library op where it applies (may be reassigned at any time)
         self.fusedLinear_ = bool(fusedLinear)   # linear layer + glue as one library op where it applies (reassignable too)
+        self.fusedSync_ = bool(fusedSync)   # with fused_: the glue stays a library op when statistics cross ranks (reassignable)
+        self.syncGroup_ = None      # the process group of those statistics (None: the default group)
         self.dropSeed_ = 0          # a fused call that drops uses the seed (dropSeed_ + dropCalls_) mod 2^32 ...
         self.dropCalls_ = 0         # ... and increments this counter
 
@@ -170,25 +178,27 @@ def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsil
 
 
 _FUSED_OP = False   # native.bn_relu_drop once the library has loaded; None when it does not
+_FUSED_SYNC_OP = None   # native.bn_relu_drop_sync, likewise
 
 
-def _fused_op():
-    global _FUSED_OP
+def _fused_op(synced=False):
+    global _FUSED_OP, _FUSED_SYNC_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
             _lib.load()
-            _FUSED_OP = native.bn_relu_drop
+            _FUSED_OP, _FUSED_SYNC_OP = native.bn_relu_drop, native.bn_relu_drop_sync
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = None
-    return _FUSED_OP
+            _FUSED_OP = _FUSED_SYNC_OP = None
+    return _FUSED_SYNC_OP if synced else _FUSED_OP
 
 
 def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
     """drop(act(batch_normalization(inputs))) as one library op, or None where the fused form does not apply (the caller
     then runs the torch code): the store's switch is off, the input is not a contiguous float32 (or bfloat16 with an even
-    c) [n, c] tensor on a HIP device, the library does not load, training statistics are synchronised across ranks, or an
-    eval call wants gradients. keepProb: the keep probability of a dropout that applies (None: none). outDtype: the
+    c) [n, c] tensor on a HIP device, the library does not load, training statistics are synchronised across ranks and
+    the store's fusedSync_ is off (with it on, that case takes the op whose statistics run over the rows of all ranks of
+    the store's syncGroup_: native.bn_relu_drop_sync), or an eval call wants gradients. keepProb: the keep probability of a dropout that applies (None: none). outDtype: the
     result's type (None: the input's; torch.float32; torch.bfloat16, which needs an even c as well)."""
     if not getattr(st, "fused_", False):
         return None
@@ -199,11 +209,12 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
         return None
     if inputs.shape[1] % 2 != 0 and (inputs.dtype == torch.bfloat16 or outDtype == torch.bfloat16):
         return None
-    if training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    synced = bool(training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+    if synced and not getattr(st, "fusedSync_", False):
         return None
     if keepProb is not None and not 0.0 < keepProb <= 1.0:
         return None
-    op = _fused_op()
+    op = _fused_op(synced)
     if op is None:
         return None
     c = inputs.shape[1]
@@ -223,6 +234,9 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
         st.dropCalls_ += 1
     else:
         keepProb = None
+    if synced:
+        return op(inputs, gamma, beta, mov_mean, mov_var, relu, keepProb, seed, momentum, epsilon, outDtype,
+                  getattr(st, "syncGroup_", None))
     if outDtype is None:
         return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon)
     return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon, outDtype)

@@ -144,6 +144,14 @@ SIGNATURES = {
                                    _sz, _vp]),
     "mccnn_bn_act_bwd_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    # ... with batch statistics across ranks: the four stages around the caller's two collectives
+    "mccnn_bn_sync_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_bn_sync_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, C.c_ulonglong, _f, C.c_uint, _vp, _i,
+                                 _vp, _vp, _vp]),
+    "mccnn_bn_sync_bwd_sums": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp,
+                                    _vp, _vp, _sz, _vp]),
+    "mccnn_bn_sync_bwd_dx": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp,
+                                  _vp, _vp]),
     # a linear layer and the dense glue behind it as one op (linear_bn.hip)
     "mccnn_linear_bn_act_workspace_bytes": (_sz, [_i, _i, _i]),
     "mccnn_linear_bn_act_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_ulonglong, _f, C.c_uint, _vp,

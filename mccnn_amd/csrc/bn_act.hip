@@ -69,10 +69,13 @@ struct BnArgs {
     float* mov_var;
     float* saved;        // [2, c]: written by the forward, read by the backward
     const float* shift;  // backward, linear_bn.hip only: per column what the exact mean has over saved's (NULL: nothing)
-    float* part;         // the slab partials: planes of [slabs, c]
+    float* part;         // the slab partials: planes of [nparts, c]
     float* dgamma;
     float* dbeta;
-    int n, c, tw_log, slab_rows, slabs, relu, want_dx;
+    float* rparts;       // statistics across ranks (mccnn_bn_sync_*): the rank partials [world, 3, c]
+    int* meta;           // ... and (rowBase, N), written by their apply
+    int n, c, tw_log, slab_rows, slabs, nparts, relu, want_dx;   // slabs: the grid's; nparts: rows of a plane of `part`
+    int rank, world;
     float momentum, eps, keep_scale;
     unsigned seed;
     unsigned long long T;
@@ -309,9 +312,9 @@ __device__ __forceinline__ void bn_merge_partials(const BnArgs& a, const BnCoord
     cnt = 0.f;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { mean[k] = 0.f; m2[k] = 0.f; }
-    const size_t plane = (size_t)a.slabs * a.c;
+    const size_t plane = (size_t)a.nparts * a.c;
     if (t.ok)
-        for (int s = t.ry; s < a.slabs; s += t.R) {
+        for (int s = t.ry; s < a.nparts; s += t.R) {
             const float* p = a.part + (size_t)s * a.c + t.col;
             float mB[VEC], qB[VEC];
             bn_ld<VEC>(p + plane, mB);
@@ -345,9 +348,10 @@ __device__ __forceinline__ void bn_finish_stats(const BnArgs& a, const BnCoord& 
     __syncthreads();
 }
 
+// base: what the mask's row index has over the local one (statistics across ranks: the rows of the lower ranks)
 template <int VEC, typename XT, typename YT>
 __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t, int row0, int row1, const float (&mean)[VEC],
-                                              const float (&rstd)[VEC], bool drop) {
+                                              const float (&rstd)[VEC], bool drop, int base = 0) {
     if (!t.ok) return;   // (no barrier follows)
     float g[VEC], b[VEC];
 #pragma unroll
@@ -366,7 +370,7 @@ __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t,
             if (ru >= row1) break;
             float v[VEC], o[VEC];
             bn_widen<VEC, XT>(wx[u], v);
-            const uint32_t rh = drop ? bn_drop_row(a.seed, (int)ru) : 0u;
+            const uint32_t rh = drop ? bn_drop_row(a.seed, base + (int)ru) : 0u;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float xh = (v[k] - mean[k]) * rstd[k];
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a) {
     float cnt, mean[VEC], m2[VEC];
     bn_slab_stats<VEC, XT>(a, t, row0, row1, cnt, mean, m2, lds);
     if (t.ry == 0 && t.ok) {
-        const size_t plane = (size_t)a.slabs * a.c;
+        const size_t plane = (size_t)a.nparts * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
         float cv[VEC];
 #pragma unroll
@@ -465,9 +469,10 @@ __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, c
 // f(r, g, xh) over rows row0 + ry, + R, ... below row1, in that order. The loads of U rows are issued before the first of
 // them is used: behind the (uniform) relu and dropout branches of a row the compiler would otherwise hold the next row's
 // loads back, one memory latency per row.
+// base: what the mask's row index has over the local one (bn_apply_rows); f sees the local row.
 template <int VEC, typename XT, typename YT, typename F>
 __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
-                                             bool drop, F&& f) {
+                                             bool drop, F&& f, int base = 0) {
     constexpr int U = 4;
     for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
         uint32_t wx[U][bn_raw_words<VEC, XT>()], wd[U][bn_raw_words<VEC, YT>()];   // (as stored: widened where they are used)
@@ -486,7 +491,7 @@ __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, 
                 float v[VEC], d[VEC], g[VEC], xh[VEC];
                 bn_widen<VEC, XT>(wx[u], v);
                 bn_widen<VEC, YT>(wd[u], d);
-                bn_row_grad<VEC>(a, t, q, (int)ru, drop, v, d, g, xh);
+                bn_row_grad<VEC>(a, t, q, base + (int)ru, drop, v, d, g, xh);
                 f((int)ru, g, xh);
             }
         }
@@ -494,7 +499,7 @@ __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, 
 }
 template <int VEC, typename XT, typename YT>
 __device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
-                                             float (&sg)[VEC], float (&sx)[VEC], float (&sh)[VEC], float* lds) {
+                                             float (&sg)[VEC], float (&sx)[VEC], float (&sh)[VEC], float* lds, int base = 0) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
     const bool drop = a.T < kBnDropAll;
@@ -502,7 +507,27 @@ __device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, 
         bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int, const float (&g)[VEC], const float (&xh)[VEC]) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) { sg[k] = sg[k] + g[k]; sx[k] = sx[k] + g[k] * xh[k]; sh[k] = sh[k] + xh[k]; }
-        });
+        }, base);
+    bn_tree_sum<VEC>(a, t, sg, sx, sh, lds);
+}
+// the slab partials of three plain sums of the thread's columns, summed: slabs ry, ry + R, ... in order per row lane, then
+// the tree
+template <int VEC>
+__device__ __forceinline__ void bn_sum_partials(const BnArgs& a, const BnCoord& t, float (&sg)[VEC], float (&sx)[VEC],
+                                                float (&sh)[VEC], float* lds) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
+    const size_t plane = (size_t)a.nparts * a.c;
+    if (t.ok)
+        for (int s = t.ry; s < a.nparts; s += t.R) {
+            const float* p = a.part + (size_t)s * a.c + t.col;
+            float gB[VEC], xB[VEC], hB[VEC];
+            bn_ld<VEC>(p, gB);
+            bn_ld<VEC>(p + plane, xB);
+            bn_ld<VEC>(p + 2 * plane, hB);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) { sg[k] = sg[k] + gB[k]; sx[k] = sx[k] + xB[k]; sh[k] = sh[k] + hB[k]; }
+        }
     bn_tree_sum<VEC>(a, t, sg, sx, sh, lds);
 }
 
@@ -510,7 +535,8 @@ __device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, 
 // saved f32 mean it is -n * (mean's rounding error) * rstd, and launch 2 takes that shift out of xhat again -- on a column
 // of few rows with |mean| >> std (var + eps barely above var) dx is the small remainder of cancelling terms, and the
 // shift alone would cost it more than 1e-4
-template <int VEC, typename XT, typename YT>
+// SYNC (statistics across ranks): the mask at the global rows, meta[0] on
+template <int VEC, typename XT, typename YT, int SYNC = 0>
 __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
     const BnCoord t = bn_coord<VEC>(a);
@@ -518,9 +544,10 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float sg[VEC], sx[VEC], sh[VEC];
-    bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds);
+    if constexpr (SYNC) bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds, a.meta[0]);
+    else bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds);
     if (t.ry == 0 && t.ok) {
-        const size_t plane = (size_t)a.slabs * a.c;
+        const size_t plane = (size_t)a.nparts * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
         bn_st<VEC>(p, sg);
         bn_st<VEC>(p + plane, sx);
@@ -542,20 +569,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
     if constexpr (SMALL) {
         bn_slab_sums<VEC, XT, YT>(a, t, q, 0, a.n, sg, sx, sh, lds);
     } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
-        const size_t plane = (size_t)a.slabs * a.c;
-        if (t.ok)
-            for (int s = t.ry; s < a.slabs; s += t.R) {
-                const float* p = a.part + (size_t)s * a.c + t.col;
-                float gB[VEC], xB[VEC], hB[VEC];
-                bn_ld<VEC>(p, gB);
-                bn_ld<VEC>(p + plane, xB);
-                bn_ld<VEC>(p + 2 * plane, hB);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) { sg[k] = sg[k] + gB[k]; sx[k] = sx[k] + xB[k]; sh[k] = sh[k] + hB[k]; }
-            }
-        bn_tree_sum<VEC>(a, t, sg, sx, sh, lds);
+        bn_sum_partials<VEC>(a, t, sg, sx, sh, lds);
     }
     const float fn = (float)a.n;
     if (t.ry == 0 && t.ok) {
@@ -589,6 +603,171 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
         for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
         bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
     });
+}
+
+// ---- batch statistics across the ranks of a process group (mccnn_bn_sync_*) ----------------------------------------------
+// The op cut in two where the collective goes. The rank partials [world, 3, c] hold per rank and column what a slab
+// partial holds per slab: (count, mean, M2) forward, (sum g, sum g * xhat, sum xhat) backward. A rank writes its own row
+// and +0.0f into every other (an all-reduce(SUM) of the tensor is then an exact gather); behind the collective every
+// workgroup merges the `world` rows of ITS columns in rank order, in the threads of row lane 0, once, ahead of its rows.
+// These few values move as single floats: nothing is asked of the tensor's alignment.
+template <int VEC>
+__device__ __forceinline__ void bn_rank_put(const BnArgs& a, const BnCoord& t, const float (&p0)[VEC], const float (&p1)[VEC],
+                                            const float (&p2)[VEC]) {
+    if (t.ry != 0 || !t.ok) return;
+    const size_t c = (size_t)a.c;
+    for (int w = 0; w < a.world; ++w) {
+        float* p = a.rparts + (size_t)w * 3 * c + t.col;
+        const bool own = w == a.rank;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            p[k] = own ? p0[k] : 0.f;
+            p[c + k] = own ? p1[k] : 0.f;
+            p[2 * c + k] = own ? p2[k] : 0.f;
+        }
+    }
+}
+
+// this rank's (count, mean, M2) into its row of the rank partials. SMALL: from x (n <= 256, the only launch); otherwise
+// from the slab partials of bn_stats_k, merged as launch 2 of the plain forward merges them. One slab deep.
+template <int VEC, typename XT, int SMALL>
+__global__ __launch_bounds__(kBnThreads) void bn_sync_stats_k(BnArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
+    const BnCoord t = bn_coord<VEC>(a);
+    float cnt, mean[VEC], m2[VEC];
+    if constexpr (SMALL) bn_slab_stats<VEC, XT>(a, t, 0, a.n, cnt, mean, m2, lds);
+    else bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
+    float cv[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) cv[k] = cnt;
+    bn_rank_put<VEC>(a, t, cv, mean, m2);
+}
+
+// the gathered rank partials merged by Chan's rule in rank order, then launch 2 of the plain forward with N rows in the
+// statistics and the mask at the global rows. Slab 0 of a column tile writes saved and the moving statistics, the first
+// workgroup meta = (rowBase, N).
+template <int VEC, typename XT, typename YT>
+__global__ __launch_bounds__(kBnThreads) void bn_sync_apply_k(BnArgs a) {
+    __shared__ float sm[2][kBnTileCols];
+    __shared__ int sbase;
+    const BnCoord t = bn_coord<VEC>(a);
+    const int slab = (int)blockIdx.y;
+    const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
+    if (t.ry == 0 && t.ok) {
+        const size_t c = (size_t)a.c;
+        float cnt = 0.f, mean[VEC], m2[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { mean[k] = 0.f; m2[k] = 0.f; }
+        int base = 0, total = 0;
+        for (int w = 0; w < a.world; ++w) {
+            const float* p = a.rparts + (size_t)w * 3 * c + t.col;
+            const float nB = p[0];   // (the columns of a rank share their count)
+            float mB[VEC], qB[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) { mB[k] = p[c + k]; qB[k] = p[2 * c + k]; }
+            if (w < a.rank) base += (int)nB;
+            total += (int)nB;
+            bn_chan<VEC>(cnt, mean, m2, nB, mB, qB);
+        }
+        const float fn = (float)total, keep = 1.0f - a.momentum;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float var = m2[k] / fn;
+            const float rstd = 1.0f / sqrtf(var + a.eps);
+            sm[0][t.cx * VEC + k] = mean[k];
+            sm[1][t.cx * VEC + k] = rstd;
+            if (slab == 0) {
+                const int j = t.col + k;
+                a.saved[j] = mean[k];
+                a.saved[c + j] = rstd;
+                a.mov_mean[j] = a.mov_mean[j] * a.momentum + mean[k] * keep;
+                a.mov_var[j] = a.mov_var[j] * a.momentum + var * keep;
+            }
+        }
+        if (t.tid == 0) {
+            sbase = base;
+            if (slab == 0 && blockIdx.x == 0) { a.meta[0] = base; a.meta[1] = total; }
+        }
+    }
+    __syncthreads();
+    float mean[VEC], rstd[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
+    bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll, sbase);
+}
+
+// this rank's (sum g, sum g * xhat, sum xhat) into its row of the rank partials, and as dbeta and dgamma. SMALL: from x and
+// dy (n <= 256, the only launch); otherwise from the slab partials of bn_bwd_sums_k<.., 1>. One slab deep.
+template <int VEC, typename XT, typename YT, int SMALL>
+__global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_sums_k(BnArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
+    const BnCoord t = bn_coord<VEC>(a);
+    float sg[VEC], sx[VEC], sh[VEC];
+    if constexpr (SMALL) {
+        const BnCols<VEC> q = bn_cols<VEC>(a, t);
+        bn_slab_sums<VEC, XT, YT>(a, t, q, 0, a.n, sg, sx, sh, lds, a.meta[0]);
+    } else {
+        bn_sum_partials<VEC>(a, t, sg, sx, sh, lds);
+    }
+    bn_rank_put<VEC>(a, t, sg, sx, sh);
+    if (t.ry == 0 && t.ok) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { a.dbeta[t.col + k] = sg[k]; a.dgamma[t.col + k] = sx[k]; }
+    }
+}
+
+// the gathered rank partials summed in rank order, then launch 2 of the plain backward with N rows. dgamma (when given):
+// this rank's sum g * (xhat - mh) from its own row and the global mean of xhat, mh -- the shift the plain backward takes
+// out of its dgamma; the ranks' values still add up to the whole batch's.
+template <int VEC, typename XT, typename YT>
+__global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_dx_k(BnArgs a) {
+    __shared__ float sm[3][kBnTileCols];
+    const BnCoord t = bn_coord<VEC>(a);
+    const BnCols<VEC> q = bn_cols<VEC>(a, t);
+    const int slab = (int)blockIdx.y;
+    const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
+    const int base = a.meta[0];
+    const float fn = (float)a.meta[1];
+    if (t.ry == 0 && t.ok) {
+        const size_t c = (size_t)a.c;
+        float sg[VEC], sx[VEC], sh[VEC], og[VEC], ox[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; og[k] = 0.f; ox[k] = 0.f; }
+        for (int w = 0; w < a.world; ++w) {
+            const float* p = a.rparts + (size_t)w * 3 * c + t.col;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float gB = p[k], xB = p[c + k];
+                sg[k] = sg[k] + gB; sx[k] = sx[k] + xB; sh[k] = sh[k] + p[2 * c + k];
+                if (w == a.rank) { og[k] = gB; ox[k] = xB; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float mh = sh[k] / fn;
+            sm[0][t.cx * VEC + k] = sg[k];
+            sm[1][t.cx * VEC + k] = sx[k] - mh * sg[k];
+            sm[2][t.cx * VEC + k] = mh;
+            if (slab == 0 && a.dgamma) a.dgamma[t.col + k] = ox[k] - mh * og[k];
+        }
+    }
+    __syncthreads();
+    if (!a.want_dx || !t.ok) return;
+    const bool drop = a.T < kBnDropAll;
+    float kb[VEC], kg[VEC], gr[VEC], mh[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        kb[k] = sm[0][t.cx * VEC + k] / fn;
+        kg[k] = sm[1][t.cx * VEC + k] / fn;
+        mh[k] = sm[2][t.cx * VEC + k];
+        gr[k] = q.g[k] * q.rstd[k];
+    }
+    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
+        float o[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
+        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
+    }, base);
 }
 
 // a caller's row pointer allows the wide form: f32 x -> 4 columns per thread (f32 rows move as 16 bytes, bf16 rows as 8),
@@ -633,6 +812,35 @@ struct BnBwdDxL {
     template <int VEC, typename XT, typename YT>
     static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_dx_k<VEC, XT, YT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
 };
+template <int SMALL>
+struct BnSyncStatsL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_stats_k<VEC, XT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
+};
+struct BnSyncApplyL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_apply_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
+};
+struct BnSyncSlabSumsL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_sums_k<VEC, XT, YT, 1><<<grid, kBnThreads, 0, st>>>(a); }
+};
+template <int SMALL>
+struct BnSyncBwdSumsL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_bwd_sums_k<VEC, XT, YT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
+};
+struct BnSyncBwdDxL {
+    template <int VEC, typename XT, typename YT>
+    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_bwd_dx_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
+};
+
+// what every mccnn_bn_sync_* entry checks of its shard before it looks at anything else; 0 or the error
+inline int bn_sync_check(int n, int c, int rank, int world) {
+    if (n < 1 || c < 1 || world < 1 || rank < 0 || rank >= world) return MCCNN_E_BADARG;
+    if (n > (1 << 24)) return MCCNN_E_TOOLARGE;   // counts travel as f32
+    return 0;
+}
 
 }  // namespace mccnn
 
@@ -656,7 +864,7 @@ int mccnn::bn_act_bwd_impl(const void* x, int x_bf16, const void* dy, int dy_bf1
     BnArgs a = {};
     a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
     a.part = (float*)ws; a.dgamma = dgamma; a.dbeta = dbeta; a.shift = shift;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
     a.want_dx = dx ? 1 : 0;
     a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
     hipStream_t st = (hipStream_t)stream;
@@ -693,7 +901,7 @@ int mccnn_bn_act_fwd_rows(const void* x, int x_bf16, int n, int c, const float* 
     BnArgs a = {};
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
     a.part = (float*)ws;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
     a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed;
     a.T = training ? keep_threshold : kBnDropAll;
     hipStream_t st = (hipStream_t)stream;
@@ -730,6 +938,93 @@ int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float*
                      float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
     return mccnn_bn_act_bwd_rows(x, 0, dy, 0, n, c, gamma, beta, saved, relu, keep_threshold, keep_scale, seed, dx, dgamma, dbeta,
                                  ws, ws_bytes, stream);
+}
+
+// ---- statistics across ranks (ABI 22): the four stages around the caller's two collectives ----
+int mccnn_bn_sync_stats(const void* x, int x_bf16, int n, int c, int rank, int world, float* parts, void* ws, size_t ws_bytes,
+                        mccnn_stream_t stream) {
+    if (const int e = bn_sync_check(n, c, rank, world)) return e;
+    if (!x || !parts) return MCCNN_E_BADARG;
+    if (x_bf16 & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c)) return MCCNN_E_SHAPE;
+    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
+    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && (!need || bn_aligned16(ws)), x_bf16);
+    BnArgs a = {};
+    a.x = x; a.part = (float*)ws; a.rparts = parts;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs;
+    a.rank = rank; a.world = world;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 one((unsigned)p.tiles, 1u);
+    if (n <= kBnSmallRows) return bn_launch<BnSyncStatsL<1>>(p.vec, x_bf16, 0, one, st, a);
+    if (const int e = bn_launch<BnStatsL>(p.vec, x_bf16, 0, dim3((unsigned)p.tiles, (unsigned)p.slabs), st, a)) return e;
+    return bn_launch<BnSyncStatsL<0>>(p.vec, x_bf16, 0, one, st, a);
+}
+
+int mccnn_bn_sync_apply(const void* x, int x_bf16, int n, int c, int rank, int world, const float* parts, const float* gamma,
+                        const float* beta, float* moving_mean, float* moving_var, float momentum, float eps, int relu,
+                        unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16, float* saved,
+                        int* meta, mccnn_stream_t stream) {
+    if (const int e = bn_sync_check(n, c, rank, world)) return e;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!x || !parts || !gamma || !beta || !moving_mean || !moving_var || !y || !saved || !meta) return MCCNN_E_BADARG;
+    if ((x_bf16 | y_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(y, y_bf16, c)) return MCCNN_E_SHAPE;
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(y, y_bf16, x_bf16), x_bf16);
+    BnArgs a = {};
+    a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
+    a.rparts = const_cast<float*>(parts); a.meta = meta;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
+    a.rank = rank; a.world = world;
+    a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    return bn_launch<BnSyncApplyL>(p.vec, x_bf16, y_bf16, dim3((unsigned)p.tiles, (unsigned)p.slabs), (hipStream_t)stream, a);
+}
+
+int mccnn_bn_sync_bwd_sums(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
+                           const float* gamma, const float* beta, const float* saved, const int* meta, int relu,
+                           unsigned long long keep_threshold, float keep_scale, unsigned seed, float* parts_b, float* dgamma,
+                           float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+    if (const int e = bn_sync_check(n, c, rank, world)) return e;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!x || !dy || !gamma || !beta || !saved || !meta || !parts_b || !dgamma || !dbeta) return MCCNN_E_BADARG;
+    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c)) return MCCNN_E_SHAPE;
+    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
+    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
+                                       (!need || bn_aligned16(ws)), x_bf16);
+    BnArgs a = {};
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved); a.part = (float*)ws;
+    a.rparts = parts_b; a.meta = const_cast<int*>(meta); a.dgamma = dgamma; a.dbeta = dbeta;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
+    a.rank = rank; a.world = world;
+    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 one((unsigned)p.tiles, 1u);
+    if (n <= kBnSmallRows) return bn_launch<BnSyncBwdSumsL<1>>(p.vec, x_bf16, dy_bf16, one, st, a);
+    if (const int e = bn_launch<BnSyncSlabSumsL>(p.vec, x_bf16, dy_bf16, dim3((unsigned)p.tiles, (unsigned)p.slabs), st, a)) return e;
+    return bn_launch<BnSyncBwdSumsL<0>>(p.vec, x_bf16, dy_bf16, one, st, a);
+}
+
+int mccnn_bn_sync_bwd_dx(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
+                         const float* gamma, const float* beta, const float* parts_b, const float* saved, const int* meta,
+                         int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed, void* dx, float* dgamma,
+                         mccnn_stream_t stream) {
+    if (const int e = bn_sync_check(n, c, rank, world)) return e;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!x || !dy || !gamma || !beta || !parts_b || !saved || !meta || (!dx && !dgamma)) return MCCNN_E_BADARG;
+    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
+    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
+    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
+                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)), x_bf16);
+    BnArgs a = {};
+    a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
+    a.rparts = const_cast<float*>(parts_b); a.meta = const_cast<int*>(meta); a.dgamma = dgamma;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
+    a.want_dx = dx ? 1 : 0; a.rank = rank; a.world = world;
+    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    return bn_launch<BnSyncBwdDxL>(p.vec, x_bf16, dy_bf16, dim3((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u),
+                                   (hipStream_t)stream, a);
 }
 
 }  // extern "C"

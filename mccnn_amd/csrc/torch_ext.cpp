@@ -1485,6 +1485,104 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
     return y;
 }
 
+// ---- ... with batch statistics across ranks (mccnn_bn_sync_*): the four stages as they are. The collectives between them
+// are torch.distributed's, so the autograd node is Python's (MCConvModule._BnReluDropoutSync), which has checked the
+// arguments; here only what keeps a call inside its tensors. x / dx and y / dy are each f32 or bf16 rows.
+struct BnSyncShape {
+    int n, c, x_bf16;
+};
+BnSyncShape bn_sync_shape(const Tensor& x, int64_t rank, int64_t world, const Tensor& parts) {
+    TORCH_CHECK(x.defined() && (x.scalar_type() == at::kFloat || is_bf16(x)), "bn_relu_drop_sync: x must be float32 or bfloat16");
+    check_dev(x, x.scalar_type(), "x");
+    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31),
+                "bn_relu_drop_sync expects x with dimensions (n, c), n, c >= 1");
+    TORCH_CHECK(world >= 1 && rank >= 0 && rank < world, "bn_relu_drop_sync: rank outside [0, world)");
+    check_dev(parts, at::kFloat, "rank partials");
+    TORCH_CHECK(parts.numel() == world * 3 * x.size(1) && parts.device() == x.device(), "bn_relu_drop_sync: the rank partials must be [world, 3, c]");
+    return {(int)x.size(0), (int)x.size(1), is_bf16(x) ? 1 : 0};
+}
+void bn_sync_cols(const Tensor& x, int64_t rows, std::initializer_list<const Tensor*> ts) {
+    for (const Tensor* t : ts) {
+        check_dev(*t, at::kFloat, "per-column tensor");
+        TORCH_CHECK(t->numel() == rows * x.size(1) && t->device() == x.device(), "bn_relu_drop_sync: per-column tensors must have shape (c,)");
+    }
+}
+void bn_sync_rows(const Tensor& x, const Tensor& t, const char* name) {
+    TORCH_CHECK(t.defined() && (t.scalar_type() == at::kFloat || is_bf16(t)), "bn_relu_drop_sync: ", name, " must be float32 or bfloat16");
+    check_dev(t, t.scalar_type(), name);
+    TORCH_CHECK(t.sizes() == x.sizes() && t.device() == x.device(), "bn_relu_drop_sync: ", name, " must have x's shape");
+}
+void bn_sync_meta(const Tensor& x, const Tensor& meta) {
+    check_dev(meta, at::kInt, "meta");
+    TORCH_CHECK(meta.numel() == 2 && meta.device() == x.device(), "bn_relu_drop_sync: meta must be int32 [2]");
+}
+
+void bn_sync_stats(const Tensor& x, int64_t rank, int64_t world, const Tensor& parts) {
+    const BnSyncShape s = bn_sync_shape(x, rank, world, parts);
+    const DevGuard device_guard((int)x.device().index());
+    void* st = cur_stream(x);
+    Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(s.n, s.c), x, st);
+    check(mccnn_bn_sync_stats(x.data_ptr(), s.x_bf16, s.n, s.c, (int)rank, (int)world, parts.data_ptr<float>(), ws.data_ptr(),
+                              (size_t)ws.numel(), st),
+          "bn_relu_dropout_sync");
+}
+
+void bn_sync_apply(const Tensor& x, int64_t rank, int64_t world, const Tensor& parts, const Tensor& gamma, const Tensor& beta,
+                   const Tensor& mov_mean, const Tensor& mov_var, double momentum, double eps, bool relu, unsigned long long thr,
+                   double scale, unsigned seed, const Tensor& y, const Tensor& saved, const Tensor& meta) {
+    const BnSyncShape s = bn_sync_shape(x, rank, world, parts);
+    bn_sync_cols(x, 1, {&gamma, &beta, &mov_mean, &mov_var});
+    bn_sync_cols(x, 2, {&saved});
+    bn_sync_rows(x, y, "y");
+    bn_sync_meta(x, meta);
+    const DevGuard device_guard((int)x.device().index());
+    check(mccnn_bn_sync_apply(x.data_ptr(), s.x_bf16, s.n, s.c, (int)rank, (int)world, parts.data_ptr<float>(), gamma.data_ptr<float>(),
+                              beta.data_ptr<float>(), mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum,
+                              (float)eps, relu ? 1 : 0, thr, (float)scale, seed, y.data_ptr(), is_bf16(y) ? 1 : 0,
+                              saved.data_ptr<float>(), meta.data_ptr<int>(), cur_stream(x)),
+          "bn_relu_dropout_sync");
+}
+
+void bn_sync_bwd_sums(const Tensor& x, const Tensor& dy, int64_t rank, int64_t world, const Tensor& gamma, const Tensor& beta,
+                      const Tensor& saved, const Tensor& meta, bool relu, unsigned long long thr, double scale, unsigned seed,
+                      const Tensor& parts_b, const Tensor& dgb) {
+    const BnSyncShape s = bn_sync_shape(x, rank, world, parts_b);
+    bn_sync_cols(x, 1, {&gamma, &beta});
+    bn_sync_cols(x, 2, {&saved, &dgb});
+    bn_sync_rows(x, dy, "dy");
+    bn_sync_meta(x, meta);
+    const DevGuard device_guard((int)x.device().index());
+    void* st = cur_stream(x);
+    Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(s.n, s.c), x, st);
+    check(mccnn_bn_sync_bwd_sums(x.data_ptr(), s.x_bf16, dy.data_ptr(), is_bf16(dy) ? 1 : 0, s.n, s.c, (int)rank, (int)world,
+                                 gamma.data_ptr<float>(), beta.data_ptr<float>(), saved.data_ptr<float>(), meta.data_ptr<int>(),
+                                 relu ? 1 : 0, thr, (float)scale, seed, parts_b.data_ptr<float>(), dgb.data_ptr<float>(),
+                                 dgb.data_ptr<float>() + s.c, ws.data_ptr(), (size_t)ws.numel(), st),
+          "bn_relu_dropout_sync_grad");
+}
+
+// dgb: the [2, c] (dgamma; dbeta) of bn_sync_bwd_sums, whose first row is completed here
+void bn_sync_bwd_dx(const Tensor& x, const Tensor& dy, int64_t rank, int64_t world, const Tensor& gamma, const Tensor& beta,
+                    const Tensor& parts_b, const Tensor& saved, const Tensor& meta, bool relu, unsigned long long thr, double scale,
+                    unsigned seed, const c10::optional<Tensor>& dx, const Tensor& dgb) {
+    const BnSyncShape s = bn_sync_shape(x, rank, world, parts_b);
+    bn_sync_cols(x, 1, {&gamma, &beta});
+    bn_sync_cols(x, 2, {&saved, &dgb});
+    bn_sync_rows(x, dy, "dy");
+    bn_sync_meta(x, meta);
+    const bool want_dx = dx.has_value() && dx->defined();
+    if (want_dx) {
+        bn_sync_rows(x, *dx, "dx");
+        TORCH_CHECK(dx->scalar_type() == x.scalar_type(), "bn_relu_drop_sync: dx must have x's type");
+    }
+    const DevGuard device_guard((int)x.device().index());
+    check(mccnn_bn_sync_bwd_dx(x.data_ptr(), s.x_bf16, dy.data_ptr(), is_bf16(dy) ? 1 : 0, s.n, s.c, (int)rank, (int)world,
+                               gamma.data_ptr<float>(), beta.data_ptr<float>(), parts_b.data_ptr<float>(), saved.data_ptr<float>(),
+                               meta.data_ptr<int>(), relu ? 1 : 0, thr, (float)scale, seed, want_dx ? dx->data_ptr() : nullptr,
+                               dgb.data_ptr<float>(), cur_stream(x)),
+          "bn_relu_dropout_sync_grad");
+}
+
 // ---- a linear layer and the dense glue behind it as one op (mccnn_linear_bn_act_fwd / _bwd): y = drop(act(bn(x w + b))), the
 // C++ form of MCConvModule.linear_bn_relu_dropout -- the same library calls with the same arguments, so the same bytes.
 // x, w, z and everything per column are f32; y (and dy) f32 or bf16.
@@ -1957,6 +2055,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("bn_relu_drop", &bn_relu_drop, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
             py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
             py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1, py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_sync_stats", &bn_sync_stats, py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_sync_apply", &bn_sync_apply, py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_sync_bwd_sums", &bn_sync_bwd_sums, py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_sync_bwd_dx", &bn_sync_bwd_dx, py::call_guard<py::gil_scoped_release>());
     mod.def("linear_bn_relu_drop", &linear_bn_relu_drop, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("gamma"), py::arg("beta"),
             py::arg("moving_mean"), py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"),
             py::arg("keep_scale"), py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1,

@@ -8,6 +8,9 @@ exchanges are
   * when relativeRadius=False the reference uses ONE bounding box for the whole batch
     (aabb_gpu.cu:104-114); to stay bit-identical to a single-device batch the shards all-reduce
     (MIN, MAX) their 2x3 box floats before sorting.
+  * with VariableStore(fused=True, fusedSync=True), two gathers of 3c floats per rank and batch-norm block -- the
+    statistics of the forward and the sums of the backward (gather_rows, between the stages of
+    MCConvModule.bn_relu_dropout_sync); without it the torch code's differentiable all-reduce of the same size.
 One process per GPU, torch.distributed backend "nccl" (= RCCL on ROCm); "gloo" on CPU tensors in tests.
 """
 import torch
@@ -46,6 +49,40 @@ def allreduce_aabb(aabbMin, aabbMax, group=None):
     dist.all_reduce(mn, op=dist.ReduceOp.MIN, group=group)
     dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
     return mn, mx
+
+
+def _backend_of(t, group=None):
+    """The name of the backend that serves tensors on t's device in `group` ("nccl", "gloo", ...)."""
+    name = str(dist.get_backend(group)).lower()
+    if ":" in name:   # "cpu:gloo,cuda:nccl"
+        per_device = dict(part.split(":", 1) for part in name.split(","))
+        return per_device.get("cuda" if t.is_cuda else "cpu", "")
+    return name
+
+
+def gather_rows(buf, group=None, route=None):
+    """buf [world, k]: every rank has filled ITS row and written +0.0 into the others (the stages of
+    MCConvModule.bn_relu_dropout_sync do); on return every rank holds all rows, in place. Two exact routes: an all-gather
+    of the rows ("gather": all_gather_into_tensor, each rank's input its own row of the result), or an all-reduce(SUM) of
+    the zero-padded buffer ("reduce": adding +0.0 changes no bit but the sign of a zero). route None: "gather" where the
+    backend is nccl (= RCCL), "reduce" otherwise (gloo on device tensors). With one rank, or without a process group,
+    buf comes back as it is."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return buf
+    world = dist.get_world_size(group)
+    if world == 1:
+        return buf
+    if buf.dim() != 2 or buf.shape[0] != world or not buf.is_contiguous():
+        raise ValueError("gather_rows expects a contiguous [world, k] tensor")
+    if route is None:
+        route = "gather" if _backend_of(buf, group) == "nccl" else "reduce"
+    if route == "gather":
+        dist.all_gather_into_tensor(buf, buf[dist.get_rank(group)], group=group)
+    elif route == "reduce":
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    else:
+        raise ValueError("gather_rows: route must be None, 'gather' or 'reduce'")
+    return buf
 
 
 class GradBucket:

@@ -642,6 +642,20 @@ def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, kee
                              float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
 
 
+def bn_relu_drop_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb=None, seed=0, momentum=0.99, epsilon=1e-3,
+                      outDtype=None, group=None):
+    """The training form of the dense glue with batch statistics over the rows of all ranks of `group`
+    (MCConvModule.bn_relu_dropout_sync: its definition, checks and errors). The autograd node is that module's either way
+    (the collectives between the stages are torch.distributed's); with the extension loaded its four stages are the
+    extension's calls, with the ctypes ones otherwise -- the same library calls, so the same bytes."""
+    from . import MCConvModule as M
+    if _EXT is None:
+        return M.bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype,
+                                      group)
+    return M._bn_relu_dropout_sync((_EXT.bn_sync_stats, _EXT.bn_sync_apply, _EXT.bn_sync_bwd_sums, _EXT.bn_sync_bwd_dx), x, gamma,
+                                   beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype, group)
+
+
 def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
                         epsilon=1e-3, outDtype=None):
     """A linear layer and the dense glue behind it as one op, y = drop(act(bn(x @ w + b)))
