@@ -9,19 +9,19 @@ statistics across ranks with one small all-reduce when torch.distributed is init
 so sums and counts are reduced, not means).
 
 VariableStore(fused=True) (extension, opt-in): batch norm + ReLU + dropout of a block run as ONE library op
-(MCConvModule.bn_relu_dropout, csrc/bn_act.hip) where its conditions hold (_fused_glue); everywhere else, and always
+(dense_glue.bn_relu_dropout, csrc/bn_act.hip) where its conditions hold (_fused_glue); everywhere else, and always
 with fused off, the code below is what runs. Names, shapes, initialisers and state_dict are the same either way; the
 dropout mask of the fused op is counter-based (seed dropSeed_ + dropCalls_), not torch's random stream.
 
 VariableStore(fused=True, fusedSync=True) (extension, opt-in): the one case `fused` leaves to the torch code below -- training
-statistics synchronised across the ranks of a process group -- runs as a library op too (MCConvModule.bn_relu_dropout_sync:
+statistics synchronised across the ranks of a process group -- runs as a library op too (dense_glue.bn_relu_dropout_sync:
 the op cut in two around one gather of 3c floats per rank, forward and backward). Same names, shapes and state_dict; the
 mask of a row is that of its index in the whole batch, so with one dropSeed_ on all ranks the shards drop what a single
 process would. fusedLinear leaves that case to the matmul followed by this op.
 
 VariableStore(fusedLinear=True) (extension, opt-in): a linear layer with such a block behind it -- conv_1x1 followed by
 batch_norm_RELU_drop_out (conv_1x1_batch_norm_RELU_drop_out) and the hidden layers of the MLPs -- runs as ONE library op
-(MCConvModule.linear_bn_relu_dropout, csrc/linear_bn.hip) where its conditions hold (_fused_linear); everywhere else the
+(dense_glue.linear_bn_relu_dropout, csrc/linear_bn.hip) where its conditions hold (_fused_linear); everywhere else the
 matmul and the block run as before. Names, shapes, initialisers, creation order and state_dict are the same either way,
 and a call that drops takes its seed from dropSeed_ / dropCalls_ as the fused glue does: with `fused` on as well, the
 masks of a network do not depend on this switch.
@@ -140,16 +140,25 @@ def _ones(t):
     return t
 
 
+def _bn_block(st, name, c, dev):
+    """The four variables of a batch-norm block -> (gamma, beta, moving_mean, moving_variance), created on first use in that
+    order (the order of the store's state_dict keys)."""
+    return (st.get_variable(name + "/gamma", (c,), _ones, dev), st.get_variable(name + "/beta", (c,), _zeros, dev),
+            st.get_buffer(name + "/moving_mean", (c,), 0.0, dev), st.get_buffer(name + "/moving_variance", (c,), 1.0, dev))
+
+
+def _stats_cross_ranks(training, sync):
+    """The batch statistics of this call run over the rows of more than one rank."""
+    return bool(training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+
+
 def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsilon=1e-3, sync=True):
     """tf.layers.batch_normalization(inputs, training=..., name=...) over axis 0 of an [n, c] tensor."""
     st = store or _DEFAULT_STORE
     c = inputs.shape[1]
     dev = inputs.device
-    gamma = st.get_variable(name + "/gamma", (c,), _ones, dev)
-    beta = st.get_variable(name + "/beta", (c,), _zeros, dev)
-    mov_mean = st.get_buffer(name + "/moving_mean", (c,), 0.0, dev)
-    mov_var = st.get_buffer(name + "/moving_variance", (c,), 1.0, dev)
-    distributed = sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    gamma, beta, mov_mean, mov_var = _bn_block(st, name, c, dev)
+    distributed = _stats_cross_ranks(training, sync)
     if training and not distributed and inputs.shape[0] > 1:
         # single process: the fused batch-norm kernels (one forward, one backward launch instead of ~30 element-wise
         # ones; the network is host-bound). Same arithmetic: biased batch variance for the normalisation AND for the
@@ -177,20 +186,45 @@ def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsil
     return (inputs - mean) * torch.rsqrt(var + epsilon) * gamma + beta
 
 
-_FUSED_OP = False   # native.bn_relu_drop once the library has loaded; None when it does not
-_FUSED_SYNC_OP = None   # native.bn_relu_drop_sync, likewise
+_FUSED_OP = False          # native.bn_relu_drop once the library has loaded; None when it does not
+_FUSED_SYNC_OP = None      # native.bn_relu_drop_sync, likewise
+_FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
 
 
-def _fused_op(synced=False):
-    global _FUSED_OP, _FUSED_SYNC_OP
+def _load_fused_ops():
+    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
             _lib.load()
-            _FUSED_OP, _FUSED_SYNC_OP = native.bn_relu_drop, native.bn_relu_drop_sync
+            _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP = native.bn_relu_drop, native.bn_relu_drop_sync, native.linear_bn_relu_drop
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = _FUSED_SYNC_OP = None
+            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = None
+
+
+def _fused_op(synced=False):
+    _load_fused_ops()
     return _FUSED_SYNC_OP if synced else _FUSED_OP
+
+
+def _fused_linear_op():
+    _load_fused_ops()
+    return _FUSED_LINEAR_OP
+
+
+def _on_device_f32(dev, tensors):
+    """Every tensor is contiguous float32 on the HIP device `dev`: what the library ops ask of everything per column."""
+    return all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
+
+
+def _draw_drop_seed(st, training, keepProb):
+    """(seed, keepProb) of a library call that is going to happen: a call that drops takes the store's next seed (and counts
+    as one of its dropCalls_); any other has no dropout."""
+    if not training or keepProb is None:
+        return 0, None
+    seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
+    st.dropCalls_ += 1
+    return seed, keepProb
 
 
 def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
@@ -209,7 +243,7 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
         return None
     if inputs.shape[1] % 2 != 0 and (inputs.dtype == torch.bfloat16 or outDtype == torch.bfloat16):
         return None
-    synced = bool(training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+    synced = _stats_cross_ranks(training, sync)
     if synced and not getattr(st, "fusedSync_", False):
         return None
     if keepProb is not None and not 0.0 < keepProb <= 1.0:
@@ -217,23 +251,12 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
     op = _fused_op(synced)
     if op is None:
         return None
-    c = inputs.shape[1]
-    dev = inputs.device
-    gamma = st.get_variable(name + "/gamma", (c,), _ones, dev)
-    beta = st.get_variable(name + "/beta", (c,), _zeros, dev)
-    mov_mean = st.get_buffer(name + "/moving_mean", (c,), 0.0, dev)
-    mov_var = st.get_buffer(name + "/moving_variance", (c,), 1.0, dev)
+    gamma, beta, mov_mean, mov_var = _bn_block(st, name, inputs.shape[1], inputs.device)
     if not training and torch.is_grad_enabled() and (inputs.requires_grad or gamma.requires_grad or beta.requires_grad):
         return None
-    if not all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
-               for t in (gamma, beta, mov_mean, mov_var)):
+    if not _on_device_f32(inputs.device, (gamma, beta, mov_mean, mov_var)):
         return None
-    seed = 0
-    if training and keepProb is not None:
-        seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
-        st.dropCalls_ += 1
-    else:
-        keepProb = None
+    seed, keepProb = _draw_drop_seed(st, training, keepProb)
     if synced:
         return op(inputs, gamma, beta, mov_mean, mov_var, relu, keepProb, seed, momentum, epsilon, outDtype,
                   getattr(st, "syncGroup_", None))
@@ -264,21 +287,6 @@ def _bn_relu_drop(st, inputs, training, name, useDropOut, keepProb, outDtype=Non
     return y
 
 
-_FUSED_LINEAR_OP = False   # native.linear_bn_relu_drop once the library has loaded; None when it does not
-
-
-def _fused_linear_op():
-    global _FUSED_LINEAR_OP
-    if _FUSED_LINEAR_OP is False:
-        try:
-            from . import _lib, native
-            _lib.load()
-            _FUSED_LINEAR_OP = native.linear_bn_relu_drop
-        except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_LINEAR_OP = None
-    return _FUSED_LINEAR_OP
-
-
 def _fused_linear(st, inputs, w, b, training, name, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
     """drop(relu(batch_normalization(inputs @ w + b))) as one library op, or None where that form does not apply (the
     caller then runs the matmul and the block as before): the store's switch is off, inputs is not a contiguous float32
@@ -296,30 +304,19 @@ def _fused_linear(st, inputs, w, b, training, name, keepProb=None, momentum=0.99
         return None
     if w.shape[1] % 2 != 0 and outDtype == torch.bfloat16:
         return None
-    if training and sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if _stats_cross_ranks(training, sync):
         return None
     if keepProb is not None and not 0.0 < keepProb <= 1.0:
         return None
     op = _fused_linear_op()
     if op is None:
         return None
-    c = w.shape[1]
-    dev = inputs.device
-    gamma = st.get_variable(name + "/gamma", (c,), _ones, dev)
-    beta = st.get_variable(name + "/beta", (c,), _zeros, dev)
-    mov_mean = st.get_buffer(name + "/moving_mean", (c,), 0.0, dev)
-    mov_var = st.get_buffer(name + "/moving_variance", (c,), 1.0, dev)
+    gamma, beta, mov_mean, mov_var = _bn_block(st, name, w.shape[1], inputs.device)
     if not training and torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, w, b, gamma, beta)):
         return None
-    if not all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()
-               for t in (w, b, gamma, beta, mov_mean, mov_var)):
+    if not _on_device_f32(inputs.device, (w, b, gamma, beta, mov_mean, mov_var)):
         return None
-    seed = 0
-    if training and keepProb is not None:
-        seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
-        st.dropCalls_ += 1
-    else:
-        keepProb = None
+    seed, keepProb = _draw_drop_seed(st, training, keepProb)
     return op(inputs, w, b, gamma, beta, mov_mean, mov_var, bool(training), True, keepProb, seed, momentum, epsilon, outDtype)
 
 

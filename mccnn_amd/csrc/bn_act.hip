@@ -20,6 +20,9 @@
 //   eval                one launch.
 // No atomics, no memset, no ticket or spin-wait between workgroups; a fixed merge order: the same inputs and seed give the
 // same bytes. The gate is pre > 0 (torch's relu'), not the >= 0 of the convolution kernels.
+#include <initializer_list>
+#include <type_traits>
+
 #include "common.h"
 #include "bn_drop.h"
 #include "bn_act.h"
@@ -324,12 +327,13 @@ __device__ __forceinline__ void bn_merge_partials(const BnArgs& a, const BnCoord
     bn_tree_merge<VEC>(a, t, cnt, mean, m2, lds);
 }
 
-// row lane 0: mean and rstd of the thread's columns into LDS for the workgroup; `first`: also saved and the moving statistics
+// row lane 0: mean and rstd of the thread's columns into LDS for the workgroup; `first`: also saved and the moving statistics.
+// fn: the rows in the statistics, looked at in row lane 0 only. Every thread of the workgroup calls it.
 template <int VEC>
-__device__ __forceinline__ void bn_finish_stats(const BnArgs& a, const BnCoord& t, const float (&mean)[VEC],
+__device__ __forceinline__ void bn_finish_stats(const BnArgs& a, const BnCoord& t, float fn, const float (&mean)[VEC],
                                                 const float (&m2)[VEC], bool first, float (*sm)[kBnTileCols]) {
     if (t.ry == 0 && t.ok) {
-        const float fn = (float)a.n, keep = 1.0f - a.momentum;
+        const float keep = 1.0f - a.momentum;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             const float var = m2[k] / fn;
@@ -425,7 +429,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
         float cnt, m2[VEC];
         if constexpr (MODE == 0) bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
         else bn_slab_stats<VEC, XT>(a, t, 0, a.n, cnt, mean, m2, lds);
-        bn_finish_stats<VEC>(a, t, mean, m2, slab == 0, sm);
+        bn_finish_stats<VEC>(a, t, (float)a.n, mean, m2, slab == 0, sm);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
         bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll);
@@ -531,6 +535,29 @@ __device__ __forceinline__ void bn_sum_partials(const BnArgs& a, const BnCoord& 
     bn_tree_sum<VEC>(a, t, sg, sx, sh, lds);
 }
 
+// the dx half of launch 2 of the backward: dx of rows [row0, row1) from the workgroup's (sum g, sum g * (xhat - mh), mh) in
+// sm, fn rows in the statistics. base: what the mask's row index has over the local one (bn_apply_rows)
+template <int VEC, typename XT, typename YT>
+__device__ __forceinline__ void bn_dx_rows(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1, float fn,
+                                           const float (*sm)[kBnTileCols], int base) {
+    if (!a.want_dx || !t.ok) return;
+    const bool drop = a.T < kBnDropAll;
+    float kb[VEC], kg[VEC], gr[VEC], mh[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        kb[k] = sm[0][t.cx * VEC + k] / fn;
+        kg[k] = sm[1][t.cx * VEC + k] / fn;
+        mh[k] = sm[2][t.cx * VEC + k];
+        gr[k] = q.g[k] * q.rstd[k];
+    }
+    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
+        float o[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
+        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
+    }, base);
+}
+
 // backward, launch 1: the partial (sum g, sum g * xhat, sum xhat) of a slab. sum xhat is zero for the exact mean; with the
 // saved f32 mean it is -n * (mean's rounding error) * rstd, and launch 2 takes that shift out of xhat again -- on a column
 // of few rows with |mean| >> std (var + eps barely above var) dx is the small remainder of cancelling terms, and the
@@ -587,22 +614,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
         }
     }
     __syncthreads();
-    if (!a.want_dx || !t.ok) return;
-    const bool drop = a.T < kBnDropAll;
-    float kb[VEC], kg[VEC], gr[VEC], mh[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        kb[k] = sm[0][t.cx * VEC + k] / fn;
-        kg[k] = sm[1][t.cx * VEC + k] / fn;
-        mh[k] = sm[2][t.cx * VEC + k];
-        gr[k] = q.g[k] * q.rstd[k];
-    }
-    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
-        float o[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
-        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
-    });
+    bn_dx_rows<VEC, XT, YT>(a, t, q, row0, row1, fn, sm, 0);
 }
 
 // ---- batch statistics across the ranks of a process group (mccnn_bn_sync_*) ----------------------------------------------
@@ -653,12 +665,13 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_apply_k(BnArgs a) {
     const BnCoord t = bn_coord<VEC>(a);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
+    float cnt = 0.f, mean[VEC], m2[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) { mean[k] = 0.f; m2[k] = 0.f; }
+    int total = 0;   // N: valid in row lane 0, where the merge is
     if (t.ry == 0 && t.ok) {
         const size_t c = (size_t)a.c;
-        float cnt = 0.f, mean[VEC], m2[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) { mean[k] = 0.f; m2[k] = 0.f; }
-        int base = 0, total = 0;
+        int base = 0;
         for (int w = 0; w < a.world; ++w) {
             const float* p = a.rparts + (size_t)w * 3 * c + t.col;
             const float nB = p[0];   // (the columns of a rank share their count)
@@ -669,28 +682,13 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_apply_k(BnArgs a) {
             total += (int)nB;
             bn_chan<VEC>(cnt, mean, m2, nB, mB, qB);
         }
-        const float fn = (float)total, keep = 1.0f - a.momentum;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            const float var = m2[k] / fn;
-            const float rstd = 1.0f / sqrtf(var + a.eps);
-            sm[0][t.cx * VEC + k] = mean[k];
-            sm[1][t.cx * VEC + k] = rstd;
-            if (slab == 0) {
-                const int j = t.col + k;
-                a.saved[j] = mean[k];
-                a.saved[c + j] = rstd;
-                a.mov_mean[j] = a.mov_mean[j] * a.momentum + mean[k] * keep;
-                a.mov_var[j] = a.mov_var[j] * a.momentum + var * keep;
-            }
-        }
         if (t.tid == 0) {
             sbase = base;
             if (slab == 0 && blockIdx.x == 0) { a.meta[0] = base; a.meta[1] = total; }
         }
     }
-    __syncthreads();
-    float mean[VEC], rstd[VEC];
+    bn_finish_stats<VEC>(a, t, (float)total, mean, m2, slab == 0, sm);   // (its barrier also publishes sbase)
+    float rstd[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
     bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll, sbase);
@@ -752,22 +750,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_dx_k(BnArgs a) {
         }
     }
     __syncthreads();
-    if (!a.want_dx || !t.ok) return;
-    const bool drop = a.T < kBnDropAll;
-    float kb[VEC], kg[VEC], gr[VEC], mh[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        kb[k] = sm[0][t.cx * VEC + k] / fn;
-        kg[k] = sm[1][t.cx * VEC + k] / fn;
-        mh[k] = sm[2][t.cx * VEC + k];
-        gr[k] = q.g[k] * q.rstd[k];
-    }
-    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
-        float o[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
-        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
-    }, base);
+    bn_dx_rows<VEC, XT, YT>(a, t, q, row0, row1, fn, sm, base);
 }
 
 // a caller's row pointer allows the wide form: f32 x -> 4 columns per thread (f32 rows move as 16 bytes, bf16 rows as 8),
@@ -780,65 +763,53 @@ inline bool bn_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // odd c or a pointer off a 32-bit word with bf16 storage: bf16 rows move as 32-bit words
 inline bool bn_bf16_ok(const void* p, int bf16, int c) { return !bf16 || (c % 2 == 0 && ((uintptr_t)p & 3u) == 0); }
 
-// one kernel family over (columns per thread, x's type, y's / dy's type): L::go<VEC, XT, YT> launches it; 0 or the launch's
-// hipError_t
-template <typename L>
-inline int bn_launch(int vec, int x_bf16, int y_bf16, dim3 grid, hipStream_t st, const BnArgs& a) {
+// one kernel family over (columns per thread, x's type, y's / dy's type): go(v, xt, yt) launches the member its tags name --
+// v an integral constant, xt and yt a zero of the element type; 0 or the launch's hipError_t
+template <int V>
+using BnVec = std::integral_constant<int, V>;
+template <typename F>
+inline int bn_launch(int vec, int x_bf16, int y_bf16, F&& go) {
     if (!x_bf16) {
-        if (!y_bf16) { if (vec == 4) L::template go<4, float, float>(grid, st, a); else L::template go<1, float, float>(grid, st, a); }
-        else { if (vec == 4) L::template go<4, float, bn_bf16>(grid, st, a); else L::template go<1, float, bn_bf16>(grid, st, a); }
+        if (!y_bf16) { if (vec == 4) go(BnVec<4>(), float(), float()); else go(BnVec<1>(), float(), float()); }
+        else { if (vec == 4) go(BnVec<4>(), float(), bn_bf16()); else go(BnVec<1>(), float(), bn_bf16()); }
     } else {
-        if (!y_bf16) { if (vec == 8) L::template go<8, bn_bf16, float>(grid, st, a); else L::template go<2, bn_bf16, float>(grid, st, a); }
-        else { if (vec == 8) L::template go<8, bn_bf16, bn_bf16>(grid, st, a); else L::template go<2, bn_bf16, bn_bf16>(grid, st, a); }
+        if (!y_bf16) { if (vec == 8) go(BnVec<8>(), bn_bf16(), float()); else go(BnVec<2>(), bn_bf16(), float()); }
+        else { if (vec == 8) go(BnVec<8>(), bn_bf16(), bn_bf16()); else go(BnVec<2>(), bn_bf16(), bn_bf16()); }
     }
     MCCNN_LAUNCHED();
     return 0;
 }
-struct BnStatsL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_stats_k<VEC, XT><<<grid, kBnThreads, 0, st>>>(a); }
-};
-template <int MODE>
-struct BnApplyL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_apply_k<VEC, XT, YT, MODE><<<grid, kBnThreads, 0, st>>>(a); }
-};
-struct BnBwdSumsL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_sums_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
-};
-template <int SMALL>
-struct BnBwdDxL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_dx_k<VEC, XT, YT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
-};
-template <int SMALL>
-struct BnSyncStatsL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_stats_k<VEC, XT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
-};
-struct BnSyncApplyL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_apply_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
-};
-struct BnSyncSlabSumsL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_bwd_sums_k<VEC, XT, YT, 1><<<grid, kBnThreads, 0, st>>>(a); }
-};
-template <int SMALL>
-struct BnSyncBwdSumsL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_bwd_sums_k<VEC, XT, YT, SMALL><<<grid, kBnThreads, 0, st>>>(a); }
-};
-struct BnSyncBwdDxL {
-    template <int VEC, typename XT, typename YT>
-    static void go(dim3 grid, hipStream_t st, const BnArgs& a) { bn_sync_bwd_dx_k<VEC, XT, YT><<<grid, kBnThreads, 0, st>>>(a); }
-};
 
 // what every mccnn_bn_sync_* entry checks of its shard before it looks at anything else; 0 or the error
 inline int bn_sync_check(int n, int c, int rank, int world) {
     if (n < 1 || c < 1 || world < 1 || rank < 0 || rank >= world) return MCCNN_E_BADARG;
     if (n > (1 << 24)) return MCCNN_E_TOOLARGE;   // counts travel as f32
+    return 0;
+}
+
+// a caller's rows and their type flag; the first of an entry's list is x (dx has x's type, and may be NULL: not wanted)
+struct BnRows {
+    const void* p;
+    int bf16;
+};
+
+// What the entries share behind their own checks, in this order: the type flags, bf16 rows on 32-bit words, the workspace
+// (need: its bytes, 0: the entry has none) -- 0 or the error -- then the plan from the row pointers and the workspace's, and
+// what of `a` follows from it.
+inline int bn_setup(BnArgs& a, BnPlan& p, int n, int c, std::initializer_list<BnRows> rows, size_t need = 0, void* ws = nullptr,
+                    size_t ws_bytes = 0) {
+    const int x_bf16 = rows.begin()->bf16;
+    int flags = 0;
+    for (const BnRows& r : rows) flags |= r.bf16;
+    if (flags & ~1) return MCCNN_E_BADARG;
+    for (const BnRows& r : rows)
+        if (!bn_bf16_ok(r.p, r.bf16, c)) return MCCNN_E_SHAPE;
+    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
+    bool aligned = !need || bn_aligned16(ws);
+    for (const BnRows& r : rows) aligned = aligned && bn_rows_aligned(r.p, r.bf16, x_bf16);
+    p = bn_plan(n, c, aligned, x_bf16);
+    a.part = (float*)ws;
+    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs;
     return 0;
 }
 
@@ -855,26 +826,27 @@ int mccnn::bn_act_bwd_impl(const void* x, int x_bf16, const void* dy, int dy_bf1
     if (n < 1 || c < 1) return MCCNN_E_BADARG;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
-    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
-    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
-    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
-                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)) && (!need || bn_aligned16(ws)), x_bf16);
     BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}, {dy, dy_bf16}, {dx, x_bf16}}, mccnn_bn_act_workspace_bytes(n, c), ws, ws_bytes))
+        return e;
     a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
-    a.part = (float*)ws; a.dgamma = dgamma; a.dbeta = dbeta; a.shift = shift;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
-    a.want_dx = dx ? 1 : 0;
+    a.dgamma = dgamma; a.dbeta = dbeta; a.shift = shift; a.relu = relu ? 1 : 0; a.want_dx = dx ? 1 : 0;
     a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
-    if (n <= kBnSmallRows) {
-        return bn_launch<BnBwdDxL<1>>(p.vec, x_bf16, dy_bf16, grid, st, a);
-    }
-    if (const int e = bn_launch<BnBwdSumsL>(p.vec, x_bf16, dy_bf16, grid, st, a)) return e;
+    if (n <= kBnSmallRows)
+        return bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_bwd_dx_k<v(), decltype(xt), decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a);
+        });
+    if (const int e = bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_bwd_sums_k<v(), decltype(xt), decltype(yt)><<<grid, kBnThreads, 0, st>>>(a);
+        }))
+        return e;
     const dim3 grid2((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u);
-    return bn_launch<BnBwdDxL<0>>(p.vec, x_bf16, dy_bf16, grid2, st, a);
+    return bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+        bn_bwd_dx_k<v(), decltype(xt), decltype(yt), 0><<<grid2, kBnThreads, 0, st>>>(a);
+    });
 }
 
 extern "C" {
@@ -892,28 +864,30 @@ int mccnn_bn_act_fwd_rows(const void* x, int x_bf16, int n, int c, const float* 
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !gamma || !beta || !moving_mean || !moving_var || !y) return MCCNN_E_BADARG;
     if (training && !saved) return MCCNN_E_BADARG;
-    if ((x_bf16 | y_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(y, y_bf16, c)) return MCCNN_E_SHAPE;
-    const size_t need = training ? mccnn_bn_act_workspace_bytes(n, c) : 0;
-    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(y, y_bf16, x_bf16) && (!need || bn_aligned16(ws)),
-                             x_bf16);
     BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}, {y, y_bf16}}, training ? mccnn_bn_act_workspace_bytes(n, c) : 0, ws, ws_bytes))
+        return e;
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
-    a.part = (float*)ws;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
-    a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed;
+    a.relu = relu ? 1 : 0; a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed;
     a.T = training ? keep_threshold : kBnDropAll;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
-    if (!training) {
-        return bn_launch<BnApplyL<2>>(p.vec, x_bf16, y_bf16, grid, st, a);
-    }
-    if (n <= kBnSmallRows) {
-        return bn_launch<BnApplyL<1>>(p.vec, x_bf16, y_bf16, grid, st, a);
-    }
-    if (const int e = bn_launch<BnStatsL>(p.vec, x_bf16, 0, grid, st, a)) return e;
-    return bn_launch<BnApplyL<0>>(p.vec, x_bf16, y_bf16, grid, st, a);
+    if (!training)
+        return bn_launch(p.vec, x_bf16, y_bf16, [&](auto v, auto xt, auto yt) {
+            bn_apply_k<v(), decltype(xt), decltype(yt), 2><<<grid, kBnThreads, 0, st>>>(a);
+        });
+    if (n <= kBnSmallRows)
+        return bn_launch(p.vec, x_bf16, y_bf16, [&](auto v, auto xt, auto yt) {
+            bn_apply_k<v(), decltype(xt), decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a);
+        });
+    if (const int e = bn_launch(p.vec, x_bf16, 0, [&](auto v, auto xt, auto) {
+            bn_stats_k<v(), decltype(xt)><<<grid, kBnThreads, 0, st>>>(a);
+        }))
+        return e;
+    return bn_launch(p.vec, x_bf16, y_bf16, [&](auto v, auto xt, auto yt) {
+        bn_apply_k<v(), decltype(xt), decltype(yt), 0><<<grid, kBnThreads, 0, st>>>(a);
+    });
 }
 
 int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, const float* gamma,
@@ -945,20 +919,23 @@ int mccnn_bn_sync_stats(const void* x, int x_bf16, int n, int c, int rank, int w
                         mccnn_stream_t stream) {
     if (const int e = bn_sync_check(n, c, rank, world)) return e;
     if (!x || !parts) return MCCNN_E_BADARG;
-    if (x_bf16 & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c)) return MCCNN_E_SHAPE;
-    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
-    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && (!need || bn_aligned16(ws)), x_bf16);
     BnArgs a = {};
-    a.x = x; a.part = (float*)ws; a.rparts = parts;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs;
-    a.rank = rank; a.world = world;
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}}, mccnn_bn_act_workspace_bytes(n, c), ws, ws_bytes)) return e;
+    a.x = x; a.rparts = parts; a.rank = rank; a.world = world;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 one((unsigned)p.tiles, 1u);
-    if (n <= kBnSmallRows) return bn_launch<BnSyncStatsL<1>>(p.vec, x_bf16, 0, one, st, a);
-    if (const int e = bn_launch<BnStatsL>(p.vec, x_bf16, 0, dim3((unsigned)p.tiles, (unsigned)p.slabs), st, a)) return e;
-    return bn_launch<BnSyncStatsL<0>>(p.vec, x_bf16, 0, one, st, a);
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs), one((unsigned)p.tiles, 1u);
+    if (n <= kBnSmallRows)
+        return bn_launch(p.vec, x_bf16, 0, [&](auto v, auto xt, auto) {
+            bn_sync_stats_k<v(), decltype(xt), 1><<<one, kBnThreads, 0, st>>>(a);
+        });
+    if (const int e = bn_launch(p.vec, x_bf16, 0, [&](auto v, auto xt, auto) {
+            bn_stats_k<v(), decltype(xt)><<<grid, kBnThreads, 0, st>>>(a);
+        }))
+        return e;
+    return bn_launch(p.vec, x_bf16, 0, [&](auto v, auto xt, auto) {
+        bn_sync_stats_k<v(), decltype(xt), 0><<<one, kBnThreads, 0, st>>>(a);
+    });
 }
 
 int mccnn_bn_sync_apply(const void* x, int x_bf16, int n, int c, int rank, int world, const float* parts, const float* gamma,
@@ -968,16 +945,17 @@ int mccnn_bn_sync_apply(const void* x, int x_bf16, int n, int c, int rank, int w
     if (const int e = bn_sync_check(n, c, rank, world)) return e;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !parts || !gamma || !beta || !moving_mean || !moving_var || !y || !saved || !meta) return MCCNN_E_BADARG;
-    if ((x_bf16 | y_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(y, y_bf16, c)) return MCCNN_E_SHAPE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(y, y_bf16, x_bf16), x_bf16);
     BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}, {y, y_bf16}})) return e;
     a.x = x; a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
-    a.rparts = const_cast<float*>(parts); a.meta = meta;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
-    a.rank = rank; a.world = world;
+    a.rparts = const_cast<float*>(parts); a.meta = meta; a.relu = relu ? 1 : 0; a.rank = rank; a.world = world;
     a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
-    return bn_launch<BnSyncApplyL>(p.vec, x_bf16, y_bf16, dim3((unsigned)p.tiles, (unsigned)p.slabs), (hipStream_t)stream, a);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
+    return bn_launch(p.vec, x_bf16, y_bf16, [&](auto v, auto xt, auto yt) {
+        bn_sync_apply_k<v(), decltype(xt), decltype(yt)><<<grid, kBnThreads, 0, st>>>(a);
+    });
 }
 
 int mccnn_bn_sync_bwd_sums(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
@@ -987,23 +965,25 @@ int mccnn_bn_sync_bwd_sums(const void* x, int x_bf16, const void* dy, int dy_bf1
     if (const int e = bn_sync_check(n, c, rank, world)) return e;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !dy || !gamma || !beta || !saved || !meta || !parts_b || !dgamma || !dbeta) return MCCNN_E_BADARG;
-    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c)) return MCCNN_E_SHAPE;
-    const size_t need = mccnn_bn_act_workspace_bytes(n, c);
-    if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
-                                       (!need || bn_aligned16(ws)), x_bf16);
     BnArgs a = {};
-    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved); a.part = (float*)ws;
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}, {dy, dy_bf16}}, mccnn_bn_act_workspace_bytes(n, c), ws, ws_bytes)) return e;
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
     a.rparts = parts_b; a.meta = const_cast<int*>(meta); a.dgamma = dgamma; a.dbeta = dbeta;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.nparts = p.slabs; a.relu = relu ? 1 : 0;
-    a.rank = rank; a.world = world;
-    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    a.relu = relu ? 1 : 0; a.rank = rank; a.world = world; a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 one((unsigned)p.tiles, 1u);
-    if (n <= kBnSmallRows) return bn_launch<BnSyncBwdSumsL<1>>(p.vec, x_bf16, dy_bf16, one, st, a);
-    if (const int e = bn_launch<BnSyncSlabSumsL>(p.vec, x_bf16, dy_bf16, dim3((unsigned)p.tiles, (unsigned)p.slabs), st, a)) return e;
-    return bn_launch<BnSyncBwdSumsL<0>>(p.vec, x_bf16, dy_bf16, one, st, a);
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs), one((unsigned)p.tiles, 1u);
+    if (n <= kBnSmallRows)
+        return bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_sync_bwd_sums_k<v(), decltype(xt), decltype(yt), 1><<<one, kBnThreads, 0, st>>>(a);
+        });
+    if (const int e = bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_bwd_sums_k<v(), decltype(xt), decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a);
+        }))
+        return e;
+    return bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+        bn_sync_bwd_sums_k<v(), decltype(xt), decltype(yt), 0><<<one, kBnThreads, 0, st>>>(a);
+    });
 }
 
 int mccnn_bn_sync_bwd_dx(const void* x, int x_bf16, const void* dy, int dy_bf16, int n, int c, int rank, int world,
@@ -1013,18 +993,18 @@ int mccnn_bn_sync_bwd_dx(const void* x, int x_bf16, const void* dy, int dy_bf16,
     if (const int e = bn_sync_check(n, c, rank, world)) return e;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!x || !dy || !gamma || !beta || !parts_b || !saved || !meta || (!dx && !dgamma)) return MCCNN_E_BADARG;
-    if ((x_bf16 | dy_bf16) & ~1) return MCCNN_E_BADARG;
-    if (!bn_bf16_ok(x, x_bf16, c) || !bn_bf16_ok(dy, dy_bf16, c) || !bn_bf16_ok(dx, x_bf16, c)) return MCCNN_E_SHAPE;
-    const BnPlan p = bn_plan(n, c, bn_rows_aligned(x, x_bf16, x_bf16) && bn_rows_aligned(dy, dy_bf16, x_bf16) &&
-                                       (!dx || bn_rows_aligned(dx, x_bf16, x_bf16)), x_bf16);
     BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{x, x_bf16}, {dy, dy_bf16}, {dx, x_bf16}})) return e;
     a.x = x; a.dy = dy; a.out = dx; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
     a.rparts = const_cast<float*>(parts_b); a.meta = const_cast<int*>(meta); a.dgamma = dgamma;
-    a.n = n; a.c = c; a.tw_log = p.tw_log; a.slab_rows = p.slab_rows; a.slabs = p.slabs; a.relu = relu ? 1 : 0;
-    a.want_dx = dx ? 1 : 0; a.rank = rank; a.world = world;
+    a.relu = relu ? 1 : 0; a.want_dx = dx ? 1 : 0; a.rank = rank; a.world = world;
     a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
-    return bn_launch<BnSyncBwdDxL>(p.vec, x_bf16, dy_bf16, dim3((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u),
-                                   (hipStream_t)stream, a);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, dx ? (unsigned)p.slabs : 1u);
+    return bn_launch(p.vec, x_bf16, dy_bf16, [&](auto v, auto xt, auto yt) {
+        bn_sync_bwd_dx_k<v(), decltype(xt), decltype(yt)><<<grid, kBnThreads, 0, st>>>(a);
+    });
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 
 #include "mccnn.h"
 #include "debug_opts.h"
+#include "bn_drop.h"
 
 namespace {
 
@@ -1366,16 +1367,37 @@ Tensor sampled_features(const Tensor& idx, const Tensor& feats) {
     return out;
 }
 
-// ---- the dense glue as one op (mccnn_bn_act_fwd / _bwd): y = drop(act(bn(x))), the C++ form of
-// MCConvModule.bn_relu_dropout -- the same library calls with the same arguments, so the same bytes; the autograd node is
-// here, so a block costs the host one Python -> C++ call forward and none backward. x and y are each f32 or bf16 rows
-// (mccnn_bn_act_fwd_rows / _bwd_rows; f32 both ways goes through the float32 entries as before): dy has y's type, dx x's.
-// bf16 rows that do not start on a 16-byte boundary are copied where they enter, as the convolutions do.
+// ---- the dense glue as one op (mccnn_bn_act_fwd_rows / _bwd_rows): y = drop(act(bn(x))), the C++ form of
+// dense_glue.bn_relu_dropout -- the same library calls with the same arguments, so the same bytes; the autograd node is
+// here, so a block costs the host one Python -> C++ call forward and none backward. x and y are each f32 or bf16 rows:
+// dy has y's type, dx x's. bf16 rows that do not start on a 16-byte boundary are copied where they enter, as the
+// convolutions do.
 inline bool is_bf16(const Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 inline Tensor bf16_rows_aligned(const Tensor& t) {
     if (is_bf16(t) && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) != 0) return t.detach().clone(at::MemoryFormat::Contiguous);
     return t;
 }
+// What the backward of a glue node (this one, LinearBnBackward) does before it computes: its buffers still there (`alive`),
+// no double backward, no input changed in place since the forward -> dy as the library reads it: zeros of `like`'s shape
+// where autograd hands none over, y's type, contiguous. op: the op's name in the messages.
+Tensor glue_grad_in(const char* op, bool alive, Tensor gy, std::initializer_list<const Tensor*> in, const uint32_t* versions,
+                    const Tensor& like, bool y_bf16) {
+    TORCH_CHECK(alive, op, ": backward through a graph whose buffers have been freed (retain_graph=True?)");
+    TORCH_CHECK(!(at::GradMode::is_enabled() && gy.defined() && gy.requires_grad()), op, " is differentiable once: no double backward");
+    int k = 0;
+    for (const Tensor* t : in) {
+        TORCH_CHECK(t->_version() == versions[k],
+                    "one of the variables needed for gradient computation has been modified by an inplace operation (", op, " input ", k,
+                    ")");
+        ++k;
+    }
+    const at::ScalarType yt = y_bf16 ? at::kBFloat16 : at::kFloat;
+    if (!gy.defined()) gy = at::zeros(like.sizes(), like.options().dtype(yt));
+    if (gy.scalar_type() != yt) gy = gy.to(yt);
+    if (!gy.is_contiguous()) gy = gy.contiguous();
+    return gy;
+}
+
 struct BnActBackward : public torch::autograd::Node {
     Tensor x_, gamma_, beta_, saved;
     bool y_bf16 = false;
@@ -1386,42 +1408,21 @@ struct BnActBackward : public torch::autograd::Node {
     unsigned seed = 0;
 
     torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        TORCH_CHECK(x_.defined() && saved.defined(), "bn_relu_drop: backward through a graph whose buffers have been freed (retain_graph=True?)");
-        Tensor gy = grads[0];
-        TORCH_CHECK(!(at::GradMode::is_enabled() && gy.defined() && gy.requires_grad()),
-                    "bn_relu_drop is differentiable once: no double backward");
-        {
-            const Tensor* in[3] = {&x_, &gamma_, &beta_};
-            for (int k = 0; k < 3; ++k)
-                TORCH_CHECK(in[k]->_version() == versions[k],
-                            "one of the variables needed for gradient computation has been modified by an inplace operation "
-                            "(bn_relu_drop input ", k, ")");
-        }
+        const Tensor gy = bf16_rows_aligned(glue_grad_in("bn_relu_drop", x_.defined() && saved.defined(), grads[0], {&x_, &gamma_, &beta_},
+                                                         versions, x_, y_bf16));
         const DevGuard device_guard((int)x_.device().index());
         const int n = (int)x_.size(0), c = (int)x_.size(1);
-        const at::ScalarType yt = y_bf16 ? at::kBFloat16 : at::kFloat;
-        if (!gy.defined()) gy = at::zeros(x_.sizes(), x_.options().dtype(yt));
-        if (gy.scalar_type() != yt) gy = gy.to(yt);
-        if (!gy.is_contiguous()) gy = gy.contiguous();
-        gy = bf16_rows_aligned(gy);
-        const bool x_bf16 = is_bf16(x_);
         const bool want_dx = task_should_compute_output(0);
         Tensor dx;
         if (want_dx) dx = at::empty_like(x_);
         Tensor dgb = at::empty({2, (int64_t)c}, gamma_.options());
         void* st = cur_stream(x_);
         Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(n, c), x_, st);
-        if (!x_bf16 && !y_bf16)
-            check(mccnn_bn_act_bwd(x_.data_ptr<float>(), gy.data_ptr<float>(), n, c, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
-                                   saved.data_ptr<float>(), relu, thr, scale, seed, want_dx ? dx.data_ptr<float>() : nullptr,
-                                   dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
-                  "bn_relu_dropout_grad");
-        else
-            check(mccnn_bn_act_bwd_rows(x_.data_ptr(), x_bf16 ? 1 : 0, gy.data_ptr(), y_bf16 ? 1 : 0, n, c, gamma_.data_ptr<float>(),
-                                        beta_.data_ptr<float>(), saved.data_ptr<float>(), relu, thr, scale, seed,
-                                        want_dx ? dx.data_ptr() : nullptr, dgb.data_ptr<float>(), dgb.data_ptr<float>() + c,
-                                        ws.data_ptr(), (size_t)ws.numel(), st),
-                  "bn_relu_dropout_grad");
+        check(mccnn_bn_act_bwd_rows(x_.data_ptr(), is_bf16(x_) ? 1 : 0, gy.data_ptr(), y_bf16 ? 1 : 0, n, c, gamma_.data_ptr<float>(),
+                                    beta_.data_ptr<float>(), saved.data_ptr<float>(), relu, thr, scale, seed,
+                                    want_dx ? dx.data_ptr() : nullptr, dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(),
+                                    (size_t)ws.numel(), st),
+              "bn_relu_dropout_grad");
         torch::autograd::variable_list out(3);
         out[0] = dx;
         if (task_should_compute_output(1)) out[1] = dgb.select(0, 0);
@@ -1459,19 +1460,11 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
         void* st = cur_stream(x);
         const size_t wsb = training ? mccnn_bn_act_workspace_bytes(n, c) : 0;
         Tensor& ws = scratch(wsb, x, st);
-        if (!x_bf16 && !y_bf16)
-            check(mccnn_bn_act_fwd(x.data_ptr<float>(), n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
-                                   mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
-                                   training ? thr : 0x100000000ull, training ? (float)scale : 1.f, seed, y.data_ptr<float>(),
-                                   training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
-                  "bn_relu_dropout");
-        else
-            check(mccnn_bn_act_fwd_rows(x.data_ptr(), x_bf16 ? 1 : 0, n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                                        mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum, (float)eps,
-                                        training ? 1 : 0, relu ? 1 : 0, training ? thr : 0x100000000ull,
-                                        training ? (float)scale : 1.f, seed, y.data_ptr(), y_bf16 ? 1 : 0,
-                                        training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
-                  "bn_relu_dropout");
+        check(mccnn_bn_act_fwd_rows(x.data_ptr(), x_bf16 ? 1 : 0, n, c, gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                                    mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0,
+                                    relu ? 1 : 0, training ? thr : mccnn::kBnDropAll, training ? (float)scale : 1.f, seed, y.data_ptr(),
+                                    y_bf16 ? 1 : 0, training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+              "bn_relu_dropout");
     }
     if (need_grad) {
         auto node = std::shared_ptr<BnActBackward>(new BnActBackward(), torch::autograd::deleteNode);
@@ -1486,7 +1479,7 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
 }
 
 // ---- ... with batch statistics across ranks (mccnn_bn_sync_*): the four stages as they are. The collectives between them
-// are torch.distributed's, so the autograd node is Python's (MCConvModule._BnReluDropoutSync), which has checked the
+// are torch.distributed's, so the autograd node is Python's (dense_glue._BnReluDropoutSync), which has checked the
 // arguments; here only what keeps a call inside its tensors. x / dx and y / dy are each f32 or bf16 rows.
 struct BnSyncShape {
     int n, c, x_bf16;
@@ -1584,7 +1577,7 @@ void bn_sync_bwd_dx(const Tensor& x, const Tensor& dy, int64_t rank, int64_t wor
 }
 
 // ---- a linear layer and the dense glue behind it as one op (mccnn_linear_bn_act_fwd / _bwd): y = drop(act(bn(x w + b))), the
-// C++ form of MCConvModule.linear_bn_relu_dropout -- the same library calls with the same arguments, so the same bytes.
+// C++ form of dense_glue.linear_bn_relu_dropout -- the same library calls with the same arguments, so the same bytes.
 // x, w, z and everything per column are f32; y (and dy) f32 or bf16.
 struct LinearBnBackward : public torch::autograd::Node {
     Tensor x_, w_, gamma_, beta_, z, saved;
@@ -1596,24 +1589,10 @@ struct LinearBnBackward : public torch::autograd::Node {
     unsigned seed = 0;
 
     torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        TORCH_CHECK(x_.defined() && z.defined() && saved.defined(),
-                    "linear_bn_relu_drop: backward through a graph whose buffers have been freed (retain_graph=True?)");
-        Tensor gy = grads[0];
-        TORCH_CHECK(!(at::GradMode::is_enabled() && gy.defined() && gy.requires_grad()),
-                    "linear_bn_relu_drop is differentiable once: no double backward");
-        {
-            const Tensor* in[4] = {&x_, &w_, &gamma_, &beta_};
-            for (int k = 0; k < 4; ++k)
-                TORCH_CHECK(in[k]->_version() == versions[k],
-                            "one of the variables needed for gradient computation has been modified by an inplace operation "
-                            "(linear_bn_relu_drop input ", k, ")");
-        }
+        const Tensor gy = glue_grad_in("linear_bn_relu_drop", x_.defined() && z.defined() && saved.defined(), grads[0],
+                                       {&x_, &w_, &gamma_, &beta_}, versions, z, y_bf16);
         const DevGuard device_guard((int)x_.device().index());
         const int n = (int)x_.size(0), cin = (int)x_.size(1), cout = (int)w_.size(1);
-        const at::ScalarType yt = y_bf16 ? at::kBFloat16 : at::kFloat;
-        if (!gy.defined()) gy = at::zeros(z.sizes(), z.options().dtype(yt));
-        if (gy.scalar_type() != yt) gy = gy.to(yt);
-        if (!gy.is_contiguous()) gy = gy.contiguous();
         const bool want_dx = task_should_compute_output(0);
         Tensor dx;
         if (want_dx) dx = at::empty_like(x_);
@@ -1672,7 +1651,7 @@ Tensor linear_bn_relu_drop(const Tensor& x, const Tensor& w, const Tensor& b, co
         Tensor& ws = scratch(training ? mccnn_linear_bn_act_workspace_bytes(n, cin, cout) : 0, x, st);
         check(mccnn_linear_bn_act_fwd(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(), n, cin, cout, gamma.data_ptr<float>(),
                                       beta.data_ptr<float>(), mov_mean.data_ptr<float>(), mov_var.data_ptr<float>(), (float)momentum,
-                                      (float)eps, training ? 1 : 0, relu ? 1 : 0, training ? thr : 0x100000000ull,
+                                      (float)eps, training ? 1 : 0, relu ? 1 : 0, training ? thr : mccnn::kBnDropAll,
                                       training ? (float)scale : 1.f, seed, training ? z.data_ptr<float>() : nullptr, y.data_ptr(),
                                       y_bf16 ? 1 : 0, training ? saved.data_ptr<float>() : nullptr, training ? ws.data_ptr() : nullptr,
                                       training ? (size_t)ws.numel() : 0, st),

@@ -1,0 +1,318 @@
+"""The dense glue between two MC convolutions as library ops (extensions; csrc/bn_act.hip, csrc/linear_bn.hip,
+include/mccnn.h "THE DENSE GLUE AS ONE OP" and the two sections behind it): y = drop(act(bn(x))) with the moving
+statistics updated in place -- on its own (bn_relu_dropout), with the batch statistics across the ranks of a process group
+(bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
+(csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream.
+
+MCConvModule imports these names back: mccnn_amd.MCConvModule.bn_relu_dropout is this module's.
+mccnn_amd.native has the forms that go through the torch extension.
+"""
+import numpy as _np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream_handle
+
+BN_DROP_ALL = 1 << 32   # keep threshold of "no dropout"
+
+
+def _drop_args(op, keepProb, seed, outDtype):
+    """The checks of keepProb, seed and outDtype that the ops share (op: the name in the messages) -> (keep threshold, keep
+    scale). A threshold of 0 (a keepProb that keeps nothing) is the caller's to refuse, behind its other checks."""
+    _req(keepProb is None or (isinstance(keepProb, (int, float)) and not isinstance(keepProb, bool) and 0.0 < keepProb <= 1.0),
+         "%s expects keepProb in (0, 1] (or None)" % op)
+    _req(isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < (1 << 32), "%s expects a seed in [0, 2^32)" % op)
+    _req(outDtype is None or outDtype in (torch.float32, torch.bfloat16),
+         "%s: outDtype must be None, torch.float32 or torch.bfloat16" % op)
+    if keepProb is None:
+        return BN_DROP_ALL, 1.0
+    kp = float(keepProb)
+    thr = int(kp * 4294967296.0)   # floor(keepProb * 2^32) in double
+    return thr, float(_np.float32(1.0) / _np.float32(kp)) if thr >= 1 else 0.0   # 1.0f / (float) keepProb
+
+
+def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
+    """Checks of bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale). x: float32 or
+    bfloat16 rows; outDtype: None (x's type), torch.float32 or torch.bfloat16; everything per column is float32."""
+    thr, scale = _drop_args("bn_relu_dropout", keepProb, seed, outDtype)
+    _req(isinstance(x, torch.Tensor) and x.dtype in (torch.float32, torch.bfloat16),
+         "bn_relu_dropout: x must be a float32 (or bfloat16 storage) tensor")
+    for t, name in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(isinstance(t, torch.Tensor) and (t is x or t.dtype == torch.float32),
+             "bn_relu_dropout: %s must be a float32 tensor" % name)
+        _req(t.is_contiguous(), "bn_relu_dropout: %s must be contiguous" % name)
+    _req(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "bn_relu_dropout expects x with dimensions (n, c), n, c >= 1")
+    _req(x.shape[0] * x.shape[1] < (1 << 62) and max(x.shape) < (1 << 31), "bn_relu_dropout: x too large")
+    _req(x.shape[1] % 2 == 0 or (x.dtype == torch.float32 and outDtype in (None, torch.float32)),
+         "bn_relu_dropout: bfloat16 rows need an even number of columns")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(t.dim() == 1 and t.shape[0] == x.shape[1], "bn_relu_dropout: %s must have shape (c,)" % name)
+        _req(t.device == x.device, "bn_relu_dropout: %s is on another device than x" % name)
+    _req(x.is_cuda, "bn_relu_dropout: x must be a CUDA tensor")
+    _req(thr >= 1, "bn_relu_dropout: keepProb keeps nothing")
+    return thr, scale
+
+
+def _bn_act_fwd(lib, x, gamma, beta, movingMean, movingVar, momentum, epsilon, training, relu, thr, scale, seed, y, saved, ws):
+    """The forward library call: the typed entry, whatever the types (the float32 entry is that one with both flags zero)."""
+    check(lib.mccnn_bn_act_fwd_rows(ptr(x), int(x.dtype == torch.bfloat16), x.shape[0], x.shape[1], ptr(gamma), ptr(beta),
+                                    ptr(movingMean), ptr(movingVar), momentum, epsilon, training, relu, thr, scale, seed,
+                                    ptr(y), int(y.dtype == torch.bfloat16), ptr(saved), ptr(ws), 0 if ws is None else ws.numel(),
+                                    stream_handle()), "bn_relu_dropout")
+
+
+class _BnReluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype=None):
+        lib = _lib.load()
+        n, c = x.shape
+        xd, gd, bd = _bf16_rows_aligned(x.detach()), gamma.detach(), beta.detach()
+        y = torch.empty((n, c), dtype=outDtype or x.dtype, device=x.device)
+        saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+        _bn_act_fwd(lib, xd, gd, bd, movingMean, movingVar, momentum, epsilon, 1, int(relu), thr, scale, seed, y, saved, ws)
+        ctx.save_for_backward(xd, gd, bd, saved)
+        ctx.attrs = (int(relu), thr, scale, seed, y.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gamma, beta, saved = ctx.saved_tensors
+        relu, thr, scale, seed, ydt = ctx.attrs
+        lib = _lib.load()
+        n, c = x.shape
+        gy = _bf16_rows_aligned(gy.to(ydt).contiguous())   # (dy has y's type; .to is a no-op when autograd hands that over)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+        check(lib.mccnn_bn_act_bwd_rows(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(ydt == torch.bfloat16), n, c,
+                                        ptr(gamma), ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx), ptr(dgb[0]),
+                                        ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_grad")
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None, None, None)
+
+
+def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
+                    epsilon=1e-3, outDtype=None):
+    """y = drop(act(bn(x))) over an [n, c] float32 contiguous tensor in one library op; differentiable (once) with respect
+    to x, gamma and beta. training: batch statistics (biased variance), movingMean / movingVar updated in place as
+    moving * momentum + stat * (1 - momentum), dropout with keep probability keepProb (None: none) from the counter-based
+    mask of `seed`. Eval: the moving statistics, no dropout, and no gradients -- an input that requires one raises.
+    x may also be bfloat16 rows (an even c), and outDtype names y's type (None: x's; torch.float32; torch.bfloat16), so the
+    op is also the cast between layers that keep different row types: bf16 is widened exactly, the statistics and all
+    arithmetic are float32 as for float32 rows, a bf16 y is rounded to nearest even at the store. x.grad has x's type,
+    gamma.grad and beta.grad are float32."""
+    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    if training:
+        return _BnReluDropout.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
+                                    float(epsilon), outDtype)
+    _req(not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
+         "bn_relu_dropout: the eval form has no gradients")
+    lib = _lib.load()
+    y = torch.empty(x.shape, dtype=outDtype or x.dtype, device=x.device)
+    _bn_act_fwd(lib, _bf16_rows_aligned(x.detach()), gamma, beta, movingMean, movingVar, float(momentum), float(epsilon), 0,
+                int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
+    return y
+
+
+# ---------------------------------------------------------------------------------------------
+# ... with batch statistics across the ranks of a process group (include/mccnn.h "... WITH BATCH STATISTICS ACROSS RANKS"):
+# the library op cut in two where the collective goes -- stats, gather, apply forward; sums, gather, dx backward. The
+# collective is torch.distributed's (mccnn_amd.dist.gather_rows), so the autograd node is Python's, over four stage calls:
+# the ctypes ones below, or the extension's (native.bn_relu_drop_sync) -- the same library calls, so the same bytes.
+def _bn_sync_stats(x, rank, world, parts):
+    lib = _lib.load()
+    n, c = x.shape
+    ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+    check(lib.mccnn_bn_sync_stats(ptr(x), int(x.dtype == torch.bfloat16), n, c, rank, world, ptr(parts), ptr(ws), ws.numel(),
+                                  stream_handle()), "bn_relu_dropout_sync")
+
+
+def _bn_sync_apply(x, rank, world, parts, gamma, beta, movingMean, movingVar, momentum, epsilon, relu, thr, scale, seed, y, saved,
+                   meta):
+    lib = _lib.load()
+    check(lib.mccnn_bn_sync_apply(ptr(x), int(x.dtype == torch.bfloat16), x.shape[0], x.shape[1], rank, world, ptr(parts), ptr(gamma),
+                                  ptr(beta), ptr(movingMean), ptr(movingVar), momentum, epsilon, int(relu), thr, scale, seed, ptr(y),
+                                  int(y.dtype == torch.bfloat16), ptr(saved), ptr(meta), stream_handle()), "bn_relu_dropout_sync")
+
+
+def _bn_sync_bwd_sums(x, gy, rank, world, gamma, beta, saved, meta, relu, thr, scale, seed, partsB, dgb):
+    lib = _lib.load()
+    n, c = x.shape
+    ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), x.device)
+    check(lib.mccnn_bn_sync_bwd_sums(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(gy.dtype == torch.bfloat16), n, c, rank,
+                                     world, ptr(gamma), ptr(beta), ptr(saved), ptr(meta), int(relu), thr, scale, seed, ptr(partsB),
+                                     ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()), "bn_relu_dropout_sync_grad")
+
+
+def _bn_sync_bwd_dx(x, gy, rank, world, gamma, beta, partsB, saved, meta, relu, thr, scale, seed, dx, dgb):
+    lib = _lib.load()
+    check(lib.mccnn_bn_sync_bwd_dx(ptr(x), int(x.dtype == torch.bfloat16), ptr(gy), int(gy.dtype == torch.bfloat16), x.shape[0],
+                                   x.shape[1], rank, world, ptr(gamma), ptr(beta), ptr(partsB), ptr(saved), ptr(meta), int(relu), thr,
+                                   scale, seed, ptr(dx), ptr(dgb[0]), stream_handle()), "bn_relu_dropout_sync_grad")
+
+
+_BN_SYNC_STAGES = (_bn_sync_stats, _bn_sync_apply, _bn_sync_bwd_sums, _bn_sync_bwd_dx)
+
+
+def _bn_sync_place(group):
+    """(rank, world) of this process in `group` (None: the default group); (0, 1) without a process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
+
+
+class _BnReluDropoutSync(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype, group, stages):
+        from .dist import gather_rows
+        rank, world = _bn_sync_place(group)
+        n, c = x.shape
+        xd, gd, bd = _bf16_rows_aligned(x.detach()), gamma.detach(), beta.detach()
+        parts = torch.empty((world, 3 * c), dtype=torch.float32, device=x.device)
+        stages[0](xd, rank, world, parts)
+        parts = gather_rows(parts, group)
+        y = torch.empty((n, c), dtype=outDtype or x.dtype, device=x.device)
+        saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        meta = torch.empty((2,), dtype=torch.int32, device=x.device)
+        stages[1](xd, rank, world, parts, gd, bd, movingMean, movingVar, momentum, epsilon, relu, thr, scale, seed, y, saved, meta)
+        ctx.save_for_backward(xd, gd, bd, saved, meta)
+        ctx.attrs = (relu, thr, scale, seed, y.dtype, group, stages, rank, world)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from .dist import gather_rows
+        x, gamma, beta, saved, meta = ctx.saved_tensors
+        relu, thr, scale, seed, ydt, group, stages, rank, world = ctx.attrs
+        c = x.shape[1]
+        gy = _bf16_rows_aligned(gy.to(ydt).contiguous())
+        partsB = torch.empty((world, 3 * c), dtype=torch.float32, device=x.device)
+        dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+        stages[2](x, gy, rank, world, gamma, beta, saved, meta, relu, thr, scale, seed, partsB, dgb)
+        partsB = gather_rows(partsB, group)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        stages[3](x, gy, rank, world, gamma, beta, partsB, saved, meta, relu, thr, scale, seed, dx, dgb)
+        return (dx, dgb[0] if ctx.needs_input_grad[1] else None, dgb[1] if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None, None, None, None, None, None, None)
+
+
+def _bn_relu_dropout_sync(stages, x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype, group):
+    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    if group is not None:
+        import torch.distributed as dist
+        _req(dist.is_available() and isinstance(group, dist.ProcessGroup), "bn_relu_dropout_sync: group must be a process group (or None)")
+    _req(x.shape[0] <= (1 << 24), "bn_relu_dropout: x too large")   # counts travel as float32
+    return _BnReluDropoutSync.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
+                                    float(epsilon), outDtype, group, stages)
+
+
+def bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb=None, seed=0, momentum=0.99, epsilon=1e-3,
+                         outDtype=None, group=None):
+    """The training form of bn_relu_dropout (its definition, types, checks and errors) with the batch statistics over the
+    rows of ALL ranks of `group` (None: the default process group; without one, this process alone): n, mean and var are
+    those of the ranks' rows concatenated in rank order, and the dropout mask of a row is the mask of its global index, so
+    with the same seed on every rank the shards reproduce the unsharded batch. Every rank of the group calls it, with at
+    least one row; row counts may differ. Two collectives of 3c floats per rank, one forward and one backward
+    (mccnn_amd.dist.gather_rows). movingMean / movingVar get the same bytes on every rank. x.grad is the gradient of the
+    SUM of the ranks' losses; gamma.grad and beta.grad are this rank's share, to be added up by the caller's gradient
+    all-reduce as for every other parameter. Differentiable once."""
+    return _bn_relu_dropout_sync(_BN_SYNC_STAGES, x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon,
+                                 outDtype, group)
+
+
+# ---------------------------------------------------------------------------------------------
+# A linear layer and the dense glue behind it as one op (csrc/linear_bn.hip, include/mccnn.h "A LINEAR LAYER AND THE DENSE
+# GLUE BEHIND IT AS ONE OP"): z = x @ w + b, y = drop(act(bn(z))).
+def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
+    """Checks of linear_bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale)."""
+    _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "linear_bn_relu_dropout: x must be a float32 tensor")
+    _req(isinstance(w, torch.Tensor) and w.dtype == torch.float32, "linear_bn_relu_dropout: w must be a float32 tensor")
+    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
+         "linear_bn_relu_dropout expects x (n, cin) and w (cin, cout), n, cin, cout >= 1")
+    _req(x.is_contiguous() and w.is_contiguous(), "linear_bn_relu_dropout: x and w must be contiguous")
+    _req(w.device == x.device, "linear_bn_relu_dropout: w is on another device than x")
+    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
+         and b.shape[0] == w.shape[1] and b.device == x.device, "linear_bn_relu_dropout: b must be a float32 (cout,) tensor on x's device")
+    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "linear_bn_relu_dropout: x too large")
+    thr, scale = _drop_args("linear_bn_relu_dropout", keepProb, seed, outDtype)
+    _req(outDtype != torch.bfloat16 or w.shape[1] % 2 == 0, "linear_bn_relu_dropout: bfloat16 rows need an even number of columns")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
+             and t.shape[0] == w.shape[1] and t.device == x.device,
+             "linear_bn_relu_dropout: %s must be a contiguous float32 (cout,) tensor on x's device" % name)
+    _req(x.is_cuda, "linear_bn_relu_dropout: x must be a CUDA tensor")
+    _req(thr >= 1, "linear_bn_relu_dropout: keepProb keeps nothing")
+    return thr, scale
+
+
+class _LinearBnReluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype=None):
+        lib = _lib.load()
+        n, cin = x.shape
+        cout = w.shape[1]
+        xd, wd, bd, gd, bed = x.detach(), w.detach(), b.detach(), gamma.detach(), beta.detach()
+        z = torch.empty((n, cout), dtype=torch.float32, device=x.device)
+        y = torch.empty((n, cout), dtype=outDtype or torch.float32, device=x.device)
+        saved = torch.empty((3, cout), dtype=torch.float32, device=x.device)
+        ws = _ws(lib.mccnn_linear_bn_act_workspace_bytes(n, cin, cout), x.device)
+        check(lib.mccnn_linear_bn_act_fwd(ptr(xd), ptr(wd), ptr(bd), n, cin, cout, ptr(gd), ptr(bed), ptr(movingMean), ptr(movingVar),
+                                          momentum, epsilon, 1, int(relu), thr, scale, seed, ptr(z), ptr(y),
+                                          int(y.dtype == torch.bfloat16), ptr(saved), ptr(ws), ws.numel(), stream_handle()),
+              "linear_bn_relu_dropout")
+        ctx.save_for_backward(xd, wd, gd, bed, z, saved)
+        ctx.attrs = (int(relu), thr, scale, seed, y.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, gamma, beta, z, saved = ctx.saved_tensors
+        relu, thr, scale, seed, ydt = ctx.attrs
+        lib = _lib.load()
+        n, cin = x.shape
+        cout = w.shape[1]
+        gy = gy.to(ydt).contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w)
+        dv = torch.empty((3, cout), dtype=torch.float32, device=x.device)   # db, dgamma, dbeta
+        ws = _ws(lib.mccnn_linear_bn_act_workspace_bytes(n, cin, cout), x.device)
+        check(lib.mccnn_linear_bn_act_bwd(ptr(x), ptr(w), ptr(z), ptr(gy), int(ydt == torch.bfloat16), n, cin, cout, ptr(gamma),
+                                          ptr(beta), ptr(saved), relu, thr, scale, seed, ptr(dx), ptr(dw), ptr(dv[0]), ptr(dv[1]),
+                                          ptr(dv[2]), ptr(ws), ws.numel(), stream_handle()), "linear_bn_relu_dropout_grad")
+        need = ctx.needs_input_grad
+        return (dx, dw if need[1] else None, dv[0] if need[2] else None, dv[1] if need[3] else None,
+                dv[2] if need[4] else None) + (None,) * 9
+
+
+def linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0,
+                           momentum=0.99, epsilon=1e-3, outDtype=None):
+    """y = drop(act(bn(x @ w + b))) in one library op: x (n, cin) and w (cin, cout) float32 contiguous, everything per
+    column float32 (cout,). bn, act and drop are bn_relu_dropout's, applied to z = x @ w + b (batch statistics and the
+    moving ones updated in place when training; the counter-based mask of `seed`); differentiable (once) with respect to
+    x, w, b, gamma and beta. outDtype: y's type, None / torch.float32 or torch.bfloat16 (an even cout). Eval: the moving
+    statistics, no dropout, and no gradients -- an input that requires one raises."""
+    thr, scale = _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    if training:
+        return _LinearBnReluDropout.apply(x, w, b, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed,
+                                          float(momentum), float(epsilon), outDtype)
+    _req(not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
+         "linear_bn_relu_dropout: the eval form has no gradients")
+    lib = _lib.load()
+    n, cin = x.shape
+    cout = w.shape[1]
+    y = torch.empty((n, cout), dtype=outDtype or torch.float32, device=x.device)
+    check(lib.mccnn_linear_bn_act_fwd(ptr(x.detach()), ptr(w.detach()), ptr(b.detach()), n, cin, cout, ptr(gamma.detach()),
+                                      ptr(beta.detach()), ptr(movingMean), ptr(movingVar), float(momentum), float(epsilon), 0,
+                                      int(bool(relu)), BN_DROP_ALL, 1.0, seed, None, ptr(y), int(y.dtype == torch.bfloat16), None,
+                                      None, 0, stream_handle()), "linear_bn_relu_dropout")
+    return y
+
+
+# At the end on purpose: MCConvModule imports this module back at ITS end, and with both imports last each module finds the
+# other one's names defined whichever of the two is imported first.
+from .MCConvModule import _bf16_rows_aligned, _req, _ws  # noqa: E402

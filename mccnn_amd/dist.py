@@ -10,7 +10,7 @@ exchanges are
     (MIN, MAX) their 2x3 box floats before sorting.
   * with VariableStore(fused=True, fusedSync=True), two gathers of 3c floats per rank and batch-norm block -- the
     statistics of the forward and the sums of the backward (gather_rows, between the stages of
-    MCConvModule.bn_relu_dropout_sync); without it the torch code's differentiable all-reduce of the same size.
+    dense_glue.bn_relu_dropout_sync); without it the torch code's differentiable all-reduce of the same size.
 One process per GPU, torch.distributed backend "nccl" (= RCCL on ROCm); "gloo" on CPU tensors in tests.
 """
 import torch
@@ -62,7 +62,7 @@ def _backend_of(t, group=None):
 
 def gather_rows(buf, group=None, route=None):
     """buf [world, k]: every rank has filled ITS row and written +0.0 into the others (the stages of
-    MCConvModule.bn_relu_dropout_sync do); on return every rank holds all rows, in place. Two exact routes: an all-gather
+    dense_glue.bn_relu_dropout_sync do); on return every rank holds all rows, in place. Two exact routes: an all-gather
     of the rows ("gather": all_gather_into_tensor, each rank's input its own row of the result), or an all-reduce(SUM) of
     the zero-padded buffer ("reduce": adding +0.0 changes no bit but the sign of a zero). route None: "gather" where the
     backend is nccl (= RCCL), "reduce" otherwise (gloo on device tensors). With one rank, or without a process group,

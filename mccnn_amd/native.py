@@ -627,11 +627,11 @@ def conv(geo, feats, w1, b1, w2, b2, w3, b3, numOutFeatures, combin, avg, determ
 
 def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
                  epsilon=1e-3, outDtype=None):
-    """The dense glue as one op, y = drop(act(bn(x))) (MCConvModule.bn_relu_dropout: its definition, checks and errors):
+    """The dense glue as one op, y = drop(act(bn(x))) (dense_glue.bn_relu_dropout: its definition, checks and errors):
     one Python -> C++ call forward and an autograd node on the C++ side when the extension is loaded, the ctypes op
     otherwise -- the same library calls either way, so the same bytes. x: float32 or bfloat16 rows; outDtype: y's type
     (None: x's)."""
-    from . import MCConvModule as M
+    from . import dense_glue as M
     if _EXT is None:
         return M.bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum, epsilon,
                                  outDtype)
@@ -645,10 +645,10 @@ def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, kee
 def bn_relu_drop_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb=None, seed=0, momentum=0.99, epsilon=1e-3,
                       outDtype=None, group=None):
     """The training form of the dense glue with batch statistics over the rows of all ranks of `group`
-    (MCConvModule.bn_relu_dropout_sync: its definition, checks and errors). The autograd node is that module's either way
+    (dense_glue.bn_relu_dropout_sync: its definition, checks and errors). The autograd node is that module's either way
     (the collectives between the stages are torch.distributed's); with the extension loaded its four stages are the
     extension's calls, with the ctypes ones otherwise -- the same library calls, so the same bytes."""
-    from . import MCConvModule as M
+    from . import dense_glue as M
     if _EXT is None:
         return M.bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype,
                                       group)
@@ -659,10 +659,10 @@ def bn_relu_drop_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb
 def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
                         epsilon=1e-3, outDtype=None):
     """A linear layer and the dense glue behind it as one op, y = drop(act(bn(x @ w + b)))
-    (MCConvModule.linear_bn_relu_dropout: its definition, checks and errors): one Python -> C++ call forward and an
+    (dense_glue.linear_bn_relu_dropout: its definition, checks and errors): one Python -> C++ call forward and an
     autograd node on the C++ side when the extension is loaded, the ctypes op otherwise -- the same library calls either
     way, so the same bytes."""
-    from . import MCConvModule as M
+    from . import dense_glue as M
     if _EXT is None:
         return M.linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum,
                                         epsilon, outDtype)

@@ -307,6 +307,27 @@ def test_plain_entries_are_untouched_and_one_rank_is_the_plain_forward(mc, shape
     assert [_bits(back[0][0]), _bits(back[1][0]), _bits(back[2][0])] == before[4:]
 
 
+@pytest.mark.parametrize("combo", [(True, True), (False, True), (True, False)], ids=["bf16-bf16", "f32-bf16", "bf16-f32"])
+@pytest.mark.parametrize("shape", [(63, 6), (257, 8), (300, 72)], ids=lambda s: "%dx%d" % s)
+def test_one_rank_on_typed_rows_is_the_typed_plain_op(mc, shape, combo):
+    """The four stages with world == 1 give the bytes of mccnn_bn_act_fwd_rows / _bwd_rows whatever the types of x and y:
+    the same merges in the same order, and the one rank's row added to nothing. Shapes: one launch on the pair form / two
+    launches on the widest form / three slabs and more than one column tile."""
+    import test_gpu_bn_act_rows as plain
+    xb, yb = combo
+    d = rows.case(shape[0], shape[1], xb, yb)
+    bs = [(0, shape[0])]
+    pf = plain._raw_fwd(d, xb, yb, True, 0.7)
+    one = _sync_forward(d, shape, True, 0.7, xb=xb, yb=yb, bs=bs)
+    assert [_bits(one[k][0]) for k in ("y", "saved", "mm", "mv")] == [_bits(pf[k]) for k in ("y", "saved", "mm", "mv")]
+    assert one["meta"][0].cpu().tolist() == [0, shape[0]]
+    for want_dx in (True, False):
+        pdx, pdg, pdb, _ = plain._raw_bwd(d, xb, yb, pf["saved"], True, 0.7, want_dx=want_dx)
+        dxs, dgs, dbs, _, _ = _sync_backward(d, shape, one, True, 0.7, xb=xb, yb=yb, want_dx=want_dx, bs=bs)
+        assert (_bits(dgs[0]), _bits(dbs[0])) == (_bits(pdg), _bits(pdb)), want_dx
+        assert (dxs[0] is None and pdx is None) if not want_dx else _bits(dxs[0]) == _bits(pdx)
+
+
 def test_errors_come_before_any_launch(mc):
     import torch
     from mccnn_amd import _lib

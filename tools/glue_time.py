@@ -1,4 +1,4 @@
-"""The dense glue as one op (VariableStore(fused=True), MCConvModule.bn_relu_dropout) against the torch path it replaces,
+"""The dense glue as one op (VariableStore(fused=True), dense_glue.bn_relu_dropout) against the torch path it replaces,
 measured in ONE process; the torch path is the yardstick: python tools/glue_time.py [--part a|b|both] (on the GPU box).
 
 (a) The op, forward + backward, per shape: the glue shapes an MCClassS 32 x 1024 step sees (taken from a forward pass) plus

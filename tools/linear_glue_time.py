@@ -1,4 +1,4 @@
-"""A linear layer + the dense glue behind it as one op (VariableStore(fusedLinear=True), MCConvModule.linear_bn_relu_dropout)
+"""A linear layer + the dense glue behind it as one op (VariableStore(fusedLinear=True), dense_glue.linear_bn_relu_dropout)
 against the path it replaces -- conv_1x1 on rocBLAS + the fused glue -- measured in ONE process; the switch-off path is the
 yardstick: python tools/linear_glue_time.py [--part a|b|c|all] (on the GPU box).
 
