@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import make_cloud, make_room, make_mlp, conv_nb, run_chain, assert_float_close
+from tests.poisson_cases import census, histogram
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +70,8 @@ def test_grid_neighbors_pdf_poisson(mc, oracle, case):
                   pdf_kwargs=dict(mode=0))
     o = run_chain(oracle, _ident, _ident, pts, bids, feats, B, radius, scaleInv, poisson_radius=prad)
     compare_chain(g, o, pdf_rtol=2e-6)  # mode 0 replays the reference arithmetic
+    if case[0] == "single_cell":  # nc = 1, 300 points per cell: the register path for cells of more than 64 points
+        assert histogram(census(o["poissonCells"]))["regs<8>"] == B
     # the single-precision KDEs (mode 1: pair sums as Gram-matrix tiles on the matrix cores, the default; mode 2: the
     # subtract-first VALU loop) stay inside the feature-path tolerance -- per VALUE, not only against the largest one
     h = g["_handles"]
@@ -110,6 +113,7 @@ def test_dense_cells(mc, oracle):
     o = run_chain(oracle, _ident, _ident, pts, bids, feats, 1, 0.1, True, poisson_radius=0.1)
     klen = np.diff(np.append(o["startIndexs"][:, 0], len(o["packedNeighs"])))
     assert klen.max() > 800
+    assert histogram(census(o["poissonCells"]))["stream"] > 0   # windows of more than 768 points (tests/poisson_cases.py)
     compare_chain(g, o, pdf_rtol=2e-6)
     # default KDE: rows of 65..192 points run several tiles per side, longer ones take the scalar loop
     assert ((klen > 64) & (klen <= 192)).any() and (klen > 192).any()
