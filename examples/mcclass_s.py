@@ -28,7 +28,7 @@ class MCClassS(torch.nn.Module):
     the reference's name, so `parameters()` / `state_dict()` / optimisers / DDP see the whole network."""
 
     def __init__(self, numInputFeatures, batchSize, k, numOutCat, device, ops=None, fused=False, rows=None, fusedLinear=False,
-                 fusedSync=False):
+                 fusedSync=False, fusedLoss=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k, numOutCat)
         # rows (extension): torch.bfloat16 keeps the input rows of the depth-wise Conv_2 and Conv_3 in bf16 (they gather
@@ -41,7 +41,9 @@ class MCClassS(torch.nn.Module):
         self.fusedLinear = bool(fusedLinear)
         # fusedSync (extension): with fused, the glue stays a library op when its statistics run across ranks
         # (VariableStore.fusedSync_)
-        self.store = VariableStore(device, fused=fused, fusedLinear=fusedLinear, fusedSync=fusedSync)
+        # fusedLoss (extension): with labels handed to forward(), the last linear of the MLP and the softmax cross-entropy
+        # behind it as one library op (VariableStore.fusedLoss_)
+        self.store = VariableStore(device, fused=fused, fusedLinear=fusedLinear, fusedSync=fusedSync, fusedLoss=fusedLoss)
         self.ops = ops  # None = the HIP op surface; the parity tests pass the CPU checker's
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
@@ -60,8 +62,10 @@ class MCClassS(torch.nn.Module):
                               prefetched=prefetched)
 
     def forward(self, points, batchIds, features, isTraining, keepProbConv=1.0, keepProbFull=0.5, useConvDropOut=False,
-                 useDropOutFull=True, prefetched=None, hierarchy=None, nextHierarchy=None):
-        """hierarchy (extension): this batch's hierarchy, built a step ago with self.hierarchy(); nextHierarchy: the NEXT
+                 useDropOutFull=True, prefetched=None, hierarchy=None, nextHierarchy=None, labels=None):
+        """labels (extension): one class per cloud -- the result is then the LossHead of MLP_2_hidden (loss, predictions, count of
+        correct rows, denominator) over the last linear instead of the logits; None: the logits, every call as before.
+        hierarchy (extension): this batch's hierarchy, built a step ago with self.hierarchy(); nextHierarchy: the NEXT
         batch's -- its grids, neighbour lists, PDFs and row plans are then started under this batch's layers
         (ConvolutionBuilder.prefetch_step) and the next forward pass finds them built."""
         numInputFeatures, batchSize, k, numOutCat = self.args
@@ -101,7 +105,7 @@ class MCClassS(torch.nn.Module):
         finalInput = batch_norm_RELU_drop_out("BNRELUDROP_final", convFeatures3, isTraining, useConvDropOut, keepProbConv, st,
                                               **toDense)
         finalLogits = MLP_2_hidden(finalInput, k * 4, k * 2, k, numOutCat, "Final_Logits", keepProbFull, isTraining,
-                                   useDropOutFull, store=st)
+                                   useDropOutFull, store=st, labels=labels)
         self.lastHierarchy = mPointHierarchy
         return finalLogits
 
@@ -180,6 +184,9 @@ def main():
     ap.add_argument("--fused-linear", action="store_true",
                     help="Reduce_k + Reduce_k_Out_BN and the hidden layers of the MLP as one library op each "
                          "(VariableStore(fusedLinear=True))")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="the last linear of the MLP + softmax cross-entropy + arg-max as one library op "
+                         "(VariableStore(fusedLoss=True)); the loop then takes the loss and the accuracy from its LossHead")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()
@@ -190,7 +197,7 @@ def main():
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
     net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None,
-                   fusedLinear=args.fused_linear)
+                   fusedLinear=args.fused_linear, fusedLoss=args.fused_loss)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \
         (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
     P, Bi, F, y = make_batch()
@@ -207,16 +214,16 @@ def main():
         ph_nxt = net.hierarchy(nxt[0], nxt[1], nxt[2], prefetched=fut_nxt)
         after = make_batch()
         fut_after = net.prefetch_hierarchy(after[0], after[1])
-        logits = net(P, Bi, F, True, hierarchy=ph_cur, nextHierarchy=ph_nxt)
+        out = net(P, Bi, F, True, hierarchy=ph_cur, nextHierarchy=ph_nxt, labels=y if args.fused_loss else None)
         cur, nxt, ph_cur, fut_nxt = nxt, after, ph_nxt, fut_after
-        loss = torch.nn.functional.cross_entropy(logits, y)
+        loss = out.loss if args.fused_loss else torch.nn.functional.cross_entropy(out, y)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
         if step % 5 == 0 or step == args.steps - 1:
+            acc = float(out.correct) / float(out.denom) if args.fused_loss else float((out.argmax(1) == y).float().mean())
             print("step %3d  loss %.4f  acc %.2f  level sizes %s" % (
-                step, float(loss), float((logits.argmax(1) == y).float().mean()),
-                [int(p.shape[0]) for p in net.lastHierarchy.points_]))
+                step, float(loss), acc, [int(p.shape[0]) for p in net.lastHierarchy.points_]))
 
 
 if __name__ == "__main__":

@@ -975,6 +975,37 @@ int mccnn_linear_bn_act_bwd(const float* x, const float* w, const float* z, cons
                             float* dx /* NULL: not wanted */, float* dw, float* db, float* dgamma, float* dbeta,
                             void* ws, size_t ws_bytes, mccnn_stream_t stream);
 
+/* THE LAST LINEAR LAYER AND THE SOFTMAX CROSS-ENTROPY BEHIND IT AS ONE OP (extension, ABI 23; linear_xent.hip):
+ *   z = x w + b,  lse_i = m_i + log(sum_j exp(z_ij - m_i)) with m_i = max_j z_ij,  l_i = lse_i - z[i, labels_i],
+ *   loss = (sum over live rows of rw_i l_i) / D,  D = max(number of live rows, 1),
+ *   pred_i = the lowest j attaining max_j z_ij (written for every row),  correct = the live rows with pred_i == labels_i.
+ * x [n, cin], w [cin, c], b [c] float32 row-major contiguous, labels [n] int32, row_weights [n] float32 (NULL: all 1); n, cin,
+ * c >= 1 with no divisibility rule. A row is LIVE iff 0 <= labels_i < c and its weight is != 0: a label outside [0, c)
+ * makes the row a weight-0 row, never an error and never an out-of-range read. No live row: loss = +0.0f and all-zero
+ * gradients. z is the z of A LINEAR LAYER AND THE DENSE GLUE above, byte for byte (one fmaf chain over k per element, then
+ * + b; row i does not depend on the other rows of the call); the maximum is subtracted before every exp.
+ *   forward:  writes loss [1], lse [n], meta = {D, correct}, pred [n] unless NULL and the logits z [n, c] unless NULL (the
+ *             other outputs have the same bytes either way). One launch up to 256 rows, two above.
+ *   backward: with g = loss_grad[0], a DEVICE word read by the kernel,
+ *               dz_ij = g rw_i / D (exp(z_ij - lse_i) - [j == labels_i]) on live rows, 0 elsewhere
+ *             recomputed from x, w, b, lse and meta (into ws), dx = dz w^T (dx == NULL: not wanted, the same bytes for
+ *             the rest), dw = x^T dz, db = sum_i dz[i, :]. At most four launches; three up to 512 rows or without dx, two
+ *             with both.
+ * No atomics, no memset, fixed merge orders: the same inputs give the same bytes. ws of
+ * mccnn_linear_xent_workspace_bytes(n, cin, c) bytes serves both directions (the forward uses the front of it, none up to
+ * 256 rows: ws may then be NULL there); the query answers 0 for sizes the op refuses. n, cin or c < 1, a NULL required
+ * pointer: MCCNN_E_BADARG; more than 65535 tiles of 64 rows, or cin * c past 2^31: MCCNN_E_TOOLARGE; a missing or short
+ * workspace: MCCNN_E_WORKSPACE; all before anything is launched. */
+size_t mccnn_linear_xent_workspace_bytes(int n, int cin, int c);
+int mccnn_linear_xent_fwd(const float* x, const float* w, const float* b, int n, int cin, int c, const int* labels,
+                          const float* row_weights /* NULL: all 1 */, float* loss /* [1] */, float* lse /* [n] */,
+                          int* meta /* [2]: D, correct */, int* pred /* [n], NULL: not wanted */,
+                          float* logits /* [n,c], NULL: not stored */, void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_linear_xent_bwd(const float* x, const float* w, const float* b, int n, int cin, int c, const int* labels,
+                          const float* row_weights, const float* lse, const int* meta, const float* loss_grad /* [1], device */,
+                          float* dx /* NULL: not wanted */, float* dw, float* db, void* ws, size_t ws_bytes,
+                          mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

@@ -25,7 +25,15 @@ batch_norm_RELU_drop_out (conv_1x1_batch_norm_RELU_drop_out) and the hidden laye
 matmul and the block run as before. Names, shapes, initialisers, creation order and state_dict are the same either way,
 and a call that drops takes its seed from dropSeed_ / dropCalls_ as the fused glue does: with `fused` on as well, the
 masks of a network do not depend on this switch.
+
+VariableStore(fusedLoss=True) (extension, opt-in): the LAST linear of a network and the sparse softmax cross-entropy behind
+it -- conv_1x1_softmax_cross_entropy, and the MLPs called with labels -- run as ONE library op
+(dense_glue.linear_softmax_xent, csrc/linear_xent.hip) where its conditions hold (_fused_loss): x -> LossHead(loss, pred,
+correct, denom, logits), the gradients of x, the weights and the biases from one autograd node. Everywhere else, and always
+with the switch off, torch code computes the same definition (_loss_head). Names, shapes, initialisers, creation order and
+state_dict are the same either way; without labels every helper returns the logits as before.
 """
+import collections
 import math
 
 import torch
@@ -38,13 +46,14 @@ class VariableStore(torch.nn.Module):
     names (`Reduce_1_weights`, `Final_Logits_BN_h1/gamma`, ...). Variables are created on first use (tf.get_variable),
     so load_state_dict() also accepts names that do not exist yet."""
 
-    def __init__(self, device=None, fused=False, fusedLinear=False, fusedSync=False):
+    def __init__(self, device=None, fused=False, fusedLinear=False, fusedSync=False, fusedLoss=False):
         super().__init__()
         self.device = device
         self.collections_ = {}
         self.fused_ = bool(fused)   # the dense glue as one library op where it applies (may be reassigned at any time)
         self.fusedLinear_ = bool(fusedLinear)   # linear layer + glue as one library op where it applies (reassignable too)
         self.fusedSync_ = bool(fusedSync)   # with fused_: the glue stays a library op when statistics cross ranks (reassignable)
+        self.fusedLoss_ = bool(fusedLoss)   # last linear + softmax cross-entropy as one library op where it applies (reassignable)
         self.syncGroup_ = None      # the process group of those statistics (None: the default group)
         self.dropSeed_ = 0          # a fused call that drops uses the seed (dropSeed_ + dropCalls_) mod 2^32 ...
         self.dropCalls_ = 0         # ... and increments this counter
@@ -189,17 +198,19 @@ def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsil
 _FUSED_OP = False          # native.bn_relu_drop once the library has loaded; None when it does not
 _FUSED_SYNC_OP = None      # native.bn_relu_drop_sync, likewise
 _FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
+_FUSED_LOSS_OP = None      # native.linear_softmax_xent, likewise
 
 
 def _load_fused_ops():
-    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP
+    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
             _lib.load()
             _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP = native.bn_relu_drop, native.bn_relu_drop_sync, native.linear_bn_relu_drop
+            _FUSED_LOSS_OP = native.linear_softmax_xent
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = None
+            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = None
 
 
 def _fused_op(synced=False):
@@ -210,6 +221,11 @@ def _fused_op(synced=False):
 def _fused_linear_op():
     _load_fused_ops()
     return _FUSED_LINEAR_OP
+
+
+def _fused_loss_op():
+    _load_fused_ops()
+    return _FUSED_LOSS_OP
 
 
 def _on_device_f32(dev, tensors):
@@ -336,9 +352,72 @@ def _dropout(x, keepProb, training=True):
     return torch.nn.functional.dropout(x, p=1.0 - float(keepProb), training=training)
 
 
+#: What a helper called with labels returns. loss: 0-dim float32, differentiable with respect to the helper's input and the
+#: variables of its last linear; pred: int32 [n], the lowest arg-max of every row; correct, denom: 0-dim int32 tensors on
+#: the device (no read-back) -- the live rows whose prediction is their label, and D = max(number of live rows, 1), so
+#: correct / denom is the accuracy over the live rows; logits: [n, C] without gradient history when asked for, else None.
+LossHead = collections.namedtuple("LossHead", "loss pred correct denom logits")
+
+
+def _fused_loss(st, inputs, w, b, labels, labelWeights, wantLogits):
+    """The LossHead of _loss_head as one library op, or None where that form does not apply (the caller then runs the torch
+    code): the store's switch is off, inputs is not a contiguous float32 [n, cin] tensor on a HIP device (w and b
+    likewise), labels / labelWeights are not contiguous int32 or int64 / float32 tensors of n elements on that device, or the
+    library does not load. The op is differentiable once: a caller that needs a double backward switches fusedLoss_ off."""
+    if not getattr(st, "fusedLoss_", False):
+        return None
+    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
+            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+        return None
+    if not (w.dim() == 2 and w.shape[0] == inputs.shape[1] and w.shape[1] >= 1 and b.dim() == 1 and b.shape[0] == w.shape[1]):
+        return None
+    n = inputs.shape[0]
+    if not (torch.is_tensor(labels) and labels.dtype in (torch.int32, torch.int64) and tuple(labels.shape) in ((n,), (n, 1))
+            and labels.device == inputs.device and labels.is_contiguous()):
+        return None
+    if labelWeights is not None and not (torch.is_tensor(labelWeights) and labelWeights.dtype == torch.float32
+                                         and tuple(labelWeights.shape) in ((n,), (n, 1)) and labelWeights.device == inputs.device
+                                         and labelWeights.is_contiguous() and not labelWeights.requires_grad):
+        return None
+    op = _fused_loss_op()
+    if op is None or not _on_device_f32(inputs.device, (w, b)):
+        return None
+    loss, pred, meta, logits = op(inputs, w, b, labels, labelWeights, wantLogits)
+    return LossHead(loss, pred, meta[1], meta[0], logits)
+
+
+def _loss_head(st, inputs, w, b, labels, labelWeights=None, wantLogits=False):
+    """The sparse softmax cross-entropy over z = inputs @ w + b -> LossHead. A row is live iff 0 <= label < C and its weight
+    (labelWeights, None: all 1) is not 0; loss = sum over live rows of weight * (logsumexp(z_i) - z[i, label_i]) / D with
+    D = max(number of live rows, 1) -- the mean of the reference's ModelNet.py:35-36 without weights, the
+    SUM_BY_NONZERO_WEIGHTS of its ScanNet.py:35-37 with them; pred = the lowest arg-max of a row, correct = the live rows
+    with pred == label. One library op where the store's fusedLoss_ says so and it applies (_fused_loss), this torch code
+    otherwise."""
+    if getattr(st, "fusedLoss_", False):
+        head = _fused_loss(st, inputs, w, b, labels, labelWeights, wantLogits)
+        if head is not None:
+            return head
+    z = inputs @ w + b
+    C = z.shape[1]
+    y = labels.reshape(-1).to(torch.int64)
+    live = (y >= 0) & (y < C)
+    logp = torch.log_softmax(z, 1)
+    rows = -logp.gather(1, y.clamp(0, C - 1).unsqueeze(1)).squeeze(1)
+    if labelWeights is not None:
+        rw = labelWeights.reshape(-1).to(z.dtype)
+        live = live & (rw != 0)
+        rows = rows * rw
+    denom = live.sum().clamp_min(1)
+    loss = torch.where(live, rows, torch.zeros_like(rows)).sum() / denom
+    pred = z.detach().argmax(1)
+    correct = (live & (pred == y)).sum()
+    return LossHead(loss, pred.to(torch.int32), correct.to(torch.int32), denom.to(torch.int32), z.detach() if wantLogits else None)
+
+
 def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOutFeatures, layerName, keepProb,
-                 isTraining, useDropOut=False, useInitBN=True, store=None):
-    """utils/MCNetworkUtils.py:20-69."""
+                 isTraining, useDropOut=False, useInitBN=True, store=None, labels=None, labelWeights=None, wantLogits=False):
+    """utils/MCNetworkUtils.py:20-69. labels (extension; None: the logits, as ever): the result is the LossHead of the sparse
+    softmax cross-entropy over the last linear (_loss_head; labelWeights: row weights, wantLogits: keep the logits in it)."""
     st = store or _DEFAULT_STORE
     dev = features.device
     if useInitBN:
@@ -358,12 +437,14 @@ def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOu
                         _fan_avg_uniform(hidden2_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases3', (numOutFeatures,), _zeros, dev)
+    if labels is not None:
+        return _loss_head(st, hidden2, w, b, labels, labelWeights, wantLogits)
     return hidden2 @ w + b
 
 
 def MLP_1_hidden(features, numInputFeatures, hidden_units, numOutFeatures, layerName, keepProb, isTraining,
-                 useDropOut=False, store=None):
-    """utils/MCNetworkUtils.py:72-106."""
+                 useDropOut=False, store=None, labels=None, labelWeights=None, wantLogits=False):
+    """utils/MCNetworkUtils.py:72-106. labels, labelWeights, wantLogits (extension): as in MLP_2_hidden."""
     st = store or _DEFAULT_STORE
     dev = features.device
     w = st.get_variable(layerName + '_weights1', (numInputFeatures, hidden_units),
@@ -375,6 +456,8 @@ def MLP_1_hidden(features, numInputFeatures, hidden_units, numOutFeatures, layer
                         _fan_avg_uniform(hidden_units, numOutFeatures), dev)
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases2', (numOutFeatures,), _zeros, dev)
+    if labels is not None:
+        return _loss_head(st, hidden, w, b, labels, labelWeights, wantLogits)
     return hidden @ w + b
 
 
@@ -386,6 +469,19 @@ def conv_1x1(layerName, inputs, numInputs, numOutFeatures, store=None):
     st.add_to_collection('weight_decay_loss', w)
     b = st.get_variable(layerName + '_biases', (numOutFeatures,), _zeros, dev)
     return inputs @ w + b
+
+
+def conv_1x1_softmax_cross_entropy(layerName, inputs, numInputs, numOutFeatures, labels, labelWeights=None, wantLogits=False,
+                                   store=None):
+    """The sparse softmax cross-entropy (_loss_head) over conv_1x1(layerName, inputs, numInputs, numOutFeatures) (extension)
+    -> LossHead: the same variables, created in the same order from the same initialisers; one library op where the store's
+    fusedLoss_ is set and the op applies, torch code otherwise."""
+    st = store or _DEFAULT_STORE
+    dev = inputs.device
+    w = st.get_variable(layerName + '_weights', (numInputs, numOutFeatures), _fan_avg_uniform(numInputs, numOutFeatures), dev)
+    st.add_to_collection('weight_decay_loss', w)
+    b = st.get_variable(layerName + '_biases', (numOutFeatures,), _zeros, dev)
+    return _loss_head(st, inputs, w, b, labels, labelWeights, wantLogits)
 
 
 def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, keepProb, store=None, outDtype=None):

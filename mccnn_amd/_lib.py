@@ -158,6 +158,10 @@ SIGNATURES = {
                                      _vp, _i, _vp, _vp, _sz, _vp]),
     "mccnn_linear_bn_act_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _sz, _vp]),
+    # the last linear layer + softmax cross-entropy as one op (linear_xent.hip)
+    "mccnn_linear_xent_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mccnn_linear_xent_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_linear_xent_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -1670,6 +1670,88 @@ Tensor linear_bn_relu_drop(const Tensor& x, const Tensor& w, const Tensor& b, co
     return y;
 }
 
+// ---- the last linear layer and the softmax cross-entropy behind it as one op (mccnn_linear_xent_fwd / _bwd), the C++ form of
+// dense_glue.linear_softmax_xent -- the same library calls with the same arguments, so the same bytes. Python has checked the
+// arguments (labels int32 [n], weights f32 [n] or None); here only what keeps a call inside its tensors. loss alone carries
+// the node: pred, meta and the logits have no history.
+struct LinearXentBackward : public torch::autograd::Node {
+    Tensor x_, w_, b_, labels, rw, lse, meta;
+    uint32_t versions[3] = {0, 0, 0};
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        const Tensor g = glue_grad_in("linear_softmax_xent", x_.defined() && lse.defined() && meta.defined(), grads[0], {&x_, &w_, &b_},
+                                      versions, lse.select(0, 0), false);
+        TORCH_CHECK(g.numel() == 1 && g.is_cuda() && g.device() == x_.device(), "linear_softmax_xent: the gradient of loss must be one word on x's device");
+        const DevGuard device_guard((int)x_.device().index());
+        const int n = (int)x_.size(0), cin = (int)x_.size(1), c = (int)w_.size(1);
+        const bool want_dx = task_should_compute_output(0);
+        Tensor dx;
+        if (want_dx) dx = at::empty_like(x_);
+        Tensor dw = at::empty_like(w_);
+        Tensor db = at::empty_like(b_);
+        void* st = cur_stream(x_);
+        Tensor& ws = scratch(mccnn_linear_xent_workspace_bytes(n, cin, c), x_, st);
+        check(mccnn_linear_xent_bwd(x_.data_ptr<float>(), w_.data_ptr<float>(), b_.data_ptr<float>(), n, cin, c, labels.data_ptr<int>(),
+                                    rw.defined() ? rw.data_ptr<float>() : nullptr, lse.data_ptr<float>(), meta.data_ptr<int>(),
+                                    g.data_ptr<float>(), want_dx ? dx.data_ptr<float>() : nullptr, dw.data_ptr<float>(),
+                                    db.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), st),
+              "linear_softmax_xent_grad");
+        torch::autograd::variable_list out(3);
+        out[0] = dx;
+        if (task_should_compute_output(1)) out[1] = dw;
+        if (task_should_compute_output(2)) out[2] = db;
+        return out;
+    }
+    void release_variables() override { x_.reset(); w_.reset(); b_.reset(); labels.reset(); rw.reset(); lse.reset(); meta.reset(); }
+};
+
+// -> (loss [], pred [n] int32, meta [2] int32 = D, correct, logits [n, c] or an undefined tensor)
+std::tuple<Tensor, Tensor, Tensor, Tensor> linear_softmax_xent(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& labels,
+                                                               const c10::optional<Tensor>& weights, bool want_logits) {
+    check_dev(x, at::kFloat, "x");
+    check_dev(w, at::kFloat, "w");
+    check_dev(b, at::kFloat, "b");
+    check_dev(labels, at::kInt, "labels");
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && w.size(1) >= 1 && w.size(0) == x.size(1) &&
+                    x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31) && w.size(1) < (1ll << 31) && w.device() == x.device(),
+                "linear_softmax_xent expects x (n, cin) and w (cin, c), n, cin, c >= 1");
+    TORCH_CHECK(b.dim() == 1 && b.size(0) == w.size(1) && b.device() == x.device(), "linear_softmax_xent: b must have shape (c,)");
+    TORCH_CHECK(labels.numel() == x.size(0) && labels.device() == x.device(), "linear_softmax_xent: labels must have n elements");
+    Tensor rw;
+    if (weights.has_value() && weights->defined()) {
+        rw = *weights;
+        check_dev(rw, at::kFloat, "weights");
+        TORCH_CHECK(rw.numel() == x.size(0) && rw.device() == x.device(), "linear_softmax_xent: weights must have n elements");
+    }
+    const DevGuard device_guard((int)x.device().index());
+    const int n = (int)x.size(0), cin = (int)x.size(1), c = (int)w.size(1);
+    const bool need_grad = at::GradMode::is_enabled() && (x.requires_grad() || w.requires_grad() || b.requires_grad());
+    Tensor loss, lse, pred, meta, logits;
+    {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        loss = at::empty({}, x.options());
+        lse = at::empty({(int64_t)n}, x.options());
+        pred = at::empty({(int64_t)n}, labels.options());
+        meta = at::empty({2}, labels.options());
+        if (want_logits) logits = at::empty({(int64_t)n, (int64_t)c}, x.options());
+        void* st = cur_stream(x);
+        Tensor& ws = scratch(mccnn_linear_xent_workspace_bytes(n, cin, c), x, st);
+        check(mccnn_linear_xent_fwd(x.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(), n, cin, c, labels.data_ptr<int>(),
+                                    rw.defined() ? rw.data_ptr<float>() : nullptr, loss.data_ptr<float>(), lse.data_ptr<float>(),
+                                    meta.data_ptr<int>(), pred.data_ptr<int>(), want_logits ? logits.data_ptr<float>() : nullptr,
+                                    ws.data_ptr(), (size_t)ws.numel(), st),
+              "linear_softmax_xent");
+    }
+    if (need_grad) {
+        auto node = std::shared_ptr<LinearXentBackward>(new LinearXentBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(x, w, b));
+        node->x_ = x; node->w_ = w; node->b_ = b; node->labels = labels; node->rw = rw; node->lse = lse; node->meta = meta;
+        node->versions[0] = x._version(); node->versions[1] = w._version(); node->versions[2] = b._version();
+        torch::autograd::set_history(loss, node);
+    }
+    return std::make_tuple(loss, pred, meta, logits);
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -2042,6 +2124,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("moving_mean"), py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"),
             py::arg("keep_scale"), py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1,
             py::call_guard<py::gil_scoped_release>());
+    mod.def("linear_softmax_xent", &linear_softmax_xent, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("labels"),
+            py::arg("weights") = py::none(), py::arg("want_logits") = false, py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

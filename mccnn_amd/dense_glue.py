@@ -1,8 +1,10 @@
 """The dense glue between two MC convolutions as library ops (extensions; csrc/bn_act.hip, csrc/linear_bn.hip,
-include/mccnn.h "THE DENSE GLUE AS ONE OP" and the two sections behind it): y = drop(act(bn(x))) with the moving
+csrc/linear_xent.hip; include/mccnn.h "THE DENSE GLUE AS ONE OP" and the two sections behind it): y = drop(act(bn(x))) with the moving
 statistics updated in place -- on its own (bn_relu_dropout), with the batch statistics across the ranks of a process group
 (bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
-(csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream.
+(csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream. And what closes the dense path: the last linear
+layer with the softmax cross-entropy, the predictions and the count of correct rows behind it (linear_softmax_xent,
+csrc/linear_xent.hip).
 
 MCConvModule imports these names back: mccnn_amd.MCConvModule.bn_relu_dropout is this module's.
 mccnn_amd.native has the forms that go through the torch extension.
@@ -311,6 +313,94 @@ def linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training
                                       int(bool(relu)), BN_DROP_ALL, 1.0, seed, None, ptr(y), int(y.dtype == torch.bfloat16), None,
                                       None, 0, stream_handle()), "linear_bn_relu_dropout")
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# The last linear layer and the softmax cross-entropy behind it as one op (csrc/linear_xent.hip, include/mccnn.h "THE LAST
+# LINEAR LAYER AND THE SOFTMAX CROSS-ENTROPY BEHIND IT AS ONE OP"): x -> (loss, predictions, count of correct rows).
+def _linear_xent_args(x, w, b, labels, weights=None):
+    """Checks of linear_softmax_xent (nothing is launched before they pass) -> (labels, weights) as the library reads them:
+    int32 [n] -- an int64 tensor is cast here, behind the checks, which is one torch launch -- and float32 [n] or None."""
+    _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "linear_softmax_xent: x must be a float32 tensor")
+    _req(isinstance(w, torch.Tensor) and w.dtype == torch.float32, "linear_softmax_xent: w must be a float32 tensor")
+    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
+         "linear_softmax_xent expects x (n, cin) and w (cin, c), n, cin, c >= 1")
+    _req(x.is_contiguous() and w.is_contiguous(), "linear_softmax_xent: x and w must be contiguous")
+    _req(w.device == x.device, "linear_softmax_xent: w is on another device than x")
+    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
+         and b.shape[0] == w.shape[1] and b.device == x.device, "linear_softmax_xent: b must be a float32 (c,) tensor on x's device")
+    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "linear_softmax_xent: x too large")
+    n = x.shape[0]
+    _req(isinstance(labels, torch.Tensor) and labels.dtype in (torch.int32, torch.int64),
+         "linear_softmax_xent: labels must be an int32 (or int64) tensor")
+    _req(tuple(labels.shape) in ((n,), (n, 1)), "linear_softmax_xent: labels must have shape (n,) or (n, 1)")
+    _req(labels.device == x.device and labels.is_contiguous(), "linear_softmax_xent: labels must be contiguous on x's device")
+    if weights is not None:
+        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "linear_softmax_xent: weights must be a float32 tensor")
+        _req(tuple(weights.shape) in ((n,), (n, 1)), "linear_softmax_xent: weights must have shape (n,) or (n, 1)")
+        _req(weights.device == x.device and weights.is_contiguous(), "linear_softmax_xent: weights must be contiguous on x's device")
+        _req(not (torch.is_grad_enabled() and weights.requires_grad), "linear_softmax_xent: no gradient with respect to weights")
+    _req(x.is_cuda, "linear_softmax_xent: x must be a CUDA tensor")
+    labels = labels.detach().reshape(n)
+    if labels.dtype != torch.int32:
+        labels = labels.to(torch.int32)
+    return labels, None if weights is None else weights.detach().reshape(n)
+
+
+class _LinearSoftmaxXent(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, labels, weights, wantLogits):
+        lib = _lib.load()
+        n, cin = x.shape
+        c = w.shape[1]
+        xd, wd, bd = x.detach(), w.detach(), b.detach()
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        lse = torch.empty((n,), dtype=torch.float32, device=x.device)
+        pred = torch.empty((n,), dtype=torch.int32, device=x.device)
+        meta = torch.empty((2,), dtype=torch.int32, device=x.device)
+        logits = torch.empty((n, c), dtype=torch.float32, device=x.device) if wantLogits else None
+        ws = _ws(lib.mccnn_linear_xent_workspace_bytes(n, cin, c), x.device)
+        check(lib.mccnn_linear_xent_fwd(ptr(xd), ptr(wd), ptr(bd), n, cin, c, ptr(labels), ptr(weights), ptr(loss), ptr(lse), ptr(meta),
+                                        ptr(pred), ptr(logits), ptr(ws), ws.numel(), stream_handle()), "linear_softmax_xent")
+        ctx.save_for_backward(xd, wd, bd, labels, lse, meta)
+        ctx.weights = weights
+        if wantLogits:
+            ctx.mark_non_differentiable(pred, meta, logits)
+            return loss, pred, meta, logits
+        ctx.mark_non_differentiable(pred, meta)
+        return loss, pred, meta
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gl, *unused):
+        x, w, b, labels, lse, meta = ctx.saved_tensors
+        lib = _lib.load()
+        n, cin = x.shape
+        c = w.shape[1]
+        gl = gl.to(torch.float32).contiguous()   # (one word on the device, read by the kernel: no read-back)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w)
+        db = torch.empty_like(b)
+        ws = _ws(lib.mccnn_linear_xent_workspace_bytes(n, cin, c), x.device)
+        check(lib.mccnn_linear_xent_bwd(ptr(x), ptr(w), ptr(b), n, cin, c, ptr(labels), ptr(ctx.weights), ptr(lse), ptr(meta), ptr(gl),
+                                        ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), stream_handle()), "linear_softmax_xent_grad")
+        need = ctx.needs_input_grad
+        return dx, dw if need[1] else None, db if need[2] else None, None, None, None
+
+
+def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
+    """The sparse softmax cross-entropy of z = x @ w + b in one library op -> (loss, pred, meta, logits or None). x (n, cin),
+    w (cin, c), b (c,) float32 contiguous; labels (n,) or (n, 1), int32 taken as it is, int64 cast to int32 (one torch
+    launch); weights: float32 (n,) row weights, None: all 1. A row is live iff 0 <= label < c and its weight is not 0 -- a label
+    outside [0, c) makes a weight-0 row, never an error. loss (0-dim float32) = sum over live rows of weight * (logsumexp(z_i)
+    - z[i, label_i]) / D with D = max(number of live rows, 1): the mean without weights, TF's SUM_BY_NONZERO_WEIGHTS with
+    them; +0 and zero gradients when no row is live. pred (int32 (n,)): the lowest arg-max of every row; meta (int32 (2,)):
+    D and the number of live rows with pred == label. loss is differentiable (once) with respect to x, w and b, all three
+    gradients from one autograd node whose upstream gradient stays on the device. pred, meta and logits are NOT
+    differentiable: whoever needs gradients through the logits uses the unfused path (x @ w + b and torch's loss)."""
+    labels, weights = _linear_xent_args(x, w, b, labels, weights)
+    out = _LinearSoftmaxXent.apply(x, w, b, labels, weights, bool(wantLogits))
+    return out if wantLogits else out + (None,)
 
 
 # At the end on purpose: MCConvModule imports this module back at ITS end, and with both imports last each module finds the

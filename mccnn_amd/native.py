@@ -671,3 +671,15 @@ def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, r
            "linear_bn_relu_dropout: the eval form has no gradients")
     return _EXT.linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
                                     float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
+
+
+def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
+    """The last linear layer and the softmax cross-entropy behind it as one op -> (loss, pred, meta, logits or None)
+    (dense_glue.linear_softmax_xent: its definition, checks and errors): one Python -> C++ call forward and an autograd
+    node on the C++ side (LinearXentBackward) when the extension is loaded, the ctypes op otherwise -- the same library
+    calls either way, so the same bytes."""
+    from . import dense_glue as M
+    if _EXT is None:
+        return M.linear_softmax_xent(x, w, b, labels, weights, wantLogits)
+    labels, weights = M._linear_xent_args(x, w, b, labels, weights)
+    return _EXT.linear_softmax_xent(x, w, b, labels, weights, bool(wantLogits))
