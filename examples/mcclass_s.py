@@ -4,6 +4,7 @@
 tiny synthetic training loop. The graph builders keep the reference's structure line by line; only `tf.` is gone.
 
     python examples/mcclass_s.py [--steps 20] [--device-loader]
+    python examples/mcclass_s.py --normals [--fused-glue] [--fused-loss]     # MCNormS on the ellipsoids' analytic normals
 
 --device-loader builds the batches on the GPU (mccnn_amd.device_batcher.DeviceBatcher: a pool of synthetic models uploaded
 once, non-uniform sampling and rotation per batch on the device) instead of uploading host arrays.
@@ -19,7 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mccnn_amd.MCConvBuilder import PointHierarchy, ConvolutionBuilder
 from mccnn_amd.MCNetworkUtils import (MLP_2_hidden, batch_norm_RELU_drop_out, conv_1x1, conv_1x1_batch_norm_RELU_drop_out,
-                                      VariableStore)
+                                      VariableStore, cosine_distance_loss, mean_angle)
 
 
 class MCClassS(torch.nn.Module):
@@ -113,23 +114,73 @@ class MCClassS(torch.nn.Module):
 class MCNormS(torch.nn.Module):
     """models/MCNormS.py create_network(): two same-level multi-feature convolutions (normal estimation)."""
 
-    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False, fusedSync=False):
+    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False, fusedSync=False, fusedLoss=False):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k)
-        self.store = VariableStore(device, fused=fused, fusedSync=fusedSync)
+        # fusedLoss (extension): with normals handed to forward(), the cosine-distance loss and its metrics as one library op
+        # (VariableStore.fusedLoss_, cosine_distance_loss)
+        self.store = VariableStore(device, fused=fused, fusedSync=fusedSync, fusedLoss=fusedLoss)
         self.ops = ops
         self.convBuilder = ConvolutionBuilder(KDEWindow=0.2, device=device, ops=ops)
 
-    def forward(self, points, batchIds, features, isTraining):
+    def hierarchy(self, points, batchIds, features):
+        """The network's point hierarchy for a batch (the input level only)."""
+        return PointHierarchy(points, features, batchIds, [], "MCNormS_PH", self.args[1], ops=self.ops)
+
+    def forward(self, points, batchIds, features, isTraining, normals=None, normalWeights=None, hierarchy=None,
+                nextHierarchy=None):
+        """normals (extension): the [N, 3] target normals -- the result is then the NormalHead of cosine_distance_loss (loss,
+        sum of cosines, sum of angles, denominator) over the last convolution's output, normalWeights its row weights; None:
+        the [N, 3] prediction, every call as before. hierarchy / nextHierarchy (extension): as in MCClassS.forward."""
         numInputFeatures, batchSize, k = self.args
         cb = self.convBuilder
         cb.reset()
-        ph = PointHierarchy(points, features, batchIds, [], "MCNormS_PH", batchSize, ops=self.ops)
+        if nextHierarchy is not None:
+            cb.prefetch_step(nextHierarchy)
+        ph = hierarchy if hierarchy is not None else self.hierarchy(points, batchIds, features)
         c1 = cb.create_convolution(convName="Conv_1", inPointHierarchy=ph, inPointLevel=0, inFeatures=features,
                                    inNumFeatures=numInputFeatures, outNumFeatures=k, convRadius=0.15, multiFeatureConv=True)
         c1 = batch_norm_RELU_drop_out("BN_RELU", c1, isTraining, False, False, self.store)
-        return cb.create_convolution(convName="Conv_2", inPointHierarchy=ph, inPointLevel=0, inFeatures=c1,
+        pred = cb.create_convolution(convName="Conv_2", inPointHierarchy=ph, inPointLevel=0, inFeatures=c1,
                                      inNumFeatures=k, outNumFeatures=3, convRadius=0.15, multiFeatureConv=True)
+        if normals is None:
+            return pred
+        return cosine_distance_loss(pred, normals, normalWeights, store=self.store)
+
+
+def synthetic_normals_batch(batchSize, nPts, rng, device):
+    """Ellipsoids as in synthetic_batch with their analytic normals: n is proportional to p / axes^2 in the unscaled frame
+    (the gradient of sum (p_j / axes_j)^2), and the unit-box normalisation, a translation and one scale, leaves it as it is.
+    -> (points, batch ids, features, normals)."""
+    pts, bids, nrm = [], [], []
+    for b in range(batchSize):
+        axes = np.array([1.0, rng.uniform(0.3, 1.0), rng.uniform(0.3, 1.0)])
+        v = rng.normal(size=(nPts, 3))
+        p = v / np.linalg.norm(v, axis=1, keepdims=True) * axes
+        g = p / (axes * axes)
+        nrm.append((g / np.linalg.norm(g, axis=1, keepdims=True)).astype(np.float32))
+        p = (p - p.min(0)) / (p.max(0) - p.min(0)).max()
+        pts.append(p.astype(np.float32))
+        bids.append(np.full((nPts, 1), b, np.int32))
+    t = lambda a: torch.from_numpy(a).to(device)
+    P, Bi = t(np.concatenate(pts)), t(np.concatenate(bids))
+    return P, Bi, torch.ones((P.shape[0], 1), dtype=torch.float32, device=device), t(np.concatenate(nrm))
+
+
+def train_normals(args, device, rng):
+    """--normals: MCNormS on the synthetic ellipsoids, the loss and the mean angle from the NormalHead of the model."""
+    net = MCNormS(1, args.batch, 16, device, fused=args.fused_glue, fusedLoss=args.fused_loss)
+    P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
+    net(P, Bi, F, True)  # creates the variables
+    opt = torch.optim.Adam(net.parameters(), lr=5e-3)
+    for step in range(args.steps):
+        P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
+        head = net(P, Bi, F, True, normals=N)
+        opt.zero_grad(set_to_none=True)
+        head.loss.backward()
+        opt.step()
+        if step % 5 == 0 or step == args.steps - 1:
+            print("step %3d  loss %.4f  mean angle %.2f deg" % (step, float(head.loss), math.degrees(float(mean_angle(head)))))
 
 
 def synthetic_batch(batchSize, nPts, numCat, rng, device):
@@ -186,7 +237,10 @@ def main():
                          "(VariableStore(fusedLinear=True))")
     ap.add_argument("--fused-loss", action="store_true",
                     help="the last linear of the MLP + softmax cross-entropy + arg-max as one library op "
-                         "(VariableStore(fusedLoss=True)); the loop then takes the loss and the accuracy from its LossHead")
+                         "(VariableStore(fusedLoss=True)); the loop then takes the loss and the accuracy from its LossHead. "
+                         "With --normals: the cosine-distance loss and its metrics as one library op")
+    ap.add_argument("--normals", action="store_true",
+                    help="train MCNormS (normal estimation) on the ellipsoids' analytic normals instead of MCClassS")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()
@@ -196,6 +250,8 @@ def main():
     # one process per GPU: run the backward pass on the calling thread -- the autograd engine's per-device worker thread
     # only adds a hand-off per backward() and this network is host-bound (cfg1 step: 4.0 -> 3.3 ms, tools/e2e_time.py)
     torch.autograd.set_multithreading_enabled(False)
+    if args.normals:
+        return train_normals(args, device, rng)
     net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None,
                    fusedLinear=args.fused_linear, fusedLoss=args.fused_loss)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \

@@ -1006,6 +1006,37 @@ int mccnn_linear_xent_bwd(const float* x, const float* w, const float* b, int n,
                           float* dx /* NULL: not wanted */, float* dw, float* db, void* ws, size_t ws_bytes,
                           mccnn_stream_t stream);
 
+/* THE COSINE-DISTANCE LOSS OF NORMAL ESTIMATION AS ONE OP (extension, ABI 24; cosine_loss.hip): per row i, all in float32,
+ * every sum over j ascending as one fmaf chain, eps = 1e-12f (tf.nn.l2_normalize's),
+ *   sp = sum_j p_j^2,  rp = 1 / sqrt(max(sp, eps)),  u_j = p_j rp;     st, rt, v_j = t_j rt likewise from the target,
+ *   cos_i = sum_j u_j v_j,  l_i = 1 - cos_i,
+ *   a_i = 2 atan2f(sqrt(sum_j (u_j - v_j)^2), sqrt(sum_j (u_j + v_j)^2))   (pi / 2 when both sums are 0),
+ *   loss = (sum over live rows of rw_i l_i) / D,  cosSum = sum over live rows of cos_i,  angleSum = sum over live rows of a_i,
+ *   D = max(number of live rows, 1).
+ * pred, target [n, c] float32 row-major contiguous, row_weights [n] float32 (NULL: all 1); n, c >= 1, n * c < 2^31, no
+ * divisibility rule and no alignment rule beyond 4 bytes (rows of three floats are never 16-byte aligned). Inputs are finite and
+ * their squares do not overflow. A row is LIVE iff its weight is != 0 (without weights: every row); a zero target is live and
+ * has cos = 0. loss is tf.losses.cosine_distance with SUM_BY_NONZERO_WEIGHTS (without weights: the mean); the two sums are
+ * unweighted metrics. The angle is NOT acos(cos_i): that form loses half the digits near +-1, this one is exact at u = +-v.
+ * No live row: loss = +0.0f, zero sums, all-zero dpred.
+ *   forward:  writes loss [1], sums = {cosSum, angleSum}, meta = {D}. One launch up to 256 rows, two above.
+ *   backward: with g = loss_grad[0], a DEVICE word read by the kernel, and s = g rw_i / D,
+ *               dpred_ij = -s rp (v_j - cos_i u_j)   on live rows with sp >= eps
+ *               dpred_ij = -s 1e6f v_j               on live rows with sp <  eps (the clamp makes u linear in p)
+ *               dpred_ij = 0                         on the other rows
+ *             recomputed from pred, target and meta; nothing per row is kept. One launch. No gradient with respect to target
+ *             or the weights.
+ * No atomics, no memset, fixed merge orders: the same inputs give the same bytes. The forward's ws holds
+ * mccnn_cosine_loss_workspace_bytes(n, c) bytes: 0 up to 256 rows (ws may then be NULL) and for sizes the op refuses. n or
+ * c < 1, a NULL required pointer: MCCNN_E_BADARG; n * c >= 2^31: MCCNN_E_TOOLARGE; a missing or short workspace:
+ * MCCNN_E_WORKSPACE; all before anything is launched. */
+size_t mccnn_cosine_loss_workspace_bytes(int n, int c);
+int mccnn_cosine_loss_fwd(const float* pred, const float* target, int n, int c, const float* row_weights /* NULL: all 1 */,
+                          float* loss /* [1] */, float* sums /* [2]: cosSum, angleSum */, int* meta /* [1]: D */,
+                          void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_cosine_loss_bwd(const float* pred, const float* target, int n, int c, const float* row_weights, const int* meta,
+                          const float* loss_grad /* [1], device */, float* dpred, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

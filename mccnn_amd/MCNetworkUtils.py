@@ -32,6 +32,9 @@ it -- conv_1x1_softmax_cross_entropy, and the MLPs called with labels -- run as 
 correct, denom, logits), the gradients of x, the weights and the biases from one autograd node. Everywhere else, and always
 with the switch off, torch code computes the same definition (_loss_head). Names, shapes, initialisers, creation order and
 state_dict are the same either way; without labels every helper returns the logits as before.
+The same switch covers the loss of the third task, normal estimation: cosine_distance_loss(pred, target) -> NormalHead(loss,
+cosSum, angleSum, denom) runs as ONE library op (dense_glue.cosine_distance_loss, csrc/cosine_loss.hip) where its conditions
+hold (_fused_cosine), as torch code of the same definition (_normal_head) everywhere else.
 """
 import collections
 import math
@@ -199,18 +202,20 @@ _FUSED_OP = False          # native.bn_relu_drop once the library has loaded; No
 _FUSED_SYNC_OP = None      # native.bn_relu_drop_sync, likewise
 _FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
 _FUSED_LOSS_OP = None      # native.linear_softmax_xent, likewise
+_FUSED_COSINE_OP = None    # native.cosine_distance_loss, likewise
 
 
 def _load_fused_ops():
-    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP
+    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
             _lib.load()
             _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP = native.bn_relu_drop, native.bn_relu_drop_sync, native.linear_bn_relu_drop
             _FUSED_LOSS_OP = native.linear_softmax_xent
+            _FUSED_COSINE_OP = native.cosine_distance_loss
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = None
+            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = _FUSED_COSINE_OP = None
 
 
 def _fused_op(synced=False):
@@ -226,6 +231,11 @@ def _fused_linear_op():
 def _fused_loss_op():
     _load_fused_ops()
     return _FUSED_LOSS_OP
+
+
+def _fused_cosine_op():
+    _load_fused_ops()
+    return _FUSED_COSINE_OP
 
 
 def _on_device_f32(dev, tensors):
@@ -412,6 +422,95 @@ def _loss_head(st, inputs, w, b, labels, labelWeights=None, wantLogits=False):
     pred = z.detach().argmax(1)
     correct = (live & (pred == y)).sum()
     return LossHead(loss, pred.to(torch.int32), correct.to(torch.int32), denom.to(torch.int32), z.detach() if wantLogits else None)
+
+
+#: What cosine_distance_loss returns. loss: 0-dim float32, differentiable with respect to the prediction; cosSum, angleSum:
+#: 0-dim float32 tensors, the sums over the live rows of cos_i and of the angle between prediction and target in radians;
+#: denom: 0-dim int32, D = max(number of live rows, 1). All on the prediction's device: no read-back until printed. The last
+#: three are metrics without gradient history (mean_angle, reference_angle).
+NormalHead = collections.namedtuple("NormalHead", "loss cosSum angleSum denom")
+
+_L2_EPS = 1e-12   # tf.nn.l2_normalize's epsilon
+
+
+def _fused_cosine(st, pred, target, weights):
+    """The NormalHead of _normal_head as one library op, or None where that form does not apply (the caller then runs the
+    torch code): the store's fusedLoss_ switch is off, pred and target are not float32 [n, c] tensors on one HIP device laid
+    out as .contiguous() would leave them (a view that starts anywhere in its buffer is fine), target or the weights want
+    a gradient, the weights are not a contiguous float32 [n] / [n, 1] tensor on that device, or the library does not load.
+    The op is differentiable once: a caller that needs a double backward switches fusedLoss_ off."""
+    if not getattr(st, "fusedLoss_", False):
+        return None
+    if not (torch.is_tensor(pred) and torch.is_tensor(target) and pred.is_cuda and pred.dtype == torch.float32
+            and target.dtype == torch.float32 and pred.dim() == 2 and pred.shape[0] >= 1 and pred.shape[1] >= 1
+            and tuple(target.shape) == tuple(pred.shape) and target.device == pred.device and pred.is_contiguous()
+            and target.is_contiguous() and pred.shape[0] * pred.shape[1] < (1 << 31)):
+        return None
+    if torch.is_grad_enabled() and target.requires_grad:
+        return None
+    n = pred.shape[0]
+    if weights is not None and not (torch.is_tensor(weights) and weights.dtype == torch.float32
+                                    and tuple(weights.shape) in ((n,), (n, 1)) and weights.device == pred.device
+                                    and weights.is_contiguous() and not weights.requires_grad):
+        return None
+    op = _fused_cosine_op()
+    if op is None:
+        return None
+    loss, sums, meta = op(pred, target, weights)
+    return NormalHead(loss, sums[0], sums[1], meta[0])
+
+
+def _normal_head(pred, target, weights=None):
+    """The cosine-distance loss in torch code -> NormalHead: both rows normalised as tf.nn.l2_normalize does (x / sqrt(max(sum
+    x^2, 1e-12)): below the clamp the unit row is LINEAR in x, which is also what its gradient says), cos_i their dot product,
+    a row live iff its weight is not 0, loss = sum over live rows of weight * (1 - cos_i) / D with D = max(number of live rows,
+    1), and the angle of a row as 2 atan2(|u - v|, |u + v|) (pi / 2 where both lengths are 0)."""
+    u = pred / torch.sqrt((pred * pred).sum(1, keepdim=True).clamp_min(_L2_EPS))
+    v = target / torch.sqrt((target * target).sum(1, keepdim=True).clamp_min(_L2_EPS))
+    cos = (u * v).sum(1)
+    rows = 1.0 - cos
+    if weights is not None:
+        rw = weights.reshape(-1).to(pred.dtype)
+        live = rw != 0
+        rows = rows * rw
+    else:
+        live = torch.ones_like(cos, dtype=torch.bool)
+    denom = live.sum().clamp_min(1)
+    loss = torch.where(live, rows, torch.zeros_like(rows)).sum() / denom
+    with torch.no_grad():
+        ud, vd = u.detach(), v.detach()
+        far = ((ud - vd) ** 2).sum(1).sqrt()
+        near = ((ud + vd) ** 2).sum(1).sqrt()
+        ang = torch.where((far == 0) & (near == 0), torch.full_like(far, math.pi / 2), 2.0 * torch.atan2(far, near))
+        zero = torch.zeros_like(ang)
+        cosSum = torch.where(live, cos.detach(), zero).sum()
+        angleSum = torch.where(live, ang, zero).sum()
+    return NormalHead(loss, cosSum, angleSum, denom.to(torch.int32))
+
+
+def cosine_distance_loss(pred, target, weights=None, store=None):
+    """The loss of normal estimation (the reference's ModelNetNormals.py:34-44: tf.losses.cosine_distance over the two
+    l2_normalize'd [n, c] tensors, with its default SUM_BY_NONZERO_WEIGHTS) -> NormalHead(loss, cosSum, angleSum, denom).
+    weights: [n] or [n, 1] row weights, None: all 1; a row with weight 0 takes no part, neither in the loss nor in the two
+    sums. One library op where the store's fusedLoss_ says so and it applies (_fused_cosine), torch code of the same definition
+    (_normal_head) otherwise."""
+    st = store or _DEFAULT_STORE
+    if getattr(st, "fusedLoss_", False):
+        head = _fused_cosine(st, pred, target, weights)
+        if head is not None:
+            return head
+    return _normal_head(pred, target, weights)
+
+
+def mean_angle(head):
+    """The mean over the live rows of the angle between prediction and target, in radians (a 0-dim tensor)."""
+    return head.angleSum / head.denom
+
+
+def reference_angle(head, c):
+    """The figure the reference prints as its angle (ModelNetNormals.py): acos of the mean of u * v over all ELEMENTS, i.e.
+    acos(cosSum / (c * D)) for rows of c columns -- not the angle of any row; kept for comparing with its logs."""
+    return torch.acos(head.cosSum / (c * head.denom))
 
 
 def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOutFeatures, layerName, keepProb,

@@ -162,6 +162,10 @@ SIGNATURES = {
     "mccnn_linear_xent_workspace_bytes": (_sz, [_i, _i, _i]),
     "mccnn_linear_xent_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_linear_xent_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the cosine-distance loss of normal estimation as one op (cosine_loss.hip)
+    "mccnn_cosine_loss_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_cosine_loss_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mccnn_cosine_loss_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

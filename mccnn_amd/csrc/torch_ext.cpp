@@ -1752,6 +1752,71 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> linear_softmax_xent(const Tensor& x, 
     return std::make_tuple(loss, pred, meta, logits);
 }
 
+// ---- the cosine-distance loss of normal estimation as one op (mccnn_cosine_loss_fwd / _bwd), the C++ form of
+// dense_glue.cosine_distance_loss -- the same library calls with the same arguments, so the same bytes. Python has checked the
+// arguments (weights f32 [n] or None, no gradient asked of target or weights); here only what keeps a call inside its tensors.
+// loss alone carries the node: sums and meta have no history.
+struct CosineLossBackward : public torch::autograd::Node {
+    Tensor pred_, target_, rw, sums, meta;
+    uint32_t versions[2] = {0, 0};
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        const Tensor g = glue_grad_in("cosine_distance_loss", pred_.defined() && sums.defined() && meta.defined(), grads[0],
+                                      {&pred_, &target_}, versions, sums.select(0, 0), false);
+        TORCH_CHECK(g.numel() == 1 && g.is_cuda() && g.device() == pred_.device(),
+                    "cosine_distance_loss: the gradient of loss must be one word on pred's device");
+        const DevGuard device_guard((int)pred_.device().index());
+        const int n = (int)pred_.size(0), c = (int)pred_.size(1);
+        Tensor dp = at::empty_like(pred_);
+        check(mccnn_cosine_loss_bwd(pred_.data_ptr<float>(), target_.data_ptr<float>(), n, c, rw.defined() ? rw.data_ptr<float>() : nullptr,
+                                    meta.data_ptr<int>(), g.data_ptr<float>(), dp.data_ptr<float>(), cur_stream(pred_)),
+              "cosine_distance_loss_grad");
+        torch::autograd::variable_list out(1);
+        out[0] = dp;
+        return out;
+    }
+    void release_variables() override { pred_.reset(); target_.reset(); rw.reset(); sums.reset(); meta.reset(); }
+};
+
+// -> (loss [], sums [2] = cosSum, angleSum, meta [1] int32 = D)
+std::tuple<Tensor, Tensor, Tensor> cosine_distance_loss(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& weights) {
+    check_dev(pred, at::kFloat, "pred");
+    check_dev(target, at::kFloat, "target");
+    TORCH_CHECK(pred.dim() == 2 && pred.size(0) >= 1 && pred.size(1) >= 1 && pred.size(0) * pred.size(1) < (1ll << 31) &&
+                    target.sizes() == pred.sizes() && target.device() == pred.device(),
+                "cosine_distance_loss expects pred (n, c) and target (n, c), n, c >= 1");
+    Tensor rw;
+    if (weights.has_value() && weights->defined()) {
+        rw = *weights;
+        check_dev(rw, at::kFloat, "weights");
+        TORCH_CHECK(rw.numel() == pred.size(0) && rw.device() == pred.device(), "cosine_distance_loss: weights must have n elements");
+    }
+    const DevGuard device_guard((int)pred.device().index());
+    const int n = (int)pred.size(0), c = (int)pred.size(1);
+    const bool need_grad = at::GradMode::is_enabled() && pred.requires_grad();
+    Tensor loss, sums, meta;
+    {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        loss = at::empty({}, pred.options());
+        sums = at::empty({2}, pred.options());
+        meta = at::empty({1}, pred.options().dtype(at::kInt));
+        void* st = cur_stream(pred);
+        Tensor& ws = scratch(mccnn_cosine_loss_workspace_bytes(n, c), pred, st);
+        check(mccnn_cosine_loss_fwd(pred.data_ptr<float>(), target.data_ptr<float>(), n, c, rw.defined() ? rw.data_ptr<float>() : nullptr,
+                                    loss.data_ptr<float>(), sums.data_ptr<float>(), meta.data_ptr<int>(), ws.data_ptr(),
+                                    (size_t)ws.numel(), st),
+              "cosine_distance_loss");
+    }
+    if (need_grad) {
+        auto node = std::shared_ptr<CosineLossBackward>(new CosineLossBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(pred));
+        node->pred_ = pred; node->target_ = target; node->rw = rw; node->sums = sums; node->meta = meta;
+        node->versions[0] = pred._version(); node->versions[1] = target._version();
+        torch::autograd::set_history(loss, node);
+    }
+    return std::make_tuple(loss, sums, meta);
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -2126,6 +2191,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::call_guard<py::gil_scoped_release>());
     mod.def("linear_softmax_xent", &linear_softmax_xent, py::arg("x"), py::arg("w"), py::arg("b"), py::arg("labels"),
             py::arg("weights") = py::none(), py::arg("want_logits") = false, py::call_guard<py::gil_scoped_release>());
+    mod.def("cosine_distance_loss", &cosine_distance_loss, py::arg("pred"), py::arg("target"), py::arg("weights") = py::none(),
+            py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

@@ -4,7 +4,7 @@ statistics updated in place -- on its own (bn_relu_dropout), with the batch stat
 (bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
 (csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream. And what closes the dense path: the last linear
 layer with the softmax cross-entropy, the predictions and the count of correct rows behind it (linear_softmax_xent,
-csrc/linear_xent.hip).
+csrc/linear_xent.hip), and the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip).
 
 MCConvModule imports these names back: mccnn_amd.MCConvModule.bn_relu_dropout is this module's.
 mccnn_amd.native has the forms that go through the torch extension.
@@ -401,6 +401,74 @@ def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
     labels, weights = _linear_xent_args(x, w, b, labels, weights)
     out = _LinearSoftmaxXent.apply(x, w, b, labels, weights, bool(wantLogits))
     return out if wantLogits else out + (None,)
+
+
+# ---------------------------------------------------------------------------------------------
+# The cosine-distance loss of normal estimation as one op (csrc/cosine_loss.hip, include/mccnn.h "THE COSINE-DISTANCE LOSS OF
+# NORMAL ESTIMATION AS ONE OP"): (pred, target) -> (loss, sums, meta).
+def _cosine_loss_args(pred, target, weights=None):
+    """Checks of cosine_distance_loss (nothing is launched before they pass) -> the weights as the library reads them:
+    float32 [n] or None."""
+    _req(isinstance(pred, torch.Tensor) and pred.dtype == torch.float32, "cosine_distance_loss: pred must be a float32 tensor")
+    _req(isinstance(target, torch.Tensor) and target.dtype == torch.float32, "cosine_distance_loss: target must be a float32 tensor")
+    _req(pred.dim() == 2 and pred.shape[0] >= 1 and pred.shape[1] >= 1 and tuple(target.shape) == tuple(pred.shape),
+         "cosine_distance_loss expects pred (n, c) and target (n, c), n, c >= 1")
+    _req(pred.is_contiguous() and target.is_contiguous(), "cosine_distance_loss: pred and target must be contiguous")
+    _req(target.device == pred.device, "cosine_distance_loss: target is on another device than pred")
+    _req(pred.shape[0] * pred.shape[1] < (1 << 31), "cosine_distance_loss: pred too large")
+    _req(not (torch.is_grad_enabled() and target.requires_grad), "cosine_distance_loss: no gradient with respect to target")
+    n = pred.shape[0]
+    if weights is not None:
+        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "cosine_distance_loss: weights must be a float32 tensor")
+        _req(tuple(weights.shape) in ((n,), (n, 1)), "cosine_distance_loss: weights must have shape (n,) or (n, 1)")
+        _req(weights.device == pred.device and weights.is_contiguous(), "cosine_distance_loss: weights must be contiguous on pred's device")
+        _req(not (torch.is_grad_enabled() and weights.requires_grad), "cosine_distance_loss: no gradient with respect to weights")
+    _req(pred.is_cuda, "cosine_distance_loss: pred must be a CUDA tensor")
+    return None if weights is None else weights.detach().reshape(n)
+
+
+class _CosineDistanceLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, weights):
+        lib = _lib.load()
+        n, c = pred.shape
+        pd, td = pred.detach(), target.detach()
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        sums = torch.empty((2,), dtype=torch.float32, device=pred.device)
+        meta = torch.empty((1,), dtype=torch.int32, device=pred.device)
+        ws = _ws(lib.mccnn_cosine_loss_workspace_bytes(n, c), pred.device)
+        check(lib.mccnn_cosine_loss_fwd(ptr(pd), ptr(td), n, c, ptr(weights), ptr(loss), ptr(sums), ptr(meta), ptr(ws), ws.numel(),
+                                        stream_handle()), "cosine_distance_loss")
+        ctx.save_for_backward(pd, td, meta)
+        ctx.weights = weights
+        ctx.mark_non_differentiable(sums, meta)
+        return loss, sums, meta
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gl, *unused):
+        pred, target, meta = ctx.saved_tensors
+        lib = _lib.load()
+        n, c = pred.shape
+        gl = gl.to(torch.float32).contiguous()   # (one word on the device, read by the kernel: no read-back)
+        dpred = torch.empty_like(pred)
+        check(lib.mccnn_cosine_loss_bwd(ptr(pred), ptr(target), n, c, ptr(ctx.weights), ptr(meta), ptr(gl), ptr(dpred),
+                                        stream_handle()), "cosine_distance_loss_grad")
+        return dpred, None, None
+
+
+def cosine_distance_loss(pred, target, weights=None):
+    """The cosine-distance loss of normal estimation in one library op -> (loss, sums, meta). pred, target (n, c) float32
+    contiguous (no alignment rule: a view that starts anywhere in its buffer is fine); weights: float32 (n,) or (n, 1) row
+    weights, None: all 1. Both rows are normalised as tf.nn.l2_normalize does (x / sqrt(max(sum x^2, 1e-12))), cos_i is
+    their dot product. A row is live iff its weight is not 0. loss (0-dim float32) = sum over live rows of weight * (1 - cos_i)
+    / D with D = max(number of live rows, 1): the mean without weights, TF's SUM_BY_NONZERO_WEIGHTS with them; +0 and zero
+    gradients when no row is live. sums (float32 (2,)): the sum over live rows of cos_i and of the angle between the two
+    unit rows in radians, 2 atan2(|u - v|, |u + v|); meta (int32 (1,)): D. loss is differentiable (once) with respect to pred,
+    the upstream gradient stays on the device; there is no gradient with respect to target or weights (asking for one
+    raises), and sums and meta are NOT differentiable."""
+    weights = _cosine_loss_args(pred, target, weights)
+    return _CosineDistanceLoss.apply(pred, target, weights)
 
 
 # At the end on purpose: MCConvModule imports this module back at ITS end, and with both imports last each module finds the

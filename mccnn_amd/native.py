@@ -683,3 +683,14 @@ def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
         return M.linear_softmax_xent(x, w, b, labels, weights, wantLogits)
     labels, weights = M._linear_xent_args(x, w, b, labels, weights)
     return _EXT.linear_softmax_xent(x, w, b, labels, weights, bool(wantLogits))
+
+
+def cosine_distance_loss(pred, target, weights=None):
+    """The cosine-distance loss of normal estimation as one op -> (loss, sums, meta) (dense_glue.cosine_distance_loss: its
+    definition, checks and errors): one Python -> C++ call forward and an autograd node on the C++ side (CosineLossBackward)
+    when the extension is loaded, the ctypes op otherwise -- the same library calls either way, so the same bytes."""
+    from . import dense_glue as M
+    if _EXT is None:
+        return M.cosine_distance_loss(pred, target, weights)
+    weights = M._cosine_loss_args(pred, target, weights)
+    return _EXT.cosine_distance_loss(pred, target, weights)
