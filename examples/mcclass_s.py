@@ -5,6 +5,7 @@ tiny synthetic training loop. The graph builders keep the reference's structure 
 
     python examples/mcclass_s.py [--steps 20] [--device-loader]
     python examples/mcclass_s.py --normals [--fused-glue] [--fused-loss]     # MCNormS on the ellipsoids' analytic normals
+    python examples/mcclass_s.py --parts [--fused-glue] [--fused-loss]       # per-point part labels, part IoU from device counts
 
 --device-loader builds the batches on the GPU (mccnn_amd.device_batcher.DeviceBatcher: a pool of synthetic models uploaded
 once, non-uniform sampling and rotation per batch on the device) instead of uploading host arrays.
@@ -20,7 +21,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mccnn_amd.MCConvBuilder import PointHierarchy, ConvolutionBuilder
 from mccnn_amd.MCNetworkUtils import (MLP_2_hidden, batch_norm_RELU_drop_out, conv_1x1, conv_1x1_batch_norm_RELU_drop_out,
-                                      VariableStore, cosine_distance_loss, mean_angle)
+                                      VariableStore, conv_1x1_softmax_cross_entropy, cosine_distance_loss, mean_angle, part_iou,
+                                      segmentation_counts)
 
 
 class MCClassS(torch.nn.Module):
@@ -114,9 +116,13 @@ class MCClassS(torch.nn.Module):
 class MCNormS(torch.nn.Module):
     """models/MCNormS.py create_network(): two same-level multi-feature convolutions (normal estimation)."""
 
-    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False, fusedSync=False, fusedLoss=False):
+    def __init__(self, numInputFeatures, batchSize, k, device, ops=None, fused=False, fusedSync=False, fusedLoss=False,
+                 outFeatures=3):
         super().__init__()
         self.args = (numInputFeatures, batchSize, k)
+        # outFeatures (extension): the width of the second convolution -- 3, the normal, in the reference; wider for the
+        # per-point features of forward(partLabels=...)
+        self.outFeatures = int(outFeatures)
         # fusedLoss (extension): with normals handed to forward(), the cosine-distance loss and its metrics as one library op
         # (VariableStore.fusedLoss_, cosine_distance_loss)
         self.store = VariableStore(device, fused=fused, fusedSync=fusedSync, fusedLoss=fusedLoss)
@@ -128,10 +134,13 @@ class MCNormS(torch.nn.Module):
         return PointHierarchy(points, features, batchIds, [], "MCNormS_PH", self.args[1], ops=self.ops)
 
     def forward(self, points, batchIds, features, isTraining, normals=None, normalWeights=None, hierarchy=None,
-                nextHierarchy=None):
+                nextHierarchy=None, partLabels=None, numParts=None):
         """normals (extension): the [N, 3] target normals -- the result is then the NormalHead of cosine_distance_loss (loss,
         sum of cosines, sum of angles, denominator) over the last convolution's output, normalWeights its row weights; None:
-        the [N, 3] prediction, every call as before. hierarchy / nextHierarchy (extension): as in MCClassS.forward."""
+        the [N, 3] prediction, every call as before. partLabels (extension): one part label per point -- the second
+        convolution's output (outFeatures wide) is then the per-point feature of a segmentation head, batch norm + ReLU and
+        conv_1x1_softmax_cross_entropy over numParts classes, and the result is its LossHead. hierarchy / nextHierarchy
+        (extension): as in MCClassS.forward."""
         numInputFeatures, batchSize, k = self.args
         cb = self.convBuilder
         cb.reset()
@@ -142,7 +151,10 @@ class MCNormS(torch.nn.Module):
                                    inNumFeatures=numInputFeatures, outNumFeatures=k, convRadius=0.15, multiFeatureConv=True)
         c1 = batch_norm_RELU_drop_out("BN_RELU", c1, isTraining, False, False, self.store)
         pred = cb.create_convolution(convName="Conv_2", inPointHierarchy=ph, inPointLevel=0, inFeatures=c1,
-                                     inNumFeatures=k, outNumFeatures=3, convRadius=0.15, multiFeatureConv=True)
+                                     inNumFeatures=k, outNumFeatures=self.outFeatures, convRadius=0.15, multiFeatureConv=True)
+        if partLabels is not None:
+            feats = batch_norm_RELU_drop_out("Parts_BN_RELU", pred, isTraining, False, False, self.store)
+            return conv_1x1_softmax_cross_entropy("Parts_Logits", feats, self.outFeatures, numParts, partLabels, store=self.store)
         if normals is None:
             return pred
         return cosine_distance_loss(pred, normals, normalWeights, store=self.store)
@@ -181,6 +193,41 @@ def train_normals(args, device, rng):
         opt.step()
         if step % 5 == 0 or step == args.steps - 1:
             print("step %3d  loss %.4f  mean angle %.2f deg" % (step, float(head.loss), math.degrees(float(mean_angle(head)))))
+
+
+NUM_PARTS = 8
+
+
+def part_labels(normals):
+    """The part of a point as a pure function of its analytic normal: the octant of the normal, 8 parts (int32 [N])."""
+    s = (normals >= 0).to(torch.int32)
+    return s[:, 0] + 2 * s[:, 1] + 4 * s[:, 2]
+
+
+def train_parts(args, device, rng):
+    """--parts: a per-point network (MCNormS's two convolutions, 16 features wide, and a softmax cross-entropy head) on the
+    synthetic ellipsoids with the octant of the normal as part label. The counts behind the part IoU are accumulated on the
+    device over the steps between two prints (segmentation_counts into one tensor); a print reads back the loss, the
+    accuracy and the mean of part_iou over the clouds seen since the last one -- nothing is read back per step."""
+    net = MCNormS(1, args.batch, 16, device, fused=args.fused_glue, fusedLoss=args.fused_loss, outFeatures=16)
+    P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
+    net(P, Bi, F, True, partLabels=part_labels(N), numParts=NUM_PARTS)  # creates the variables
+    opt = torch.optim.Adam(net.parameters(), lr=5e-3)
+    mask = torch.ones((args.batch, NUM_PARTS), dtype=torch.bool, device=device)   # every cloud has all eight parts
+    counts = torch.zeros((args.batch, NUM_PARTS, 3), dtype=torch.int64, device=device)
+    for step in range(args.steps):
+        P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
+        y = part_labels(N)
+        head = net(P, Bi, F, True, partLabels=y, numParts=NUM_PARTS)
+        opt.zero_grad(set_to_none=True)
+        head.loss.backward()
+        opt.step()
+        segmentation_counts(head, y, NUM_PARTS, Bi, args.batch, out=counts, store=net.store)
+        if step % 5 == 0 or step == args.steps - 1:
+            line = torch.stack([head.loss.detach().double(), head.correct.double() / head.denom.double(), part_iou(counts, mask).mean()])
+            loss, acc, iou = line.tolist()   # (the one read-back of this print)
+            print("step %3d  loss %.4f  acc %.2f  part IoU %.3f" % (step, loss, acc, iou))
+            counts.zero_()
 
 
 def synthetic_batch(batchSize, nPts, numCat, rng, device):
@@ -241,6 +288,9 @@ def main():
                          "With --normals: the cosine-distance loss and its metrics as one library op")
     ap.add_argument("--normals", action="store_true",
                     help="train MCNormS (normal estimation) on the ellipsoids' analytic normals instead of MCClassS")
+    ap.add_argument("--parts", action="store_true",
+                    help="train a per-point part segmentation (the octant of the normal, 8 parts) and print the part IoU from "
+                         "counts kept on the device (segmentation_counts, part_iou)")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()
@@ -252,6 +302,8 @@ def main():
     torch.autograd.set_multithreading_enabled(False)
     if args.normals:
         return train_normals(args, device, rng)
+    if args.parts:
+        return train_parts(args, device, rng)
     net = MCClassS(1, args.batch, 16, 4, device, fused=args.fused_glue, rows=torch.bfloat16 if args.bf16_rows else None,
                    fusedLinear=args.fused_linear, fusedLoss=args.fused_loss)
     make_batch = device_loader(args.batch, args.points, 4, rng, device) if args.device_loader else \

@@ -1037,6 +1037,31 @@ int mccnn_cosine_loss_fwd(const float* pred, const float* target, int n, int c, 
 int mccnn_cosine_loss_bwd(const float* pred, const float* target, int n, int c, const float* row_weights, const int* meta,
                           const float* loss_grad /* [1], device */, float* dpred, mccnn_stream_t stream);
 
+/* SEGMENTATION SCORES ON THE DEVICE: PER-CLOUD, PER-CLASS COUNTS (extension, ABI 25; seg_counts.hip). With B = num_clouds,
+ * C = num_classes, l = labels[i], p = pred[i] and b = batch_ids[i] (0 when batch_ids is NULL), row i is LIVE iff
+ *   0 <= l < C,  l != ignore_label,  its weight is not 0 (-0.0f is 0; a NaN is "not 0": the live rule of
+ *   mccnn_linear_xent_fwd),  0 <= b < B.
+ * A dead row changes nothing. A bad batch id makes the row dead: it is never clamped into another cloud's counts and nothing
+ * is read or written out of range. For a live row
+ *   counts[b, l, 2] += 1                                                    (ground truth G)
+ *   p == l:  counts[b, l, 0] += 1 (intersection I),  counts[b, l, 1] += 1    (union U)
+ *   p != l:  counts[b, l, 1] += 1,  and counts[b, p, 1] += 1 when 0 <= p < C
+ * so a prediction outside [0, C) on a live row is a miss of l and touches nothing else. With ignore_label = 0 and B = 1 these
+ * are the per-class sums of the reference's ScanNet.py:307-315, per cloud the intersection / union of ShapeNet.py:294-302.
+ * counts [B, C, 3] int64 is ADDED to: the caller zeroes it once and accumulates over as many calls as it likes. pred, labels,
+ * batch_ids [n] int32, row_weights [n] float32 (NULL: all 1), 4-byte aligned; where all of them are 16-byte aligned the rows
+ * are read 16 bytes at a time. One launch, no workspace, no memset; integer atomics only, so the same inputs give the same
+ * bytes in every run. Where B C 3 32-bit words fit mccnn_seg_counts_lds_bytes' budget (32 KB) every workgroup counts into a
+ * table in LDS and adds its non-zero words to counts at its end; above it live rows add straight to counts.
+ * mccnn_seg_counts_lds_bytes(B, C): the bytes of that table, 0: the route without one (and for B or C < 1).
+ * n == 0 launches nothing and returns 0. B or C < 1, n < 0, a NULL pred / labels / counts: MCCNN_E_BADARG; B C 3 >= 2^31:
+ * MCCNN_E_TOOLARGE; all before anything is launched. */
+size_t mccnn_seg_counts_lds_bytes(int num_clouds, int num_classes);
+int mccnn_seg_counts_add(const int* pred, const int* labels, const float* row_weights /* NULL: all 1 */,
+                         const int* batch_ids /* NULL: every row is cloud 0 */, int n, int num_clouds, int num_classes,
+                         int ignore_label /* < 0: none */, long long* counts /* [num_clouds, num_classes, 3], += */,
+                         mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

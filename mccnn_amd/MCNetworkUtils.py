@@ -34,7 +34,11 @@ with the switch off, torch code computes the same definition (_loss_head). Names
 state_dict are the same either way; without labels every helper returns the logits as before.
 The same switch covers the loss of the third task, normal estimation: cosine_distance_loss(pred, target) -> NormalHead(loss,
 cosSum, angleSum, denom) runs as ONE library op (dense_glue.cosine_distance_loss, csrc/cosine_loss.hip) where its conditions
-hold (_fused_cosine), as torch code of the same definition (_normal_head) everywhere else.
+hold (_fused_cosine), as torch code of the same definition (_normal_head) everywhere else. And the figure of the second task,
+segmentation: segmentation_counts(pred or LossHead, labels, ...) -> int64 [B, C, 3] counts of intersection, union and ground
+truth per cloud and class runs as ONE library launch (dense_glue.segmentation_counts, csrc/seg_counts.hip) under the same
+switch, as torch code of the same definition (_seg_counts_torch) everywhere else; segmentation_scores and part_iou form the
+reference's two IoU figures from the counts.
 """
 import collections
 import math
@@ -203,10 +207,11 @@ _FUSED_SYNC_OP = None      # native.bn_relu_drop_sync, likewise
 _FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
 _FUSED_LOSS_OP = None      # native.linear_softmax_xent, likewise
 _FUSED_COSINE_OP = None    # native.cosine_distance_loss, likewise
+_FUSED_SEG_OP = None       # native.segmentation_counts, likewise
 
 
 def _load_fused_ops():
-    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP
+    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP, _FUSED_SEG_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
@@ -214,8 +219,9 @@ def _load_fused_ops():
             _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP = native.bn_relu_drop, native.bn_relu_drop_sync, native.linear_bn_relu_drop
             _FUSED_LOSS_OP = native.linear_softmax_xent
             _FUSED_COSINE_OP = native.cosine_distance_loss
+            _FUSED_SEG_OP = native.segmentation_counts
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = _FUSED_COSINE_OP = None
+            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = _FUSED_COSINE_OP = _FUSED_SEG_OP = None
 
 
 def _fused_op(synced=False):
@@ -511,6 +517,148 @@ def reference_angle(head, c):
     """The figure the reference prints as its angle (ModelNetNormals.py): acos of the mean of u * v over all ELEMENTS, i.e.
     acos(cosSum / (c * D)) for rows of c columns -- not the angle of any row; kept for comparing with its logs."""
     return torch.acos(head.cosSum / (c * head.denom))
+
+
+#: What segmentation_scores returns, the figures of the reference's ScanNet.py:346-386. iou, acc: float64 [C], per class
+#: I / U and I / G (1.0 where the denominator is 0); meanIoU, meanAcc: 0-dim float64, their means over the classes other than
+#: ignoreLabel; totalAcc: 0-dim float64, sum I / sum G over those classes (1.0 when sum G is 0). All on the counts' device.
+SegScores = collections.namedtuple("SegScores", "iou acc meanIoU meanAcc totalAcc")
+
+
+def _fused_seg_counts(st, pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out):
+    """segmentation_counts as one library launch, or None where that form does not apply (the caller then runs the torch
+    code): the store's fusedLoss_ switch is off, pred and labels are not contiguous int32 or int64 tensors of n elements on
+    one HIP device, batchIds / weights / out are not what dense_glue.segmentation_counts takes, or the library does not
+    load."""
+    if not getattr(st, "fusedLoss_", False):
+        return None
+    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (numClasses, numClouds, ignoreLabel))
+            and numClasses >= 1 and numClouds >= 1 and numClasses * numClouds * 3 < (1 << 31) and abs(ignoreLabel) < (1 << 31)):
+        return None
+    if not (torch.is_tensor(pred) and pred.is_cuda and pred.dtype in (torch.int32, torch.int64) and pred.is_contiguous()
+            and (pred.dim() == 1 or (pred.dim() == 2 and pred.shape[1] == 1)) and pred.shape[0] < (1 << 31)):
+        return None
+    n = pred.shape[0]
+    shapes = ((n,), (n, 1))
+
+    def rows(t, dtypes):
+        return (torch.is_tensor(t) and t.dtype in dtypes and tuple(t.shape) in shapes and t.device == pred.device
+                and t.is_contiguous())
+
+    if not rows(labels, (torch.int32, torch.int64)):
+        return None
+    if batchIds is not None and not rows(batchIds, (torch.int32,)):
+        return None
+    if weights is not None and not (rows(weights, (torch.float32,)) and not weights.requires_grad):
+        return None
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int64 and out.device == pred.device
+                                and tuple(out.shape) == (numClouds, numClasses, 3) and out.is_contiguous()):
+        return None
+    _load_fused_ops()
+    if _FUSED_SEG_OP is None:
+        return None
+    return _FUSED_SEG_OP(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+
+
+def _seg_counts_torch(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
+    """segmentation_counts in torch code, on any device: the flat index of every (cloud, class, count) a row adds to, dead
+    rows and absent adds sent to one extra slot behind the table, and ONE integer scatter_add_ over all of them -- no
+    boolean indexing and no bincount, which would read a size back. Exact: integer adds in any order."""
+    B, C = int(numClouds), int(numClasses)
+    if B < 1 or C < 1:
+        raise ValueError("segmentation_counts expects numClouds, numClasses >= 1")
+    p = pred.detach().reshape(-1).to(torch.int64)
+    l = labels.detach().reshape(-1).to(torch.int64)
+    n = p.shape[0]
+    if l.shape[0] != n:
+        raise ValueError("segmentation_counts: labels must have pred's n elements")
+    live = (l >= 0) & (l < C)
+    if ignoreLabel >= 0:
+        live = live & (l != ignoreLabel)
+    if weights is not None:
+        if weights.numel() != n:
+            raise ValueError("segmentation_counts: weights must have pred's n elements")
+        live = live & (weights.detach().reshape(-1) != 0)   # (-0.0 is 0; a NaN is not)
+    if batchIds is not None:
+        if batchIds.numel() != n:
+            raise ValueError("segmentation_counts: batchIds must have pred's n elements")
+        b = batchIds.detach().reshape(-1).to(torch.int64)
+        live = live & (b >= 0) & (b < B)
+        row = b * C
+    else:
+        row = torch.zeros_like(l)
+    words = B * C * 3
+    if out is None:
+        out = torch.zeros((B, C, 3), dtype=torch.int64, device=p.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (B, C, 3) and out.device == p.device):
+        raise ValueError("segmentation_counts: out must be an int64 (numClouds, numClasses, 3) tensor on pred's device")
+    hit = live & (p == l)
+    other = live & ~hit & (p >= 0) & (p < C)
+    at = (row + l) * 3
+    dump = torch.full_like(l, words)
+    idx = torch.cat((torch.where(hit, at, dump), torch.where(live, at + 1, dump), torch.where(live, at + 2, dump),
+                     torch.where(other, (row + p) * 3 + 1, dump)))
+    flat = torch.zeros(words + 1, dtype=torch.int64, device=p.device)
+    flat.scatter_add_(0, idx, torch.ones_like(idx))
+    out += flat[:words].view(B, C, 3)
+    return out
+
+
+def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None, store=None):
+    """The counts behind every IoU of segmentation -> counts, int64 [numClouds, numClasses, 3] on pred's device: per cloud b
+    and class c the intersection I (rows with label c and prediction c), the union U (label c or prediction c) and the ground
+    truth G (label c), over the live rows. pred: [n] or [n, 1] integer predictions, or a LossHead, whose .pred is taken;
+    labels likewise; batchIds: [n] or [n, 1] int32, None: every row is cloud 0; weights: [n] or [n, 1] row weights, None:
+    all 1. A row is live iff 0 <= label < numClasses, label != ignoreLabel (< 0: none), its weight is not 0 and 0 <= batch
+    id < numClouds (a bad batch id makes a dead row; it is never counted for another cloud). A prediction outside [0,
+    numClasses) on a live row is a miss of its label and nothing else. out: None makes a zeroed tensor; a given one is ADDED
+    to and returned, so an evaluation accumulates over its batches (ShapeNet.py:291-308 at full batch size, ScanNet.py:306-315
+    with ignoreLabel = 0) and reads nothing back until it prints (segmentation_scores, part_iou). One library launch where
+    the store's fusedLoss_ says so and it applies (_fused_seg_counts, csrc/seg_counts.hip), torch code of the same definition
+    (_seg_counts_torch) otherwise, CPU tensors included; exact either way."""
+    if isinstance(pred, LossHead):
+        pred = pred.pred
+    st = store or _DEFAULT_STORE
+    if getattr(st, "fusedLoss_", False):
+        counts = _fused_seg_counts(st, pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+        if counts is not None:
+            return counts
+    return _seg_counts_torch(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+
+
+def _ratio_or_one(num, den):
+    """num / den in float64, 1.0 where den is 0 (the reference's rule for a class nobody has and nobody predicts)."""
+    return torch.where(den > 0, num / den.clamp_min(1.0), torch.ones_like(num))
+
+
+def segmentation_scores(counts, ignoreLabel=-1):
+    """The ScanNet rule (ScanNet.py:346-386) over counts [B, C, 3] of segmentation_counts -> SegScores(iou, acc, meanIoU,
+    meanAcc, totalAcc). The counts are summed over the clouds, in float64 (exact below 2^53); per class iou = I / U and acc =
+    I / G, each 1.0 where its denominator is 0; the means run over the classes other than ignoreLabel (< 0 or >= C: all of
+    them; 1.0 when none is left); totalAcc = sum I / sum G over those classes, 1.0 when sum G is 0. Torch ops on the counts'
+    device, nothing is read back."""
+    c = counts.to(torch.float64).sum(0)
+    I, U, G = c[:, 0], c[:, 1], c[:, 2]
+    iou, acc = _ratio_or_one(I, U), _ratio_or_one(I, G)
+    keep = (torch.arange(c.shape[0], device=c.device) != ignoreLabel).to(torch.float64)
+    k = keep.sum()
+    meanIoU = _ratio_or_one((iou * keep).sum(), k)
+    meanAcc = _ratio_or_one((acc * keep).sum(), k)
+    totalAcc = _ratio_or_one((I * keep).sum(), (G * keep).sum())
+    return SegScores(iou, acc, meanIoU, meanAcc, totalAcc)
+
+
+def part_iou(counts, classMask):
+    """The ShapeNet rule (ShapeNet.py:294-307) over counts [B, C, 3] of segmentation_counts -> float64 [B]: per cloud the mean
+    over its masked classes of I / U, 1.0 where U is 0. classMask: bool [B, C], row b marks the parts of cloud b's category;
+    a cloud whose mask is empty gives 1.0. The dataset figure of the reference is the plain mean of this over all models
+    (its per-category figure the mean over the models of a category). Torch ops on the counts' device, nothing is read
+    back."""
+    if tuple(classMask.shape) != tuple(counts.shape[:2]):
+        raise ValueError("part_iou: classMask must have shape (numClouds, numClasses)")
+    c = counts.to(torch.float64)
+    m = classMask.to(device=c.device, dtype=torch.float64)
+    return _ratio_or_one((_ratio_or_one(c[:, :, 0], c[:, :, 1]) * m).sum(1), m.sum(1))
 
 
 def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOutFeatures, layerName, keepProb,

@@ -166,6 +166,9 @@ SIGNATURES = {
     "mccnn_cosine_loss_workspace_bytes": (_sz, [_i, _i]),
     "mccnn_cosine_loss_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mccnn_cosine_loss_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    # per-cloud, per-class segmentation counts on the device (seg_counts.hip)
+    "mccnn_seg_counts_lds_bytes": (_sz, [_i, _i]),
+    "mccnn_seg_counts_add": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -1817,6 +1817,47 @@ std::tuple<Tensor, Tensor, Tensor> cosine_distance_loss(const Tensor& pred, cons
     return std::make_tuple(loss, sums, meta);
 }
 
+// ---- segmentation scores on the device: per-cloud, per-class counts (mccnn_seg_counts_add), the C++ form of
+// dense_glue.segmentation_counts -- the same library call with the same arguments, so the same bytes. Python has checked the
+// arguments and cast int64 pred / labels; here only what keeps the call inside its tensors. A plain function on the current
+// stream: nothing is differentiable. -> counts int64 [num_clouds, num_classes, 3] (out, added to, when given; else zeroed)
+Tensor segmentation_counts(const Tensor& pred, const Tensor& labels, int64_t num_classes, const c10::optional<Tensor>& batch_ids,
+                           int64_t num_clouds, const c10::optional<Tensor>& weights, int64_t ignore_label,
+                           const c10::optional<Tensor>& out) {
+    check_dev(pred, at::kInt, "pred");
+    check_dev(labels, at::kInt, "labels");
+    const int64_t n = pred.numel();
+    TORCH_CHECK(num_classes >= 1 && num_clouds >= 1 && num_clouds * num_classes * 3 < (1ll << 31) && n < (1ll << 31) &&
+                    labels.numel() == n && labels.device() == pred.device() && ignore_label >= -1 && ignore_label < (1ll << 31),
+                "segmentation_counts expects pred (n,) and labels (n,) int32, numClouds, numClasses >= 1");
+    Tensor bi, rw, counts;
+    if (batch_ids.has_value() && batch_ids->defined()) {
+        bi = *batch_ids;
+        check_dev(bi, at::kInt, "batchIds");
+        TORCH_CHECK(bi.numel() == n && bi.device() == pred.device(), "segmentation_counts: batchIds must have n elements");
+    }
+    if (weights.has_value() && weights->defined()) {
+        rw = *weights;
+        check_dev(rw, at::kFloat, "weights");
+        TORCH_CHECK(rw.numel() == n && rw.device() == pred.device(), "segmentation_counts: weights must have n elements");
+    }
+    const DevGuard device_guard((int)pred.device().index());
+    if (out.has_value() && out->defined()) {
+        counts = *out;
+        check_dev(counts, at::kLong, "out");
+        TORCH_CHECK(counts.dim() == 3 && counts.size(0) == num_clouds && counts.size(1) == num_classes && counts.size(2) == 3 &&
+                        counts.device() == pred.device(),
+                    "segmentation_counts: out must have shape (numClouds, numClasses, 3)");
+    } else {
+        counts = at::zeros({num_clouds, num_classes, 3}, pred.options().dtype(at::kLong));
+    }
+    check(mccnn_seg_counts_add(pred.data_ptr<int>(), labels.data_ptr<int>(), rw.defined() ? rw.data_ptr<float>() : nullptr,
+                               bi.defined() ? bi.data_ptr<int>() : nullptr, (int)n, (int)num_clouds, (int)num_classes,
+                               (int)ignore_label, reinterpret_cast<long long*>(counts.data_ptr<int64_t>()), cur_stream(pred)),
+          "segmentation_counts");
+    return counts;
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -2193,6 +2234,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("weights") = py::none(), py::arg("want_logits") = false, py::call_guard<py::gil_scoped_release>());
     mod.def("cosine_distance_loss", &cosine_distance_loss, py::arg("pred"), py::arg("target"), py::arg("weights") = py::none(),
             py::call_guard<py::gil_scoped_release>());
+    mod.def("segmentation_counts", &segmentation_counts, py::arg("pred"), py::arg("labels"), py::arg("num_classes"),
+            py::arg("batch_ids") = py::none(), py::arg("num_clouds") = 1, py::arg("weights") = py::none(),
+            py::arg("ignore_label") = -1, py::arg("out") = py::none(), py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

@@ -4,7 +4,8 @@ statistics updated in place -- on its own (bn_relu_dropout), with the batch stat
 (bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
 (csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream. And what closes the dense path: the last linear
 layer with the softmax cross-entropy, the predictions and the count of correct rows behind it (linear_softmax_xent,
-csrc/linear_xent.hip), and the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip).
+csrc/linear_xent.hip), the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip) and the
+counts behind the IoU of segmentation (segmentation_counts, csrc/seg_counts.hip).
 
 MCConvModule imports these names back: mccnn_amd.MCConvModule.bn_relu_dropout is this module's.
 mccnn_amd.native has the forms that go through the torch extension.
@@ -469,6 +470,70 @@ def cosine_distance_loss(pred, target, weights=None):
     raises), and sums and meta are NOT differentiable."""
     weights = _cosine_loss_args(pred, target, weights)
     return _CosineDistanceLoss.apply(pred, target, weights)
+
+
+# ---------------------------------------------------------------------------------------------
+# Segmentation scores on the device (csrc/seg_counts.hip, include/mccnn.h "SEGMENTATION SCORES ON THE DEVICE: PER-CLOUD,
+# PER-CLASS COUNTS"): (pred, labels) -> int64 [numClouds, numClasses, 3] counts of intersection, union and ground truth.
+def _seg_counts_args(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
+    """Checks of segmentation_counts (nothing is launched before they pass) -> (pred, labels, batchIds, weights) as the
+    library reads them: int32 [n] -- an int64 pred or labels is cast here, behind the checks, one torch launch each -- int32
+    [n] or None, float32 [n] or None."""
+    op = "segmentation_counts"
+    for v, name in ((numClasses, "numClasses"), (numClouds, "numClouds")):
+        _req(isinstance(v, int) and not isinstance(v, bool) and v >= 1, "%s expects %s >= 1" % (op, name))
+    _req(numClouds * numClasses * 3 < (1 << 31), "%s: numClouds * numClasses too large" % op)
+    _req(isinstance(ignoreLabel, int) and not isinstance(ignoreLabel, bool) and -(1 << 31) <= ignoreLabel < (1 << 31),
+         "%s expects an integer ignoreLabel (< 0: none)" % op)
+    _req(isinstance(pred, torch.Tensor) and pred.dtype in (torch.int32, torch.int64), "%s: pred must be an int32 (or int64) tensor" % op)
+    _req(pred.dim() in (1, 2) and (pred.dim() == 1 or pred.shape[1] == 1), "%s: pred must have shape (n,) or (n, 1)" % op)
+    n = pred.shape[0]
+    _req(n < (1 << 31), "%s: pred too large" % op)
+    _req(pred.is_contiguous(), "%s: pred must be contiguous" % op)
+    _req(isinstance(labels, torch.Tensor) and labels.dtype in (torch.int32, torch.int64),
+         "%s: labels must be an int32 (or int64) tensor" % op)
+    _req(tuple(labels.shape) in ((n,), (n, 1)), "%s: labels must have shape (n,) or (n, 1)" % op)
+    _req(labels.device == pred.device and labels.is_contiguous(), "%s: labels must be contiguous on pred's device" % op)
+    if batchIds is not None:
+        _req(isinstance(batchIds, torch.Tensor) and batchIds.dtype == torch.int32, "%s: batchIds must be an int32 tensor" % op)
+        _req(tuple(batchIds.shape) in ((n,), (n, 1)), "%s: batchIds must have shape (n,) or (n, 1)" % op)
+        _req(batchIds.device == pred.device and batchIds.is_contiguous(), "%s: batchIds must be contiguous on pred's device" % op)
+    if weights is not None:
+        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "%s: weights must be a float32 tensor" % op)
+        _req(tuple(weights.shape) in ((n,), (n, 1)), "%s: weights must have shape (n,) or (n, 1)" % op)
+        _req(weights.device == pred.device and weights.is_contiguous(), "%s: weights must be contiguous on pred's device" % op)
+        _req(not weights.requires_grad, "%s: no gradient with respect to weights" % op)
+    if out is not None:
+        _req(isinstance(out, torch.Tensor) and out.dtype == torch.int64, "%s: out must be an int64 tensor" % op)
+        _req(tuple(out.shape) == (numClouds, numClasses, 3), "%s: out must have shape (numClouds, numClasses, 3)" % op)
+        _req(out.device == pred.device and out.is_contiguous(), "%s: out must be contiguous on pred's device" % op)
+    _req(pred.is_cuda, "%s: pred must be a CUDA tensor" % op)
+    pred, labels = pred.detach().reshape(n), labels.detach().reshape(n)
+    if pred.dtype != torch.int32:
+        pred = pred.to(torch.int32)
+    if labels.dtype != torch.int32:
+        labels = labels.to(torch.int32)
+    return (pred, labels, None if batchIds is None else batchIds.detach().reshape(n),
+            None if weights is None else weights.detach().reshape(n))
+
+
+def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
+    """The counts behind the IoU of segmentation in one library launch -> counts, int64 (numClouds, numClasses, 3) on pred's
+    device: per cloud and class the intersection I, the union U and the ground truth G. pred, labels: (n,) or (n, 1), int32
+    taken as it is, int64 cast to int32 (one torch launch each); batchIds: int32 (n,) or (n, 1), None: every row is cloud 0;
+    weights: float32 (n,) or (n, 1), None: all 1. A row is live iff 0 <= label < numClasses, label != ignoreLabel (< 0:
+    none), its weight is not 0 and 0 <= batch id < numClouds -- a bad batch id makes a dead row, it is never counted for
+    another cloud. A live row adds 1 to G of its label; a hit adds 1 to I and U of it; a miss adds 1 to U of the label and to
+    U of the prediction where that is a class (a prediction outside [0, numClasses) is a miss and nothing else). out: None
+    makes a zeroed tensor; a given one is ADDED to and returned, so a caller accumulates over as many batches as it likes.
+    Integer atomics only: the same inputs give the same bytes. Nothing is differentiable and nothing is read back."""
+    pred, labels, batchIds, weights = _seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.zeros((numClouds, numClasses, 3), dtype=torch.int64, device=pred.device)
+    check(lib.mccnn_seg_counts_add(ptr(pred), ptr(labels), ptr(weights), ptr(batchIds), pred.shape[0], numClouds, numClasses,
+                                   max(ignoreLabel, -1), ptr(out), stream_handle()), "segmentation_counts")
+    return out
 
 
 # At the end on purpose: MCConvModule imports this module back at ITS end, and with both imports last each module finds the

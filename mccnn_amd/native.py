@@ -694,3 +694,14 @@ def cosine_distance_loss(pred, target, weights=None):
         return M.cosine_distance_loss(pred, target, weights)
     weights = M._cosine_loss_args(pred, target, weights)
     return _EXT.cosine_distance_loss(pred, target, weights)
+
+
+def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
+    """The counts behind the IoU of segmentation -> int64 (numClouds, numClasses, 3) (dense_glue.segmentation_counts: its
+    definition, checks and errors): one Python -> C++ call on the current stream when the extension is loaded, the ctypes op
+    otherwise -- the same library call either way, so the same bytes. A plain function: nothing is differentiable."""
+    from . import dense_glue as M
+    if _EXT is None:
+        return M.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    pred, labels, batchIds, weights = M._seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    return _EXT.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, max(ignoreLabel, -1), out)
