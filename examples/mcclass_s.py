@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mccnn_amd.MCConvBuilder import PointHierarchy, ConvolutionBuilder
 from mccnn_amd.MCNetworkUtils import (MLP_2_hidden, batch_norm_RELU_drop_out, conv_1x1, conv_1x1_batch_norm_RELU_drop_out,
                                       VariableStore, conv_1x1_softmax_cross_entropy, cosine_distance_loss, mean_angle, part_iou,
-                                      segmentation_counts)
+                                      segmentation_counts, voxel_counts, voxel_scores)
 
 
 class MCClassS(torch.nn.Module):
@@ -207,14 +207,18 @@ def part_labels(normals):
 def train_parts(args, device, rng):
     """--parts: a per-point network (MCNormS's two convolutions, 16 features wide, and a softmax cross-entropy head) on the
     synthetic ellipsoids with the octant of the normal as part label. The counts behind the part IoU are accumulated on the
-    device over the steps between two prints (segmentation_counts into one tensor); a print reads back the loss, the
-    accuracy and the mean of part_iou over the clouds seen since the last one -- nothing is read back per step."""
+    device over the steps between two prints (segmentation_counts into one tensor), and beside them the counts behind the
+    voxel accuracy (voxel_counts: 5 cm voxels over every cloud's own box, majority votes per voxel); a print reads back the
+    loss, the accuracy, the mean of part_iou over the clouds seen since the last one and the voxel accuracy (voxel_scores) in
+    ONE transfer -- nothing is read back per step (with --fused-loss; without it voxel_counts runs its torch code, whose
+    torch.unique waits for the device)."""
     net = MCNormS(1, args.batch, 16, device, fused=args.fused_glue, fusedLoss=args.fused_loss, outFeatures=16)
     P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
     net(P, Bi, F, True, partLabels=part_labels(N), numParts=NUM_PARTS)  # creates the variables
     opt = torch.optim.Adam(net.parameters(), lr=5e-3)
     mask = torch.ones((args.batch, NUM_PARTS), dtype=torch.bool, device=device)   # every cloud has all eight parts
     counts = torch.zeros((args.batch, NUM_PARTS, 3), dtype=torch.int64, device=device)
+    voxels = torch.zeros((args.batch, NUM_PARTS, 2), dtype=torch.int64, device=device)
     for step in range(args.steps):
         P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
         y = part_labels(N)
@@ -223,11 +227,14 @@ def train_parts(args, device, rng):
         head.loss.backward()
         opt.step()
         segmentation_counts(head, y, NUM_PARTS, Bi, args.batch, out=counts, store=net.store)
+        voxel_counts(P, head, y, NUM_PARTS, Bi, args.batch, out=voxels, store=net.store)
         if step % 5 == 0 or step == args.steps - 1:
-            line = torch.stack([head.loss.detach().double(), head.correct.double() / head.denom.double(), part_iou(counts, mask).mean()])
-            loss, acc, iou = line.tolist()   # (the one read-back of this print)
-            print("step %3d  loss %.4f  acc %.2f  part IoU %.3f" % (step, loss, acc, iou))
+            line = torch.stack([head.loss.detach().double(), head.correct.double() / head.denom.double(), part_iou(counts, mask).mean(),
+                                voxel_scores(voxels).meanAcc])
+            loss, acc, iou, vox = line.tolist()   # (the one read-back of this print)
+            print("step %3d  loss %.4f  acc %.2f  part IoU %.3f  voxel acc %.3f" % (step, loss, acc, iou, vox))
             counts.zero_()
+            voxels.zero_()
 
 
 def synthetic_batch(batchSize, nPts, numCat, rng, device):
@@ -290,7 +297,8 @@ def main():
                     help="train MCNormS (normal estimation) on the ellipsoids' analytic normals instead of MCClassS")
     ap.add_argument("--parts", action="store_true",
                     help="train a per-point part segmentation (the octant of the normal, 8 parts) and print the part IoU from "
-                         "counts kept on the device (segmentation_counts, part_iou)")
+                         "counts kept on the device (segmentation_counts, part_iou), and the voxel accuracy beside it "
+                         "(voxel_counts, voxel_scores)")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
     args = ap.parse_args()

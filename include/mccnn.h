@@ -1062,6 +1062,46 @@ int mccnn_seg_counts_add(const int* pred, const int* labels, const float* row_we
                          int ignore_label /* < 0: none */, long long* counts /* [num_clouds, num_classes, 3], += */,
                          mccnn_stream_t stream);
 
+/* VOXEL ACCURACY ON THE DEVICE: PER-VOXEL MAJORITY VOTES (extension, ABI 26; voxel_acc.hip, voxel_key.h). ScanNet's own
+ * metric (ScanNet.py:321-339): the points of a cloud are binned into the voxels of a grid of `resolution` over the cloud's box
+ * minimum, every occupied voxel votes for its most frequent label and its most frequent prediction, and the valid voxels are
+ * counted per label, all and those whose two votes agree. With B = num_clouds, C = num_classes, l = labels[i], p = pred[i] and
+ * b = batch_ids[i] (0 when batch_ids is NULL):
+ *   coordinates  v_a = ceilf((pts[i, a] - aabb_min[b, a]) / resolution) per axis a, the subtraction and the division correctly
+ *                rounded float32. Row i is DROPPED iff some v_a is not finite, below 0 or above 65535.
+ *   dead rows    l outside [0, C), b outside [0, B) (never clamped into another cloud, nothing is read out of range), or
+ *                dropped. Every other row is LIVE -- one whose label is ignore_label too: it votes and counts in the share.
+ *   voxel        of a live row: the integer tuple (b, v_x, v_y, v_z), kept as it is. (The reference flattens the triple in
+ *                float32 with strides nVoxels, which aliases (0, y, z) with (nVoxels_x, y - 1, z) and is inexact above 2^24;
+ *                the tuple does neither.)
+ *   per voxel    L[c] = its live rows with label c, P[c] = its live rows with p == c (a prediction outside [0, C) votes for
+ *                nothing), s = sum L, ul = the lowest c attaining max L, up = the lowest c attaining max P (0 when P is all
+ *                zero), g = L[ignore_label] (0 without one). VALID iff (double) g / (double) s < max_ignore_share in IEEE
+ *                double -- the reference's expression, with 0.3 -- and ul != ignore_label.
+ *   output       every valid voxel: counts[b, ul, 1] += 1 (G) and, where ul == up, counts[b, ul, 0] += 1 (V).
+ * counts [B, C, 2] int64 is ADDED to: the caller zeroes it once and accumulates over as many calls as it likes. dropped:
+ * optional int32 [1] device word, incremented by the number of rows with a label and a batch id in range that were dropped
+ * for their coordinates; the library never reads it. pts [n, 3] float32, pred, labels, batch_ids [n] int32, aabb_min [B, 3]
+ * float32: 4-byte aligned, nothing more. Integer atomics only and no float in any decision but the per-row ceilf and the
+ * per-voxel quotient: the same inputs give the same bytes in every run and in any arrival order.
+ * A hash table in the workspace: cap slots, a power of two, of one uint64 key (1 << 63 | b << 48 | v_x << 32 | v_y << 16 | v_z;
+ * 0: empty -- an all-zero workspace is the empty table) and a uint32 [2, C] histogram each; home slot a murmur-style mix of
+ * the key masked by cap - 1, linear probing. mccnn_voxel_acc_workspace_bytes(n, C) = cap_rec (8 + 8 C), cap_rec the smallest
+ * power of two >= max(2 n, 64) (0 for n < 0, n >= 2^30 or C < 1). Any 16-byte aligned workspace that holds cap_min slots, the
+ * smallest power of two > n, is accepted (an empty slot always exists); the largest power of two that fits, up to cap_rec, is
+ * used. ws_clean = 0: the used part of the workspace is cleared first (one launch more); ws_clean = 1: the caller vouches
+ * that it is all zero. Either way the call leaves what it used all zero again, so a workspace that only this entry writes
+ * is cleared once. Launches: 3 with ws_clean = 0, 2 with ws_clean = 1 (vote, score), 0 for n == 0, which returns 0.
+ * A NULL pts / pred / labels / aabb_min / counts / ws, n < 0, B or C < 1, a resolution that is not a finite positive number,
+ * a workspace off a 16-byte boundary: MCCNN_E_BADARG; B > 32768, n >= 2^30 or B C 2 >= 2^31: MCCNN_E_TOOLARGE; a workspace
+ * below cap_min (8 + 8 C) bytes: MCCNN_E_WORKSPACE; all before anything is launched. */
+size_t mccnn_voxel_acc_workspace_bytes(int n, int num_classes);
+int mccnn_voxel_acc_add(const float* pts, const int* pred, const int* labels, const int* batch_ids /* NULL: cloud 0 */,
+                        const float* aabb_min /* [num_clouds, 3] */, int n, int num_clouds, int num_classes,
+                        int ignore_label /* < 0: none */, float resolution, double max_ignore_share,
+                        long long* counts /* [num_clouds, num_classes, 2], += */, int* dropped /* NULL: not counted */,
+                        void* ws, size_t ws_bytes, int ws_clean, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

@@ -38,11 +38,15 @@ hold (_fused_cosine), as torch code of the same definition (_normal_head) everyw
 segmentation: segmentation_counts(pred or LossHead, labels, ...) -> int64 [B, C, 3] counts of intersection, union and ground
 truth per cloud and class runs as ONE library launch (dense_glue.segmentation_counts, csrc/seg_counts.hip) under the same
 switch, as torch code of the same definition (_seg_counts_torch) everywhere else; segmentation_scores and part_iou form the
-reference's two IoU figures from the counts.
+reference's two IoU figures from the counts. ScanNet's third figure, the voxel accuracy, likewise: voxel_counts(points, pred or
+LossHead, labels, ...) -> int64 [B, C, 2] counts of valid voxels whose majority label and majority prediction agree, and of
+all valid voxels, as one library op (dense_glue.voxel_counts, csrc/voxel_acc.hip: a device hash table, two launches) under
+the same switch, as torch code of the same definition (_voxel_counts_torch) everywhere else; voxel_scores forms the figure.
 """
 import collections
 import math
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -208,10 +212,11 @@ _FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
 _FUSED_LOSS_OP = None      # native.linear_softmax_xent, likewise
 _FUSED_COSINE_OP = None    # native.cosine_distance_loss, likewise
 _FUSED_SEG_OP = None       # native.segmentation_counts, likewise
+_FUSED_VOXEL_OP = None     # native.voxel_counts, likewise
 
 
 def _load_fused_ops():
-    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP, _FUSED_SEG_OP
+    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP, _FUSED_SEG_OP, _FUSED_VOXEL_OP
     if _FUSED_OP is False:
         try:
             from . import _lib, native
@@ -220,8 +225,10 @@ def _load_fused_ops():
             _FUSED_LOSS_OP = native.linear_softmax_xent
             _FUSED_COSINE_OP = native.cosine_distance_loss
             _FUSED_SEG_OP = native.segmentation_counts
+            _FUSED_VOXEL_OP = native.voxel_counts
         except (ImportError, OSError, AttributeError, RuntimeError):
             _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = _FUSED_COSINE_OP = _FUSED_SEG_OP = None
+            _FUSED_VOXEL_OP = None
 
 
 def _fused_op(synced=False):
@@ -659,6 +666,208 @@ def part_iou(counts, classMask):
     c = counts.to(torch.float64)
     m = classMask.to(device=c.device, dtype=torch.float64)
     return _ratio_or_one((_ratio_or_one(c[:, :, 0], c[:, :, 1]) * m).sum(1), m.sum(1))
+
+
+#: What voxel_scores returns, ScanNet's voxel accuracy (ScanNet.py:367-384). acc: float64 [C], per class V / G (1.0 where G is
+#: 0); meanAcc: 0-dim float64, its mean over the classes other than ignoreLabel. On the counts' device.
+VoxelScores = collections.namedtuple("VoxelScores", "acc meanAcc")
+
+
+def _voxel_res(resolution):
+    """resolution as the float32 the definition divides by, as a Python float; None where it is not a finite positive one."""
+    try:
+        with np.errstate(over="ignore"):
+            res = float(np.float32(resolution))
+    except (TypeError, ValueError):
+        return None
+    return res if 0.0 < res < float("inf") else None
+
+
+def _fused_voxel_counts(st, points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel, maxIgnoreShare,
+                        out, dropped):
+    """voxel_counts as one library op, or None where that form does not apply (the caller then runs the torch code): the
+    store's fusedLoss_ switch is off, points is not a contiguous float32 [n, 3] tensor on a HIP device, pred and labels are not
+    contiguous int32 or int64 tensors of n elements on it, batchIds / aabbMin / out / dropped are not what
+    dense_glue.voxel_counts takes, or the library does not load."""
+    if not getattr(st, "fusedLoss_", False):
+        return None
+    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (numClasses, numClouds, ignoreLabel))
+            and numClasses >= 1 and 1 <= numClouds <= 32768 and numClasses * numClouds * 2 < (1 << 31) and abs(ignoreLabel) < (1 << 31)):
+        return None
+    if _voxel_res(resolution) is None or isinstance(maxIgnoreShare, bool) or not isinstance(maxIgnoreShare, (int, float, np.floating)):
+        return None
+    if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2
+            and points.shape[1] == 3 and points.is_contiguous() and points.shape[0] < (1 << 30)):
+        return None
+    n = points.shape[0]
+    shapes = ((n,), (n, 1))
+
+    def rows(t, dtypes):
+        return (torch.is_tensor(t) and t.dtype in dtypes and tuple(t.shape) in shapes and t.device == points.device
+                and t.is_contiguous())
+
+    if not (rows(pred, (torch.int32, torch.int64)) and rows(labels, (torch.int32, torch.int64))):
+        return None
+    if batchIds is not None and not rows(batchIds, (torch.int32,)):
+        return None
+    if not (torch.is_tensor(aabbMin) and aabbMin.dtype == torch.float32 and tuple(aabbMin.shape) == (numClouds, 3)
+            and aabbMin.device == points.device and aabbMin.is_contiguous()):
+        return None
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int64 and out.device == points.device
+                                and tuple(out.shape) == (numClouds, numClasses, 2) and out.is_contiguous()):
+        return None
+    if dropped is not None and not (torch.is_tensor(dropped) and dropped.dtype == torch.int32 and dropped.numel() == 1
+                                    and dropped.device == points.device):
+        return None
+    _load_fused_ops()
+    if _FUSED_VOXEL_OP is None:
+        return None
+    return _FUSED_VOXEL_OP(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel, maxIgnoreShare,
+                           out, dropped)
+
+
+def _lowest_argmax(h):
+    """Per row of the integer table h [m, C] the LOWEST column attaining the row's maximum (0 for an all-zero row)."""
+    C = h.shape[1]
+    cols = torch.arange(C, device=h.device, dtype=torch.int64).expand_as(h)
+    return torch.where(h == h.max(1, keepdim=True).values, cols, torch.full_like(cols, C)).min(1).values
+
+
+def _voxel_counts_torch(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05,
+                        ignoreLabel=-1, maxIgnoreShare=0.3, out=None, dropped=None):
+    """voxel_counts in torch code, on any device, exact: the voxel coordinates as the float32 ceil of a correctly rounded
+    float32 quotient (formed in float64 and rounded once more: 53 >= 2 * 24 + 2 bits, so the double rounding is the single
+    one), the tuples packed into int64 keys, torch.unique over the keys, integer scatter_add_ histograms, the lowest class of
+    every tie and the double quotient of the rule. torch.unique returns a size: this path SYNCHRONISES with the device. It is
+    an evaluation path."""
+    B, C = int(numClouds), int(numClasses)
+    if B < 1 or C < 1 or B > 32768:
+        raise ValueError("voxel_counts expects numClasses >= 1 and 1 <= numClouds <= 32768")
+    res = _voxel_res(resolution)
+    if res is None:
+        raise ValueError("voxel_counts expects a finite resolution > 0 (as float32)")
+    if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 3 and points.dtype == torch.float32):
+        raise ValueError("voxel_counts: points must be a float32 (n, 3) tensor")
+    dev = points.device
+    n = points.shape[0]
+    pts = points.detach()
+    p = pred.detach().reshape(-1).to(torch.int64)
+    l = labels.detach().reshape(-1).to(torch.int64)
+    if p.shape[0] != n or l.shape[0] != n:
+        raise ValueError("voxel_counts: pred and labels must have points' n elements")
+    if not (torch.is_tensor(aabbMin) and tuple(aabbMin.shape) == (B, 3) and aabbMin.dtype == torch.float32 and aabbMin.device == dev):
+        raise ValueError("voxel_counts: aabbMin must be a float32 (numClouds, 3) tensor on points' device")
+    if out is None:
+        out = torch.zeros((B, C, 2), dtype=torch.int64, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (B, C, 2) and out.device == dev):
+        raise ValueError("voxel_counts: out must be an int64 (numClouds, numClasses, 2) tensor on points' device")
+    if dropped is not None and not (torch.is_tensor(dropped) and dropped.dtype == torch.int32 and dropped.numel() == 1
+                                    and dropped.device == dev):
+        raise ValueError("voxel_counts: dropped must be an int32 tensor of one element on points' device")
+    if n == 0:
+        return out
+    live = (l >= 0) & (l < C)
+    if batchIds is not None:
+        if batchIds.numel() != n:
+            raise ValueError("voxel_counts: batchIds must have points' n elements")
+        b = batchIds.detach().reshape(-1).to(torch.int64)
+        live = live & (b >= 0) & (b < B)
+        b = b.clamp(0, B - 1)                      # (dead rows read some box; they are dead)
+    else:
+        b = torch.zeros_like(l)
+    d = pts - aabbMin.detach()[b]                  # float32, correctly rounded everywhere
+    v = torch.ceil((d.to(torch.float64) / res).to(torch.float32))
+    inside = ((v >= 0) & (v <= 65535)).all(1)      # (a NaN fails both)
+    if dropped is not None:
+        dropped += (live & ~inside).sum().to(torch.int32).reshape(dropped.shape)
+    live = live & inside
+    vi = torch.where(inside.unsqueeze(1), v, torch.zeros_like(v)).to(torch.int64)
+    key = torch.where(live, (b << 48) | (vi[:, 0] << 32) | (vi[:, 1] << 16) | vi[:, 2], torch.full_like(b, -1))
+    ukey, slot = torch.unique(key, return_inverse=True)     # (sorted: the dead rows' -1, when there is one, is slot 0)
+    m = ukey.shape[0]
+    dump = torch.full_like(slot, m * C)
+    hl = torch.zeros(m * C + 1, dtype=torch.int64, device=dev)
+    hp = torch.zeros(m * C + 1, dtype=torch.int64, device=dev)
+    one = torch.ones_like(slot)
+    hl.scatter_add_(0, torch.where(live, slot * C + l, dump), one)
+    hp.scatter_add_(0, torch.where(live & (p >= 0) & (p < C), slot * C + p.clamp(0, C - 1), dump), one)
+    hl, hp = hl[:m * C].view(m, C), hp[:m * C].view(m, C)
+    s = hl.sum(1)
+    ul, up = _lowest_argmax(hl), _lowest_argmax(hp)
+    g = hl[:, ignoreLabel] if 0 <= ignoreLabel < C else torch.zeros_like(s)
+    valid = (ukey >= 0) & (s > 0) & (g.to(torch.float64) / s.clamp_min(1).to(torch.float64) < float(maxIgnoreShare)) & (ul != ignoreLabel)
+    at = (((ukey >> 48) & 0x7fff).clamp(0, B - 1) * C + ul) * 2
+    words = B * C * 2
+    flat = torch.zeros(words + 1, dtype=torch.int64, device=dev)
+    idx = torch.cat((torch.where(valid, at + 1, torch.full_like(at, words)), torch.where(valid & (ul == up), at, torch.full_like(at, words))))
+    flat.scatter_add_(0, idx, torch.ones_like(idx))
+    out += flat[:words].view(B, C, 2)
+    return out
+
+
+def _box_min(points, batchIds, numClouds):
+    """The per-cloud minimum corner the voxel grid starts at. On a HIP device the library's compute_aabb (scaleInv=False:
+    bit-exact to the per-cloud minimum); elsewhere torch's amin per cloud. Either way bad batch ids are CLAMPED here."""
+    n = points.shape[0]
+    if batchIds is None:
+        bids = torch.zeros((n, 1), dtype=torch.int32, device=points.device)
+    else:
+        bids = batchIds.detach().reshape(n, 1).to(torch.int32)
+    if points.is_cuda:
+        try:
+            from . import MCConvModule as M
+            return M.compute_aabb(points.detach().contiguous(), bids.contiguous(), int(numClouds), False)[0]
+        except (ImportError, OSError, AttributeError):
+            pass
+    idx = bids.reshape(-1).to(torch.int64).clamp(0, int(numClouds) - 1).unsqueeze(1).expand(n, 3)
+    mn = torch.full((int(numClouds), 3), float("inf"), dtype=torch.float32, device=points.device)
+    return mn.scatter_reduce(0, idx, points.detach(), "amin", include_self=True)
+
+
+def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05, ignoreLabel=-1,
+                 maxIgnoreShare=0.3, out=None, dropped=None, store=None):
+    """The counts behind ScanNet's voxel accuracy (ScanNet.py:321-339) -> counts, int64 [numClouds, numClasses, 2] on points'
+    device: [b, c, 1] = G, the valid voxels of cloud b whose most frequent label is c; [b, c, 0] = V, those of them whose most
+    frequent prediction is c as well. points: float32 [n, 3]; pred: [n] or [n, 1] integer predictions, or a LossHead, whose
+    .pred is taken; labels likewise; batchIds: [n] or [n, 1] int32, None: every row is cloud 0. The voxel of a row is the
+    integer tuple (b, ceil((p - aabbMin[b]) / resolution)) with float32 arithmetic per axis (resolution is taken as float32;
+    the default is the reference's 5 cm). aabbMin: float32 [numClouds, 3]; None takes the per-cloud minimum of the points
+    (compute_aabb with scaleInv=False on a HIP device) -- compute_aabb CLAMPS bad batch ids into a cloud's box, so a caller
+    whose batch ids may be out of range passes its own box. A row is dead iff its label is outside [0, numClasses), its batch
+    id outside [0, numClouds) or one of its coordinates is not finite, below 0 or above 65535 (dropped: optional int32 [1]
+    tensor on the device, incremented by the number of rows dropped for their coordinates). A row labelled ignoreLabel (< 0:
+    none) is live: it votes and counts in the share. Per voxel the lowest class wins a tie, a prediction outside [0,
+    numClasses) votes for nothing, and the voxel is valid iff the share of ignoreLabel among its rows is below maxIgnoreShare
+    (in double, the reference's 0.3) and its majority label is not ignoreLabel. Two departures from the reference: it flattens
+    the triple in float32 with strides nVoxels, which merges (0, y, z) with (nVoxels_x, y - 1, z) and loses exactness above
+    2^24; the tuple here does neither. out: None makes a zeroed tensor; a given one is ADDED to and returned, so an evaluation
+    accumulates over its rooms and reads nothing back until it prints (voxel_scores). One library op (two launches) where the
+    store's fusedLoss_ says so and it applies (_fused_voxel_counts, csrc/voxel_acc.hip), torch code of the same definition
+    (_voxel_counts_torch) otherwise, CPU tensors included; exact either way. The torch code uses torch.unique and therefore
+    synchronises with the device."""
+    if isinstance(pred, LossHead):
+        pred = pred.pred
+    st = store or _DEFAULT_STORE
+    if aabbMin is None:
+        aabbMin = _box_min(points, batchIds, numClouds)
+    if getattr(st, "fusedLoss_", False):
+        counts = _fused_voxel_counts(st, points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel,
+                                     maxIgnoreShare, out, dropped)
+        if counts is not None:
+            return counts
+    return _voxel_counts_torch(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel,
+                               maxIgnoreShare, out, dropped)
+
+
+def voxel_scores(counts, ignoreLabel=-1):
+    """ScanNet's voxel accuracy (ScanNet.py:367-384) over counts [B, C, 2] of voxel_counts -> VoxelScores(acc, meanAcc). The
+    counts are summed over the clouds, in float64 (exact below 2^53); per class acc = V / G, 1.0 where G is 0; meanAcc is the
+    mean over the classes other than ignoreLabel (< 0 or >= C: all of them; 1.0 when none is left). Torch ops on the counts'
+    device, nothing is read back."""
+    c = counts.to(torch.float64).sum(0)
+    acc = _ratio_or_one(c[:, 0], c[:, 1])
+    keep = (torch.arange(c.shape[0], device=c.device) != ignoreLabel).to(torch.float64)
+    return VoxelScores(acc, _ratio_or_one((acc * keep).sum(), keep.sum()))
 
 
 def MLP_2_hidden(features, numInputFeatures, hidden1_units, hidden2_units, numOutFeatures, layerName, keepProb,

@@ -169,6 +169,9 @@ SIGNATURES = {
     # per-cloud, per-class segmentation counts on the device (seg_counts.hip)
     "mccnn_seg_counts_lds_bytes": (_sz, [_i, _i]),
     "mccnn_seg_counts_add": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # voxel accuracy on the device: per-voxel majority votes in a hash table (voxel_acc.hip)
+    "mccnn_voxel_acc_workspace_bytes": (_sz, [_i, _i]),
+    "mccnn_voxel_acc_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_double, _vp, _vp, _vp, _sz, _i, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -1858,6 +1858,60 @@ Tensor segmentation_counts(const Tensor& pred, const Tensor& labels, int64_t num
     return counts;
 }
 
+// ---- voxel accuracy on the device: per-voxel majority votes (mccnn_voxel_acc_add), the C++ form of dense_glue.voxel_counts
+// -- the same library call with the same arguments and the same table (ws: Python's zeroed tensor, handed over clean and left
+// clean), so the same bytes. Python has checked the arguments and cast int64 pred / labels; here only what keeps the call
+// inside its tensors. -> counts int64 [num_clouds, num_classes, 2] (out, added to, when given; else zeroed)
+Tensor voxel_counts(const Tensor& points, const Tensor& pred, const Tensor& labels, int64_t num_classes,
+                    const c10::optional<Tensor>& batch_ids, int64_t num_clouds, const Tensor& aabb_min, double resolution,
+                    int64_t ignore_label, double max_ignore_share, const c10::optional<Tensor>& out,
+                    const c10::optional<Tensor>& dropped, const c10::optional<Tensor>& ws) {
+    check_dev(points, at::kFloat, "points");
+    check_dev(pred, at::kInt, "pred");
+    check_dev(labels, at::kInt, "labels");
+    check_dev(aabb_min, at::kFloat, "aabbMin");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "voxel_counts expects points (n, 3)");
+    const int64_t n = points.size(0);
+    TORCH_CHECK(num_classes >= 1 && num_clouds >= 1 && num_clouds <= 32768 && num_clouds * num_classes * 2 < (1ll << 31) &&
+                    n < (1ll << 30) && pred.numel() == n && labels.numel() == n && aabb_min.numel() == num_clouds * 3 &&
+                    pred.device() == points.device() && labels.device() == points.device() && aabb_min.device() == points.device() &&
+                    ignore_label >= -1 && ignore_label < (1ll << 31),
+                "voxel_counts expects points (n, 3) float32, pred (n,) and labels (n,) int32, aabbMin (numClouds, 3)");
+    Tensor bi, counts, dr, table;
+    if (batch_ids.has_value() && batch_ids->defined()) {
+        bi = *batch_ids;
+        check_dev(bi, at::kInt, "batchIds");
+        TORCH_CHECK(bi.numel() == n && bi.device() == points.device(), "voxel_counts: batchIds must have n elements");
+    }
+    if (dropped.has_value() && dropped->defined()) {
+        dr = *dropped;
+        check_dev(dr, at::kInt, "dropped");
+        TORCH_CHECK(dr.numel() == 1 && dr.device() == points.device(), "voxel_counts: dropped must have one element");
+    }
+    const DevGuard device_guard((int)points.device().index());
+    if (out.has_value() && out->defined()) {
+        counts = *out;
+        check_dev(counts, at::kLong, "out");
+        TORCH_CHECK(counts.dim() == 3 && counts.size(0) == num_clouds && counts.size(1) == num_classes && counts.size(2) == 2 &&
+                        counts.device() == points.device(),
+                    "voxel_counts: out must have shape (numClouds, numClasses, 2)");
+    } else {
+        counts = at::zeros({num_clouds, num_classes, 2}, points.options().dtype(at::kLong));
+    }
+    if (n == 0) return counts;
+    TORCH_CHECK(ws.has_value() && ws->defined(), "voxel_counts: no table");
+    table = *ws;
+    check_dev(table, at::kByte, "ws");
+    TORCH_CHECK(table.device() == points.device(), "voxel_counts: the table must be on points' device");
+    check(mccnn_voxel_acc_add(points.data_ptr<float>(), pred.data_ptr<int>(), labels.data_ptr<int>(),
+                              bi.defined() ? bi.data_ptr<int>() : nullptr, aabb_min.data_ptr<float>(), (int)n, (int)num_clouds,
+                              (int)num_classes, (int)ignore_label, (float)resolution, max_ignore_share,
+                              reinterpret_cast<long long*>(counts.data_ptr<int64_t>()), dr.defined() ? dr.data_ptr<int>() : nullptr,
+                              table.data_ptr(), (size_t)table.numel(), 1, cur_stream(points)),
+          "voxel_counts");
+    return counts;
+}
+
 // ---- point hierarchy of the NEXT batch, built on a stream of its own by a helper thread -------------------------------
 // A hierarchy depends on the points only. Built inline it is a chain of ~13 small dependent kernels per level that ends in
 // a read-back of the level sizes (and, for an absolute radius, starts with one of the box extent): the host cannot issue
@@ -2237,6 +2291,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("segmentation_counts", &segmentation_counts, py::arg("pred"), py::arg("labels"), py::arg("num_classes"),
             py::arg("batch_ids") = py::none(), py::arg("num_clouds") = 1, py::arg("weights") = py::none(),
             py::arg("ignore_label") = -1, py::arg("out") = py::none(), py::call_guard<py::gil_scoped_release>());
+    mod.def("voxel_counts", &voxel_counts, py::arg("points"), py::arg("pred"), py::arg("labels"), py::arg("num_classes"),
+            py::arg("batch_ids"), py::arg("num_clouds"), py::arg("aabb_min"), py::arg("resolution"), py::arg("ignore_label"),
+            py::arg("max_ignore_share"), py::arg("out") = py::none(), py::arg("dropped") = py::none(), py::arg("ws") = py::none(),
+            py::call_guard<py::gil_scoped_release>());
     mod.def("compute_aabb", &compute_aabb);
     mod.def("hierarchy_levels", &hierarchy_levels, py::call_guard<py::gil_scoped_release>());
     py::class_<HierFuture, std::shared_ptr<HierFuture>>(mod, "HierarchyFuture")

@@ -4,8 +4,9 @@ statistics updated in place -- on its own (bn_relu_dropout), with the batch stat
 (bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
 (csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream. And what closes the dense path: the last linear
 layer with the softmax cross-entropy, the predictions and the count of correct rows behind it (linear_softmax_xent,
-csrc/linear_xent.hip), the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip) and the
-counts behind the IoU of segmentation (segmentation_counts, csrc/seg_counts.hip).
+csrc/linear_xent.hip), the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip), the
+counts behind the IoU of segmentation (segmentation_counts, csrc/seg_counts.hip) and those behind ScanNet's voxel accuracy
+(voxel_counts, csrc/voxel_acc.hip).
 
 MCConvModule imports these names back: mccnn_amd.MCConvModule.bn_relu_dropout is this module's.
 mccnn_amd.native has the forms that go through the torch extension.
@@ -533,6 +534,119 @@ def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, we
         out = torch.zeros((numClouds, numClasses, 3), dtype=torch.int64, device=pred.device)
     check(lib.mccnn_seg_counts_add(ptr(pred), ptr(labels), ptr(weights), ptr(batchIds), pred.shape[0], numClouds, numClasses,
                                    max(ignoreLabel, -1), ptr(out), stream_handle()), "segmentation_counts")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Voxel accuracy on the device (csrc/voxel_acc.hip, include/mccnn.h "VOXEL ACCURACY ON THE DEVICE: PER-VOXEL MAJORITY VOTES"):
+# (points, pred, labels, box minimum) -> int64 [numClouds, numClasses, 2] counts of valid voxels whose votes agree (V) and of
+# all valid voxels (G), per cloud and majority label.
+_VOXEL_WS = {}   # (device index, raw stream, cap_rec, numClasses) -> the hash table: all zero between calls
+_VOXEL_WS_MAX = 8
+
+
+def voxel_cap_rec(n):
+    """The recommended slots of the table for n rows: the smallest power of two >= max(2 n, 64)."""
+    cap = 64
+    while cap < 2 * n:
+        cap <<= 1
+    return cap
+
+
+def _voxel_ws(n, numClasses, device):
+    """The op's hash table: a torch.zeros tensor of mccnn_voxel_acc_workspace_bytes(n, C) bytes kept per (device, stream,
+    cap_rec, C). Zeroed ONCE: every call leaves what it used all zero again, so it is handed over with ws_clean = 1. Calls on
+    one stream are ordered; another stream gets a table of its own."""
+    cap = voxel_cap_rec(n)
+    key = (device.index, stream_handle(), cap, numClasses)
+    ws = _VOXEL_WS.get(key)
+    if ws is None:
+        while len(_VOXEL_WS) >= _VOXEL_WS_MAX:
+            _VOXEL_WS.pop(next(iter(_VOXEL_WS)))
+        ws = _VOXEL_WS[key] = torch.zeros(cap * (8 + 8 * numClasses), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _voxel_counts_args(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05,
+                       ignoreLabel=-1, maxIgnoreShare=0.3, out=None, dropped=None):
+    """Checks of voxel_counts (nothing is launched before they pass) -> (points, pred, labels, batchIds, aabbMin, resolution,
+    maxIgnoreShare) as the library reads them: float32 [n, 3], int32 [n] -- an int64 pred or labels is cast here, behind the
+    checks, one torch launch each -- int32 [n] or None, float32 [numClouds, 3], the float32 value of resolution as a float, a
+    float."""
+    op = "voxel_counts"
+    for v, name in ((numClasses, "numClasses"), (numClouds, "numClouds")):
+        _req(isinstance(v, int) and not isinstance(v, bool) and v >= 1, "%s expects %s >= 1" % (op, name))
+    _req(numClouds <= 32768 and numClouds * numClasses * 2 < (1 << 31), "%s: numClouds (<= 32768) * numClasses too large" % op)
+    _req(isinstance(ignoreLabel, int) and not isinstance(ignoreLabel, bool) and -(1 << 31) <= ignoreLabel < (1 << 31),
+         "%s expects an integer ignoreLabel (< 0: none)" % op)
+    _req(isinstance(resolution, (int, float, _np.floating)) and not isinstance(resolution, bool), "%s expects a number as resolution" % op)
+    with _np.errstate(over="ignore"):
+        res = float(_np.float32(resolution))
+    _req(res > 0.0 and res != float("inf"), "%s expects a finite resolution > 0 (as float32)" % op)
+    _req(isinstance(maxIgnoreShare, (int, float, _np.floating)) and not isinstance(maxIgnoreShare, bool),
+         "%s expects a number as maxIgnoreShare" % op)
+    _req(isinstance(points, torch.Tensor) and points.dtype == torch.float32, "%s: points must be a float32 tensor" % op)
+    _req(points.dim() == 2 and points.shape[1] == 3, "%s: points must have shape (n, 3)" % op)
+    n = points.shape[0]
+    _req(n < (1 << 30), "%s: points too large" % op)
+    _req(points.is_contiguous(), "%s: points must be contiguous" % op)
+    for t, name in ((pred, "pred"), (labels, "labels")):
+        _req(isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64), "%s: %s must be an int32 (or int64) tensor" % (op, name))
+        _req(tuple(t.shape) in ((n,), (n, 1)), "%s: %s must have shape (n,) or (n, 1)" % (op, name))
+        _req(t.device == points.device and t.is_contiguous(), "%s: %s must be contiguous on points' device" % (op, name))
+    if batchIds is not None:
+        _req(isinstance(batchIds, torch.Tensor) and batchIds.dtype == torch.int32, "%s: batchIds must be an int32 tensor" % op)
+        _req(tuple(batchIds.shape) in ((n,), (n, 1)), "%s: batchIds must have shape (n,) or (n, 1)" % op)
+        _req(batchIds.device == points.device and batchIds.is_contiguous(), "%s: batchIds must be contiguous on points' device" % op)
+    _req(isinstance(aabbMin, torch.Tensor) and aabbMin.dtype == torch.float32, "%s: aabbMin must be a float32 tensor" % op)
+    _req(tuple(aabbMin.shape) == (numClouds, 3), "%s: aabbMin must have shape (numClouds, 3)" % op)
+    _req(aabbMin.device == points.device and aabbMin.is_contiguous(), "%s: aabbMin must be contiguous on points' device" % op)
+    if out is not None:
+        _req(isinstance(out, torch.Tensor) and out.dtype == torch.int64, "%s: out must be an int64 tensor" % op)
+        _req(tuple(out.shape) == (numClouds, numClasses, 2), "%s: out must have shape (numClouds, numClasses, 2)" % op)
+        _req(out.device == points.device and out.is_contiguous(), "%s: out must be contiguous on points' device" % op)
+    if dropped is not None:
+        _req(isinstance(dropped, torch.Tensor) and dropped.dtype == torch.int32, "%s: dropped must be an int32 tensor" % op)
+        _req(dropped.numel() == 1 and dropped.device == points.device, "%s: dropped must have one element on points' device" % op)
+    _req(points.is_cuda, "%s: points must be a CUDA tensor" % op)
+    pred, labels = pred.detach().reshape(n), labels.detach().reshape(n)
+    if pred.dtype != torch.int32:
+        pred = pred.to(torch.int32)
+    if labels.dtype != torch.int32:
+        labels = labels.to(torch.int32)
+    return (points.detach(), pred, labels, None if batchIds is None else batchIds.detach().reshape(n), aabbMin.detach(), res,
+            float(maxIgnoreShare))
+
+
+def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05, ignoreLabel=-1,
+                 maxIgnoreShare=0.3, out=None, dropped=None):
+    """The counts behind ScanNet's voxel accuracy in two library launches -> counts, int64 (numClouds, numClasses, 2) on
+    points' device: per cloud b and class c, [b, c, 1] = G, the valid voxels whose most frequent label is c, and [b, c, 0] =
+    V, those of them whose most frequent prediction is c too. points: float32 (n, 3); pred, labels: (n,) or (n, 1), int32
+    taken as it is, int64 cast to int32 (one torch launch each); batchIds: int32 (n,) or (n, 1), None: every row is cloud 0;
+    aabbMin: float32 (numClouds, 3), the corner the grid of every cloud starts at (required here; the helper of
+    MCNetworkUtils computes it). A row's voxel is (b, ceilf((p - aabbMin[b]) / resolution)) per axis in float32; a row is dead
+    iff its label is outside [0, numClasses), its batch id outside [0, numClouds) -- never counted for another cloud -- or a
+    coordinate is not finite, below 0 or above 65535 (dropped, optional int32 device word, is incremented by the number of
+    such rows; it is never read here). A row with label ignoreLabel (< 0: none) is live. Ties go to the lowest class; a
+    prediction outside [0, numClasses) votes for nothing. A voxel is valid iff the share of ignoreLabel among its labels is
+    below maxIgnoreShare (in double) and its majority label is not ignoreLabel. out: None makes a zeroed tensor; a given one
+    is ADDED to and returned. The table lives in a zeroed tensor kept per (device, stream, capacity, numClasses), 8 + 8
+    numClasses bytes for each of the >= 2 n slots; the op leaves it zeroed. Integer atomics only: the same inputs give the
+    same bytes. Nothing is differentiable and nothing is read back."""
+    points, pred, labels, batchIds, aabbMin, res, share = _voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds,
+                                                                             aabbMin, resolution, ignoreLabel, maxIgnoreShare, out,
+                                                                             dropped)
+    lib = _lib.load()
+    if out is None:
+        out = torch.zeros((numClouds, numClasses, 2), dtype=torch.int64, device=points.device)
+    n = points.shape[0]
+    if n == 0:
+        return out
+    ws = _voxel_ws(n, numClasses, points.device)
+    check(lib.mccnn_voxel_acc_add(ptr(points), ptr(pred), ptr(labels), ptr(batchIds), ptr(aabbMin), n, numClouds, numClasses,
+                                  max(ignoreLabel, -1), res, share, ptr(out), ptr(dropped), ptr(ws), ws.numel(), 1,
+                                  stream_handle()), "voxel_counts")
     return out
 
 

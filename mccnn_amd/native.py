@@ -705,3 +705,20 @@ def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, we
         return M.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
     pred, labels, batchIds, weights = M._seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
     return _EXT.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, max(ignoreLabel, -1), out)
+
+
+def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05, ignoreLabel=-1,
+                 maxIgnoreShare=0.3, out=None, dropped=None):
+    """The counts behind ScanNet's voxel accuracy -> int64 (numClouds, numClasses, 2) (dense_glue.voxel_counts: its
+    definition, checks, errors and its table): one Python -> C++ call on the current stream when the extension is loaded, the
+    ctypes op otherwise -- the same library call either way, so the same bytes. A plain function: nothing is differentiable."""
+    from . import dense_glue as M
+    if _EXT is None:
+        return M.voxel_counts(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel,
+                              maxIgnoreShare, out, dropped)
+    points, pred, labels, batchIds, aabbMin, res, share = M._voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds,
+                                                                               aabbMin, resolution, ignoreLabel, maxIgnoreShare,
+                                                                               out, dropped)
+    ws = M._voxel_ws(points.shape[0], numClasses, points.device) if points.shape[0] else None
+    return _EXT.voxel_counts(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, res, max(ignoreLabel, -1), share, out,
+                             dropped, ws)
