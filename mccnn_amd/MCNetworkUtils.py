@@ -50,6 +50,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import dense_glue
+from .MCConvModule import InvalidArgumentError
+
 
 class VariableStore(torch.nn.Module):
     """name -> torch.nn.Parameter / buffer; tf.get_variable + tf.add_to_collection semantics on a torch.nn.Module, so
@@ -206,64 +209,31 @@ def batch_normalization(inputs, training, name, store=None, momentum=0.99, epsil
     return (inputs - mean) * torch.rsqrt(var + epsilon) * gamma + beta
 
 
-_FUSED_OP = False          # native.bn_relu_drop once the library has loaded; None when it does not
-_FUSED_SYNC_OP = None      # native.bn_relu_drop_sync, likewise
-_FUSED_LINEAR_OP = None    # native.linear_bn_relu_drop, likewise
-_FUSED_LOSS_OP = None      # native.linear_softmax_xent, likewise
-_FUSED_COSINE_OP = None    # native.cosine_distance_loss, likewise
-_FUSED_SEG_OP = None       # native.segmentation_counts, likewise
-_FUSED_VOXEL_OP = None     # native.voxel_counts, likewise
+_NATIVE = False   # mccnn_amd.native once the library has loaded; None when it does not
 
 
-def _load_fused_ops():
-    global _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP, _FUSED_LOSS_OP, _FUSED_COSINE_OP, _FUSED_SEG_OP, _FUSED_VOXEL_OP
-    if _FUSED_OP is False:
+def _fused_native():
+    """mccnn_amd.native, whose _X_run functions the gates below hand their checked arguments to -- once the library has
+    loaded; None when it does not. Cached."""
+    global _NATIVE
+    if _NATIVE is False:
         try:
             from . import _lib, native
             _lib.load()
-            _FUSED_OP, _FUSED_SYNC_OP, _FUSED_LINEAR_OP = native.bn_relu_drop, native.bn_relu_drop_sync, native.linear_bn_relu_drop
-            _FUSED_LOSS_OP = native.linear_softmax_xent
-            _FUSED_COSINE_OP = native.cosine_distance_loss
-            _FUSED_SEG_OP = native.segmentation_counts
-            _FUSED_VOXEL_OP = native.voxel_counts
+            _NATIVE = native
         except (ImportError, OSError, AttributeError, RuntimeError):
-            _FUSED_OP = _FUSED_SYNC_OP = _FUSED_LINEAR_OP = _FUSED_LOSS_OP = _FUSED_COSINE_OP = _FUSED_SEG_OP = None
-            _FUSED_VOXEL_OP = None
+            _NATIVE = None
+    return _NATIVE
 
 
-def _fused_op(synced=False):
-    _load_fused_ops()
-    return _FUSED_SYNC_OP if synced else _FUSED_OP
-
-
-def _fused_linear_op():
-    _load_fused_ops()
-    return _FUSED_LINEAR_OP
-
-
-def _fused_loss_op():
-    _load_fused_ops()
-    return _FUSED_LOSS_OP
-
-
-def _fused_cosine_op():
-    _load_fused_ops()
-    return _FUSED_COSINE_OP
-
-
-def _on_device_f32(dev, tensors):
-    """Every tensor is contiguous float32 on the HIP device `dev`: what the library ops ask of everything per column."""
-    return all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
-
-
-def _draw_drop_seed(st, training, keepProb):
-    """(seed, keepProb) of a library call that is going to happen: a call that drops takes the store's next seed (and counts
-    as one of its dropCalls_); any other has no dropout."""
-    if not training or keepProb is None:
-        return 0, None
+def _draw_drop_seed(st, keepProb):
+    """The seed of a library call that is going to happen -- every decline lies behind it: a call that drops (keepProb: its keep
+    probability, None: none, as for every eval call) takes the store's next seed and counts as one of its dropCalls_."""
+    if keepProb is None:
+        return 0
     seed = (int(st.dropSeed_) + int(st.dropCalls_)) % (1 << 32)
     st.dropCalls_ += 1
-    return seed, keepProb
+    return seed
 
 
 def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
@@ -271,37 +241,32 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
     then runs the torch code): the store's switch is off, the input is not a contiguous float32 (or bfloat16 with an even
     c) [n, c] tensor on a HIP device, the library does not load, training statistics are synchronised across ranks and
     the store's fusedSync_ is off (with it on, that case takes the op whose statistics run over the rows of all ranks of
-    the store's syncGroup_: native.bn_relu_drop_sync), or an eval call wants gradients. keepProb: the keep probability of a dropout that applies (None: none). outDtype: the
-    result's type (None: the input's; torch.float32; torch.bfloat16, which needs an even c as well)."""
+    the store's syncGroup_: native.bn_relu_drop_sync), or an eval call wants gradients -- whatever the op's own rule
+    (dense_glue._bn_act_args), asked once, refuses. keepProb: the keep probability of a dropout that applies (None: none).
+    outDtype: the result's type (None: the input's; torch.float32; torch.bfloat16, which needs an even c as well)."""
     if not getattr(st, "fused_", False):
-        return None
-    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype in (torch.float32, torch.bfloat16) and inputs.dim() == 2
-            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
-        return None
-    if outDtype not in (None, torch.float32, torch.bfloat16):
-        return None
-    if inputs.shape[1] % 2 != 0 and (inputs.dtype == torch.bfloat16 or outDtype == torch.bfloat16):
         return None
     synced = _stats_cross_ranks(training, sync)
     if synced and not getattr(st, "fusedSync_", False):
         return None
+    native = _fused_native()
+    if native is None or not torch.is_tensor(inputs) or inputs.dim() != 2:   # (the block below is as wide as inputs.shape[1])
+        return None
+    # residual: the rule is never shown the keepProb of an eval call; this gate has always declined a bad one there too
     if keepProb is not None and not 0.0 < keepProb <= 1.0:
         return None
-    op = _fused_op(synced)
-    if op is None:
-        return None
     gamma, beta, mov_mean, mov_var = _bn_block(st, name, inputs.shape[1], inputs.device)
-    if not training and torch.is_grad_enabled() and (inputs.requires_grad or gamma.requires_grad or beta.requires_grad):
+    group = getattr(st, "syncGroup_", None) if synced else None
+    keep = keepProb if training else None
+    try:   # (the seed is drawn behind the checks: they see 0 in its place)
+        checked = dense_glue._bn_act_args(inputs, gamma, beta, mov_mean, mov_var, keep, 0, outDtype, training=training,
+                                          sync=synced, group=group)
+    except InvalidArgumentError:
         return None
-    if not _on_device_f32(inputs.device, (gamma, beta, mov_mean, mov_var)):
-        return None
-    seed, keepProb = _draw_drop_seed(st, training, keepProb)
+    seed = _draw_drop_seed(st, keep)
     if synced:
-        return op(inputs, gamma, beta, mov_mean, mov_var, relu, keepProb, seed, momentum, epsilon, outDtype,
-                  getattr(st, "syncGroup_", None))
-    if outDtype is None:
-        return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon)
-    return op(inputs, gamma, beta, mov_mean, mov_var, bool(training), relu, keepProb, seed, momentum, epsilon, outDtype)
+        return native._bn_sync_run(inputs, gamma, beta, mov_mean, mov_var, relu, seed, momentum, epsilon, outDtype, group, *checked)
+    return native._bn_act_run(inputs, gamma, beta, mov_mean, mov_var, training, relu, seed, momentum, epsilon, outDtype, *checked)
 
 
 def _keep_prob(useDropOut, keepProb):
@@ -330,33 +295,26 @@ def _fused_linear(st, inputs, w, b, training, name, keepProb=None, momentum=0.99
     """drop(relu(batch_normalization(inputs @ w + b))) as one library op, or None where that form does not apply (the
     caller then runs the matmul and the block as before): the store's switch is off, inputs is not a contiguous float32
     [n, cin] tensor on a HIP device (w and b likewise), the library does not load, training statistics are synchronised
-    across ranks, or an eval call wants gradients. The variables of the block are created as batch_normalization creates
-    them, and a call that drops takes its seed as _fused_glue does."""
-    if not getattr(st, "fusedLinear_", False):
+    across ranks, or an eval call wants gradients -- whatever the op's own rule (dense_glue._linear_bn_args), asked once,
+    refuses. The variables of the block are created as batch_normalization creates them, and a call that drops takes its seed
+    as _fused_glue does."""
+    if not getattr(st, "fusedLinear_", False) or _stats_cross_ranks(training, sync):
         return None
-    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
-            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+    native = _fused_native()
+    if native is None or not torch.is_tensor(inputs) or w.dim() != 2:   # (the block below is as wide as w.shape[1])
         return None
-    if not (w.dim() == 2 and w.shape[0] == inputs.shape[1] and w.shape[1] >= 1 and b.dim() == 1 and b.shape[0] == w.shape[1]):
-        return None
-    if outDtype not in (None, torch.float32, torch.bfloat16):
-        return None
-    if w.shape[1] % 2 != 0 and outDtype == torch.bfloat16:
-        return None
-    if _stats_cross_ranks(training, sync):
-        return None
+    # residual: the rule is never shown the keepProb of an eval call; this gate has always declined a bad one there too
     if keepProb is not None and not 0.0 < keepProb <= 1.0:
         return None
-    op = _fused_linear_op()
-    if op is None:
-        return None
     gamma, beta, mov_mean, mov_var = _bn_block(st, name, w.shape[1], inputs.device)
-    if not training and torch.is_grad_enabled() and any(t.requires_grad for t in (inputs, w, b, gamma, beta)):
+    keep = keepProb if training else None
+    try:   # (the seed is drawn behind the checks: they see 0 in its place)
+        checked = dense_glue._linear_bn_args(inputs, w, b, gamma, beta, mov_mean, mov_var, keep, 0, outDtype, training=training)
+    except InvalidArgumentError:
         return None
-    if not _on_device_f32(inputs.device, (w, b, gamma, beta, mov_mean, mov_var)):
-        return None
-    seed, keepProb = _draw_drop_seed(st, training, keepProb)
-    return op(inputs, w, b, gamma, beta, mov_mean, mov_var, bool(training), True, keepProb, seed, momentum, epsilon, outDtype)
+    seed = _draw_drop_seed(st, keep)
+    return native._linear_bn_run(inputs, w, b, gamma, beta, mov_mean, mov_var, training, True, seed, momentum, epsilon, outDtype,
+                                 *checked)
 
 
 def _linear_bn_relu_drop(st, inputs, w, b, training, name, useDropOut, keepProb, outDtype=None):
@@ -386,26 +344,19 @@ def _fused_loss(st, inputs, w, b, labels, labelWeights, wantLogits):
     """The LossHead of _loss_head as one library op, or None where that form does not apply (the caller then runs the torch
     code): the store's switch is off, inputs is not a contiguous float32 [n, cin] tensor on a HIP device (w and b
     likewise), labels / labelWeights are not contiguous int32 or int64 / float32 tensors of n elements on that device, or the
-    library does not load. The op is differentiable once: a caller that needs a double backward switches fusedLoss_ off."""
+    library does not load -- whatever the op's own rule (dense_glue._linear_xent_args), asked once, refuses. The op is
+    differentiable once: a caller that needs a double backward switches fusedLoss_ off."""
     if not getattr(st, "fusedLoss_", False):
         return None
-    if not (torch.is_tensor(inputs) and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2
-            and inputs.shape[0] >= 1 and inputs.shape[1] >= 1 and inputs.is_contiguous()):
+    native = _fused_native()
+    # residual: the rule takes row weights that want a gradient while grad mode is off; this gate never has
+    if native is None or getattr(labelWeights, "requires_grad", False):
         return None
-    if not (w.dim() == 2 and w.shape[0] == inputs.shape[1] and w.shape[1] >= 1 and b.dim() == 1 and b.shape[0] == w.shape[1]):
+    try:
+        checked = dense_glue._linear_xent_args(inputs, w, b, labels, labelWeights, wantLogits)
+    except InvalidArgumentError:
         return None
-    n = inputs.shape[0]
-    if not (torch.is_tensor(labels) and labels.dtype in (torch.int32, torch.int64) and tuple(labels.shape) in ((n,), (n, 1))
-            and labels.device == inputs.device and labels.is_contiguous()):
-        return None
-    if labelWeights is not None and not (torch.is_tensor(labelWeights) and labelWeights.dtype == torch.float32
-                                         and tuple(labelWeights.shape) in ((n,), (n, 1)) and labelWeights.device == inputs.device
-                                         and labelWeights.is_contiguous() and not labelWeights.requires_grad):
-        return None
-    op = _fused_loss_op()
-    if op is None or not _on_device_f32(inputs.device, (w, b)):
-        return None
-    loss, pred, meta, logits = op(inputs, w, b, labels, labelWeights, wantLogits)
+    loss, pred, meta, logits = native._linear_xent_run(*checked)
     return LossHead(loss, pred, meta[1], meta[0], logits)
 
 
@@ -450,26 +401,20 @@ def _fused_cosine(st, pred, target, weights):
     """The NormalHead of _normal_head as one library op, or None where that form does not apply (the caller then runs the
     torch code): the store's fusedLoss_ switch is off, pred and target are not float32 [n, c] tensors on one HIP device laid
     out as .contiguous() would leave them (a view that starts anywhere in its buffer is fine), target or the weights want
-    a gradient, the weights are not a contiguous float32 [n] / [n, 1] tensor on that device, or the library does not load.
-    The op is differentiable once: a caller that needs a double backward switches fusedLoss_ off."""
+    a gradient, the weights are not a contiguous float32 [n] / [n, 1] tensor on that device, or the library does not load --
+    whatever the op's own rule (dense_glue._cosine_loss_args), asked once, refuses. The op is differentiable once: a caller
+    that needs a double backward switches fusedLoss_ off."""
     if not getattr(st, "fusedLoss_", False):
         return None
-    if not (torch.is_tensor(pred) and torch.is_tensor(target) and pred.is_cuda and pred.dtype == torch.float32
-            and target.dtype == torch.float32 and pred.dim() == 2 and pred.shape[0] >= 1 and pred.shape[1] >= 1
-            and tuple(target.shape) == tuple(pred.shape) and target.device == pred.device and pred.is_contiguous()
-            and target.is_contiguous() and pred.shape[0] * pred.shape[1] < (1 << 31)):
+    native = _fused_native()
+    # residual: the rule takes row weights that want a gradient while grad mode is off; this gate never has
+    if native is None or getattr(weights, "requires_grad", False):
         return None
-    if torch.is_grad_enabled() and target.requires_grad:
+    try:
+        checked = dense_glue._cosine_loss_args(pred, target, weights)
+    except InvalidArgumentError:
         return None
-    n = pred.shape[0]
-    if weights is not None and not (torch.is_tensor(weights) and weights.dtype == torch.float32
-                                    and tuple(weights.shape) in ((n,), (n, 1)) and weights.device == pred.device
-                                    and weights.is_contiguous() and not weights.requires_grad):
-        return None
-    op = _fused_cosine_op()
-    if op is None:
-        return None
-    loss, sums, meta = op(pred, target, weights)
+    loss, sums, meta = native._cosine_loss_run(*checked)
     return NormalHead(loss, sums[0], sums[1], meta[0])
 
 
@@ -536,35 +481,18 @@ def _fused_seg_counts(st, pred, labels, numClasses, batchIds, numClouds, weights
     """segmentation_counts as one library launch, or None where that form does not apply (the caller then runs the torch
     code): the store's fusedLoss_ switch is off, pred and labels are not contiguous int32 or int64 tensors of n elements on
     one HIP device, batchIds / weights / out are not what dense_glue.segmentation_counts takes, or the library does not
-    load."""
+    load -- whatever the op's own rule (dense_glue._seg_counts_args), asked once, refuses."""
     if not getattr(st, "fusedLoss_", False):
         return None
-    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (numClasses, numClouds, ignoreLabel))
-            and numClasses >= 1 and numClouds >= 1 and numClasses * numClouds * 3 < (1 << 31) and abs(ignoreLabel) < (1 << 31)):
+    native = _fused_native()
+    # residual: the rule takes ignoreLabel = -2^31; this gate never has
+    if native is None or ignoreLabel == -(1 << 31):
         return None
-    if not (torch.is_tensor(pred) and pred.is_cuda and pred.dtype in (torch.int32, torch.int64) and pred.is_contiguous()
-            and (pred.dim() == 1 or (pred.dim() == 2 and pred.shape[1] == 1)) and pred.shape[0] < (1 << 31)):
+    try:
+        checked = dense_glue._seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    except InvalidArgumentError:
         return None
-    n = pred.shape[0]
-    shapes = ((n,), (n, 1))
-
-    def rows(t, dtypes):
-        return (torch.is_tensor(t) and t.dtype in dtypes and tuple(t.shape) in shapes and t.device == pred.device
-                and t.is_contiguous())
-
-    if not rows(labels, (torch.int32, torch.int64)):
-        return None
-    if batchIds is not None and not rows(batchIds, (torch.int32,)):
-        return None
-    if weights is not None and not (rows(weights, (torch.float32,)) and not weights.requires_grad):
-        return None
-    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int64 and out.device == pred.device
-                                and tuple(out.shape) == (numClouds, numClasses, 3) and out.is_contiguous()):
-        return None
-    _load_fused_ops()
-    if _FUSED_SEG_OP is None:
-        return None
-    return _FUSED_SEG_OP(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    return native._seg_counts_run(*checked)
 
 
 def _seg_counts_torch(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
@@ -688,42 +616,20 @@ def _fused_voxel_counts(st, points, pred, labels, numClasses, batchIds, numCloud
     """voxel_counts as one library op, or None where that form does not apply (the caller then runs the torch code): the
     store's fusedLoss_ switch is off, points is not a contiguous float32 [n, 3] tensor on a HIP device, pred and labels are not
     contiguous int32 or int64 tensors of n elements on it, batchIds / aabbMin / out / dropped are not what
-    dense_glue.voxel_counts takes, or the library does not load."""
+    dense_glue.voxel_counts takes, or the library does not load -- whatever the op's own rule (dense_glue._voxel_counts_args),
+    asked once, refuses."""
     if not getattr(st, "fusedLoss_", False):
         return None
-    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (numClasses, numClouds, ignoreLabel))
-            and numClasses >= 1 and 1 <= numClouds <= 32768 and numClasses * numClouds * 2 < (1 << 31) and abs(ignoreLabel) < (1 << 31)):
+    native = _fused_native()
+    # residual: the rule takes ignoreLabel = -2^31; this gate never has
+    if native is None or ignoreLabel == -(1 << 31):
         return None
-    if _voxel_res(resolution) is None or isinstance(maxIgnoreShare, bool) or not isinstance(maxIgnoreShare, (int, float, np.floating)):
+    try:
+        checked = dense_glue._voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution,
+                                                ignoreLabel, maxIgnoreShare, out, dropped)
+    except InvalidArgumentError:
         return None
-    if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2
-            and points.shape[1] == 3 and points.is_contiguous() and points.shape[0] < (1 << 30)):
-        return None
-    n = points.shape[0]
-    shapes = ((n,), (n, 1))
-
-    def rows(t, dtypes):
-        return (torch.is_tensor(t) and t.dtype in dtypes and tuple(t.shape) in shapes and t.device == points.device
-                and t.is_contiguous())
-
-    if not (rows(pred, (torch.int32, torch.int64)) and rows(labels, (torch.int32, torch.int64))):
-        return None
-    if batchIds is not None and not rows(batchIds, (torch.int32,)):
-        return None
-    if not (torch.is_tensor(aabbMin) and aabbMin.dtype == torch.float32 and tuple(aabbMin.shape) == (numClouds, 3)
-            and aabbMin.device == points.device and aabbMin.is_contiguous()):
-        return None
-    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int64 and out.device == points.device
-                                and tuple(out.shape) == (numClouds, numClasses, 2) and out.is_contiguous()):
-        return None
-    if dropped is not None and not (torch.is_tensor(dropped) and dropped.dtype == torch.int32 and dropped.numel() == 1
-                                    and dropped.device == points.device):
-        return None
-    _load_fused_ops()
-    if _FUSED_VOXEL_OP is None:
-        return None
-    return _FUSED_VOXEL_OP(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel, maxIgnoreShare,
-                           out, dropped)
+    return native._voxel_counts_run(*checked)
 
 
 def _lowest_argmax(h):

@@ -20,12 +20,75 @@ from ._lib import check, ptr, stream_handle
 BN_DROP_ALL = 1 << 32   # keep threshold of "no dropout"
 
 
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+# The checks the ops repeat, written once; (dtypes, their name in the messages):
+_F32, _I32, _I64 = ((torch.float32,), "a float32"), ((torch.int32,), "an int32"), ((torch.int64,), "an int64")
+_INT = ((torch.int32, torch.int64), "an int32 (or int64)")
+
+
+def _typed(op, t, name, kind):
+    _req(isinstance(t, torch.Tensor) and t.dtype in kind[0], "%s: %s must be %s tensor" % (op, name, kind[1]))
+
+
+def _rows(op, t, name, kind, n, first, whose):
+    """A row tensor: n elements of `kind` as (n,) or (n, 1), contiguous on the device of the op's first tensor (`whose` in the
+    message) -> t as the library reads it, detached [n] (a view: nothing is launched)."""
+    _typed(op, t, name, kind)
+    _req(tuple(t.shape) in ((n,), (n, 1)), "%s: %s must have shape (n,) or (n, 1)" % (op, name))
+    _req(t.device == first.device and t.is_contiguous(), "%s: %s must be contiguous on %s device" % (op, name, whose))
+    return t.detach().reshape(n)
+
+
+def _opt_rows(op, t, name, kind, n, first, whose):
+    """An optional row tensor: None, or _rows."""
+    return None if t is None else _rows(op, t, name, kind, n, first, whose)
+
+
+def _shaped(op, t, name, kind, shape, text, first, whose):
+    """A tensor of one given shape (`text` in the message) -- an `out`, a box: contiguous on the first tensor's device."""
+    _typed(op, t, name, kind)
+    _req(tuple(t.shape) == shape, "%s: %s must have shape %s" % (op, name, text))
+    _req(t.device == first.device and t.is_contiguous(), "%s: %s must be contiguous on %s device" % (op, name, whose))
+
+
+def _pos_int(op, v, name):
+    _req(_is_int(v) and v >= 1, "%s expects %s >= 1" % (op, name))
+
+
+def _ignore_label(op, v):
+    """-> ignoreLabel as the library reads it: every negative value is -1, none."""
+    _req(_is_int(v) and -(1 << 31) <= v < (1 << 31), "%s expects an integer ignoreLabel (< 0: none)" % op)
+    return max(v, -1)
+
+
+def _int32(t):
+    """A checked int32 or int64 tensor as int32: the cast of an int64 one is one torch launch, so it comes behind the checks."""
+    return t if t.dtype == torch.int32 else t.to(torch.int32)
+
+
+def _linear_args(op, x, w, b, c):
+    """The checks of x (n, cin), w (cin, c) and b (c,) that the two ops behind a linear layer share (c: the width's name in
+    the messages)."""
+    _typed(op, x, "x", _F32)
+    _typed(op, w, "w", _F32)
+    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
+         "%s expects x (n, cin) and w (cin, %s), n, cin, %s >= 1" % (op, c, c))
+    _req(x.is_contiguous() and w.is_contiguous(), "%s: x and w must be contiguous" % op)
+    _req(w.device == x.device, "%s: w is on another device than x" % op)
+    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
+         and b.shape[0] == w.shape[1] and b.device == x.device, "%s: b must be a float32 (%s,) tensor on x's device" % (op, c))
+    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "%s: x too large" % op)
+
+
 def _drop_args(op, keepProb, seed, outDtype):
     """The checks of keepProb, seed and outDtype that the ops share (op: the name in the messages) -> (keep threshold, keep
     scale). A threshold of 0 (a keepProb that keeps nothing) is the caller's to refuse, behind its other checks."""
     _req(keepProb is None or (isinstance(keepProb, (int, float)) and not isinstance(keepProb, bool) and 0.0 < keepProb <= 1.0),
          "%s expects keepProb in (0, 1] (or None)" % op)
-    _req(isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < (1 << 32), "%s expects a seed in [0, 2^32)" % op)
+    _req(_is_int(seed) and 0 <= seed < (1 << 32), "%s expects a seed in [0, 2^32)" % op)
     _req(outDtype is None or outDtype in (torch.float32, torch.bfloat16),
          "%s: outDtype must be None, torch.float32 or torch.bfloat16" % op)
     if keepProb is None:
@@ -35,9 +98,10 @@ def _drop_args(op, keepProb, seed, outDtype):
     return thr, float(_np.float32(1.0) / _np.float32(kp)) if thr >= 1 else 0.0   # 1.0f / (float) keepProb
 
 
-def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
+def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None, *, training=True, sync=False, group=None):
     """Checks of bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale). x: float32 or
-    bfloat16 rows; outDtype: None (x's type), torch.float32 or torch.bfloat16; everything per column is float32."""
+    bfloat16 rows; outDtype: None (x's type), torch.float32 or torch.bfloat16; everything per column is float32. training=False
+    adds the eval form's check, sync=True those of bn_relu_dropout_sync (its group, its rows), behind all the others."""
     thr, scale = _drop_args("bn_relu_dropout", keepProb, seed, outDtype)
     _req(isinstance(x, torch.Tensor) and x.dtype in (torch.float32, torch.bfloat16),
          "bn_relu_dropout: x must be a float32 (or bfloat16 storage) tensor")
@@ -54,6 +118,14 @@ def _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype
         _req(t.device == x.device, "bn_relu_dropout: %s is on another device than x" % name)
     _req(x.is_cuda, "bn_relu_dropout: x must be a CUDA tensor")
     _req(thr >= 1, "bn_relu_dropout: keepProb keeps nothing")
+    if not training:
+        _req(not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
+             "bn_relu_dropout: the eval form has no gradients")
+    if sync:
+        if group is not None:
+            import torch.distributed as dist
+            _req(dist.is_available() and isinstance(group, dist.ProcessGroup), "bn_relu_dropout_sync: group must be a process group (or None)")
+        _req(x.shape[0] <= (1 << 24), "bn_relu_dropout: x too large")   # counts travel as float32
     return thr, scale
 
 
@@ -107,12 +179,15 @@ def bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu=True, 
     op is also the cast between layers that keep different row types: bf16 is widened exactly, the statistics and all
     arithmetic are float32 as for float32 rows, a bf16 y is rounded to nearest even at the store. x.grad has x's type,
     gamma.grad and beta.grad are float32."""
-    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    return _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                       *_bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
+def _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
+    """bn_relu_dropout behind its checks: the arguments as given and what _bn_act_args made of keepProb."""
     if training:
         return _BnReluDropout.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
                                     float(epsilon), outDtype)
-    _req(not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
-         "bn_relu_dropout: the eval form has no gradients")
     lib = _lib.load()
     y = torch.empty(x.shape, dtype=outDtype or x.dtype, device=x.device)
     _bn_act_fwd(lib, _bf16_rows_aligned(x.detach()), gamma, beta, movingMean, movingVar, float(momentum), float(epsilon), 0,
@@ -205,11 +280,14 @@ class _BnReluDropoutSync(torch.autograd.Function):
 
 
 def _bn_relu_dropout_sync(stages, x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype, group):
-    thr, scale = _bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
-    if group is not None:
-        import torch.distributed as dist
-        _req(dist.is_available() and isinstance(group, dist.ProcessGroup), "bn_relu_dropout_sync: group must be a process group (or None)")
-    _req(x.shape[0] <= (1 << 24), "bn_relu_dropout: x too large")   # counts travel as float32
+    return _bn_sync_run(x, gamma, beta, movingMean, movingVar, relu, seed, momentum, epsilon, outDtype, group,
+                        *_bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, sync=True, group=group),
+                        stages=stages)
+
+
+def _bn_sync_run(x, gamma, beta, movingMean, movingVar, relu, seed, momentum, epsilon, outDtype, group, thr, scale,
+                 stages=_BN_SYNC_STAGES):
+    """bn_relu_dropout_sync behind its checks, over the four stage calls `stages` (the ctypes ones, or the extension's)."""
     return _BnReluDropoutSync.apply(x, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
                                     float(epsilon), outDtype, group, stages)
 
@@ -231,17 +309,10 @@ def bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepP
 # ---------------------------------------------------------------------------------------------
 # A linear layer and the dense glue behind it as one op (csrc/linear_bn.hip, include/mccnn.h "A LINEAR LAYER AND THE DENSE
 # GLUE BEHIND IT AS ONE OP"): z = x @ w + b, y = drop(act(bn(z))).
-def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None):
-    """Checks of linear_bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale)."""
-    _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "linear_bn_relu_dropout: x must be a float32 tensor")
-    _req(isinstance(w, torch.Tensor) and w.dtype == torch.float32, "linear_bn_relu_dropout: w must be a float32 tensor")
-    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
-         "linear_bn_relu_dropout expects x (n, cin) and w (cin, cout), n, cin, cout >= 1")
-    _req(x.is_contiguous() and w.is_contiguous(), "linear_bn_relu_dropout: x and w must be contiguous")
-    _req(w.device == x.device, "linear_bn_relu_dropout: w is on another device than x")
-    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
-         and b.shape[0] == w.shape[1] and b.device == x.device, "linear_bn_relu_dropout: b must be a float32 (cout,) tensor on x's device")
-    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "linear_bn_relu_dropout: x too large")
+def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None, *, training=True):
+    """Checks of linear_bn_relu_dropout (nothing is launched before they pass) -> (keep threshold, keep scale).
+    training=False adds the eval form's check, behind all the others."""
+    _linear_args("linear_bn_relu_dropout", x, w, b, "cout")
     thr, scale = _drop_args("linear_bn_relu_dropout", keepProb, seed, outDtype)
     _req(outDtype != torch.bfloat16 or w.shape[1] % 2 == 0, "linear_bn_relu_dropout: bfloat16 rows need an even number of columns")
     for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
@@ -250,6 +321,9 @@ def _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed,
              "linear_bn_relu_dropout: %s must be a contiguous float32 (cout,) tensor on x's device" % name)
     _req(x.is_cuda, "linear_bn_relu_dropout: x must be a CUDA tensor")
     _req(thr >= 1, "linear_bn_relu_dropout: keepProb keeps nothing")
+    if not training:
+        _req(not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
+             "linear_bn_relu_dropout: the eval form has no gradients")
     return thr, scale
 
 
@@ -300,12 +374,15 @@ def linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training
     moving ones updated in place when training; the counter-based mask of `seed`); differentiable (once) with respect to
     x, w, b, gamma and beta. outDtype: y's type, None / torch.float32 or torch.bfloat16 (an even cout). Eval: the moving
     statistics, no dropout, and no gradients -- an input that requires one raises."""
-    thr, scale = _linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
+    return _linear_bn_run(x, w, b, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                          *_linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
+def _linear_bn_run(x, w, b, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
+    """linear_bn_relu_dropout behind its checks: the arguments as given and what _linear_bn_args made of keepProb."""
     if training:
         return _LinearBnReluDropout.apply(x, w, b, gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed,
                                           float(momentum), float(epsilon), outDtype)
-    _req(not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
-         "linear_bn_relu_dropout: the eval form has no gradients")
     lib = _lib.load()
     n, cin = x.shape
     cout = w.shape[1]
@@ -320,33 +397,18 @@ def linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training
 # ---------------------------------------------------------------------------------------------
 # The last linear layer and the softmax cross-entropy behind it as one op (csrc/linear_xent.hip, include/mccnn.h "THE LAST
 # LINEAR LAYER AND THE SOFTMAX CROSS-ENTROPY BEHIND IT AS ONE OP"): x -> (loss, predictions, count of correct rows).
-def _linear_xent_args(x, w, b, labels, weights=None):
-    """Checks of linear_softmax_xent (nothing is launched before they pass) -> (labels, weights) as the library reads them:
-    int32 [n] -- an int64 tensor is cast here, behind the checks, which is one torch launch -- and float32 [n] or None."""
-    _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "linear_softmax_xent: x must be a float32 tensor")
-    _req(isinstance(w, torch.Tensor) and w.dtype == torch.float32, "linear_softmax_xent: w must be a float32 tensor")
-    _req(x.dim() == 2 and w.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and w.shape[1] >= 1 and w.shape[0] == x.shape[1],
-         "linear_softmax_xent expects x (n, cin) and w (cin, c), n, cin, c >= 1")
-    _req(x.is_contiguous() and w.is_contiguous(), "linear_softmax_xent: x and w must be contiguous")
-    _req(w.device == x.device, "linear_softmax_xent: w is on another device than x")
-    _req(isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.is_contiguous() and b.dim() == 1
-         and b.shape[0] == w.shape[1] and b.device == x.device, "linear_softmax_xent: b must be a float32 (c,) tensor on x's device")
-    _req(max(x.shape[0], x.shape[1], w.shape[1]) < (1 << 31), "linear_softmax_xent: x too large")
+def _linear_xent_args(x, w, b, labels, weights=None, wantLogits=False):
+    """Checks of linear_softmax_xent (nothing is launched before they pass) -> what _linear_xent_run takes: (x, w, b, labels,
+    weights, wantLogits) with labels and weights as the library reads them: int32 [n] -- an int64 tensor is cast here, behind
+    the checks, which is one torch launch -- and float32 [n] or None."""
+    op = "linear_softmax_xent"
+    _linear_args(op, x, w, b, "c")
     n = x.shape[0]
-    _req(isinstance(labels, torch.Tensor) and labels.dtype in (torch.int32, torch.int64),
-         "linear_softmax_xent: labels must be an int32 (or int64) tensor")
-    _req(tuple(labels.shape) in ((n,), (n, 1)), "linear_softmax_xent: labels must have shape (n,) or (n, 1)")
-    _req(labels.device == x.device and labels.is_contiguous(), "linear_softmax_xent: labels must be contiguous on x's device")
-    if weights is not None:
-        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "linear_softmax_xent: weights must be a float32 tensor")
-        _req(tuple(weights.shape) in ((n,), (n, 1)), "linear_softmax_xent: weights must have shape (n,) or (n, 1)")
-        _req(weights.device == x.device and weights.is_contiguous(), "linear_softmax_xent: weights must be contiguous on x's device")
-        _req(not (torch.is_grad_enabled() and weights.requires_grad), "linear_softmax_xent: no gradient with respect to weights")
-    _req(x.is_cuda, "linear_softmax_xent: x must be a CUDA tensor")
-    labels = labels.detach().reshape(n)
-    if labels.dtype != torch.int32:
-        labels = labels.to(torch.int32)
-    return labels, None if weights is None else weights.detach().reshape(n)
+    labels = _rows(op, labels, "labels", _INT, n, x, "x's")
+    rw = _opt_rows(op, weights, "weights", _F32, n, x, "x's")
+    _req(rw is None or not (torch.is_grad_enabled() and weights.requires_grad), "%s: no gradient with respect to weights" % op)
+    _req(x.is_cuda, "%s: x must be a CUDA tensor" % op)
+    return x, w, b, _int32(labels), rw, bool(wantLogits)
 
 
 class _LinearSoftmaxXent(torch.autograd.Function):
@@ -400,8 +462,12 @@ def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
     D and the number of live rows with pred == label. loss is differentiable (once) with respect to x, w and b, all three
     gradients from one autograd node whose upstream gradient stays on the device. pred, meta and logits are NOT
     differentiable: whoever needs gradients through the logits uses the unfused path (x @ w + b and torch's loss)."""
-    labels, weights = _linear_xent_args(x, w, b, labels, weights)
-    out = _LinearSoftmaxXent.apply(x, w, b, labels, weights, bool(wantLogits))
+    return _linear_xent_run(*_linear_xent_args(x, w, b, labels, weights, wantLogits))
+
+
+def _linear_xent_run(x, w, b, labels, weights, wantLogits):
+    """linear_softmax_xent behind its checks, over what _linear_xent_args returns."""
+    out = _LinearSoftmaxXent.apply(x, w, b, labels, weights, wantLogits)
     return out if wantLogits else out + (None,)
 
 
@@ -409,24 +475,20 @@ def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
 # The cosine-distance loss of normal estimation as one op (csrc/cosine_loss.hip, include/mccnn.h "THE COSINE-DISTANCE LOSS OF
 # NORMAL ESTIMATION AS ONE OP"): (pred, target) -> (loss, sums, meta).
 def _cosine_loss_args(pred, target, weights=None):
-    """Checks of cosine_distance_loss (nothing is launched before they pass) -> the weights as the library reads them:
-    float32 [n] or None."""
-    _req(isinstance(pred, torch.Tensor) and pred.dtype == torch.float32, "cosine_distance_loss: pred must be a float32 tensor")
-    _req(isinstance(target, torch.Tensor) and target.dtype == torch.float32, "cosine_distance_loss: target must be a float32 tensor")
+    """Checks of cosine_distance_loss (nothing is launched before they pass) -> what _cosine_loss_run takes: (pred, target,
+    weights) with the weights as the library reads them: float32 [n] or None."""
+    _typed("cosine_distance_loss", pred, "pred", _F32)
+    _typed("cosine_distance_loss", target, "target", _F32)
     _req(pred.dim() == 2 and pred.shape[0] >= 1 and pred.shape[1] >= 1 and tuple(target.shape) == tuple(pred.shape),
          "cosine_distance_loss expects pred (n, c) and target (n, c), n, c >= 1")
     _req(pred.is_contiguous() and target.is_contiguous(), "cosine_distance_loss: pred and target must be contiguous")
     _req(target.device == pred.device, "cosine_distance_loss: target is on another device than pred")
     _req(pred.shape[0] * pred.shape[1] < (1 << 31), "cosine_distance_loss: pred too large")
     _req(not (torch.is_grad_enabled() and target.requires_grad), "cosine_distance_loss: no gradient with respect to target")
-    n = pred.shape[0]
-    if weights is not None:
-        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "cosine_distance_loss: weights must be a float32 tensor")
-        _req(tuple(weights.shape) in ((n,), (n, 1)), "cosine_distance_loss: weights must have shape (n,) or (n, 1)")
-        _req(weights.device == pred.device and weights.is_contiguous(), "cosine_distance_loss: weights must be contiguous on pred's device")
-        _req(not (torch.is_grad_enabled() and weights.requires_grad), "cosine_distance_loss: no gradient with respect to weights")
+    rw = _opt_rows("cosine_distance_loss", weights, "weights", _F32, pred.shape[0], pred, "pred's")
+    _req(rw is None or not (torch.is_grad_enabled() and weights.requires_grad), "cosine_distance_loss: no gradient with respect to weights")
     _req(pred.is_cuda, "cosine_distance_loss: pred must be a CUDA tensor")
-    return None if weights is None else weights.detach().reshape(n)
+    return pred, target, rw
 
 
 class _CosineDistanceLoss(torch.autograd.Function):
@@ -469,7 +531,11 @@ def cosine_distance_loss(pred, target, weights=None):
     unit rows in radians, 2 atan2(|u - v|, |u + v|); meta (int32 (1,)): D. loss is differentiable (once) with respect to pred,
     the upstream gradient stays on the device; there is no gradient with respect to target or weights (asking for one
     raises), and sums and meta are NOT differentiable."""
-    weights = _cosine_loss_args(pred, target, weights)
+    return _cosine_loss_run(*_cosine_loss_args(pred, target, weights))
+
+
+def _cosine_loss_run(pred, target, weights):
+    """cosine_distance_loss behind its checks, over what _cosine_loss_args returns."""
     return _CosineDistanceLoss.apply(pred, target, weights)
 
 
@@ -477,45 +543,27 @@ def cosine_distance_loss(pred, target, weights=None):
 # Segmentation scores on the device (csrc/seg_counts.hip, include/mccnn.h "SEGMENTATION SCORES ON THE DEVICE: PER-CLOUD,
 # PER-CLASS COUNTS"): (pred, labels) -> int64 [numClouds, numClasses, 3] counts of intersection, union and ground truth.
 def _seg_counts_args(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
-    """Checks of segmentation_counts (nothing is launched before they pass) -> (pred, labels, batchIds, weights) as the
-    library reads them: int32 [n] -- an int64 pred or labels is cast here, behind the checks, one torch launch each -- int32
-    [n] or None, float32 [n] or None."""
+    """Checks of segmentation_counts (nothing is launched before they pass) -> what _seg_counts_run takes: its own arguments
+    with pred, labels, batchIds and weights as the library reads them -- int32 [n] (an int64 pred or labels is cast here,
+    behind the checks, one torch launch each), int32 [n] or None, float32 [n] or None -- and every negative ignoreLabel as -1."""
     op = "segmentation_counts"
-    for v, name in ((numClasses, "numClasses"), (numClouds, "numClouds")):
-        _req(isinstance(v, int) and not isinstance(v, bool) and v >= 1, "%s expects %s >= 1" % (op, name))
+    _pos_int(op, numClasses, "numClasses")
+    _pos_int(op, numClouds, "numClouds")
     _req(numClouds * numClasses * 3 < (1 << 31), "%s: numClouds * numClasses too large" % op)
-    _req(isinstance(ignoreLabel, int) and not isinstance(ignoreLabel, bool) and -(1 << 31) <= ignoreLabel < (1 << 31),
-         "%s expects an integer ignoreLabel (< 0: none)" % op)
-    _req(isinstance(pred, torch.Tensor) and pred.dtype in (torch.int32, torch.int64), "%s: pred must be an int32 (or int64) tensor" % op)
+    ignoreLabel = _ignore_label(op, ignoreLabel)
+    _typed(op, pred, "pred", _INT)
     _req(pred.dim() in (1, 2) and (pred.dim() == 1 or pred.shape[1] == 1), "%s: pred must have shape (n,) or (n, 1)" % op)
     n = pred.shape[0]
     _req(n < (1 << 31), "%s: pred too large" % op)
     _req(pred.is_contiguous(), "%s: pred must be contiguous" % op)
-    _req(isinstance(labels, torch.Tensor) and labels.dtype in (torch.int32, torch.int64),
-         "%s: labels must be an int32 (or int64) tensor" % op)
-    _req(tuple(labels.shape) in ((n,), (n, 1)), "%s: labels must have shape (n,) or (n, 1)" % op)
-    _req(labels.device == pred.device and labels.is_contiguous(), "%s: labels must be contiguous on pred's device" % op)
-    if batchIds is not None:
-        _req(isinstance(batchIds, torch.Tensor) and batchIds.dtype == torch.int32, "%s: batchIds must be an int32 tensor" % op)
-        _req(tuple(batchIds.shape) in ((n,), (n, 1)), "%s: batchIds must have shape (n,) or (n, 1)" % op)
-        _req(batchIds.device == pred.device and batchIds.is_contiguous(), "%s: batchIds must be contiguous on pred's device" % op)
-    if weights is not None:
-        _req(isinstance(weights, torch.Tensor) and weights.dtype == torch.float32, "%s: weights must be a float32 tensor" % op)
-        _req(tuple(weights.shape) in ((n,), (n, 1)), "%s: weights must have shape (n,) or (n, 1)" % op)
-        _req(weights.device == pred.device and weights.is_contiguous(), "%s: weights must be contiguous on pred's device" % op)
-        _req(not weights.requires_grad, "%s: no gradient with respect to weights" % op)
+    labels = _rows(op, labels, "labels", _INT, n, pred, "pred's")
+    batchIds = _opt_rows(op, batchIds, "batchIds", _I32, n, pred, "pred's")
+    rw = _opt_rows(op, weights, "weights", _F32, n, pred, "pred's")
+    _req(rw is None or not weights.requires_grad, "%s: no gradient with respect to weights" % op)
     if out is not None:
-        _req(isinstance(out, torch.Tensor) and out.dtype == torch.int64, "%s: out must be an int64 tensor" % op)
-        _req(tuple(out.shape) == (numClouds, numClasses, 3), "%s: out must have shape (numClouds, numClasses, 3)" % op)
-        _req(out.device == pred.device and out.is_contiguous(), "%s: out must be contiguous on pred's device" % op)
+        _shaped(op, out, "out", _I64, (numClouds, numClasses, 3), "(numClouds, numClasses, 3)", pred, "pred's")
     _req(pred.is_cuda, "%s: pred must be a CUDA tensor" % op)
-    pred, labels = pred.detach().reshape(n), labels.detach().reshape(n)
-    if pred.dtype != torch.int32:
-        pred = pred.to(torch.int32)
-    if labels.dtype != torch.int32:
-        labels = labels.to(torch.int32)
-    return (pred, labels, None if batchIds is None else batchIds.detach().reshape(n),
-            None if weights is None else weights.detach().reshape(n))
+    return _int32(pred.detach().reshape(n)), _int32(labels), numClasses, batchIds, numClouds, rw, ignoreLabel, out
 
 
 def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
@@ -528,12 +576,16 @@ def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, we
     U of the prediction where that is a class (a prediction outside [0, numClasses) is a miss and nothing else). out: None
     makes a zeroed tensor; a given one is ADDED to and returned, so a caller accumulates over as many batches as it likes.
     Integer atomics only: the same inputs give the same bytes. Nothing is differentiable and nothing is read back."""
-    pred, labels, batchIds, weights = _seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
+    return _seg_counts_run(*_seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out))
+
+
+def _seg_counts_run(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out):
+    """segmentation_counts behind its checks, over what _seg_counts_args returns."""
     lib = _lib.load()
     if out is None:
         out = torch.zeros((numClouds, numClasses, 3), dtype=torch.int64, device=pred.device)
     check(lib.mccnn_seg_counts_add(ptr(pred), ptr(labels), ptr(weights), ptr(batchIds), pred.shape[0], numClouds, numClasses,
-                                   max(ignoreLabel, -1), ptr(out), stream_handle()), "segmentation_counts")
+                                   ignoreLabel, ptr(out), stream_handle()), "segmentation_counts")
     return out
 
 
@@ -569,53 +621,38 @@ def _voxel_ws(n, numClasses, device):
 
 def _voxel_counts_args(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05,
                        ignoreLabel=-1, maxIgnoreShare=0.3, out=None, dropped=None):
-    """Checks of voxel_counts (nothing is launched before they pass) -> (points, pred, labels, batchIds, aabbMin, resolution,
-    maxIgnoreShare) as the library reads them: float32 [n, 3], int32 [n] -- an int64 pred or labels is cast here, behind the
-    checks, one torch launch each -- int32 [n] or None, float32 [numClouds, 3], the float32 value of resolution as a float, a
-    float."""
+    """Checks of voxel_counts (nothing is launched before they pass) -> what _voxel_counts_run takes: its own arguments with
+    points, pred, labels, batchIds, aabbMin, resolution and maxIgnoreShare as the library reads them -- float32 [n, 3], int32
+    [n] (an int64 pred or labels is cast here, behind the checks, one torch launch each), int32 [n] or None, float32
+    [numClouds, 3], the float32 value of resolution as a float, a float -- and every negative ignoreLabel as -1."""
     op = "voxel_counts"
-    for v, name in ((numClasses, "numClasses"), (numClouds, "numClouds")):
-        _req(isinstance(v, int) and not isinstance(v, bool) and v >= 1, "%s expects %s >= 1" % (op, name))
+    _pos_int(op, numClasses, "numClasses")
+    _pos_int(op, numClouds, "numClouds")
     _req(numClouds <= 32768 and numClouds * numClasses * 2 < (1 << 31), "%s: numClouds (<= 32768) * numClasses too large" % op)
-    _req(isinstance(ignoreLabel, int) and not isinstance(ignoreLabel, bool) and -(1 << 31) <= ignoreLabel < (1 << 31),
-         "%s expects an integer ignoreLabel (< 0: none)" % op)
+    ignoreLabel = _ignore_label(op, ignoreLabel)
     _req(isinstance(resolution, (int, float, _np.floating)) and not isinstance(resolution, bool), "%s expects a number as resolution" % op)
     with _np.errstate(over="ignore"):
         res = float(_np.float32(resolution))
     _req(res > 0.0 and res != float("inf"), "%s expects a finite resolution > 0 (as float32)" % op)
     _req(isinstance(maxIgnoreShare, (int, float, _np.floating)) and not isinstance(maxIgnoreShare, bool),
          "%s expects a number as maxIgnoreShare" % op)
-    _req(isinstance(points, torch.Tensor) and points.dtype == torch.float32, "%s: points must be a float32 tensor" % op)
+    _typed(op, points, "points", _F32)
     _req(points.dim() == 2 and points.shape[1] == 3, "%s: points must have shape (n, 3)" % op)
     n = points.shape[0]
     _req(n < (1 << 30), "%s: points too large" % op)
     _req(points.is_contiguous(), "%s: points must be contiguous" % op)
-    for t, name in ((pred, "pred"), (labels, "labels")):
-        _req(isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64), "%s: %s must be an int32 (or int64) tensor" % (op, name))
-        _req(tuple(t.shape) in ((n,), (n, 1)), "%s: %s must have shape (n,) or (n, 1)" % (op, name))
-        _req(t.device == points.device and t.is_contiguous(), "%s: %s must be contiguous on points' device" % (op, name))
-    if batchIds is not None:
-        _req(isinstance(batchIds, torch.Tensor) and batchIds.dtype == torch.int32, "%s: batchIds must be an int32 tensor" % op)
-        _req(tuple(batchIds.shape) in ((n,), (n, 1)), "%s: batchIds must have shape (n,) or (n, 1)" % op)
-        _req(batchIds.device == points.device and batchIds.is_contiguous(), "%s: batchIds must be contiguous on points' device" % op)
-    _req(isinstance(aabbMin, torch.Tensor) and aabbMin.dtype == torch.float32, "%s: aabbMin must be a float32 tensor" % op)
-    _req(tuple(aabbMin.shape) == (numClouds, 3), "%s: aabbMin must have shape (numClouds, 3)" % op)
-    _req(aabbMin.device == points.device and aabbMin.is_contiguous(), "%s: aabbMin must be contiguous on points' device" % op)
+    pred = _rows(op, pred, "pred", _INT, n, points, "points'")
+    labels = _rows(op, labels, "labels", _INT, n, points, "points'")
+    batchIds = _opt_rows(op, batchIds, "batchIds", _I32, n, points, "points'")
+    _shaped(op, aabbMin, "aabbMin", _F32, (numClouds, 3), "(numClouds, 3)", points, "points'")
     if out is not None:
-        _req(isinstance(out, torch.Tensor) and out.dtype == torch.int64, "%s: out must be an int64 tensor" % op)
-        _req(tuple(out.shape) == (numClouds, numClasses, 2), "%s: out must have shape (numClouds, numClasses, 2)" % op)
-        _req(out.device == points.device and out.is_contiguous(), "%s: out must be contiguous on points' device" % op)
+        _shaped(op, out, "out", _I64, (numClouds, numClasses, 2), "(numClouds, numClasses, 2)", points, "points'")
     if dropped is not None:
-        _req(isinstance(dropped, torch.Tensor) and dropped.dtype == torch.int32, "%s: dropped must be an int32 tensor" % op)
+        _typed(op, dropped, "dropped", _I32)
         _req(dropped.numel() == 1 and dropped.device == points.device, "%s: dropped must have one element on points' device" % op)
     _req(points.is_cuda, "%s: points must be a CUDA tensor" % op)
-    pred, labels = pred.detach().reshape(n), labels.detach().reshape(n)
-    if pred.dtype != torch.int32:
-        pred = pred.to(torch.int32)
-    if labels.dtype != torch.int32:
-        labels = labels.to(torch.int32)
-    return (points.detach(), pred, labels, None if batchIds is None else batchIds.detach().reshape(n), aabbMin.detach(), res,
-            float(maxIgnoreShare))
+    return (points.detach(), _int32(pred), _int32(labels), numClasses, batchIds, numClouds, aabbMin.detach(), res, ignoreLabel,
+            float(maxIgnoreShare), out, dropped)
 
 
 def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05, ignoreLabel=-1,
@@ -634,9 +671,12 @@ def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, a
     is ADDED to and returned. The table lives in a zeroed tensor kept per (device, stream, capacity, numClasses), 8 + 8
     numClasses bytes for each of the >= 2 n slots; the op leaves it zeroed. Integer atomics only: the same inputs give the
     same bytes. Nothing is differentiable and nothing is read back."""
-    points, pred, labels, batchIds, aabbMin, res, share = _voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds,
-                                                                             aabbMin, resolution, ignoreLabel, maxIgnoreShare, out,
-                                                                             dropped)
+    return _voxel_counts_run(*_voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution,
+                                                 ignoreLabel, maxIgnoreShare, out, dropped))
+
+
+def _voxel_counts_run(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, res, ignoreLabel, share, out, dropped):
+    """voxel_counts behind its checks, over what _voxel_counts_args returns."""
     lib = _lib.load()
     if out is None:
         out = torch.zeros((numClouds, numClasses, 2), dtype=torch.int64, device=points.device)
@@ -645,8 +685,8 @@ def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, a
         return out
     ws = _voxel_ws(n, numClasses, points.device)
     check(lib.mccnn_voxel_acc_add(ptr(points), ptr(pred), ptr(labels), ptr(batchIds), ptr(aabbMin), n, numClouds, numClasses,
-                                  max(ignoreLabel, -1), res, share, ptr(out), ptr(dropped), ptr(ws), ws.numel(), 1,
-                                  stream_handle()), "voxel_counts")
+                                  ignoreLabel, res, share, ptr(out), ptr(dropped), ptr(ws), ws.numel(), 1, stream_handle()),
+          "voxel_counts")
     return out
 
 

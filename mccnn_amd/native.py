@@ -16,6 +16,7 @@ import torch
 from . import _env, _lib
 from ._lib import check, ptr, stream_handle
 from .MCConvModule import _edge_guess, _remember_edges, _ws, _bf16_rows_aligned
+from . import dense_glue as M   # (behind MCConvModule, whose import brings dense_glue in)
 
 
 def _load_ext():
@@ -625,21 +626,37 @@ def conv(geo, feats, w1, b1, w2, b2, w3, b3, numOutFeatures, combin, avg, determ
     return _Conv.apply(feats, w1, b1, w2, b2, w3, b3, geo, numOutFeatures, combin, avg, deterministic)
 
 
+# ---------------------------------------------------------------------------------------------
+# The dense ops (dense_glue.py), each in two steps: X(...) = _X_run(*M._X_args(...)). M._X_args is the op's argument rule,
+# the only one there is; _X_run takes what the rule returns to the extension when that is loaded, to the ctypes form
+# (M._X_run) otherwise -- the same library calls either way, so the same bytes. A caller that has run the rule itself (the
+# gates of MCNetworkUtils) calls _X_run.
+def _out_flag(outDtype):
+    return -1 if outDtype is None else int(outDtype == torch.bfloat16)
+
+
+def _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
+    if _EXT is None:
+        return M._bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale)
+    return _EXT.bn_relu_drop(x, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
+                             float(momentum), float(epsilon), _out_flag(outDtype))
+
+
 def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
                  epsilon=1e-3, outDtype=None):
     """The dense glue as one op, y = drop(act(bn(x))) (dense_glue.bn_relu_dropout: its definition, checks and errors):
     one Python -> C++ call forward and an autograd node on the C++ side when the extension is loaded, the ctypes op
     otherwise -- the same library calls either way, so the same bytes. x: float32 or bfloat16 rows; outDtype: y's type
     (None: x's)."""
-    from . import dense_glue as M
-    if _EXT is None:
-        return M.bn_relu_dropout(x, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum, epsilon,
-                                 outDtype)
-    thr, scale = M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
-    M._req(training or not (torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad or beta.requires_grad)),
-           "bn_relu_dropout: the eval form has no gradients")
-    return _EXT.bn_relu_drop(x, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
-                             float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
+    return _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                       *M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
+_EXT_SYNC_STAGES = None if _EXT is None else (_EXT.bn_sync_stats, _EXT.bn_sync_apply, _EXT.bn_sync_bwd_sums, _EXT.bn_sync_bwd_dx)
+
+
+def _bn_sync_run(*checked):
+    return M._bn_sync_run(*checked, stages=_EXT_SYNC_STAGES or M._BN_SYNC_STAGES)
 
 
 def bn_relu_drop_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb=None, seed=0, momentum=0.99, epsilon=1e-3,
@@ -648,12 +665,16 @@ def bn_relu_drop_sync(x, gamma, beta, movingMean, movingVar, relu=True, keepProb
     (dense_glue.bn_relu_dropout_sync: its definition, checks and errors). The autograd node is that module's either way
     (the collectives between the stages are torch.distributed's); with the extension loaded its four stages are the
     extension's calls, with the ctypes ones otherwise -- the same library calls, so the same bytes."""
-    from . import dense_glue as M
+    return _bn_sync_run(x, gamma, beta, movingMean, movingVar, relu, seed, momentum, epsilon, outDtype, group,
+                        *M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, sync=True, group=group))
+
+
+def _linear_bn_run(x, w, b, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
     if _EXT is None:
-        return M.bn_relu_dropout_sync(x, gamma, beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype,
-                                      group)
-    return M._bn_relu_dropout_sync((_EXT.bn_sync_stats, _EXT.bn_sync_apply, _EXT.bn_sync_bwd_sums, _EXT.bn_sync_bwd_dx), x, gamma,
-                                   beta, movingMean, movingVar, relu, keepProb, seed, momentum, epsilon, outDtype, group)
+        return M._linear_bn_run(x, w, b, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                                thr, scale)
+    return _EXT.linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
+                                    float(momentum), float(epsilon), _out_flag(outDtype))
 
 
 def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
@@ -662,15 +683,12 @@ def linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, training, r
     (dense_glue.linear_bn_relu_dropout: its definition, checks and errors): one Python -> C++ call forward and an
     autograd node on the C++ side when the extension is loaded, the ctypes op otherwise -- the same library calls either
     way, so the same bytes."""
-    from . import dense_glue as M
-    if _EXT is None:
-        return M.linear_bn_relu_dropout(x, w, b, gamma, beta, movingMean, movingVar, training, relu, keepProb, seed, momentum,
-                                        epsilon, outDtype)
-    thr, scale = M._linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype)
-    M._req(training or not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, w, b, gamma, beta))),
-           "linear_bn_relu_dropout: the eval form has no gradients")
-    return _EXT.linear_bn_relu_drop(x, w, b, gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
-                                    float(momentum), float(epsilon), -1 if outDtype is None else int(outDtype == torch.bfloat16))
+    return _linear_bn_run(x, w, b, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                          *M._linear_bn_args(x, w, b, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
+def _linear_xent_run(*checked):
+    return (M._linear_xent_run if _EXT is None else _EXT.linear_softmax_xent)(*checked)
 
 
 def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
@@ -678,33 +696,36 @@ def linear_softmax_xent(x, w, b, labels, weights=None, wantLogits=False):
     (dense_glue.linear_softmax_xent: its definition, checks and errors): one Python -> C++ call forward and an autograd
     node on the C++ side (LinearXentBackward) when the extension is loaded, the ctypes op otherwise -- the same library
     calls either way, so the same bytes."""
-    from . import dense_glue as M
-    if _EXT is None:
-        return M.linear_softmax_xent(x, w, b, labels, weights, wantLogits)
-    labels, weights = M._linear_xent_args(x, w, b, labels, weights)
-    return _EXT.linear_softmax_xent(x, w, b, labels, weights, bool(wantLogits))
+    return _linear_xent_run(*M._linear_xent_args(x, w, b, labels, weights, wantLogits))
+
+
+def _cosine_loss_run(*checked):
+    return (M._cosine_loss_run if _EXT is None else _EXT.cosine_distance_loss)(*checked)
 
 
 def cosine_distance_loss(pred, target, weights=None):
     """The cosine-distance loss of normal estimation as one op -> (loss, sums, meta) (dense_glue.cosine_distance_loss: its
     definition, checks and errors): one Python -> C++ call forward and an autograd node on the C++ side (CosineLossBackward)
     when the extension is loaded, the ctypes op otherwise -- the same library calls either way, so the same bytes."""
-    from . import dense_glue as M
-    if _EXT is None:
-        return M.cosine_distance_loss(pred, target, weights)
-    weights = M._cosine_loss_args(pred, target, weights)
-    return _EXT.cosine_distance_loss(pred, target, weights)
+    return _cosine_loss_run(*M._cosine_loss_args(pred, target, weights))
+
+
+def _seg_counts_run(*checked):
+    return (M._seg_counts_run if _EXT is None else _EXT.segmentation_counts)(*checked)
 
 
 def segmentation_counts(pred, labels, numClasses, batchIds=None, numClouds=1, weights=None, ignoreLabel=-1, out=None):
     """The counts behind the IoU of segmentation -> int64 (numClouds, numClasses, 3) (dense_glue.segmentation_counts: its
     definition, checks and errors): one Python -> C++ call on the current stream when the extension is loaded, the ctypes op
     otherwise -- the same library call either way, so the same bytes. A plain function: nothing is differentiable."""
-    from . import dense_glue as M
+    return _seg_counts_run(*M._seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out))
+
+
+def _voxel_counts_run(*checked):
     if _EXT is None:
-        return M.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
-    pred, labels, batchIds, weights = M._seg_counts_args(pred, labels, numClasses, batchIds, numClouds, weights, ignoreLabel, out)
-    return _EXT.segmentation_counts(pred, labels, numClasses, batchIds, numClouds, weights, max(ignoreLabel, -1), out)
+        return M._voxel_counts_run(*checked)
+    points, numClasses = checked[0], checked[3]
+    return _EXT.voxel_counts(*checked, M._voxel_ws(points.shape[0], numClasses, points.device) if points.shape[0] else None)
 
 
 def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, aabbMin=None, resolution=0.05, ignoreLabel=-1,
@@ -712,13 +733,7 @@ def voxel_counts(points, pred, labels, numClasses, batchIds=None, numClouds=1, a
     """The counts behind ScanNet's voxel accuracy -> int64 (numClouds, numClasses, 2) (dense_glue.voxel_counts: its
     definition, checks, errors and its table): one Python -> C++ call on the current stream when the extension is loaded, the
     ctypes op otherwise -- the same library call either way, so the same bytes. A plain function: nothing is differentiable."""
-    from . import dense_glue as M
-    if _EXT is None:
-        return M.voxel_counts(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution, ignoreLabel,
-                              maxIgnoreShare, out, dropped)
-    points, pred, labels, batchIds, aabbMin, res, share = M._voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds,
-                                                                               aabbMin, resolution, ignoreLabel, maxIgnoreShare,
-                                                                               out, dropped)
-    ws = M._voxel_ws(points.shape[0], numClasses, points.device) if points.shape[0] else None
-    return _EXT.voxel_counts(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, res, max(ignoreLabel, -1), share, out,
-                             dropped, ws)
+    return _voxel_counts_run(*M._voxel_counts_args(points, pred, labels, numClasses, batchIds, numClouds, aabbMin, resolution,
+                                                   ignoreLabel, maxIgnoreShare, out, dropped))
+
+
