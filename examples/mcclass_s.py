@@ -6,6 +6,7 @@ tiny synthetic training loop. The graph builders keep the reference's structure 
     python examples/mcclass_s.py [--steps 20] [--device-loader]
     python examples/mcclass_s.py --normals [--fused-glue] [--fused-loss]     # MCNormS on the ellipsoids' analytic normals
     python examples/mcclass_s.py --parts [--fused-glue] [--fused-loss]       # per-point part labels, part IoU from device counts
+    python examples/mcclass_s.py --fused-adam [--weight-decay 1e-4]          # the optimiser step as one library op (any mode)
 
 --device-loader builds the batches on the GPU (mccnn_amd.device_batcher.DeviceBatcher: a pool of synthetic models uploaded
 once, non-uniform sampling and rotation per batch on the device) instead of uploading host arrays.
@@ -179,12 +180,23 @@ def synthetic_normals_batch(batchSize, nPts, rng, device):
     return P, Bi, torch.ones((P.shape[0], 1), dtype=torch.float32, device=device), t(np.concatenate(nrm))
 
 
+def make_optimizer(net, args, lr=5e-3):
+    """The optimiser of all three training loops. Default: torch.optim.Adam, as before. --fused-adam: mccnn_amd.optim.FusedAdam,
+    the step as one library op, with the reference's L2 term (ModelNet.py:33-56: l2_regularizer over the 'weight_decay_loss'
+    collection, added to the loss) as --weight-decay C over the two collections of the network."""
+    if not args.fused_adam:
+        return torch.optim.Adam(net.parameters(), lr=lr)
+    from mccnn_amd.optim import FusedAdam
+    decay = net.store.get_collection('weight_decay_loss') + net.convBuilder.get_collection('weight_decay_loss')
+    return FusedAdam(net.parameters(), lr=lr, weightDecay=args.weight_decay, decayParams=decay)
+
+
 def train_normals(args, device, rng):
     """--normals: MCNormS on the synthetic ellipsoids, the loss and the mean angle from the NormalHead of the model."""
     net = MCNormS(1, args.batch, 16, device, fused=args.fused_glue, fusedLoss=args.fused_loss)
     P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
     net(P, Bi, F, True)  # creates the variables
-    opt = torch.optim.Adam(net.parameters(), lr=5e-3)
+    opt = make_optimizer(net, args)
     for step in range(args.steps):
         P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
         head = net(P, Bi, F, True, normals=N)
@@ -215,7 +227,7 @@ def train_parts(args, device, rng):
     net = MCNormS(1, args.batch, 16, device, fused=args.fused_glue, fusedLoss=args.fused_loss, outFeatures=16)
     P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)
     net(P, Bi, F, True, partLabels=part_labels(N), numParts=NUM_PARTS)  # creates the variables
-    opt = torch.optim.Adam(net.parameters(), lr=5e-3)
+    opt = make_optimizer(net, args)
     mask = torch.ones((args.batch, NUM_PARTS), dtype=torch.bool, device=device)   # every cloud has all eight parts
     counts = torch.zeros((args.batch, NUM_PARTS, 3), dtype=torch.int64, device=device)
     voxels = torch.zeros((args.batch, NUM_PARTS, 2), dtype=torch.int64, device=device)
@@ -301,7 +313,14 @@ def main():
                          "(voxel_counts, voxel_scores)")
     ap.add_argument("--bf16-rows", action="store_true",
                     help="keep the input rows of the depth-wise convolutions in bfloat16 (MCClassS(rows=torch.bfloat16))")
+    ap.add_argument("--fused-adam", action="store_true",
+                    help="the optimiser step as one library op (mccnn_amd.optim.FusedAdam) instead of torch.optim.Adam")
+    ap.add_argument("--weight-decay", type=float, default=0.0, metavar="C",
+                    help="with --fused-adam: L2 decay C over the 'weight_decay_loss' collections (the reference's "
+                         "l2_regularizer(scale=C) term)")
     args = ap.parse_args()
+    if args.weight_decay and not args.fused_adam:
+        ap.error("--weight-decay needs --fused-adam")
     device = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -318,7 +337,7 @@ def main():
         (lambda: synthetic_batch(args.batch, args.points, 4, rng, device))
     P, Bi, F, y = make_batch()
     net(P, Bi, F, True)  # creates the variables
-    opt = torch.optim.Adam(net.parameters(), lr=5e-3)
+    opt = make_optimizer(net, args)
     # the loader runs two batches ahead: the hierarchy of batch k + 2 is requested (helper thread, own stream) while batch
     # k trains; the one of batch k + 1 is complete by then, and its geometry is started under batch k's layers
     cur = make_batch()

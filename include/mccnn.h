@@ -1102,6 +1102,46 @@ int mccnn_voxel_acc_add(const float* pts, const int* pred, const int* labels, co
                         long long* counts /* [num_clouds, num_classes, 2], += */, int* dropped /* NULL: not counted */,
                         void* ws, size_t ws_bytes, int ws_clean, mccnn_stream_t stream);
 
+/* THE OPTIMISER STEP AS ONE OP: ADAM WITH L2 DECAY OVER MANY TENSORS (extension, ABI 27; adam.hip). Per element, in float32,
+ * with the record's step_size, bc2_sqrt, weight_decay and the call's beta1, beta2, eps, grad_scale, every operation rounded
+ * once and in this order (1 - beta is the float32 difference):
+ *   g   = grad_scale * grad                      (skipped when grad_scale == 1.0f)
+ *   g   = weight_decay * p + g                   (skipped when weight_decay == 0.0f; L2 in the gradient, not AdamW)
+ *   m'  = m + (1 - beta1) * (g - m)
+ *   v'  = beta2 * v + ((1 - beta2) * g) * g
+ *   den = sqrt(v') / bc2_sqrt + eps
+ *   p'  = p - step_size * (m' / den)
+ * p, m and v [n] float32 are updated in place, g [n] is only read. The caller computes the per-tensor scalars from the
+ * tensor's own step count t >= 1, in double from the float32 betas the call passes, rounded once to float:
+ *   torch.optim.Adam's arithmetic:      step_size = lr / (1 - beta1^t),                      bc2_sqrt = sqrt(1 - beta2^t)
+ *   tf.train.AdamOptimizer's (epsilon outside the bias correction):
+ *                                       step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t),    bc2_sqrt = 1
+ * `tensors` is a HOST array of `count` records, read before the call returns; the records of up to mccnn_adam_max_tensors()
+ * tensors travel by value in the arguments of one launch, so nothing is uploaded and nothing has to stay valid afterwards. A
+ * record with n == 0 is skipped: its pointers and scalars are not looked at. A call issues ceil(live / max) launches, live =
+ * the records with n > 0, and none for count == 0 or live == 0 (MCCNN_OK). Pointers need 4-byte alignment only; a tensor whose
+ * four pointers are all 16-byte aligned is read and written 16 bytes at a time, every other one float by float, and nothing
+ * outside [0, n) of any array is touched either way. No atomics, no workspace, no memset, nothing read back: the same inputs
+ * give the same bytes. The library cannot check that the arrays of a call do not overlap one another (p, m, v of one tensor,
+ * or any array of two tensors): the result is then unspecified.
+ * count < 0, a NULL array with count > 0, a record with n < 0, a record with n > 0 and a NULL or not 4-byte aligned pointer, a
+ * non-finite step_size / weight_decay / bc2_sqrt or bc2_sqrt <= 0, beta1 or beta2 outside [0, 1), eps < 0, a non-finite beta1 /
+ * beta2 / eps / grad_scale: MCCNN_E_BADARG; more than 2^31 - 1 workgroups in one launch: MCCNN_E_TOOLARGE (out of reach while
+ * a workgroup takes 4096 elements of a tensor of at most 2^31 - 1); all before anything is launched. */
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int n;
+    float step_size;
+    float bc2_sqrt;
+    float weight_decay;
+} mccnn_adam_tensor;
+int mccnn_adam_max_tensors(void); /* tensors one launch takes */
+int mccnn_adam_step(const mccnn_adam_tensor* tensors /* HOST array */, int count, float beta1, float beta2, float eps,
+                    float grad_scale, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

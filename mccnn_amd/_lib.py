@@ -172,6 +172,9 @@ SIGNATURES = {
     # voxel accuracy on the device: per-voxel majority votes in a hash table (voxel_acc.hip)
     "mccnn_voxel_acc_workspace_bytes": (_sz, [_i, _i]),
     "mccnn_voxel_acc_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_double, _vp, _vp, _vp, _sz, _i, _vp]),
+    # the optimiser step as one op: Adam with L2 decay over many tensors (adam.hip); the records are a HOST array
+    "mccnn_adam_max_tensors": (_i, []),
+    "mccnn_adam_step": (_i, [_vp, _i, _f, _f, _f, _f, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -86,7 +86,11 @@ def gather_rows(buf, group=None, route=None):
 
 
 class GradBucket:
-    """One flat buffer for all kernel-MLP gradients -> a single all-reduce per step."""
+    """One flat buffer for all kernel-MLP gradients -> a single all-reduce per step.
+
+    allreduce(average=True) divides the flat buffer in wait(): one launch (flat.div_(world)). With
+    mccnn_amd.optim.FusedAdam(..., gradScale=1.0 / world) and allreduce(average=False) that launch is not needed: the
+    optimiser multiplies every gradient by gradScale as it loads it. The bucket itself does the same either way."""
 
     def __init__(self, params, single_rank=False):
         """single_rank=True runs the collective even in a process group of one rank (tests of the RCCL path on a 1-GPU
