@@ -1666,10 +1666,11 @@ def spatial_conv(inPts, inFeatures, inBatchIds, inPDFs, inSamplePts, neighStartI
 
 
 # ---------------------------------------------------------------------------------------------
-# The dense glue between two convolutions as library ops (bn_relu_dropout, bn_relu_dropout_sync, linear_bn_relu_dropout)
+# The dense glue between two convolutions as library ops (bn_relu_dropout, bn_relu_dropout_cat, bn_relu_dropout_sync,
+# linear_bn_relu_dropout)
 # lives in dense_glue.py; its names stay importable from here. At the end on purpose: dense_glue imports _req, _ws and
 # _bf16_rows_aligned from this module at ITS end, so either module may be the first one imported.
-from .dense_glue import (BN_DROP_ALL, _BN_SYNC_STAGES, _bn_act_args, _bn_relu_dropout_sync, _cosine_loss_args,  # noqa: E402,F401
+from .dense_glue import (BN_DROP_ALL, _BN_SYNC_STAGES, _bn_act_args, _bn_cat_args, _bn_relu_dropout_sync, _cosine_loss_args,  # noqa: E402,F401
                          _linear_bn_args, _linear_xent_args, _seg_counts_args, _voxel_counts_args, bn_relu_dropout,
-                         bn_relu_dropout_sync, cosine_distance_loss, linear_bn_relu_dropout, linear_softmax_xent,
+                         bn_relu_dropout_cat, bn_relu_dropout_sync, cosine_distance_loss, linear_bn_relu_dropout, linear_softmax_xent,
                          segmentation_counts, voxel_counts)

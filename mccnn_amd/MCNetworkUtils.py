@@ -19,6 +19,13 @@ the op cut in two around one gather of 3c floats per rank, forward and backward)
 mask of a row is that of its index in the whole batch, so with one dropSeed_ on all ranks the shards drop what a single
 process would. fusedLinear leaves that case to the matmul followed by this op.
 
+VariableStore(fused=True, fusedCat=True) (extension, opt-in): batch_norm_RELU_drop_out also takes a list or tuple of 2-D
+tensors, meaning their concatenation along axis 1. With both switches on the block reads the segments where they are
+(dense_glue.bn_relu_dropout_cat, csrc/bn_act.hip: one op, no torch.cat, one contiguous gradient per segment) where its
+conditions hold (_fused_cat: 1 .. 8 float32 contiguous segments on one HIP device, statistics of this process alone);
+everywhere else -- the switch off, CPU, bfloat16 segments, statistics across ranks -- the list is torch.cat'ed and takes
+the path of a single tensor. Names, shapes, initialisers, state_dict and the dropSeed_ / dropCalls_ counting are the same.
+
 VariableStore(fusedLinear=True) (extension, opt-in): a linear layer with such a block behind it -- conv_1x1 followed by
 batch_norm_RELU_drop_out (conv_1x1_batch_norm_RELU_drop_out) and the hidden layers of the MLPs -- runs as ONE library op
 (dense_glue.linear_bn_relu_dropout, csrc/linear_bn.hip) where its conditions hold (_fused_linear); everywhere else the
@@ -60,7 +67,7 @@ class VariableStore(torch.nn.Module):
     names (`Reduce_1_weights`, `Final_Logits_BN_h1/gamma`, ...). Variables are created on first use (tf.get_variable),
     so load_state_dict() also accepts names that do not exist yet."""
 
-    def __init__(self, device=None, fused=False, fusedLinear=False, fusedSync=False, fusedLoss=False):
+    def __init__(self, device=None, fused=False, fusedLinear=False, fusedSync=False, fusedLoss=False, fusedCat=False):
         super().__init__()
         self.device = device
         self.collections_ = {}
@@ -68,6 +75,7 @@ class VariableStore(torch.nn.Module):
         self.fusedLinear_ = bool(fusedLinear)   # linear layer + glue as one library op where it applies (reassignable too)
         self.fusedSync_ = bool(fusedSync)   # with fused_: the glue stays a library op when statistics cross ranks (reassignable)
         self.fusedLoss_ = bool(fusedLoss)   # last linear + softmax cross-entropy as one library op where it applies (reassignable)
+        self.fusedCat_ = bool(fusedCat)   # with fused_: the glue over a list of segments reads them in place (reassignable)
         self.syncGroup_ = None      # the process group of those statistics (None: the default group)
         self.dropSeed_ = 0          # a fused call that drops uses the seed (dropSeed_ + dropCalls_) mod 2^32 ...
         self.dropCalls_ = 0         # ... and increments this counter
@@ -267,6 +275,31 @@ def _fused_glue(st, inputs, training, name, relu, keepProb=None, momentum=0.99, 
     if synced:
         return native._bn_sync_run(inputs, gamma, beta, mov_mean, mov_var, relu, seed, momentum, epsilon, outDtype, group, *checked)
     return native._bn_act_run(inputs, gamma, beta, mov_mean, mov_var, training, relu, seed, momentum, epsilon, outDtype, *checked)
+
+
+def _fused_cat(st, segments, training, name, relu, keepProb=None, momentum=0.99, epsilon=1e-3, sync=True, outDtype=None):
+    """drop(act(batch_normalization(torch.cat(segments, 1)))) as one library op that reads the segments where they are, or
+    None where that form does not apply (the caller then concatenates and goes on as for a single tensor): fused_ or
+    fusedCat_ is off, training statistics are synchronised across ranks, the library does not load, or whatever the op's own
+    rule (dense_glue._bn_cat_args), asked once, refuses -- more than 8 segments, one that is not a contiguous float32 2-D tensor
+    on a HIP device, an eval call that wants gradients. The block's variables and the seed of a call that drops are those of
+    _fused_glue on the concatenated tensor."""
+    if not (getattr(st, "fused_", False) and getattr(st, "fusedCat_", False)) or _stats_cross_ranks(training, sync):
+        return None
+    native = _fused_native()
+    if native is None or not all(torch.is_tensor(x) and x.dim() == 2 for x in segments):
+        return None
+    # residual: as in _fused_glue
+    if keepProb is not None and not 0.0 < keepProb <= 1.0:
+        return None
+    gamma, beta, mov_mean, mov_var = _bn_block(st, name, sum(x.shape[1] for x in segments), segments[0].device)
+    keep = keepProb if training else None
+    try:   # (the seed is drawn behind the checks: they see 0 in its place)
+        checked = dense_glue._bn_cat_args(segments, gamma, beta, mov_mean, mov_var, keep, 0, outDtype, training=training)
+    except InvalidArgumentError:
+        return None
+    seed = _draw_drop_seed(st, keep)
+    return native._bn_cat_run(segments, gamma, beta, mov_mean, mov_var, training, relu, seed, momentum, epsilon, outDtype, *checked)
 
 
 def _keep_prob(useDropOut, keepProb):
@@ -849,8 +882,16 @@ def conv_1x1_softmax_cross_entropy(layerName, inputs, numInputs, numOutFeatures,
 def batch_norm_RELU_drop_out(layerName, inFeatures, isTraining, usedDropOut, keepProb, store=None, outDtype=None):
     """utils/MCNetworkUtils.py:129-144. outDtype (extension): the result's type, torch.float32 or torch.bfloat16 (None: as
     computed) -- with a fused store the one library op reads float32 or bfloat16 rows and writes either, so the block is
-    also the cast between layers that keep different row types."""
+    also the cast between layers that keep different row types. inFeatures (extension): also a list or tuple of 2-D tensors,
+    meaning torch.cat(inFeatures, 1) -- one library op over the segments where the store's fused_ and fusedCat_ say so and it
+    applies (_fused_cat), the concatenation followed by the path of a single tensor otherwise."""
     st = store or _DEFAULT_STORE
+    if isinstance(inFeatures, (list, tuple)):
+        if len(inFeatures) >= 1:
+            y = _fused_cat(st, inFeatures, isTraining, layerName + "_BN", True, _keep_prob(usedDropOut, keepProb), outDtype=outDtype)
+            if y is not None:
+                return y
+        inFeatures = torch.cat(list(inFeatures), 1)
     return _bn_relu_drop(st, inFeatures, isTraining, layerName + "_BN", usedDropOut, keepProb, outDtype)
 
 

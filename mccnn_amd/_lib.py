@@ -144,6 +144,12 @@ SIGNATURES = {
                                    _sz, _vp]),
     "mccnn_bn_act_bwd_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    # ... over a column-wise concatenation of up to 8 f32 segments; xs, cs and dxs are HOST arrays
+    "mccnn_bn_act_cat_max_segments": (_i, []),
+    "mccnn_bn_act_cat_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_ulonglong, _f, C.c_uint, _vp, _i, _vp, _vp,
+                                  _sz, _vp]),
+    "mccnn_bn_act_cat_bwd": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz,
+                                  _vp]),
     # ... with batch statistics across ranks: the four stages around the caller's two collectives
     "mccnn_bn_sync_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mccnn_bn_sync_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, C.c_ulonglong, _f, C.c_uint, _vp, _i,

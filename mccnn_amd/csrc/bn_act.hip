@@ -18,6 +18,10 @@
 //                       are recomputed from x, saved and the seed.
 //   n <= 256            one workgroup per column tile does both halves in ONE launch, forward and backward.
 //   eval                one launch.
+//   over a concatenation (mccnn_bn_act_cat_fwd / _bwd): up to 8 f32 segments [n, c_s] in place of x, never concatenated. The
+//                       plan, the launches and the arithmetic are those of f32 x at width C = sum c_s; a thread looks its
+//                       segment up once (bn_cat.h) and reads x_s + r * c_s + (col - col0_s). The table is a kernel argument
+//                       of those instantiations alone.
 // No atomics, no memset, no ticket or spin-wait between workgroups; a fixed merge order: the same inputs and seed give the
 // same bytes. The gate is pre > 0 (torch's relu'), not the >= 0 of the convolution kernels.
 #include <initializer_list>
@@ -26,41 +30,16 @@
 #include "common.h"
 #include "bn_drop.h"
 #include "bn_act.h"
+#include "bn_cat.h"   // the plan (BnPlan, bn_plan and its constants) and the segment table of the op over a concatenation
 
 namespace mccnn {
-
-constexpr int kBnThreads = 256;
-constexpr int kBnTileCols = 64;     // most columns of a workgroup: 128 bytes of a row of x (32 f32, 64 bf16)
-constexpr int kBnSmallRows = 256;   // up to here: the one-launch form
-constexpr int kBnSlabRows = 128;    // rows of a slab ...
-constexpr int kBnMaxSlabs = 64;     // ... until there would be more slabs than this: then the slabs grow
 
 // rows of a thread whose loads are in flight together in the streaming loops of the forward. 8 columns per thread (bf16 x)
 // come with half the workgroups of the f32 layout for the same c, each moving up to twice the bytes: they keep more ahead
 template <int VEC>
 constexpr int kBnRowsAhead = VEC == 8 ? 8 : 4;
 
-struct BnPlan {
-    int vec, tw_log, tiles, slab_rows, slabs;
-};
-int bn_slab_rows(int n) {
-    if (n <= kBnSmallRows) return n;
-    if (ceil_div(n, kBnSlabRows) <= kBnMaxSlabs) return kBnSlabRows;
-    return ceil_div(ceil_div(n, kBnMaxSlabs), 32) * 32;
-}
-// aligned: every row pointer allows the wide form (bn_rows_aligned); x_bf16: the thread layout follows x's type
-inline BnPlan bn_plan(int n, int c, bool aligned, int x_bf16 = 0) {
-    BnPlan p;
-    if (x_bf16) p.vec = (c % 8 == 0 && aligned) ? 8 : 2;
-    else p.vec = (c % 4 == 0 && aligned) ? 4 : 1;
-    const int units = c / p.vec, most = (x_bf16 ? 64 : 32) / p.vec;
-    p.tw_log = 0;
-    while ((1 << p.tw_log) < most && (1 << p.tw_log) < units) ++p.tw_log;
-    p.tiles = ceil_div(units, 1 << p.tw_log);
-    p.slab_rows = bn_slab_rows(n);
-    p.slabs = ceil_div(n, p.slab_rows);
-    return p;
-}
+int bn_slab_rows(int n) { return bn_slab_rows_of(n); }
 
 struct BnArgs {
     const void* x;       // XT
@@ -100,6 +79,27 @@ __device__ __forceinline__ BnCoord bn_coord(const BnArgs& a) {
     t.col = t.ok ? (int)col : 0;
     return t;
 }
+
+// Where the rows of a thread's columns of x (and dx) are. The contiguous op (BnXPlain): the tensor itself at the global
+// column; over a concatenation (BnXCat, bn_cat.h): the thread's segment, found once. Everything else a thread touches -- y,
+// dy, gamma, beta, saved, the partials, the mask -- is at the global column t.col either way.
+// x / dx: the rows; at: the element offset of the thread's first column in row r; want (backward): dx is wanted. The helpers
+// and kernels below take either as XS / X.
+struct BnXPlain {
+    __device__ __forceinline__ const void* x(const BnArgs& a) const { return a.x; }
+    __device__ __forceinline__ void* dx(const BnArgs& a) const { return a.out; }
+    __device__ __forceinline__ size_t at(const BnArgs& a, const BnCoord& t, size_t r) const { return r * a.c + t.col; }
+    __device__ __forceinline__ bool want(const BnArgs& a) const { return a.want_dx; }
+};
+struct BnXCat {
+    BnCatAt s;
+    __device__ __forceinline__ const void* x(const BnArgs&) const { return s.x; }
+    __device__ __forceinline__ void* dx(const BnArgs&) const { return s.dx; }
+    __device__ __forceinline__ size_t at(const BnArgs&, const BnCoord&, size_t r) const { return r * s.ld + s.col; }
+    __device__ __forceinline__ bool want(const BnArgs&) const { return s.dx != nullptr; }
+};
+__device__ __forceinline__ BnXPlain bn_x(const BnArgs&, const BnCoord&) { return BnXPlain(); }
+__device__ __forceinline__ BnXCat bn_x(const BnArgs&, const BnCoord& t, const BnCat& s) { return BnXCat{bn_cat_at(s, t.col)}; }
 
 // VEC f32 values of the library's own memory (LDS, the slab partials): p is on VEC * 4 bytes, 16 at the most
 template <int VEC>
@@ -275,19 +275,19 @@ __device__ __forceinline__ void bn_tree_sum(const BnArgs& a, const BnCoord& t, f
 }
 
 // (count, mean, M2) of rows [row0, row1) of the thread's columns, merged over the row lanes
-template <int VEC, typename XT>
-__device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t, int row0, int row1, float& cnt,
+template <int VEC, typename XT, typename XS>
+__device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t, const XS& X, int row0, int row1, float& cnt,
                                               float (&mean)[VEC], float (&m2)[VEC], float* lds) {
     float s1[VEC], s2[VEC], K[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { s1[k] = 0.f; s2[k] = 0.f; K[k] = 0.f; }
     int rows = 0;
     if (t.ok && row0 < row1) {
-        bn_ldr<VEC, XT>(a.x, (size_t)row0 * a.c + t.col, K);   // the shift: the slab's first row
+        bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)row0), K);   // the shift: the slab's first row
 #pragma unroll kBnRowsAhead<VEC>
         for (int r = row0 + t.ry; r < row1; r += t.R) {
             float v[VEC];
-            bn_ldr<VEC, XT>(a.x, (size_t)r * a.c + t.col, v);
+            bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)r), v);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 const float d = v[k] - K[k];
@@ -353,8 +353,8 @@ __device__ __forceinline__ void bn_finish_stats(const BnArgs& a, const BnCoord& 
 }
 
 // base: what the mask's row index has over the local one (statistics across ranks: the rows of the lower ranks)
-template <int VEC, typename XT, typename YT>
-__device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t, int row0, int row1, const float (&mean)[VEC],
+template <int VEC, typename XT, typename YT, typename XS>
+__device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t, const XS& X, int row0, int row1, const float (&mean)[VEC],
                                               const float (&rstd)[VEC], bool drop, int base = 0) {
     if (!t.ok) return;   // (no barrier follows)
     float g[VEC], b[VEC];
@@ -367,7 +367,7 @@ __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t,
         uint32_t wx[U][bn_raw_words<VEC, XT>()];
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (r + u * t.R < row1) bn_ld_raw<VEC, XT>(a.x, (size_t)(r + u * t.R) * a.c + t.col, wx[u]);
+            if (r + u * t.R < row1) bn_ld_raw<VEC, XT>(X.x(a), X.at(a, t, (size_t)(r + u * t.R)), wx[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const long long ru = r + u * t.R;
@@ -389,14 +389,18 @@ __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t,
 }
 
 // forward, training, launch 1
-template <int VEC, typename XT>
-__global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a) {
+// CAT (here and in the three kernels that read x below): nothing -- the contiguous op, the kernel's only argument is BnArgs --
+// or BnCat, the segment table of the op over a concatenation (mccnn_bn_act_cat_fwd / _bwd; XT float), an argument of those
+// instantiations alone. The body is the same: it asks X where the thread's rows are.
+template <int VEC, typename XT, typename... CAT>
+__global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a, CAT... s) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
     const BnCoord t = bn_coord<VEC>(a);
+    const auto X = bn_x(a, t, s...);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float cnt, mean[VEC], m2[VEC];
-    bn_slab_stats<VEC, XT>(a, t, row0, row1, cnt, mean, m2, lds);
+    bn_slab_stats<VEC, XT>(a, t, X, row0, row1, cnt, mean, m2, lds);
     if (t.ry == 0 && t.ok) {
         const size_t plane = (size_t)a.nparts * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
@@ -410,11 +414,12 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a) {
 }
 
 // MODE 0: forward, training, launch 2 (partials from launch 1); 1: the one-launch form (n <= 256); 2: eval
-template <int VEC, typename XT, typename YT, int MODE>
-__global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
+template <int VEC, typename XT, typename YT, int MODE, typename... CAT>
+__global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a, CAT... s) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
     __shared__ float sm[2][kBnTileCols];
     const BnCoord t = bn_coord<VEC>(a);
+    const auto X = bn_x(a, t, s...);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float mean[VEC], rstd[VEC];
@@ -424,15 +429,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a) {
             mean[k] = t.ok ? a.mov_mean[t.col + k] : 0.f;
             rstd[k] = t.ok ? 1.0f / sqrtf(a.mov_var[t.col + k] + a.eps) : 0.f;
         }
-        bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, false);
+        bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, false);
     } else {
         float cnt, m2[VEC];
         if constexpr (MODE == 0) bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
-        else bn_slab_stats<VEC, XT>(a, t, 0, a.n, cnt, mean, m2, lds);
+        else bn_slab_stats<VEC, XT>(a, t, X, 0, a.n, cnt, mean, m2, lds);
         bn_finish_stats<VEC>(a, t, (float)a.n, mean, m2, slab == 0, sm);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
-        bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll);
+        bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, a.T < kBnDropAll);
     }
 }
 
@@ -474,8 +479,8 @@ __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, c
 // them is used: behind the (uniform) relu and dropout branches of a row the compiler would otherwise hold the next row's
 // loads back, one memory latency per row.
 // base: what the mask's row index has over the local one (bn_apply_rows); f sees the local row.
-template <int VEC, typename XT, typename YT, typename F>
-__device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
+template <int VEC, typename XT, typename YT, typename F, typename XS>
+__device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, const XS& X, const BnCols<VEC>& q, int row0, int row1,
                                              bool drop, F&& f, int base = 0) {
     constexpr int U = 4;
     for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
@@ -484,7 +489,7 @@ __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, 
         for (int u = 0; u < U; ++u) {
             const long long ru = r + u * t.R;
             if (ru < row1) {
-                bn_ld_raw<VEC, XT>(a.x, (size_t)ru * a.c + t.col, wx[u]);
+                bn_ld_raw<VEC, XT>(X.x(a), X.at(a, t, (size_t)ru), wx[u]);
                 bn_ld_raw<VEC, YT>(a.dy, (size_t)ru * a.c + t.col, wd[u]);
             }
         }
@@ -501,14 +506,14 @@ __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, 
         }
     }
 }
-template <int VEC, typename XT, typename YT>
-__device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1,
+template <int VEC, typename XT, typename YT, typename XS>
+__device__ __forceinline__ void bn_slab_sums(const BnArgs& a, const BnCoord& t, const XS& X, const BnCols<VEC>& q, int row0, int row1,
                                              float (&sg)[VEC], float (&sx)[VEC], float (&sh)[VEC], float* lds, int base = 0) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { sg[k] = 0.f; sx[k] = 0.f; sh[k] = 0.f; }
     const bool drop = a.T < kBnDropAll;
     if (t.ok)
-        bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int, const float (&g)[VEC], const float (&xh)[VEC]) {
+        bn_grad_rows<VEC, XT, YT>(a, t, X, q, row0, row1, drop, [&](int, const float (&g)[VEC], const float (&xh)[VEC]) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) { sg[k] = sg[k] + g[k]; sx[k] = sx[k] + g[k] * xh[k]; sh[k] = sh[k] + xh[k]; }
         }, base);
@@ -537,10 +542,10 @@ __device__ __forceinline__ void bn_sum_partials(const BnArgs& a, const BnCoord& 
 
 // the dx half of launch 2 of the backward: dx of rows [row0, row1) from the workgroup's (sum g, sum g * (xhat - mh), mh) in
 // sm, fn rows in the statistics. base: what the mask's row index has over the local one (bn_apply_rows)
-template <int VEC, typename XT, typename YT>
-__device__ __forceinline__ void bn_dx_rows(const BnArgs& a, const BnCoord& t, const BnCols<VEC>& q, int row0, int row1, float fn,
+template <int VEC, typename XT, typename YT, typename XS>
+__device__ __forceinline__ void bn_dx_rows(const BnArgs& a, const BnCoord& t, const XS& X, const BnCols<VEC>& q, int row0, int row1, float fn,
                                            const float (*sm)[kBnTileCols], int base) {
-    if (!a.want_dx || !t.ok) return;
+    if (!X.want(a) || !t.ok) return;
     const bool drop = a.T < kBnDropAll;
     float kb[VEC], kg[VEC], gr[VEC], mh[VEC];
 #pragma unroll
@@ -550,11 +555,11 @@ __device__ __forceinline__ void bn_dx_rows(const BnArgs& a, const BnCoord& t, co
         mh[k] = sm[2][t.cx * VEC + k];
         gr[k] = q.g[k] * q.rstd[k];
     }
-    bn_grad_rows<VEC, XT, YT>(a, t, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
+    bn_grad_rows<VEC, XT, YT>(a, t, X, q, row0, row1, drop, [&](int r, const float (&g)[VEC], const float (&xh)[VEC]) {
         float o[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) o[k] = gr[k] * (g[k] - kb[k] - (xh[k] - mh[k]) * kg[k]);
-        bn_str<VEC, XT>(a.out, (size_t)r * a.c + t.col, o);
+        bn_str<VEC, XT>(X.dx(a), X.at(a, t, (size_t)r), o);
     }, base);
 }
 
@@ -563,16 +568,17 @@ __device__ __forceinline__ void bn_dx_rows(const BnArgs& a, const BnCoord& t, co
 // of few rows with |mean| >> std (var + eps barely above var) dx is the small remainder of cancelling terms, and the
 // shift alone would cost it more than 1e-4
 // SYNC (statistics across ranks): the mask at the global rows, meta[0] on
-template <int VEC, typename XT, typename YT, int SYNC = 0>
-__global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
+template <int VEC, typename XT, typename YT, int SYNC = 0, typename... CAT>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a, CAT... s) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
     const BnCoord t = bn_coord<VEC>(a);
+    const auto X = bn_x(a, t, s...);
     const BnCols<VEC> q = bn_cols<VEC>(a, t);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float sg[VEC], sx[VEC], sh[VEC];
-    if constexpr (SYNC) bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds, a.meta[0]);
-    else bn_slab_sums<VEC, XT, YT>(a, t, q, row0, row1, sg, sx, sh, lds);
+    if constexpr (SYNC) bn_slab_sums<VEC, XT, YT>(a, t, X, q, row0, row1, sg, sx, sh, lds, a.meta[0]);
+    else bn_slab_sums<VEC, XT, YT>(a, t, X, q, row0, row1, sg, sx, sh, lds);
     if (t.ry == 0 && t.ok) {
         const size_t plane = (size_t)a.nparts * a.c;
         float* p = a.part + (size_t)slab * a.c + t.col;
@@ -584,17 +590,18 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_k(BnArgs a) {
 
 // backward, launch 2 (SMALL = 0: partials from launch 1, merged per workgroup) or the one-launch form (SMALL = 1): dgamma and
 // dbeta from slab 0, dx when wanted (without it the grid is one slab deep: the merge alone, in the same order)
-template <int VEC, typename XT, typename YT, int SMALL>
-__global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
+template <int VEC, typename XT, typename YT, int SMALL, typename... CAT>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a, CAT... s) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * 3 * VEC];
     __shared__ float sm[3][kBnTileCols];
     const BnCoord t = bn_coord<VEC>(a);
+    const auto X = bn_x(a, t, s...);
     const BnCols<VEC> q = bn_cols<VEC>(a, t);
     const int slab = (int)blockIdx.y;
     const int row0 = slab * a.slab_rows, row1 = min(a.n, row0 + a.slab_rows);
     float sg[VEC], sx[VEC], sh[VEC];
     if constexpr (SMALL) {
-        bn_slab_sums<VEC, XT, YT>(a, t, q, 0, a.n, sg, sx, sh, lds);
+        bn_slab_sums<VEC, XT, YT>(a, t, X, q, 0, a.n, sg, sx, sh, lds);
     } else {
         bn_sum_partials<VEC>(a, t, sg, sx, sh, lds);
     }
@@ -614,7 +621,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a) {
         }
     }
     __syncthreads();
-    bn_dx_rows<VEC, XT, YT>(a, t, q, row0, row1, fn, sm, 0);
+    bn_dx_rows<VEC, XT, YT>(a, t, X, q, row0, row1, fn, sm, 0);
 }
 
 // ---- batch statistics across the ranks of a process group (mccnn_bn_sync_*) ----------------------------------------------
@@ -647,7 +654,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_stats_k(BnArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
     const BnCoord t = bn_coord<VEC>(a);
     float cnt, mean[VEC], m2[VEC];
-    if constexpr (SMALL) bn_slab_stats<VEC, XT>(a, t, 0, a.n, cnt, mean, m2, lds);
+    if constexpr (SMALL) bn_slab_stats<VEC, XT>(a, t, BnXPlain(), 0, a.n, cnt, mean, m2, lds);
     else bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
     float cv[VEC];
 #pragma unroll
@@ -691,7 +698,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_apply_k(BnArgs a) {
     float rstd[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
-    bn_apply_rows<VEC, XT, YT>(a, t, row0, row1, mean, rstd, a.T < kBnDropAll, sbase);
+    bn_apply_rows<VEC, XT, YT>(a, t, BnXPlain(), row0, row1, mean, rstd, a.T < kBnDropAll, sbase);
 }
 
 // this rank's (sum g, sum g * xhat, sum xhat) into its row of the rank partials, and as dbeta and dgamma. SMALL: from x and
@@ -703,7 +710,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_sums_k(BnArgs a) {
     float sg[VEC], sx[VEC], sh[VEC];
     if constexpr (SMALL) {
         const BnCols<VEC> q = bn_cols<VEC>(a, t);
-        bn_slab_sums<VEC, XT, YT>(a, t, q, 0, a.n, sg, sx, sh, lds, a.meta[0]);
+        bn_slab_sums<VEC, XT, YT>(a, t, BnXPlain(), q, 0, a.n, sg, sx, sh, lds, a.meta[0]);
     } else {
         bn_sum_partials<VEC>(a, t, sg, sx, sh, lds);
     }
@@ -750,7 +757,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_sync_bwd_dx_k(BnArgs a) {
         }
     }
     __syncthreads();
-    bn_dx_rows<VEC, XT, YT>(a, t, q, row0, row1, fn, sm, base);
+    bn_dx_rows<VEC, XT, YT>(a, t, BnXPlain(), q, row0, row1, fn, sm, base);
 }
 
 // a caller's row pointer allows the wide form: f32 x -> 4 columns per thread (f32 rows move as 16 bytes, bf16 rows as 8),
@@ -796,8 +803,9 @@ struct BnRows {
 // What the entries share behind their own checks, in this order: the type flags, bf16 rows on 32-bit words, the workspace
 // (need: its bytes, 0: the entry has none) -- 0 or the error -- then the plan from the row pointers and the workspace's, and
 // what of `a` follows from it.
+// wide: false takes the wide form away whatever the pointers of `rows` say (over a concatenation: a segment's width or pointer).
 inline int bn_setup(BnArgs& a, BnPlan& p, int n, int c, std::initializer_list<BnRows> rows, size_t need = 0, void* ws = nullptr,
-                    size_t ws_bytes = 0) {
+                    size_t ws_bytes = 0, bool wide = true) {
     const int x_bf16 = rows.begin()->bf16;
     int flags = 0;
     for (const BnRows& r : rows) flags |= r.bf16;
@@ -805,7 +813,7 @@ inline int bn_setup(BnArgs& a, BnPlan& p, int n, int c, std::initializer_list<Bn
     for (const BnRows& r : rows)
         if (!bn_bf16_ok(r.p, r.bf16, c)) return MCCNN_E_SHAPE;
     if (need && (!ws || ws_bytes < need)) return MCCNN_E_WORKSPACE;
-    bool aligned = !need || bn_aligned16(ws);
+    bool aligned = wide && (!need || bn_aligned16(ws));
     for (const BnRows& r : rows) aligned = aligned && bn_rows_aligned(r.p, r.bf16, x_bf16);
     p = bn_plan(n, c, aligned, x_bf16);
     a.part = (float*)ws;
@@ -912,6 +920,123 @@ int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float*
                      float* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
     return mccnn_bn_act_bwd_rows(x, 0, dy, 0, n, c, gamma, beta, saved, relu, keep_threshold, keep_scale, seed, dx, dgamma, dbeta,
                                  ws, ws_bytes, stream);
+}
+
+// ---- over a column-wise concatenation of f32 segments (ABI 28): the plan, launches and arithmetic of the f32-x entries at
+// width C = sum c_s; wherever that plan is the one the contiguous op takes on the concatenated tensor, the same bytes ----
+}  // extern "C"
+
+namespace mccnn {
+
+// the family over (columns per thread, y's / dy's type): go(v, yt) as in bn_launch
+template <typename F>
+inline int bn_cat_launch(int vec, int y_bf16, F&& go) {
+    if (!y_bf16) { if (vec == 4) go(BnVec<4>(), float()); else go(BnVec<1>(), float()); }
+    else { if (vec == 4) go(BnVec<4>(), bn_bf16()); else go(BnVec<1>(), bn_bf16()); }
+    MCCNN_LAUNCHED();
+    return 0;
+}
+
+// The segments of a call, checked, as the table the kernels take: 0 or the error. dxs: NULL, or per segment where its
+// gradient goes (NULL: not wanted). c: C; wide: every width and every segment pointer allows 4 columns per thread;
+// any_dx: some gradient is wanted.
+inline int bn_cat_table(BnCat& s, int& c, bool& wide, bool& any_dx, const float* const* xs, const int* cs, int nseg, int n,
+                        float* const* dxs) {
+    if (nseg < 1 || nseg > kBnCatMax || n < 1 || !xs || !cs) return MCCNN_E_BADARG;
+    for (int k = 0; k < nseg; ++k)
+        if (cs[k] < 1 || !xs[k]) return MCCNN_E_BADARG;
+    if (bn_cat_fill(s, cs, nseg) > 0x7fffffffll) return MCCNN_E_TOOLARGE;
+    c = s.col0[kBnCatMax];
+    wide = bn_cat_widths_by4(cs, nseg);
+    any_dx = false;
+    for (int k = 0; k < kBnCatMax; ++k) {
+        const int from = k < nseg ? k : 0;
+        s.x[k] = xs[from];
+        s.dx[k] = dxs ? dxs[from] : nullptr;
+        if (k < nseg) {
+            wide = wide && bn_aligned16(s.x[k]) && bn_aligned16(s.dx[k]);
+            any_dx = any_dx || s.dx[k];
+        }
+    }
+    return 0;
+}
+
+}  // namespace mccnn
+
+extern "C" {
+
+int mccnn_bn_act_cat_max_segments(void) { return kBnCatMax; }
+
+int mccnn_bn_act_cat_fwd(const float* const* xs, const int* cs, int nseg, int n, const float* gamma, const float* beta,
+                         float* moving_mean, float* moving_var, float momentum, float eps, int training, int relu,
+                         unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16, float* saved,
+                         void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+    BnCat s = {};
+    int c = 0;
+    bool wide = false, any_dx = false;
+    const int table = bn_cat_table(s, c, wide, any_dx, xs, cs, nseg, n, nullptr);
+    if (table == MCCNN_E_BADARG) return table;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!gamma || !beta || !moving_mean || !moving_var || !y) return MCCNN_E_BADARG;
+    if (training && !saved) return MCCNN_E_BADARG;
+    if (table) return table;   // (C past 2^31 - 1: behind the other argument errors)
+    BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{s.x[0], 0}, {y, y_bf16}}, training ? mccnn_bn_act_workspace_bytes(n, c) : 0, ws, ws_bytes, wide))
+        return e;
+    a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
+    a.relu = relu ? 1 : 0; a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed;
+    a.T = training ? keep_threshold : kBnDropAll;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
+    if (!training)
+        return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
+            bn_apply_k<v(), float, decltype(yt), 2><<<grid, kBnThreads, 0, st>>>(a, s);
+        });
+    if (n <= kBnSmallRows)
+        return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
+            bn_apply_k<v(), float, decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
+        });
+    if (const int e = bn_cat_launch(p.vec, 0, [&](auto v, auto) { bn_stats_k<v(), float><<<grid, kBnThreads, 0, st>>>(a, s); }))
+        return e;
+    return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
+        bn_apply_k<v(), float, decltype(yt), 0><<<grid, kBnThreads, 0, st>>>(a, s);
+    });
+}
+
+int mccnn_bn_act_cat_bwd(const float* const* xs, const int* cs, int nseg, const void* dy, int dy_bf16, int n, const float* gamma,
+                         const float* beta, const float* saved, int relu, unsigned long long keep_threshold, float keep_scale,
+                         unsigned seed, float* const* dxs, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                         mccnn_stream_t stream) {
+    BnCat s = {};
+    int c = 0;
+    bool wide = false, any_dx = false;
+    const int table = bn_cat_table(s, c, wide, any_dx, xs, cs, nseg, n, dxs);
+    if (table == MCCNN_E_BADARG) return table;
+    if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
+    if (!dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
+    if (table) return table;
+    BnArgs a = {};
+    BnPlan p;
+    if (const int e = bn_setup(a, p, n, c, {{s.x[0], 0}, {dy, dy_bf16}}, mccnn_bn_act_workspace_bytes(n, c), ws, ws_bytes, wide))
+        return e;
+    a.dy = dy; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
+    a.dgamma = dgamma; a.dbeta = dbeta; a.relu = relu ? 1 : 0; a.want_dx = any_dx ? 1 : 0;
+    a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
+    if (n <= kBnSmallRows)
+        return bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
+            bn_bwd_dx_k<v(), float, decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
+        });
+    if (const int e = bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
+            bn_bwd_sums_k<v(), float, decltype(yt)><<<grid, kBnThreads, 0, st>>>(a, s);
+        }))
+        return e;
+    const dim3 grid2((unsigned)p.tiles, any_dx ? (unsigned)p.slabs : 1u);
+    return bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
+        bn_bwd_dx_k<v(), float, decltype(yt), 0><<<grid2, kBnThreads, 0, st>>>(a, s);
+    });
 }
 
 // ---- statistics across ranks (ABI 22): the four stages around the caller's two collectives ----

@@ -1478,6 +1478,118 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
     return y;
 }
 
+// ---- ... over a column-wise concatenation that is never materialised (mccnn_bn_act_cat_fwd / _bwd): the C++ form of
+// dense_glue.bn_relu_dropout_cat -- the same library calls with the same arguments, so the same bytes. f32 segments; a segment
+// that does not require a gradient gets none (a NULL pointer in the call, an undefined tensor out of the node).
+struct BnCatBackward : public torch::autograd::Node {
+    std::vector<Tensor> xs;
+    std::vector<uint32_t> x_versions;
+    Tensor gamma_, beta_, saved;
+    bool y_bf16 = false;
+    uint32_t versions[2] = {0, 0};
+    int relu = 1;
+    unsigned long long thr = 0;
+    float scale = 1.f;
+    unsigned seed = 0;
+
+    // inputs of the node: the segments in order, then gamma, then beta
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        TORCH_CHECK(!xs.empty(), "bn_relu_drop_cat: backward through a graph whose buffers have been freed (retain_graph=True?)");
+        const int nseg = (int)xs.size(), n = (int)xs[0].size(0), c = (int)gamma_.size(0);
+        Tensor g0 = grads[0];   // (no tensor of y's shape is kept: zeros where autograd hands nothing over are made here)
+        if (!g0.defined()) g0 = at::zeros({(int64_t)n, (int64_t)c}, gamma_.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
+        const Tensor gy = bf16_rows_aligned(glue_grad_in("bn_relu_drop_cat", saved.defined(), g0, {&gamma_, &beta_}, versions, g0, y_bf16));
+        for (int k = 0; k < nseg; ++k)
+            TORCH_CHECK(xs[k]._version() == x_versions[k],
+                        "one of the variables needed for gradient computation has been modified by an inplace operation (bn_relu_drop_cat "
+                        "segment ", k, ")");
+        const DevGuard device_guard((int)gamma_.device().index());
+        std::vector<Tensor> dxs(nseg);
+        const float* px[8];
+        float* pdx[8];
+        int cs[8];
+        bool any = false;
+        for (int k = 0; k < nseg; ++k) {
+            px[k] = xs[k].data_ptr<float>();
+            cs[k] = (int)xs[k].size(1);
+            pdx[k] = nullptr;
+            if (task_should_compute_output(k)) {
+                dxs[k] = at::empty_like(xs[k]);
+                pdx[k] = dxs[k].data_ptr<float>();
+                any = true;
+            }
+        }
+        Tensor dgb = at::empty({2, (int64_t)c}, gamma_.options());
+        void* st = cur_stream(gamma_);
+        Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(n, c), gamma_, st);
+        check(mccnn_bn_act_cat_bwd(px, cs, nseg, gy.data_ptr(), y_bf16 ? 1 : 0, n, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
+                                   saved.data_ptr<float>(), relu, thr, scale, seed, any ? pdx : nullptr, dgb.data_ptr<float>(),
+                                   dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
+              "bn_relu_dropout_cat_grad");
+        torch::autograd::variable_list out(nseg + 2);
+        for (int k = 0; k < nseg; ++k) out[k] = dxs[k];
+        if (task_should_compute_output(nseg)) out[nseg] = dgb.select(0, 0);
+        if (task_should_compute_output(nseg + 1)) out[nseg + 1] = dgb.select(0, 1);
+        return out;
+    }
+    void release_variables() override { xs.clear(); gamma_.reset(); beta_.reset(); saved.reset(); }
+};
+
+// out_type: -1 / 0 float32, 1 bfloat16. The caller (dense_glue._bn_cat_args) has checked the arguments; what is looked at
+// here again is what this function itself relies on.
+Tensor bn_relu_drop_cat(const std::vector<Tensor>& xs, const Tensor& gamma, const Tensor& beta, const Tensor& mov_mean,
+                        const Tensor& mov_var, bool training, bool relu, unsigned long long thr, double scale, unsigned seed,
+                        double momentum, double eps, int out_type) {
+    TORCH_CHECK(!xs.empty() && (int)xs.size() <= mccnn_bn_act_cat_max_segments(), "bn_relu_drop_cat expects 1 to 8 segments");
+    TORCH_CHECK(out_type >= -1 && out_type <= 1, "bn_relu_drop_cat: out_type must be -1 / 0 (float32) or 1 (bfloat16)");
+    const bool y_bf16 = out_type == 1;
+    int64_t c64 = 0;
+    bool need_grad = at::GradMode::is_enabled() && (gamma.requires_grad() || beta.requires_grad());
+    for (const Tensor& x : xs) {
+        check_dev(x, at::kFloat, "segment");
+        TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) == xs[0].size(0) && x.device() == xs[0].device(),
+                    "bn_relu_drop_cat expects segments with dimensions (n, c_s) on one device, n, c_s >= 1");
+        c64 += x.size(1);
+        need_grad = need_grad || (at::GradMode::is_enabled() && x.requires_grad());
+    }
+    TORCH_CHECK(xs[0].size(0) < (1ll << 31) && c64 < (1ll << 31), "bn_relu_drop_cat: x too large");
+    TORCH_CHECK(!y_bf16 || c64 % 2 == 0, "bn_relu_drop_cat: bfloat16 rows need an even number of columns");
+    for (const Tensor* t : {&gamma, &beta, &mov_mean, &mov_var}) {
+        check_dev(*t, at::kFloat, "per-column tensor");
+        TORCH_CHECK(t->dim() == 1 && t->size(0) == c64 && t->device() == xs[0].device(), "bn_relu_drop_cat: per-column tensors must have shape (C,)");
+    }
+    TORCH_CHECK(training || !need_grad, "bn_relu_drop_cat: the eval form has no gradients");
+    const DevGuard device_guard((int)gamma.device().index());
+    const int nseg = (int)xs.size(), n = (int)xs[0].size(0), c = (int)c64;
+    Tensor y, saved;
+    {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        y = at::empty({(int64_t)n, c64}, gamma.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
+        if (training) saved = at::empty({2, c64}, gamma.options());
+        const float* px[8];
+        int cs[8];
+        for (int k = 0; k < nseg; ++k) { px[k] = xs[k].data_ptr<float>(); cs[k] = (int)xs[k].size(1); }
+        void* st = cur_stream(gamma);
+        Tensor& ws = scratch(training ? mccnn_bn_act_workspace_bytes(n, c) : 0, gamma, st);
+        check(mccnn_bn_act_cat_fwd(px, cs, nseg, n, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
+                                   mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
+                                   training ? thr : mccnn::kBnDropAll, training ? (float)scale : 1.f, seed, y.data_ptr(), y_bf16 ? 1 : 0,
+                                   training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+              "bn_relu_dropout_cat");
+    }
+    if (need_grad) {
+        auto node = std::shared_ptr<BnCatBackward>(new BnCatBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(xs, gamma, beta));
+        for (const Tensor& x : xs) { node->xs.push_back(x.detach()); node->x_versions.push_back(x._version()); }
+        node->gamma_ = gamma; node->beta_ = beta; node->y_bf16 = y_bf16;
+        node->versions[0] = gamma._version(); node->versions[1] = beta._version();
+        node->saved = saved;
+        node->relu = relu ? 1 : 0; node->thr = thr; node->scale = (float)scale; node->seed = seed;
+        torch::autograd::set_history(y, node);
+    }
+    return y;
+}
+
 // ---- ... with batch statistics across ranks (mccnn_bn_sync_*): the four stages as they are. The collectives between them
 // are torch.distributed's, so the autograd node is Python's (dense_glue._BnReluDropoutSync), which has checked the
 // arguments; here only what keeps a call inside its tensors. x / dx and y / dy are each f32 or bf16 rows.
@@ -2274,6 +2386,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("w3"), py::arg("b3"), py::arg("fout"), py::arg("combin"), py::arg("avg"), py::arg("deterministic") = false,
             py::call_guard<py::gil_scoped_release>());
     mod.def("bn_relu_drop", &bn_relu_drop, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
+            py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
+            py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1, py::call_guard<py::gil_scoped_release>());
+    mod.def("bn_relu_drop_cat", &bn_relu_drop_cat, py::arg("xs"), py::arg("gamma"), py::arg("beta"), py::arg("moving_mean"),
             py::arg("moving_var"), py::arg("training"), py::arg("relu"), py::arg("keep_threshold"), py::arg("keep_scale"),
             py::arg("seed"), py::arg("momentum"), py::arg("epsilon"), py::arg("out_type") = -1, py::call_guard<py::gil_scoped_release>());
     mod.def("bn_sync_stats", &bn_sync_stats, py::call_guard<py::gil_scoped_release>());

@@ -1,7 +1,8 @@
 """The dense glue between two MC convolutions as library ops (extensions; csrc/bn_act.hip, csrc/linear_bn.hip,
 csrc/linear_xent.hip; include/mccnn.h "THE DENSE GLUE AS ONE OP" and the two sections behind it): y = drop(act(bn(x))) with the moving
-statistics updated in place -- on its own (bn_relu_dropout), with the batch statistics across the ranks of a process group
-(bn_relu_dropout_sync) and behind a linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
+statistics updated in place -- on its own (bn_relu_dropout), over a column-wise concatenation that is never materialised
+(bn_relu_dropout_cat), with the batch statistics across the ranks of a process group (bn_relu_dropout_sync) and behind a
+linear layer (linear_bn_relu_dropout). The dropout mask is counter-based
 (csrc/bn_drop.h): reproducible from the seed, NOT torch's random stream. And what closes the dense path: the last linear
 layer with the softmax cross-entropy, the predictions and the count of correct rows behind it (linear_softmax_xent,
 csrc/linear_xent.hip), the cosine-distance loss of normal estimation (cosine_distance_loss, csrc/cosine_loss.hip), the
@@ -192,6 +193,114 @@ def _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, mom
     y = torch.empty(x.shape, dtype=outDtype or x.dtype, device=x.device)
     _bn_act_fwd(lib, _bf16_rows_aligned(x.detach()), gamma, beta, movingMean, movingVar, float(momentum), float(epsilon), 0,
                 int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
+    return y
+
+
+# ---------------------------------------------------------------------------------------------
+# ... over a column-wise concatenation that is never materialised (include/mccnn.h "... OVER A CONCATENATION"): up to 8
+# float32 segments [n, c_s]; y, and everything per column, at width C = sum c_s.
+BN_CAT_MAX = 8
+
+
+def _bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None, *, training=True):
+    """Checks of bn_relu_dropout_cat (nothing is launched before they pass) -> (keep threshold, keep scale). xs: a list or
+    tuple of 1 .. 8 float32 contiguous (n, c_s) tensors on one device; outDtype: None / torch.float32, or torch.bfloat16;
+    everything per column is float32 (C,). training=False adds the eval form's check, behind all the others."""
+    op = "bn_relu_dropout_cat"
+    thr, scale = _drop_args(op, keepProb, seed, outDtype)
+    _req(isinstance(xs, (list, tuple)) and 1 <= len(xs) <= BN_CAT_MAX, "%s expects a list of 1 to %d segments" % (op, BN_CAT_MAX))
+    for x in xs:
+        _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "%s: every segment must be a float32 tensor" % op)
+        _req(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "%s expects segments with dimensions (n, c_s), n, c_s >= 1" % op)
+        _req(x.shape[0] == xs[0].shape[0], "%s: the segments must have the same number of rows" % op)
+        _req(x.is_contiguous(), "%s: every segment must be contiguous" % op)
+        _req(x.device == xs[0].device, "%s: the segments must be on one device" % op)
+    n, c = xs[0].shape[0], sum(x.shape[1] for x in xs)
+    _req(n < (1 << 31) and c < (1 << 31), "%s: x too large" % op)
+    _req(c % 2 == 0 or outDtype in (None, torch.float32), "%s: bfloat16 rows need an even number of columns" % op)
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
+        _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32, "%s: %s must be a float32 tensor" % (op, name))
+        _req(t.is_contiguous(), "%s: %s must be contiguous" % (op, name))
+        _req(t.dim() == 1 and t.shape[0] == c, "%s: %s must have shape (C,), C the sum of the segments' widths" % (op, name))
+        _req(t.device == xs[0].device, "%s: %s is on another device than the segments" % (op, name))
+    _req(xs[0].is_cuda, "%s: the segments must be CUDA tensors" % op)
+    _req(thr >= 1, "%s: keepProb keeps nothing" % op)
+    if not training:
+        _req(not (torch.is_grad_enabled() and any(t.requires_grad for t in tuple(xs) + (gamma, beta))),
+             "%s: the eval form has no gradients" % op)
+    return thr, scale
+
+
+def _cat_table(ts):
+    """The host arrays of a call: (pointers, widths) of the tensors ts (None: a NULL pointer, width 0)."""
+    import ctypes as C
+    return ((C.c_void_p * len(ts))(*[ptr(t) for t in ts]), (C.c_int * len(ts))(*[0 if t is None else t.shape[1] for t in ts]))
+
+
+def _bn_cat_fwd(lib, xs, gamma, beta, movingMean, movingVar, momentum, epsilon, training, relu, thr, scale, seed, y, saved, ws):
+    px, cs = _cat_table(xs)
+    check(lib.mccnn_bn_act_cat_fwd(px, cs, len(xs), xs[0].shape[0], ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar), momentum,
+                                   epsilon, training, relu, thr, scale, seed, ptr(y), int(y.dtype == torch.bfloat16), ptr(saved),
+                                   ptr(ws), 0 if ws is None else ws.numel(), stream_handle()), "bn_relu_dropout_cat")
+
+
+class _BnReluDropoutCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gamma, beta, movingMean, movingVar, relu, thr, scale, seed, momentum, epsilon, outDtype, *xs):
+        lib = _lib.load()
+        n, c = xs[0].shape[0], gamma.shape[0]
+        xd, gd, bd = tuple(x.detach() for x in xs), gamma.detach(), beta.detach()
+        y = torch.empty((n, c), dtype=outDtype or torch.float32, device=gamma.device)
+        saved = torch.empty((2, c), dtype=torch.float32, device=gamma.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), gamma.device)
+        _bn_cat_fwd(lib, xd, gd, bd, movingMean, movingVar, momentum, epsilon, 1, int(relu), thr, scale, seed, y, saved, ws)
+        ctx.save_for_backward(gd, bd, saved, *xd)
+        ctx.attrs = (int(relu), thr, scale, seed, y.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        gamma, beta, saved = ctx.saved_tensors[:3]
+        xs = ctx.saved_tensors[3:]
+        relu, thr, scale, seed, ydt = ctx.attrs
+        lib = _lib.load()
+        n, c = xs[0].shape[0], gamma.shape[0]
+        gy = _bf16_rows_aligned(gy.to(ydt).contiguous())
+        need = ctx.needs_input_grad
+        dxs = tuple(torch.empty_like(x) if need[11 + k] else None for k, x in enumerate(xs))
+        dgb = torch.empty((2, c), dtype=torch.float32, device=gamma.device)
+        ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), gamma.device)
+        px, cs = _cat_table(xs)
+        pdx = _cat_table(dxs)[0] if any(d is not None for d in dxs) else None
+        check(lib.mccnn_bn_act_cat_bwd(px, cs, len(xs), ptr(gy), int(ydt == torch.bfloat16), n, ptr(gamma), ptr(beta), ptr(saved), relu,
+                                       thr, scale, seed, pdx, ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()),
+              "bn_relu_dropout_cat_grad")
+        return (dgb[0] if need[0] else None, dgb[1] if need[1] else None) + (None,) * 9 + dxs
+
+
+def bn_relu_dropout_cat(xs, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
+                        epsilon=1e-3, outDtype=None):
+    """bn_relu_dropout over torch.cat(xs, 1) in one library op, without the concatenation: xs a list or tuple of 1 .. 8
+    float32 contiguous (n, c_s) tensors, gamma, beta and the moving statistics (C,), C = sum c_s; y is (n, C), float32 or
+    (outDtype=torch.bfloat16, an even C) bfloat16. The definition, the moving statistics, the mask -- element (row, column
+    of the concatenation) -- and the eval form are bn_relu_dropout's; differentiable (once) with respect to every segment,
+    gamma and beta: each segment that requires a gradient gets a contiguous one of its own, the others None. The launches
+    are those of bn_relu_dropout on the concatenated tensor, and wherever the library takes the same plan for both (C % 4 != 0,
+    or every c_s % 4 == 0 and every tensor on a 16-byte boundary) so are the bytes."""
+    return _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                       *_bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
+def _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
+    """bn_relu_dropout_cat behind its checks: the arguments as given and what _bn_cat_args made of keepProb."""
+    if training:
+        return _BnReluDropoutCat.apply(gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
+                                       float(epsilon), outDtype, *xs)
+    lib = _lib.load()
+    y = torch.empty((xs[0].shape[0], gamma.shape[0]), dtype=outDtype or torch.float32, device=gamma.device)
+    _bn_cat_fwd(lib, tuple(x.detach() for x in xs), gamma.detach(), beta.detach(), movingMean, movingVar, float(momentum),
+                float(epsilon), 0, int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
     return y
 
 

@@ -652,6 +652,23 @@ def bn_relu_drop(x, gamma, beta, movingMean, movingVar, training, relu=True, kee
                        *M._bn_act_args(x, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
 
 
+def _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale):
+    if _EXT is None:
+        return M._bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype, thr, scale)
+    return _EXT.bn_relu_drop_cat(list(xs), gamma, beta, movingMean, movingVar, bool(training), bool(relu), thr, scale, seed,
+                                 float(momentum), float(epsilon), _out_flag(outDtype))
+
+
+def bn_relu_drop_cat(xs, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
+                     epsilon=1e-3, outDtype=None):
+    """The dense glue over torch.cat(xs, 1) as one op that reads the segments where they are
+    (dense_glue.bn_relu_dropout_cat: its definition, checks and errors): one Python -> C++ call forward and an autograd
+    node on the C++ side (BnCatBackward) when the extension is loaded, the ctypes op otherwise -- the same library calls
+    either way, so the same bytes. A segment that does not require a gradient gets None."""
+    return _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
+                       *M._bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
+
+
 _EXT_SYNC_STAGES = None if _EXT is None else (_EXT.bn_sync_stats, _EXT.bn_sync_apply, _EXT.bn_sync_bwd_sums, _EXT.bn_sync_bwd_dx)
 
 
