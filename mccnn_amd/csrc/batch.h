@@ -3,8 +3,30 @@
 // ScanBatch, SpanBatch: common.h); kernels and item builders live next to their single forms (grid.hip, neighbors.hip, scan.hip).
 #pragma once
 #include "common.h"
+#include <cmath>
+#include <cstring>
 
 namespace mccnn {
+
+// sqrt_threshold (common.h) on the host: the same float operations, both square roots correctly rounded. An absolute radius
+// has ONE threshold, computed once per call (the search, the per-point density and its gradients: NeighItem / PointPdfItem::Tabs).
+inline float sqrt_threshold_host(float R) {
+    auto prev = [](float v) { uint32_t u; memcpy(&u, &v, 4); --u; memcpy(&v, &u, 4); return v; };
+    auto next = [](float v) { uint32_t u; memcpy(&u, &v, 4); ++u; memcpy(&v, &u, 4); return v; };
+    float t = R * R;
+    for (int it = 0; it < 8 && t > 0.0f && sqrtf(prev(t)) >= R; ++it) t = prev(t);
+    for (int it = 0; it < 8 && sqrtf(t) < R; ++it) t = next(t);
+    return t;
+}
+
+// Members per wave of a window kernel (cell_window.h) that runs beside others -- background searches, every batch item, the
+// per-point density and, up to 4, its gradients: 8 consecutive members of a cell-coherent order share most of their windows on
+// a large list (~8 points per cell), but a list with few members needs the waves -- 6 344 pooling centres with ~900
+// candidates each ran 139 us per pass on 793 waves (BASELINE cfg2 Pool_1), the coarse levels of a hierarchy 20 us on a handful.
+#ifndef MCCNN_NW_G
+#define MCCNN_NW_G 8
+#endif
+inline int window_group(long long m) { return m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1)); }
 
 // one counting sort: the grid build of a geometry, or the visiting order of its foreign centres (newIdx == nullptr)
 struct GridItem {

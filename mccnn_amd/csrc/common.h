@@ -105,6 +105,15 @@ __device__ __forceinline__ int batch_item(const BatchBlocks& b, int blk, int& lo
     blocks = b.first[k + 1] - b.first[k];
     return k;
 }
+// the host's side of it: the first `count` items with blocks_of(k) workgroups each -> the grid size
+template <class F>
+inline int batch_blocks(BatchBlocks& bb, int count, F blocks_of) {
+    bb.count = count;
+    int run = 0;
+    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += blocks_of(k); }
+    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    return run;
+}
 // generic single-pass prefix sum item (scan.hip: scan_chained_batch)
 struct ScanItem {
     const int* in;

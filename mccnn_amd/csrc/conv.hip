@@ -863,10 +863,7 @@ int tr_chain_item(TrChainItem& t, ScanItem& sc, ClearSpan& head, const int* pack
 }
 int launch_tr_chain_batch(const TrChainBatch& tb, int count, int phase, hipStream_t s) {
     BatchBlocks bb;
-    bb.count = count;
-    int run = 0;
-    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += (phase == 2 && tb.it[k].norank) ? 0 : ceil_div(tb.it[k].e, 256); }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    const int run = batch_blocks(bb, count, [&](int k) { return (phase == 2 && tb.it[k].norank) ? 0 : ceil_div(tb.it[k].e, 256); });
     if (run == 0) return 0;
     if (phase == 0) tr_count_batch<<<run, 256, 0, s>>>(tb, bb);
     else if (phase == 1) tr_fill_batch<<<run, 256, 0, s>>>(tb, bb);

@@ -1187,10 +1187,7 @@ int launch_plan_small_batch(const PlanSmallBatch& pb, int count, hipStream_t s) 
 }
 int launch_sell_fill_batch(const SellFillBatch& fb, int count, int transposed, hipStream_t s) {
     BatchBlocks bb;
-    bb.count = count;
-    int run = 0;
-    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += fb.it[k].S * fb.it[k].chunks; }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    const int run = batch_blocks(bb, count, [&](int k) { return fb.it[k].S * fb.it[k].chunks; });
     if (run == 0) return 0;
     if (transposed) sell_fill_batch<true><<<run, 256, 0, s>>>(fb, bb);
     else sell_fill_batch<false><<<run, 256, 0, s>>>(fb, bb);

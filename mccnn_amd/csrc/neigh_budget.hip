@@ -370,20 +370,16 @@ int launch_budget_scan_batch(const BudgetItem* items, int count, hipStream_t s) 
     if (count == 0) return 0;
     ScanBatch sc;
     ClampBatch cb;
-    BatchBlocks bb;
-    int run = 0;
     for (int k = 0; k < count; ++k) {
         const BudgetItem& b = items[k];
         const int tiles = ceil_div(b.m, SCAN_TILE);
         if (b.m <= 0 || tiles > 1024) return MCCNN_E_TOOLARGE;
         sc.it[k] = ScanItem{b.kfull, b.start_idx, budget_ws(b.region, b.m).status, b.total_dev, b.total_host, b.m, tiles};
         cb.cap[k] = b.cap_dev;
-        bb.first[k] = run;
-        run += tiles;
     }
     for (int k = count; k < MCCNN_BATCH_MAX; ++k) { sc.it[k] = sc.it[0]; cb.cap[k] = cb.cap[0]; }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
-    bb.count = count;
+    BatchBlocks bb;
+    const int run = batch_blocks(bb, count, [&](int k) { return sc.it[k].tiles; });
     scan_chained_clamp_batch<<<run, SCAN_THREADS, 0, s>>>(sc, cb, bb);
     MCCNN_LAUNCHED();
     return 0;

@@ -1,6 +1,7 @@
 // Fixed-radius neighbour search over the 27-cell window and the per-edge kernel density
 // estimate. Replaces tf_ops/find_neighbors.cu and tf_ops/compute_pdf.cu.
 #include "batch.h"
+#include "cell_window.h"
 #include "neigh_sample.h"
 #include <cstdlib>
 #include <cstring>
@@ -8,29 +9,6 @@
 #include <type_traits>
 
 namespace mccnn {
-
-struct CentreCtx {
-    float cx, cy, cz, R, T;  // T: squared-distance threshold equivalent to sqrt(d2) < R (common.h)
-    int b, x, y, z;
-};
-
-__device__ __forceinline__ CentreCtx centre_ctx(const float* __restrict__ centres, const int* __restrict__ cb,
-                                                const float* __restrict__ mn, const float* __restrict__ mx,
-                                                int i, int B, int nc, float radius, int scaleInv, float Tabs) {
-    CentreCtx c;
-    c.b = clamp_batch(cb[i], B);
-    c.cx = centres[(size_t)i * 3];
-    c.cy = centres[(size_t)i * 3 + 1];
-    c.cz = centres[(size_t)i * 3 + 2];
-    float ext = max_extent(mn, mx, c.b);
-    float cs = ext / (float)nc;
-    c.R = scaleInv ? radius * ext : radius;  // find_neighbors.cu:73
-    c.T = scaleInv ? sqrt_threshold(c.R) : Tabs;  // an absolute radius has ONE threshold: the host computes it
-    c.x = cell_coord(c.cx, mn[c.b * 3], cs, nc);
-    c.y = cell_coord(c.cy, mn[c.b * 3 + 1], cs, nc);
-    c.z = cell_coord(c.cz, mn[c.b * 3 + 2], cs, nc);
-    return c;
-}
 
 // One wave per 8 consecutive centres of the visiting order (`order`, identity when null; a cell-coherent order --
 // the inverse sort permutation, or the centres' own counting-sort order in this grid -- makes neighbouring centres share a cell, and never
@@ -44,6 +22,9 @@ __device__ __forceinline__ CentreCtx centre_ctx(const float* __restrict__ centre
 // thread per (centre, cell) 60 + 82 us, this one 31 + 37 us. FILL == false counts per centre, FILL == true writes the
 // (j, i) rows at startIdx[i].
 // Windows larger than MCCNN_NW_CAP points are processed in segments of the flat candidate list.
+// The walk itself -- a centre's context, the groups of a wave, the window table, the cell of a flat position -- is
+// cell_window.h's, shared with the per-point density sweeps; the staging below is the search's own (the LEAN padding, j in
+// .w, the compaction path that stages nothing).
 // v[lane L] = val (wave-uniform), L a compile-time lane: v_writelane_b32 (one SGPR operand per instruction on gfx9, so the
 // lane select is an inline constant)
 template <int L>
@@ -51,12 +32,6 @@ __device__ __forceinline__ void writelane_u(unsigned& v, unsigned val) {
     const unsigned sv = __builtin_amdgcn_readfirstlane(val);
     asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(sv), "n"(L));
 }
-__device__ __forceinline__ float readlane_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-#ifndef MCCNN_NW_G
-#define MCCNN_NW_G 8
-#endif
 #ifndef MCCNN_NW_CAP
 #define MCCNN_NW_CAP 256
 #endif
@@ -175,7 +150,7 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
     const bool own = lane < G && ci < m;
     const int i = own ? (order ? order[ci] : ci) : 0;
     CentreCtx c = centre_ctx(centres, cb, mn, mx, i, B, nc, radius, scaleInv, Tabs);
-    const int key = own ? ((c.b * nc + c.x) * nc + c.y) * nc + c.z : -1;
+    const int key = cell_key(c, nc, own);
     int count = 0;                                   // hits of this lane's centre so far
     const int base = (FILL && own) ? (scanCnt ? scanLds[i] : startIdx[i]) : 0;
     int krow = 0;                                    // CAPPED fill: the true row length of this lane's centre
@@ -184,46 +159,15 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
     const int2* ct = reinterpret_cast<const int2*>(cells);
     int2* out = reinterpret_cast<int2*>(packed);
     while (todo) {
-        const int lead = __builtin_ctz(todo);
-        const int wkey = __builtin_amdgcn_readlane(key, lead);
-        const unsigned members = (unsigned)(__ballot(own && key == wkey)) & todo;
-        todo &= ~members;
-        // the 27 cell ranges of the window: lane o < 27 owns table entry o
-        const int wb = __builtin_amdgcn_readlane(c.b, lead), wx = __builtin_amdgcn_readlane(c.x, lead);
-        const int wy = __builtin_amdgcn_readlane(c.y, lead), wz = __builtin_amdgcn_readlane(c.z, lead);
-        int j0 = 0, len = 0;
-        if (lane < 27) {
-            const int slab = lane / 9, u = lane - slab * 9;
-            const int X = wx + 1 - (u % 3), Y = wy + 1 - (u / 3), Z = wz + 1 - slab;
-            if (X >= 0 && X < nc && Y >= 0 && Y < nc && Z >= 0 && Z < nc) {
-                const int2 r = ct[(size_t)wb * nc * nc * nc + (size_t)X * nc * nc + (size_t)Y * nc + Z];
-                j0 = r.x;
-                len = r.y - r.x;
-            }
-        }
-        const int off = wave_incl_scan(len) - len;   // flat offset of cell `lane` in the canonical candidate list
-        const int total = __builtin_amdgcn_readlane(off + len, 26);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 27) tab[lane] = make_int2(j0 - off, off + len);
-        __builtin_amdgcn_wave_barrier();
-        // neighbour index of flat position f of the window: its cell is found by a 5-step binary search over the 27
-        // cell end offsets (kept in LDS)
-        auto flat_to_j = [&](int f) -> int {
-            int lo = 0, hi = 26;  // smallest o with end[o] > f
-#pragma unroll
-            for (int it = 0; it < 5; ++it) {
-                const int mid = (lo + hi) >> 1;
-                const bool right = tab[mid].y <= f;
-                lo = right ? mid + 1 : lo;
-                hi = right ? hi : mid;
-            }
-            return tab[lo].x + f;  // (j0 - off) + f
-        };
+        int lead;
+        const unsigned members = window_next_group(todo, own, key, lead);
+        const int total = window_table(__builtin_amdgcn_readlane(c.b, lead), __builtin_amdgcn_readlane(c.x, lead),
+                                       __builtin_amdgcn_readlane(c.y, lead), __builtin_amdgcn_readlane(c.z, lead), nc, ct, lane, tab);
         if (FILL && total <= MCCNN_NW_ROUNDS * 64) {
             // pure compaction from the saved ballots: lane = candidate of round r, the same for every centre of the cell
             int jr[MCCNN_NW_ROUNDS];
 #pragma unroll
-            for (int r = 0; r < MCCNN_NW_ROUNDS; ++r) jr[r] = (r * 64 < total) ? flat_to_j(min(r * 64 + lane, total - 1)) : 0;
+            for (int r = 0; r < MCCNN_NW_ROUNDS; ++r) jr[r] = (r * 64 < total) ? flat_to_j(tab, min(r * 64 + lane, total - 1)) : 0;
             unsigned mem = members;
             while (mem) {
                 const int cl = __builtin_ctz(mem);
@@ -281,7 +225,7 @@ __device__ __forceinline__ void neigh_window_impl(const int blk, const int nblk,
             const int segN = min(MCCNN_NW_CAP, total - seg);
             // stage [seg, seg + segN) of the flat list: lane = flat position, one load and one LDS write per position
             for (int r = 0; r < segN; r += 64) {
-                const int j = flat_to_j(min(seg + r + lane, total - 1));
+                const int j = flat_to_j(tab, min(seg + r + lane, total - 1));
                 const float* q = pts + (size_t)j * 3;  // 12-byte rows: one dwordx3 load
                 if (LEAN) {
                     const bool real = r + lane < segN;
@@ -1008,19 +952,6 @@ size_t mccnn_find_neighbors_capped_workspace_bytes(int m, int n) {
     return mccnn_find_neighbors_workspace_bytes(m, n) + align_up(m1 * 4);
 }
 
-// Centres per wave: 8 consecutive centres of the visiting order share most of their windows on a large list (~8 points
-// per cell), but a list with few centres needs the waves -- 6 344 pooling centres with ~900 candidates each ran 139 us per
-// pass on 793 waves (BASELINE cfg2 Pool_1), the coarse levels of a hierarchy 20 us on a handful.
-// sqrt_threshold (common.h) on the host: the same float operations, both square roots correctly rounded
-static float sqrt_threshold_host(float R) {
-    auto prev = [](float v) { uint32_t u; memcpy(&u, &v, 4); --u; memcpy(&v, &u, 4); return v; };
-    auto next = [](float v) { uint32_t u; memcpy(&u, &v, 4); ++u; memcpy(&v, &u, 4); return v; };
-    float t = R * R;
-    for (int it = 0; it < 8 && t > 0.0f && sqrtf(prev(t)) >= R; ++it) t = prev(t);
-    for (int it = 0; it < 8 && sqrtf(t) < R; ++it) t = next(t);
-    return t;
-}
-
 // Background launches (mccnn_background_launches: the geometry of the next batch on a side queue, under the convolution
 // kernels of the current one): the search kernels ask for 36 KB of LDS they do not use, which leaves 2-3 of their
 // workgroups per CU instead of 8. Beside them the convolution waves of the same SIMD wait on LDS weight reads and MFMA
@@ -1040,12 +971,11 @@ static bool neigh_lean() {
     if (forced >= 0) return forced != 0;
     return !g_background;
 }
-static int neigh_group_background(int m) { return m >= 32768 ? MCCNN_NW_G : (m >= 16384 ? 4 : (m >= 8192 ? 2 : 1)); }
 static int neigh_group(int m) {
     // centres per wave: more of them share a window's staging and the per-wave set-up (8 rooms, 800 k centres: 0.309 ms at
     // 8, 0.274 at 16, 0.269 at 24) -- as long as the launch still fills the chip (100 k centres: 0.0588 / 0.0580 / 0.0650)
     // (background launches keep 8: beside the convolution kernels the pipelined step of the room reads 0.596 ms at 8, 0.602-0.610 at 16)
-    if (g_background || m < 65536) return neigh_group_background(m);
+    if (g_background || m < 65536) return window_group(m);
     return m >= 400000 ? 24 : 16;
 }
 
@@ -1081,7 +1011,7 @@ static int neigh_item(const NeighSearch& q, bool batch, NeighItem& it, NeighCapI
     it.cnt = w.cnt; it.masks = w.masks; it.startIdx = q.start_idx; it.packed = q.packed;
     it.zeroWords = reinterpret_cast<unsigned long long*>(w.scanws);
     it.m = q.m; it.B = q.B; it.nc = q.nc; it.scaleInv = q.scale_inv; it.capacity = q.capacity;
-    it.G = batch ? neigh_group_background(q.m) : neigh_group(q.m);
+    it.G = batch ? window_group(q.m) : neigh_group(q.m);
     it.numZero = batch ? ceil_div(q.m, 2048) + 1 : (int)(scan_status_bytes(q.m) / sizeof(unsigned long long));
     it.radius = q.radius;
     it.Tabs = q.scale_inv ? 0.0f : sqrt_threshold_host(q.radius);
@@ -1421,14 +1351,6 @@ int neigh_batch_item(NeighItem& it, NeighCapItem& cap, ScanItem& sc, const Neigh
     sc = ScanItem{w.cnt, q.start_idx, it.zeroWords, q.total_dev, q.total_host, q.m, it.numZero - 1};
     return 0;
 }
-// the workgroups of the first `count` items of a batch -> the grid size
-static int neigh_batch_blocks(const NeighBatch& nbt, int count, BatchBlocks& bb) {
-    bb.count = count;
-    int run = 0;
-    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += ceil_div(nbt.it[k].m, 4 * nbt.it[k].G); }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
-    return run;
-}
 int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int count, int mode, hipStream_t s) {
     // The items of each kind -- plain, capped, sampled (its count pass is the capped one) -- go out together, one launch per
     // kind that is present: a chunk without a capped item is the one plain launch over all its items.
@@ -1454,7 +1376,7 @@ int launch_neigh_batch(const NeighBatch& nbt, const NeighCapBatch& caps, int cou
         if (cnt == 0) continue;
         for (int k = cnt; k < MCCNN_BATCH_MAX; ++k) { sub.it[k] = sub.it[0]; subc.it[k] = subc.it[0]; }   // (never addressed: defined bytes)
         BatchBlocks bb;
-        const int run = neigh_batch_blocks(sub, cnt, bb);
+        const int run = batch_blocks(bb, cnt, [&](int k) { return ceil_div(sub.it[k].m, 4 * sub.it[k].G); });
         if (run == 0) continue;
         if (kind > NEIGH_SAMPLED) {
             if (kind == NEIGH_BUDGET) neigh_window_batch_budget<false><<<run, 256, 24000, s>>>(sub, subc, bb);
@@ -1489,10 +1411,7 @@ int launch_pdf(const PdfItem& it, hipStream_t s) {
 }
 int launch_pdf_batch(const PdfBatch& pb, int count, hipStream_t s) {
     BatchBlocks bb;
-    bb.count = count;
-    int run = 0;
-    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += ceil_div(pb.it[k].m, 16 * pb.it[k].rowsPerWave); }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    const int run = batch_blocks(bb, count, [&](int k) { return ceil_div(pb.it[k].m, 16 * pb.it[k].rowsPerWave); });
     if (run == 0) return 0;
     bool anyRec = false;
     for (int k = 0; k < count; ++k) anyRec = anyRec || pb.it[k].rec != nullptr;

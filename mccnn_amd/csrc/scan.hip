@@ -148,10 +148,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_chained_batch(ScanBatch sb,
 }
 int launch_scan_batch(const ScanBatch& sb, int count, hipStream_t s) {
     BatchBlocks bb;
-    bb.count = count;
-    int run = 0;
-    for (int k = 0; k < count; ++k) { bb.first[k] = run; run += sb.it[k].tiles; }
-    for (int k = count; k <= MCCNN_BATCH_MAX; ++k) bb.first[k] = run;
+    const int run = batch_blocks(bb, count, [&](int k) { return sb.it[k].tiles; });
     if (run == 0) return 0;
     scan_chained_batch<<<run, SCAN_THREADS, 0, s>>>(sb, bb);
     MCCNN_LAUNCHED();
