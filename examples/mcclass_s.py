@@ -7,6 +7,7 @@ tiny synthetic training loop. The graph builders keep the reference's structure 
     python examples/mcclass_s.py --normals [--fused-glue] [--fused-loss]     # MCNormS on the ellipsoids' analytic normals
     python examples/mcclass_s.py --parts [--fused-glue] [--fused-loss]       # per-point part labels, part IoU from device counts
     python examples/mcclass_s.py --fused-adam [--weight-decay 1e-4]          # the optimiser step as one library op (any mode)
+    python examples/mcclass_s.py --fused-adam --clip-norm 1.0 --skip-nonfinite   # ... clipped by the global gradient norm, inside the op
 
 --device-loader builds the batches on the GPU (mccnn_amd.device_batcher.DeviceBatcher: a pool of synthetic models uploaded
 once, non-uniform sampling and rotation per batch on the device) instead of uploading host arrays.
@@ -183,12 +184,17 @@ def synthetic_normals_batch(batchSize, nPts, rng, device):
 def make_optimizer(net, args, lr=5e-3):
     """The optimiser of all three training loops. Default: torch.optim.Adam, as before. --fused-adam: mccnn_amd.optim.FusedAdam,
     the step as one library op, with the reference's L2 term (ModelNet.py:33-56: l2_regularizer over the 'weight_decay_loss'
-    collection, added to the loss) as --weight-decay C over the two collections of the network."""
+    collection, added to the loss) as --weight-decay C over the two collections of the network. --clip-norm C and
+    --skip-nonfinite (both with --fused-adam): the gradients clipped to the global norm C, and a step with a non-finite norm
+    left out, both inside the op (FusedAdam(maxGradNorm, skipNonFinite))."""
+    clip, skip = getattr(args, "clip_norm", None), bool(getattr(args, "skip_nonfinite", False))
     if not args.fused_adam:
+        if clip is not None or skip:
+            raise ValueError("--clip-norm and --skip-nonfinite need --fused-adam")
         return torch.optim.Adam(net.parameters(), lr=lr)
     from mccnn_amd.optim import FusedAdam
     decay = net.store.get_collection('weight_decay_loss') + net.convBuilder.get_collection('weight_decay_loss')
-    return FusedAdam(net.parameters(), lr=lr, weightDecay=args.weight_decay, decayParams=decay)
+    return FusedAdam(net.parameters(), lr=lr, weightDecay=args.weight_decay, decayParams=decay, maxGradNorm=clip, skipNonFinite=skip)
 
 
 def train_normals(args, device, rng):
@@ -318,9 +324,15 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=0.0, metavar="C",
                     help="with --fused-adam: L2 decay C over the 'weight_decay_loss' collections (the reference's "
                          "l2_regularizer(scale=C) term)")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="C",
+                    help="with --fused-adam: clip the gradients to the global norm C inside the optimiser op")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="with --fused-adam: a step whose gradient norm is inf or NaN changes nothing")
     args = ap.parse_args()
     if args.weight_decay and not args.fused_adam:
         ap.error("--weight-decay needs --fused-adam")
+    if (args.clip_norm is not None or args.skip_nonfinite) and not args.fused_adam:
+        ap.error("--clip-norm and --skip-nonfinite need --fused-adam")
     device = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
     torch.manual_seed(0)

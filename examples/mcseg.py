@@ -9,6 +9,7 @@ the block then reads the segments where they are (one library op, no torch.cat, 
 in every other case the helper concatenates and runs what it ran before.
 
     python examples/mcseg.py [--steps 20] [--fused-glue] [--fused-cat] [--fused-linear] [--fused-loss] [--fused-adam]
+                             [--clip-norm C] [--skip-nonfinite]
 """
 import argparse
 import math
@@ -163,9 +164,13 @@ def main():
                          "device counts")
     ap.add_argument("--fused-adam", action="store_true", help="the optimiser step as one library op (mccnn_amd.optim.FusedAdam)")
     ap.add_argument("--weight-decay", type=float, default=0.0, metavar="C", help="with --fused-adam: L2 decay")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="C", help="with --fused-adam: clip to the global gradient norm C")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="with --fused-adam: leave out a step with a non-finite gradient norm")
     args = ap.parse_args()
     if args.weight_decay and not args.fused_adam:
         ap.error("--weight-decay needs --fused-adam")
+    if (args.clip_norm is not None or args.skip_nonfinite) and not args.fused_adam:
+        ap.error("--clip-norm and --skip-nonfinite need --fused-adam")
     device = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
     torch.manual_seed(0)

@@ -1171,6 +1171,42 @@ int mccnn_adam_max_tensors(void); /* tensors one launch takes */
 int mccnn_adam_step(const mccnn_adam_tensor* tensors /* HOST array */, int count, float beta1, float beta2, float eps,
                     float grad_scale, mccnn_stream_t stream);
 
+/* ... CLIPPED BY THE GLOBAL GRADIENT NORM, AND SKIPPED WHEN THAT NORM IS NOT FINITE (extension, ABI 29; adam.hip, grad_clip.h).
+ * With gs = grad_scale and the live tensors = the records with n > 0, in record order, e = 2^-23:
+ *   S       = sum over live tensors and elements of (gs * grad)^2
+ *   norm    = float32(sqrt(S))
+ *   coef    = 1                                          if max_norm == 0, or norm is not finite
+ *           = min(1.0f, max_norm / (norm + 1e-6f))       otherwise, in float32: one add, one divide, one min
+ *                                                        (torch.nn.utils.clip_grad_norm_'s formula)
+ *   skipped = 1 if skip_nonfinite and norm is not finite, else 0
+ *   skips  += skipped
+ * mccnn_grad_norm writes {norm, coef, skipped, skips} into `record`, 16 bytes of DEVICE memory on a 16-byte boundary that
+ * the caller zeroes once when allocating it (skips is cumulative over the calls; a call reads nothing else of it). Nothing is
+ * read back. Of a tensor record it looks at g and n only -- p, m, v and the scalars can hold anything -- so it serves as
+ * the norm of any list of float32 arrays. Products and squares are float32; the sums inside a chunk of 4096 elements are
+ * float32 and tree-shaped, the chunks' partials float64 and summed in index order: norm is within 7.25 e of the exact value
+ * (derivation in adam.hip). A square or a chunk sum beyond FLT_MAX (|gs * grad| above about 1.8e19) is inf, and the step then
+ * reads as non-finite: nothing is rescaled. `ws` is DEVICE memory on an 8-byte boundary of at least mccnn_grad_norm_ws(tensors,
+ * count) bytes (8 per chunk of every live tensor; 0 for none, or for a table the call would refuse); every partial in it is
+ * written before it is read, so it needs no clearing. No atomics, no memset: the same inputs give the same bytes, record
+ * included. Launches: ceil(live / mccnn_adam_max_tensors()) + 1, none with no live tensor (MCCNN_OK; the record stays).
+ * count < 0, a NULL table with count > 0, n < 0, a NULL or not 4-byte aligned g with n > 0, a non-finite grad_scale, a
+ * negative or non-finite max_norm, a NULL record or one off a 16-byte boundary, a ws off an 8-byte boundary: MCCNN_E_BADARG;
+ * a ws that is NULL or too small with live tensors: MCCNN_E_WORKSPACE; 2^31 chunks or more: MCCNN_E_TOOLARGE; all before
+ * anything is launched.
+ * mccnn_adam_step_clipped is mccnn_adam_step (its checks, its launches) with a record: every workgroup reads the 16 bytes
+ * once; with skipped == 1 the whole grid returns before its first access to p, m, v; otherwise the element definition runs with
+ * grad_scale' = float32(grad_scale * coef), rounded once, in place of grad_scale (coef == 1.0f changes no bit). A NULL record
+ * or one off a 16-byte boundary: MCCNN_E_BADARG. The step counts behind step_size and bc2_sqrt are the caller's: a caller
+ * that reads nothing back counts a skipped step too. */
+typedef struct { float norm; float coef; int skipped; int skips; } mccnn_grad_record;   /* 16 bytes, DEVICE memory */
+size_t mccnn_grad_norm_ws(const mccnn_adam_tensor* tensors /* HOST array */, int count);   /* bytes of partials */
+int mccnn_grad_norm(const mccnn_adam_tensor* tensors /* HOST array */, int count, float grad_scale,
+                    float max_norm /* 0: no clipping */, int skip_nonfinite, mccnn_grad_record* record, void* ws, size_t ws_bytes,
+                    mccnn_stream_t stream);
+int mccnn_adam_step_clipped(const mccnn_adam_tensor* tensors /* HOST array */, int count, float beta1, float beta2, float eps,
+                            float grad_scale, const mccnn_grad_record* record, mccnn_stream_t stream);
+
 /* TEST HOOK, not part of the operator surface: selects the convolution implementation for A/B
  * parity tests (bit 0: VALU fallback kernels, bit 1: general MFMA kernels for one-input-feature
  * layers; bit 2: one-input-feature backward passes never take the cooperative edge kernel, bit 3:

@@ -181,6 +181,10 @@ SIGNATURES = {
     # the optimiser step as one op: Adam with L2 decay over many tensors (adam.hip); the records are a HOST array
     "mccnn_adam_max_tensors": (_i, []),
     "mccnn_adam_step": (_i, [_vp, _i, _f, _f, _f, _f, _vp]),
+    # ... clipped by the global gradient norm; the 16-byte record and the partials are DEVICE memory
+    "mccnn_grad_norm_ws": (_sz, [_vp, _i]),
+    "mccnn_grad_norm": (_i, [_vp, _i, _f, _f, _i, _vp, _vp, _sz, _vp]),
+    "mccnn_adam_step_clipped": (_i, [_vp, _i, _f, _f, _f, _f, _vp, _vp]),
     "mccnn_conv_backward": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 6 + [_vp] * 7 + [_vp, _sz, _vp]),
 }
 

@@ -14,7 +14,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, os.environ.get("MCCNN_LIB_NAME", "libmccnn_hip.so"))  # override only for A/B experiments
 SOURCES = ["api_misc.hip", "scan.hip", "grid.hip", "neighbors.hip", "neigh_budget.hip", "pdf_points.hip", "poisson.hip", "conv.hip", "conv_f1.hip", "conv_rows.hip", "conv_points.hip", "exec.hip", "batch_sample.hip", "bn_act.hip", "linear_bn.hip", "linear_xent.hip", "cosine_loss.hip", "seg_counts.hip", "voxel_acc.hip", "adam.hip"]
-HEADERS = ["common.h", "chain.h", "batch.h", "cell_window.h", "conv_mfma.h", "debug_opts.h", "neigh_sample.h", "neigh_budget.h", "batch_sample.h", "bn_drop.h", "bn_act.h", "bn_cat.h", "lin_tile.h", "voxel_key.h"]
+HEADERS = ["common.h", "chain.h", "batch.h", "cell_window.h", "conv_mfma.h", "debug_opts.h", "neigh_sample.h", "neigh_budget.h", "batch_sample.h", "bn_drop.h", "bn_act.h", "bn_cat.h", "lin_tile.h", "voxel_key.h", "grad_clip.h"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # bit-exact geometry: no FMA contraction, correctly rounded f32 divide / sqrt (see csrc/common.h)

@@ -17,10 +17,22 @@ with the per-tensor scalars computed here, in double, from the tensor's own step
     form 'tf'    (tf.train.AdamOptimizer's, the reference's: epsilon outside the bias correction)
                                                          step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t),  bc2_sqrt = 1
 
+With maxGradNorm or skipNonFinite set, one reduction stands in front (mccnn_grad_norm, the same file), with gs = float32(gradScale)
+and the live tensors of ALL param groups in record order:
+
+    S       = sum over live tensors and elements of (gs * grad)^2       (float32 products and chunk sums, float64 across chunks)
+    norm    = float32(sqrt(S))
+    coef    = 1 if max_norm == 0 or norm is not finite, else min(1.0f, max_norm / (norm + 1e-6f))   (clip_grad_norm_'s formula)
+    skipped = 1 if skipNonFinite and norm is not finite, else 0;   skips += skipped
+
+and the step runs with grad_scale' = float32(gs * coef) in place of grad_scale, or not at all when skipped == 1. The four values
+are a 16-byte record on the device, which the step kernel reads; nothing is read back.
+
 The host side is the point of the op: one persistent array of records (the C struct's layout as a NumPy structured array) for
 all parameters, handed to the library by address. A step writes the parameter and gradient pointers, the live flags where
 they changed, and the two step scalars as array operations; no ctypes object is built per tensor.
 """
+import collections
 import math
 
 import numpy as np
@@ -35,6 +47,8 @@ RECORD = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n",
 assert RECORD.itemsize == 48
 CHUNK = 4096   # elements one workgroup of the kernel takes (csrc/adam.hip: kAdamChunk)
 FORMS = ("torch", "tf")
+# mccnn_grad_record (include/mccnn.h) as 0-dim views of its 16 bytes: float32 norm and coef, int32 skipped and skips
+GradRecord = collections.namedtuple("GradRecord", ["norm", "coef", "skipped", "skips"])
 
 
 def _f32(x):
@@ -71,16 +85,39 @@ def _adam_torch(p, g, m, v, step_size, bc2_sqrt, weight_decay, beta1, beta2, eps
     p.sub_((m / den).mul_(step_size))
 
 
+def _grad_norm_host(grads, gs):
+    """The norm's definition on the CPU -> float32 norm: float32 products, squares and per-chunk sums, float64 across the chunks
+    (a square or a chunk sum beyond float32 is inf, as in the kernel)."""
+    total = 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        for g in grads:
+            x = g.detach().reshape(-1).numpy() * np.float32(gs)
+            x = x * x
+            for a in range(0, len(x), CHUNK):
+                total += float(x[a:a + CHUNK].sum(dtype=np.float32))
+    return np.float32(math.sqrt(total))   # (inf and NaN pass through)
+
+
+def clip_coef(norm, max_norm):
+    """csrc/grad_clip.h in NumPy float32: norm, max_norm float32 -> float32 coef."""
+    norm, max_norm = np.float32(norm), np.float32(max_norm)
+    if max_norm == 0 or not np.isfinite(norm):
+        return np.float32(1.0)
+    with np.errstate(over="ignore"):   # (max_norm / 1e-6 beyond float32 is inf, and the min 1)
+        return min(np.float32(1.0), max_norm / (norm + np.float32(1e-6)))
+
+
 class _Plan:
     """What a step reuses: the flat parameter list, the record array and its address, the step counts."""
     __slots__ = ("params", "slices", "device", "rec", "addr", "numel", "decays", "t", "step_buf", "step_np", "has_state", "all_state",
-                 "same_t", "live", "checked", "group_wd")
+                 "same_t", "live", "checked", "group_wd", "ws_bytes")
 
 
 class FusedAdam(torch.optim.Optimizer):
     """Adam with L2 weight decay, one library op per step (see the module's docstring for the arithmetic).
 
-        FusedAdam(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weightDecay=0.0, decayParams=None, form='torch', gradScale=1.0)
+        FusedAdam(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weightDecay=0.0, decayParams=None, form='torch', gradScale=1.0,
+                  maxGradNorm=None, skipNonFinite=False)
 
     params       tensors or param groups. lr, betas, eps, weight_decay and form live in param_groups: a scheduler, or the
                  reference's staircase decay with a floor, assigns group['lr']. lr is a Python float; a tensor raises. Groups
@@ -91,6 +128,24 @@ class FusedAdam(torch.optim.Optimizer):
                  weightDecay = c that is the gradient of the reference's l2_regularizer(scale=c) term, c sum(w^2) / 2.
     form         'torch' (default) or 'tf': where epsilon stands relative to the bias correction.
     gradScale    multiplies every gradient as it is loaded (1 / world after GradBucket.allreduce(average=False)).
+    maxGradNorm  None, or a finite Python number > 0: the gradients, gradScale included, are scaled so that their norm over ALL
+                 param groups is at most this (torch.nn.utils.clip_grad_norm_'s formula), inside the op.
+    skipNonFinite  True: a step whose gradient norm is inf or NaN changes nothing of p, exp_avg, exp_avg_sq.
+
+    gradScale, maxGradNorm and skipNonFinite are plain attributes and may be assigned between steps; pickle and deepcopy keep
+    them; they stay out of param_groups and state_dict(). With maxGradNorm None and skipNonFinite False a step is the library
+    call it was without them. With either set, one mccnn_grad_norm over the whole record array runs first (one norm, whatever
+    the groups), then mccnn_adam_step_clipped per group of shared betas and eps: ceil(tensors / 76) + 1 launches more. The
+    optimiser owns the partials buffer (it grows when needed) and the 16-byte record (zeroed when created, not pickled).
+    grad_record is None before the first such step, afterwards GradRecord(norm, coef, skipped, skips): 0-dim float32 and int32
+    views of the record on the parameters' device, rewritten by every such step. The class never reads them back; a training
+    loop stacks norm into the read-back it already does for its progress line. skips counts the skipped steps. A gradient with
+    |gradScale * grad| above about 1.8e19 overflows its float32 square and reads as non-finite.
+    Step counts live on the host and nothing is read back, so a SKIPPED STEP IS STILL COUNTED: state[p]['step'] and the bias
+    corrections then run ahead by the number of skips (one skip at t = 100 with beta2 = 0.999 changes sqrt(1 - beta2^t) by
+    0.5 %; after a few thousand steps it changes nothing). There is no collective: the norm is that of the gradients this
+    optimiser sees. After GradBucket.allreduce those of the all-reduced tensors agree across ranks; ranks whose other gradients
+    differ clip differently.
 
     state[p] holds step (a 0-dim float32 CPU tensor; the steps of all parameters are views of one buffer, so that a step
     counts them with one operation), exp_avg and exp_avg_sq under torch.optim.Adam's names; state_dict()
@@ -102,10 +157,10 @@ class FusedAdam(torch.optim.Optimizer):
 
     CUDA parameters go through mccnn_adam_step on torch's current stream, CPU parameters through the same definition in
     torch (_adam_torch). Not covered: AMSGrad, maximize, decoupled decay (AdamW), bf16 parameters, capturable / graph
-    capture, gradient clipping, a found-inf skip."""
+    capture, device step counts (GradScaler-style exactness of a skipped step)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weightDecay=0.0, decayParams=None, form="torch",
-                 gradScale=1.0):
+                 gradScale=1.0, maxGradNorm=None, skipNonFinite=False):
         if isinstance(lr, torch.Tensor):
             raise InvalidArgumentError("FusedAdam: lr must be a Python float, not a tensor")
         if not (isinstance(gradScale, (int, float)) and math.isfinite(gradScale)):
@@ -114,16 +169,34 @@ class FusedAdam(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weightDecay, form=form, amsgrad=False, maximize=False,
                         foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
         self._check_group(defaults)
+        self._check_clip(maxGradNorm, skipNonFinite)
         self._plan = None
         self._decay_ids = None
+        self._clip_rec = self._clip_ws = self.grad_record = None
         super().__init__(params, defaults)
         self.gradScale = float(gradScale)
+        self.maxGradNorm = maxGradNorm
+        self.skipNonFinite = skipNonFinite
         if decayParams is not None:
             decay = list(decayParams)
             own = {id(p) for g in self.param_groups for p in g["params"]}
             if not all(isinstance(p, torch.Tensor) and id(p) in own for p in decay):
                 raise InvalidArgumentError("FusedAdam: decayParams holds something that is not among params")
             self._decay_ids = {id(p) for p in decay}
+
+    @staticmethod
+    def _check_clip(max_norm, skip):
+        """-> the float32 max_norm the library is handed (0: no clipping)."""
+        if type(skip) is not bool:
+            raise InvalidArgumentError("FusedAdam: skipNonFinite must be a bool, got %r" % (skip,))
+        if max_norm is None:
+            return 0.0
+        ok = isinstance(max_norm, (int, float)) and not isinstance(max_norm, bool) and math.isfinite(max_norm)
+        with np.errstate(over="ignore"):
+            ok = ok and math.isfinite(_f32(max_norm)) and _f32(max_norm) > 0.0
+        if not ok:
+            raise InvalidArgumentError("FusedAdam: maxGradNorm must be None or a finite Python number > 0 (in float32), got %r" % (max_norm,))
+        return _f32(max_norm)
 
     @staticmethod
     def _check_group(g):
@@ -148,6 +221,8 @@ class FusedAdam(torch.optim.Optimizer):
         d = dict(super().__getstate__())
         flat = [p for g in self.param_groups for p in g["params"]]
         d["gradScale"] = self.gradScale
+        d["maxGradNorm"] = self.maxGradNorm
+        d["skipNonFinite"] = self.skipNonFinite
         d["_decay_index"] = None if self._decay_ids is None else [i for i, p in enumerate(flat) if id(p) in self._decay_ids]
         return d
 
@@ -160,6 +235,8 @@ class FusedAdam(torch.optim.Optimizer):
             flat = [p for g in self.param_groups for p in g["params"]]
             self._decay_ids = None if index is None else {id(flat[i]) for i in index}
         self._plan = None   # (the record array holds addresses and aliases the step counts: rebuilt at the next step)
+        for k, v in (("maxGradNorm", None), ("skipNonFinite", False), ("_clip_rec", None), ("_clip_ws", None), ("grad_record", None)):
+            self.__dict__.setdefault(k, v)   # (a copy starts with a fresh record; load_state_dict keeps what is there)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -205,6 +282,8 @@ class FusedAdam(torch.optim.Optimizer):
         pl.rec = np.zeros(n, dtype=RECORD)
         pl.addr = pl.rec.ctypes.data
         pl.numel = np.array([p.numel() for p in pl.params], dtype=np.int32)
+        # the partials of mccnn_grad_norm, 8 bytes per chunk: of ALL tensors, what any set of live ones needs at most
+        pl.ws_bytes = 8 * int((-(-pl.numel.astype(np.int64) // CHUNK)).sum())
         ids = self._decay_ids
         pl.decays = np.array([1.0 if ids is None or id(p) in ids else 0.0 for p in pl.params], dtype=np.float64)
         pl.t = np.zeros(n, dtype=np.int64)
@@ -276,6 +355,9 @@ class FusedAdam(torch.optim.Optimizer):
         n = len(params)
         if n == 0:
             return loss
+        clip = None   # (max_norm as float32 with 0 for none, skip) when the norm pass runs
+        if self.maxGradNorm is not None or self.skipNonFinite is not False:
+            clip = (self._check_clip(self.maxGradNorm, self.skipNonFinite), self.skipNonFinite)
         f32, strided = torch.float32, torch.strided
         grads = [p.grad for p in params]
         keep = None
@@ -341,7 +423,7 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 runs.append((key, sl.start, sl.stop))
         if pl.device.type == "cpu":
-            self._step_cpu(pl, runs, grads, keep)
+            self._step_cpu(pl, runs, grads, keep, clip)
             return loss
         calls = {}
         for key, a, b in runs:
@@ -350,25 +432,57 @@ class FusedAdam(torch.optim.Optimizer):
         cur = _lib._cur_device() if _lib._cur_device is not None else torch.cuda.current_device()
         if cur != pl.device.index:
             with torch.cuda.device(pl.device):
-                self._launch(lib, pl, calls)
+                self._launch(lib, pl, calls, clip)
         else:
-            self._launch(lib, pl, calls)
+            self._launch(lib, pl, calls, clip)
         return loss
 
-    def _launch(self, lib, pl, calls):
+    def _record(self, device):
+        """The 16-byte record on `device`, zeroed once, and its four views."""
+        r = self._clip_rec
+        if r is None or r.device != device:
+            r = self._clip_rec = torch.zeros(4, dtype=torch.int32, device=device)
+            f = r.view(torch.float32)
+            self.grad_record = GradRecord(f[0], f[1], r[2], r[3])
+        return r
+
+    def _launch(self, lib, pl, calls, clip=None):
         stream = _lib.stream_handle()
+        if clip is not None:   # one norm over the records of all groups, left in the record on the device
+            rec = self._record(pl.device)
+            ws = self._clip_ws
+            if ws is None or ws.device != pl.device or ws.numel() * 8 < pl.ws_bytes:
+                ws = self._clip_ws = torch.empty(max(pl.ws_bytes // 8, 1), dtype=torch.float64, device=pl.device)
+            _lib.check(lib.mccnn_grad_norm(pl.addr, len(pl.rec), self.gradScale, clip[0], int(clip[1]), rec.data_ptr(), ws.data_ptr(),
+                                           ws.numel() * 8, stream), "mccnn_grad_norm")
+            rp = rec.data_ptr()
         for (b1, b2, eps), spans in calls.items():
             if len(spans) == 1:
                 a, b = spans[0]
-                rc = lib.mccnn_adam_step(pl.addr + a * RECORD.itemsize, b - a, b1, b2, eps, self.gradScale, stream)
+                addr, count = pl.addr + a * RECORD.itemsize, b - a
             else:   # (groups that share betas and eps but do not stand side by side: their records, copied together)
                 tmp = np.concatenate([pl.rec[a:b] for a, b in spans])
-                rc = lib.mccnn_adam_step(tmp.ctypes.data, len(tmp), b1, b2, eps, self.gradScale, stream)
-            _lib.check(rc, "mccnn_adam_step")
+                addr, count = tmp.ctypes.data, len(tmp)
+            if clip is None:
+                _lib.check(lib.mccnn_adam_step(addr, count, b1, b2, eps, self.gradScale, stream), "mccnn_adam_step")
+            else:
+                _lib.check(lib.mccnn_adam_step_clipped(addr, count, b1, b2, eps, self.gradScale, rp, stream), "mccnn_adam_step_clipped")
 
-    def _step_cpu(self, pl, runs, grads, keep):
+    def _step_cpu(self, pl, runs, grads, keep, clip=None):
         rec = pl.rec
         gs = _f32(self.gradScale)
+        if clip is not None:   # the same definition, the record as CPU tensors
+            live = [keep[i] if keep and i in keep else grads[i] for i in range(len(rec)) if rec["n"][i] > 0]
+            norm = _grad_norm_host(live, gs)
+            coef = clip_coef(norm, clip[0])
+            skipped = int(clip[1] and not np.isfinite(norm))
+            r = self._record(pl.device).numpy()
+            r.view(np.float32)[:2] = (norm, coef)
+            r[2] = skipped
+            r[3] += skipped
+            if skipped:
+                return
+            gs = _f32(np.float32(gs) * coef)
         for (b1, b2, eps), a, b in runs:
             for i in range(a, b):
                 if rec["n"][i] == 0:

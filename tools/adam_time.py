@@ -1,6 +1,6 @@
 """The optimiser step as one op (mccnn_amd.optim.FusedAdam, mccnn_adam_step) against torch's two Adams, measured in ONE process
 with the settings taken in turn block by block; torch.optim.Adam (default, foreach) and torch.optim.Adam(fused=True) are the
-yardsticks: python tools/adam_time.py [--part a|b|all] (on the GPU box).
+yardsticks: python tools/adam_time.py [--part a|b|c|all] (on the GPU box).
 
 (a) The optimiser step alone, gradients resident, on two parameter sets: the 44 tensors of MCClassS (k = 16, 40 classes) and a
     200-tensor set with the shapes of the MCSegScanNet graph (workloads.mcseg_scannet(64): the six tensors of every
@@ -9,6 +9,10 @@ yardsticks: python tools/adam_time.py [--part a|b|all] (on the GPU box).
     blocks [worst], and the library's launches per step for FusedAdam.
 (b) The MCClassS cfg1 training step of tools/e2e_time.py's deepest loop (hierarchy two batches ahead + prefetch_step) with
     fused, fusedLinear and fusedLoss on, the three optimisers alternating: five blocks of 200 steps each, best block and worst.
+
+(c) The clipped step alone, on the parameter sets of (a): FusedAdam(maxGradNorm=C), the norm and the coefficient inside the op,
+    against torch.nn.utils.clip_grad_norm_(params, C, foreach=True) in front of the unclipped FusedAdam.step() -- how clipping is
+    done without it -- with the unclipped FusedAdam beside them. Same windows, blocks and columns as (a).
 
 torch's launches per step come from a kernel trace in a run of its own:
     rocprofv3 --kernel-trace --stats ... -- python tools/adam_time.py --part trace --opt torch --set mcclass --steps S
@@ -65,39 +69,72 @@ def make_params(shapes, seed):
     return ps
 
 
-def part_a(blocks=5, steps=200):
+def time_steps(steppers, blocks, steps):
+    """steppers: callables that run one step each -> per stepper the wall and HIP-event us per step of every block, and the
+    library's launches per step; the steppers take the blocks in turn."""
     lib = _lib.load()
+    wall, ev, launches = [[] for _ in steppers], [[] for _ in steppers], [0.0] * len(steppers)
+    for step in steppers:
+        for _ in range(20):
+            step()
+    for _ in range(blocks):
+        for i, step in enumerate(steppers):
+            for _ in range(10):
+                step()
+            torch.cuda.synchronize()
+            before = lib.mccnn_debug_launch_count()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            for _ in range(steps):
+                step()
+            e1.record()
+            torch.cuda.synchronize()
+            wall[i].append((time.perf_counter() - t0) / steps * 1e6)
+            ev[i].append(e0.elapsed_time(e1) * 1e3 / steps)
+            launches[i] = (lib.mccnn_debug_launch_count() - before) / float(steps)
+    return wall, ev, launches
+
+
+def part_a(blocks=5, steps=200):
     print("(a) the optimiser step alone, us per step: best of %d blocks of %d steps [worst], the optimisers in turn block by block"
           % (blocks, steps))
     print("| parameter set | tensors | elements | optimiser | wall us | HIP-event us | library launches per step |")
     print("|---|---|---|---|---|---|---|")
     for name, shapes in (("MCClassS", mcclass_shapes()), ("MCSegScanNet-like", seg_shapes())):
         opts = [make(make_params(shapes, 3)) for _, make in OPTIMISERS]
-        wall, ev, launches = [[] for _ in opts], [[] for _ in opts], [0.0] * len(opts)
-        for o in opts:
-            for _ in range(20):
-                o.step()
-        for _ in range(blocks):
-            for i, o in enumerate(opts):
-                for _ in range(10):
-                    o.step()
-                torch.cuda.synchronize()
-                before = lib.mccnn_debug_launch_count()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0 = time.perf_counter()
-                e0.record()
-                for _ in range(steps):
-                    o.step()
-                e1.record()
-                torch.cuda.synchronize()
-                wall[i].append((time.perf_counter() - t0) / steps * 1e6)
-                ev[i].append(e0.elapsed_time(e1) * 1e3 / steps)
-                launches[i] = (lib.mccnn_debug_launch_count() - before) / float(steps)
+        wall, ev, launches = time_steps([o.step for o in opts], blocks, steps)
         elements = sum(int(np.prod(s)) for s in shapes)
         for i, (oname, _) in enumerate(OPTIMISERS):
             print("| %s | %d | %d | %s | %.1f [%.1f] | %.1f [%.1f] | %s |" % (
                 name, len(shapes), elements, oname, min(wall[i]), max(wall[i]), min(ev[i]), max(ev[i]),
                 "%.1f" % launches[i] if oname == "FusedAdam" else "-"))
+
+
+CLIP = 1.0   # (below the norm of the standard normal gradients of either set: the clip is active)
+
+
+def part_c(blocks=5, steps=200):
+    print("(c) the clipped optimiser step alone, us per step: best of %d blocks of %d steps [worst], the settings in turn block by block"
+          % (blocks, steps))
+    print("| parameter set | tensors | setting | wall us | HIP-event us | library launches per step |")
+    print("|---|---|---|---|---|---|")
+    for name, shapes in (("MCClassS", mcclass_shapes()), ("MCSegScanNet-like", seg_shapes())):
+        ps = [make_params(shapes, 3) for _ in range(3)]
+        plain, behind, inside = FusedAdam(ps[0], lr=1e-3), FusedAdam(ps[1], lr=1e-3), FusedAdam(ps[2], lr=1e-3, maxGradNorm=CLIP)
+
+        def yardstick(params=ps[1], opt=behind):
+            torch.nn.utils.clip_grad_norm_(params, CLIP, foreach=True)
+            opt.step()
+
+        names = ["FusedAdam (no clipping)", "clip_grad_norm_(foreach=True) + FusedAdam", "FusedAdam(maxGradNorm=%g)" % CLIP]
+        wall, ev, launches = time_steps([plain.step, yardstick, inside.step], blocks, steps)
+        for i, sname in enumerate(names):
+            print("| %s | %d | %s | %.1f [%.1f] | %.1f [%.1f] | %.1f%s |" % (
+                name, len(shapes), sname, min(wall[i]), max(wall[i]), min(ev[i]), max(ev[i]), launches[i],
+                " + torch's" if i == 1 else ""))
+        win = max(wall[2]) < min(wall[1])
+        print("every block of FusedAdam(maxGradNorm) below every block of the yardstick (wall): %s" % ("yes" if win else "no"))
 
 
 def part_b(blocks=5, steps=200):
@@ -157,7 +194,7 @@ def part_trace(opt, which, steps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=["a", "b", "all", "trace"])
+    ap.add_argument("--part", default="all", choices=["a", "b", "c", "all", "trace"])
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--opt", default="torch", choices=sorted(SHORT))
     ap.add_argument("--set", default="mcclass", choices=["mcclass", "seg"])
@@ -168,6 +205,8 @@ def main():
         part_a(steps=args.steps)
     if args.part in ("b", "all"):
         part_b(steps=args.steps)
+    if args.part in ("c", "all"):
+        part_c(steps=args.steps)
 
 
 if __name__ == "__main__":
