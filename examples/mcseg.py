@@ -158,6 +158,9 @@ def main():
     ap.add_argument("--fused-glue", action="store_true", help="the glue blocks as one library op each (VariableStore(fused=True))")
     ap.add_argument("--fused-cat", action="store_true",
                     help="with --fused-glue: the blocks over a concatenation read its segments in place (VariableStore(fusedCat=True))")
+    ap.add_argument("--bf16-rows", action="store_true",
+                    help="bf16 input rows for the depth-wise layers (MCSeg(rows=torch.bfloat16)); the blocks over a concatenation "
+                         "then see bf16 and mixed-type segments")
     ap.add_argument("--fused-linear", action="store_true", help="the six conv_1x1 + ..._Out_BN pairs as one library op each")
     ap.add_argument("--fused-loss", action="store_true",
                     help="the last linear of the MLP + softmax cross-entropy as one library op; part IoU and voxel accuracy from "
@@ -177,7 +180,7 @@ def main():
     torch.autograd.set_multithreading_enabled(False)   # (one process per GPU: see examples/mcclass_s.py)
     numCats = 4
     net = MCSeg(1, args.batch, args.k, numCats, NUM_PARTS, device, fused=args.fused_glue, fusedCat=args.fused_cat,
-                fusedLinear=args.fused_linear, fusedLoss=args.fused_loss)
+                fusedLinear=args.fused_linear, fusedLoss=args.fused_loss, rows=torch.bfloat16 if args.bf16_rows else None)
 
     def batch():
         P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, device)

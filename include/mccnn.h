@@ -888,24 +888,34 @@ int mccnn_bn_act_bwd_rows(const void* x, int x_bf16, const void* dy, int dy_bf16
                           const float* beta, const float* saved, int relu, unsigned long long keep_threshold,
                           float keep_scale, unsigned seed, void* dx /* x's type; NULL: not wanted */, float* dgamma,
                           float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream);
-/* ... OVER A CONCATENATION (extension, ABI 28; bn_act.hip): the same op over the column-wise concatenation of nseg segments,
- * 1 <= nseg <= mccnn_bn_act_cat_max_segments() (8), which is never materialised. x_s is [n, c_s] float32 row-major
- * contiguous, c_s >= 1, C = sum c_s; y / dy are [n, C], float32 or bfloat16 storage as in the _rows entries; everything per
- * column ([C], saved [2, C]) is indexed by the global column, and so is the dropout mask: element (row, global column). The
- * backward writes one contiguous dx_s [n, c_s] per segment that wants one (dxs == NULL: none; dxs[s] == NULL: not that one;
- * dgamma and dbeta keep their bytes either way). xs, cs and dxs are HOST arrays of nseg entries, read before the call
- * returns: the table travels in the kernel arguments, nothing is uploaded.
- * The plan is the contiguous op's at (n, C) -- grid, column tile, slabs, merge order and the thread -> global column mapping;
- * a thread looks its segment up once and reads x_s + r * c_s + (col - col0_s). 4 columns per thread iff every c_s % 4 == 0,
- * every x_s and wanted dx_s is 16-byte aligned and y / dy / ws pass the rule of the _rows entries; otherwise 1. Whenever the
- * contiguous op takes the same plan on the concatenated tensor -- C % 4 != 0, or every c_s % 4 == 0 and every pointer
- * aligned -- every output is byte for byte that op's (dx_s: the column slice of its dx); nseg == 1 is always
- * mccnn_bn_act_fwd_rows / _bwd_rows with f32 x. The same launch counts whatever nseg is, ws of
- * mccnn_bn_act_workspace_bytes(n, C) bytes, no atomics, no memset.
- * nseg outside [1, 8], n < 1, a c_s < 1, a bad threshold, a NULL required pointer or a type flag outside {0, 1}:
- * MCCNN_E_BADARG; C > 2^31 - 1: MCCNN_E_TOOLARGE; bf16 y / dy with an odd C or off a 4-byte boundary: MCCNN_E_SHAPE; a missing
- * or short workspace: MCCNN_E_WORKSPACE; all before anything is launched.
- * Not covered: bf16 segments, the cross-rank form over segments, a linear layer reading segments, more than 8 segments. */
+/* ... OVER A CONCATENATION (extension, ABI 28; typed segments: ABI 30; bn_act.hip): the same op over the column-wise
+ * concatenation of nseg segments, 1 <= nseg <= mccnn_bn_act_cat_max_segments() (8), which is never materialised. x_s is
+ * [n, c_s] row-major contiguous, c_s >= 1, C = sum c_s, float32 or -- the _rows entries, xs_bf16[s] == 1 -- bfloat16 storage,
+ * every segment on its own; y / dy are [n, C], float32 or bfloat16 storage as in the _rows entries of the contiguous op;
+ * everything per column ([C], saved [2, C]) is indexed by the global column, and so is the dropout mask: element (row, global
+ * column). The backward writes one contiguous dx_s [n, c_s] of x_s's type per segment that wants one (dxs == NULL: none;
+ * dxs[s] == NULL: not that one; dgamma and dbeta keep their bytes either way). xs, xs_bf16 (NULL: all float32), cs and dxs are
+ * HOST arrays of nseg entries, read before the call returns: the table travels in the kernel arguments, nothing is uploaded.
+ * mccnn_bn_act_cat_fwd / _bwd are the _rows entries with xs_bf16 == NULL.
+ * The plan is ALWAYS the contiguous op's at (n, C) with float32 x -- grid, 32-column tile, slabs, merge order and the
+ * thread -> global column mapping -- also when every segment is bf16; a thread looks its segment up once and reads
+ * x_s + r * c_s + (col - col0_s) in the segment's type: bf16 is widened exactly on load and dx_s rounded to nearest even at
+ * the store, everything in between is the float32 arithmetic. 4 columns per thread iff every c_s % 4 == 0, every f32 x_s and
+ * wanted f32 dx_s is 16-byte aligned, every bf16 x_s and wanted bf16 dx_s 8-byte aligned and y / dy / ws pass the rule of the
+ * _rows entries; otherwise 1 (a bf16 element then moves as one 16-bit access).
+ * Let w(x_s) be x_s widened to float32 in a fresh allocation. Whenever the op on (x_s) and mccnn_bn_act_cat_fwd / _bwd on
+ * (w(x_s)) take the same number of columns per thread -- some c_s % 4 != 0, or every c_s % 4 == 0 and every pointer aligned as
+ * above -- y, saved, both moving statistics, dgamma, dbeta and the dx_s of every f32 segment are byte for byte equal, and the
+ * dx_s of a bf16 segment is the round-to-nearest-even of the other's f32 dx_s. And whenever the contiguous op takes the same
+ * plan on the concatenated f32 tensor -- C % 4 != 0, or every c_s % 4 == 0 and every pointer aligned -- every output is byte
+ * for byte that op's (dx_s: the column slice of its dx); nseg == 1 with an f32 segment is always mccnn_bn_act_fwd_rows /
+ * _bwd_rows with f32 x. The same launch counts whatever nseg and the types are, ws of mccnn_bn_act_workspace_bytes(n, C)
+ * bytes, no atomics, no memset.
+ * nseg outside [1, 8], n < 1, a c_s < 1, a bad threshold, a NULL required pointer or a type flag (of y / dy or of a segment)
+ * outside {0, 1}: MCCNN_E_BADARG; C > 2^31 - 1: MCCNN_E_TOOLARGE; bf16 y / dy with an odd C or off a 4-byte boundary, a bf16 x_s
+ * or wanted dx_s off a 2-byte boundary: MCCNN_E_SHAPE; a missing or short workspace: MCCNN_E_WORKSPACE; all before anything is
+ * launched.
+ * Not covered: the cross-rank form over segments, a linear layer reading segments, more than 8 segments. */
 int mccnn_bn_act_cat_max_segments(void);
 int mccnn_bn_act_cat_fwd(const float* const* xs, const int* cs, int nseg, int n, const float* gamma, const float* beta,
                          float* moving_mean, float* moving_var, float momentum, float eps,
@@ -917,6 +927,16 @@ int mccnn_bn_act_cat_bwd(const float* const* xs, const int* cs, int nseg, const 
                          unsigned long long keep_threshold, float keep_scale, unsigned seed,
                          float* const* dxs /* NULL: none wanted; entries may be NULL */, float* dgamma, float* dbeta,
                          void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_act_cat_fwd_rows(const void* const* xs, const int* xs_bf16 /* NULL: all float32 */, const int* cs, int nseg, int n,
+                              const float* gamma, const float* beta, float* moving_mean, float* moving_var, float momentum,
+                              float eps, int training, int relu, unsigned long long keep_threshold, float keep_scale,
+                              unsigned seed, void* y, int y_bf16, float* saved /* [2,C]; may be NULL when !training */,
+                              void* ws, size_t ws_bytes, mccnn_stream_t stream);
+int mccnn_bn_act_cat_bwd_rows(const void* const* xs, const int* xs_bf16 /* NULL: all float32 */, const int* cs, int nseg,
+                              const void* dy, int dy_bf16, int n, const float* gamma, const float* beta, const float* saved,
+                              int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed,
+                              void* const* dxs /* dx_s has x_s's type; NULL: none wanted; entries may be NULL */,
+                              float* dgamma, float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream);
 /* ... WITH BATCH STATISTICS ACROSS RANKS (extension, ABI 22; bn_act.hip): the training form of the same op when the rows of
  * a batch are sharded over the `world` ranks of a process group. n, mean and var of the definition above are those of the
  * concatenation of the ranks' rows in rank order (N rows); the op is cut in two where the caller's collective goes, forward

@@ -281,8 +281,9 @@ def _fused_cat(st, segments, training, name, relu, keepProb=None, momentum=0.99,
     """drop(act(batch_normalization(torch.cat(segments, 1)))) as one library op that reads the segments where they are, or
     None where that form does not apply (the caller then concatenates and goes on as for a single tensor): fused_ or
     fusedCat_ is off, training statistics are synchronised across ranks, the library does not load, or whatever the op's own
-    rule (dense_glue._bn_cat_args), asked once, refuses -- more than 8 segments, one that is not a contiguous float32 2-D tensor
-    on a HIP device, an eval call that wants gradients. The block's variables and the seed of a call that drops are those of
+    rule (dense_glue._bn_cat_args), asked once, refuses -- more than 8 segments, one that is not a contiguous float32 or bfloat16 2-D
+    tensor on a HIP device (the types may differ from segment to segment; the result has torch.cat's: bfloat16 iff every
+    segment is), an eval call that wants gradients. The block's variables and the seed of a call that drops are those of
     _fused_glue on the concatenated tensor."""
     if not (getattr(st, "fused_", False) and getattr(st, "fusedCat_", False)) or _stats_cross_ranks(training, sync):
         return None

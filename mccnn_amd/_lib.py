@@ -150,6 +150,11 @@ SIGNATURES = {
                                   _sz, _vp]),
     "mccnn_bn_act_cat_bwd": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp, _vp, _sz,
                                   _vp]),
+    # ... with a type per segment: xs_bf16, a HOST array of flags (NULL: all f32), behind xs
+    "mccnn_bn_act_cat_fwd_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, C.c_ulonglong, _f, C.c_uint, _vp, _i,
+                                       _vp, _vp, _sz, _vp]),
+    "mccnn_bn_act_cat_bwd_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, C.c_ulonglong, _f, C.c_uint, _vp, _vp, _vp,
+                                       _vp, _sz, _vp]),
     # ... with batch statistics across ranks: the four stages around the caller's two collectives
     "mccnn_bn_sync_stats": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mccnn_bn_sync_apply": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, C.c_ulonglong, _f, C.c_uint, _vp, _i,

@@ -18,10 +18,11 @@
 //                       are recomputed from x, saved and the seed.
 //   n <= 256            one workgroup per column tile does both halves in ONE launch, forward and backward.
 //   eval                one launch.
-//   over a concatenation (mccnn_bn_act_cat_fwd / _bwd): up to 8 f32 segments [n, c_s] in place of x, never concatenated. The
-//                       plan, the launches and the arithmetic are those of f32 x at width C = sum c_s; a thread looks its
-//                       segment up once (bn_cat.h) and reads x_s + r * c_s + (col - col0_s). The table is a kernel argument
-//                       of those instantiations alone.
+//   over a concatenation (mccnn_bn_act_cat_fwd / _bwd, _fwd_rows / _bwd_rows): up to 8 segments [n, c_s] in place of x, never
+//                       concatenated, each f32 or bf16. The plan, the launches and the arithmetic are those of f32 x at width
+//                       C = sum c_s; a thread looks its segment up once (bn_cat.h) and reads x_s + r * c_s + (col - col0_s),
+//                       in its segment's type when one of them is bf16 (BnXSeg). The table is a kernel argument of those
+//                       instantiations alone.
 // No atomics, no memset, no ticket or spin-wait between workgroups; a fixed merge order: the same inputs and seed give the
 // same bytes. The gate is pre > 0 (torch's relu'), not the >= 0 of the convolution kernels.
 #include <initializer_list>
@@ -101,6 +102,15 @@ struct BnXCat {
 __device__ __forceinline__ BnXPlain bn_x(const BnArgs&, const BnCoord&) { return BnXPlain(); }
 __device__ __forceinline__ BnXCat bn_x(const BnArgs&, const BnCoord& t, const BnCat& s) { return BnXCat{bn_cat_at(s, t.col)}; }
 
+// XT of the typed-segment instantiations over a concatenation (mccnn_bn_act_cat_fwd_rows / _bwd_rows with a bf16 segment): x
+// and dx have the type of the thread's SEGMENT (BnCatAt::bf16), float or bn_bf16 below. The row loops -- bn_slab_stats's,
+// bn_apply_rows, bn_grad_rows, bn_dx_rows, none with a barrier inside -- branch on it (bn_seg_typed)
+// once, ahead of the loop, into their float or bn_bf16 member; the threads of a wave may take different sides (a tile may
+// straddle a type boundary) and meet again before the next barrier. Everything else does not know x's type.
+struct BnXSeg {};
+template <typename XT>
+constexpr bool kBnXSeg = std::is_same<XT, BnXSeg>::value;
+
 // VEC f32 values of the library's own memory (LDS, the slab partials): p is on VEC * 4 bytes, 16 at the most
 template <int VEC>
 __device__ __forceinline__ void bn_ld(const float* __restrict__ p, float (&v)[VEC]) {
@@ -133,6 +143,13 @@ __device__ __forceinline__ void bn_st(float* __restrict__ p, const float (&v)[VE
 
 // The element types of a caller's rows: float, or bf16 storage (bn_bf16: 16 bits, widened exactly / rounded to nearest even)
 typedef uint16_t bn_bf16;
+
+// f(xt) for a thread of a typed-segment instantiation, xt a zero of the element type of its segment. f has no barrier inside.
+template <typename F>
+__device__ __forceinline__ void bn_seg_typed(const BnXCat& X, F&& f) {
+    if (X.s.bf16) f(bn_bf16());
+    else f(float());
+}
 
 // VEC elements at element offset `at` of a caller's tensor: bn_ld_raw moves them as they are stored (bn_raw_words 32-bit
 // words; one bf16 alone sits in the low half of a word), bn_widen makes f32 of them (bf16: exactly), bn_ldr is both. The
@@ -274,6 +291,30 @@ __device__ __forceinline__ void bn_tree_sum(const BnArgs& a, const BnCoord& t, f
     }
 }
 
+// The row loop of bn_slab_stats below for a thread of a typed-segment instantiation, T its segment's element type: K, the
+// shift -- the slab's first row -- and the sums of (x - K) and (x - K)^2 over rows row0 + ry, + R, ... below row1; -> the rows
+// taken. (A second copy of that loop on purpose: as a function called from bn_slab_stats it changes the code the compiler
+// makes of the contiguous, f32-segment and cross-rank kernels, which keep theirs.)
+template <int VEC, typename T>
+__device__ __forceinline__ int bn_seg_rows_acc(const BnArgs& a, const BnCoord& t, const BnXCat& X, int row0, int row1, float (&K)[VEC],
+                                               float (&s1)[VEC], float (&s2)[VEC]) {
+    int rows = 0;
+    bn_ldr<VEC, T>(X.x(a), X.at(a, t, (size_t)row0), K);
+#pragma unroll kBnRowsAhead<VEC>
+    for (int r = row0 + t.ry; r < row1; r += t.R) {
+        float v[VEC];
+        bn_ldr<VEC, T>(X.x(a), X.at(a, t, (size_t)r), v);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float d = v[k] - K[k];
+            s1[k] = s1[k] + d;
+            s2[k] = s2[k] + d * d;
+        }
+        ++rows;
+    }
+    return rows;
+}
+
 // (count, mean, M2) of rows [row0, row1) of the thread's columns, merged over the row lanes
 template <int VEC, typename XT, typename XS>
 __device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t, const XS& X, int row0, int row1, float& cnt,
@@ -283,18 +324,22 @@ __device__ __forceinline__ void bn_slab_stats(const BnArgs& a, const BnCoord& t,
     for (int k = 0; k < VEC; ++k) { s1[k] = 0.f; s2[k] = 0.f; K[k] = 0.f; }
     int rows = 0;
     if (t.ok && row0 < row1) {
-        bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)row0), K);   // the shift: the slab's first row
+        if constexpr (kBnXSeg<XT>) {
+            bn_seg_typed(X, [&](auto xt) { rows = bn_seg_rows_acc<VEC, decltype(xt)>(a, t, X, row0, row1, K, s1, s2); });
+        } else {
+            bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)row0), K);   // the shift: the slab's first row
 #pragma unroll kBnRowsAhead<VEC>
-        for (int r = row0 + t.ry; r < row1; r += t.R) {
-            float v[VEC];
-            bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)r), v);
+            for (int r = row0 + t.ry; r < row1; r += t.R) {
+                float v[VEC];
+                bn_ldr<VEC, XT>(X.x(a), X.at(a, t, (size_t)r), v);
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const float d = v[k] - K[k];
-                s1[k] = s1[k] + d;
-                s2[k] = s2[k] + d * d;
+                for (int k = 0; k < VEC; ++k) {
+                    const float d = v[k] - K[k];
+                    s1[k] = s1[k] + d;
+                    s2[k] = s2[k] + d * d;
+                }
+                ++rows;
             }
-            ++rows;
         }
     }
     cnt = (float)rows;
@@ -390,8 +435,9 @@ __device__ __forceinline__ void bn_apply_rows(const BnArgs& a, const BnCoord& t,
 
 // forward, training, launch 1
 // CAT (here and in the three kernels that read x below): nothing -- the contiguous op, the kernel's only argument is BnArgs --
-// or BnCat, the segment table of the op over a concatenation (mccnn_bn_act_cat_fwd / _bwd; XT float), an argument of those
-// instantiations alone. The body is the same: it asks X where the thread's rows are.
+// or BnCat, the segment table of the op over a concatenation (mccnn_bn_act_cat_fwd / _bwd and their _rows forms; XT float, or
+// BnXSeg when a segment is bf16), an argument of those instantiations alone. The body is the same: it asks X where the
+// thread's rows are.
 template <int VEC, typename XT, typename... CAT>
 __global__ __launch_bounds__(kBnThreads) void bn_stats_k(BnArgs a, CAT... s) {
     __shared__ __attribute__((aligned(16))) float lds[kBnThreads * (1 + 2 * VEC)];
@@ -429,7 +475,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a, CAT... s) {
             mean[k] = t.ok ? a.mov_mean[t.col + k] : 0.f;
             rstd[k] = t.ok ? 1.0f / sqrtf(a.mov_var[t.col + k] + a.eps) : 0.f;
         }
-        bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, false);
+        if constexpr (kBnXSeg<XT>) bn_seg_typed(X, [&](auto xt) { bn_apply_rows<VEC, decltype(xt), YT>(a, t, X, row0, row1, mean, rstd, false); });
+        else bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, false);
     } else {
         float cnt, m2[VEC];
         if constexpr (MODE == 0) bn_merge_partials<VEC>(a, t, cnt, mean, m2, lds);
@@ -437,7 +484,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(BnArgs a, CAT... s) {
         bn_finish_stats<VEC>(a, t, (float)a.n, mean, m2, slab == 0, sm);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { mean[k] = sm[0][t.cx * VEC + k]; rstd[k] = sm[1][t.cx * VEC + k]; }
-        bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, a.T < kBnDropAll);
+        if constexpr (kBnXSeg<XT>) bn_seg_typed(X, [&](auto xt) { bn_apply_rows<VEC, decltype(xt), YT>(a, t, X, row0, row1, mean, rstd, a.T < kBnDropAll); });
+        else bn_apply_rows<VEC, XT, YT>(a, t, X, row0, row1, mean, rstd, a.T < kBnDropAll);
     }
 }
 
@@ -482,26 +530,31 @@ __device__ __forceinline__ void bn_row_grad(const BnArgs& a, const BnCoord& t, c
 template <int VEC, typename XT, typename YT, typename F, typename XS>
 __device__ __forceinline__ void bn_grad_rows(const BnArgs& a, const BnCoord& t, const XS& X, const BnCols<VEC>& q, int row0, int row1,
                                              bool drop, F&& f, int base = 0) {
-    constexpr int U = 4;
-    for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
-        uint32_t wx[U][bn_raw_words<VEC, XT>()], wd[U][bn_raw_words<VEC, YT>()];   // (as stored: widened where they are used)
+    if constexpr (kBnXSeg<XT>) {   // (bn_slab_sums; bn_dx_rows has branched already)
+        if (X.s.bf16) bn_grad_rows<VEC, bn_bf16, YT>(a, t, X, q, row0, row1, drop, f, base);
+        else bn_grad_rows<VEC, float, YT>(a, t, X, q, row0, row1, drop, f, base);
+    } else {
+        constexpr int U = 4;
+        for (long long r = row0 + t.ry; r < row1; r += U * t.R) {
+            uint32_t wx[U][bn_raw_words<VEC, XT>()], wd[U][bn_raw_words<VEC, YT>()];   // (as stored: widened where they are used)
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long ru = r + u * t.R;
-            if (ru < row1) {
-                bn_ld_raw<VEC, XT>(X.x(a), X.at(a, t, (size_t)ru), wx[u]);
-                bn_ld_raw<VEC, YT>(a.dy, (size_t)ru * a.c + t.col, wd[u]);
+            for (int u = 0; u < U; ++u) {
+                const long long ru = r + u * t.R;
+                if (ru < row1) {
+                    bn_ld_raw<VEC, XT>(X.x(a), X.at(a, t, (size_t)ru), wx[u]);
+                    bn_ld_raw<VEC, YT>(a.dy, (size_t)ru * a.c + t.col, wd[u]);
+                }
             }
-        }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long ru = r + u * t.R;
-            if (ru < row1) {
-                float v[VEC], d[VEC], g[VEC], xh[VEC];
-                bn_widen<VEC, XT>(wx[u], v);
-                bn_widen<VEC, YT>(wd[u], d);
-                bn_row_grad<VEC>(a, t, q, base + (int)ru, drop, v, d, g, xh);
-                f((int)ru, g, xh);
+            for (int u = 0; u < U; ++u) {
+                const long long ru = r + u * t.R;
+                if (ru < row1) {
+                    float v[VEC], d[VEC], g[VEC], xh[VEC];
+                    bn_widen<VEC, XT>(wx[u], v);
+                    bn_widen<VEC, YT>(wd[u], d);
+                    bn_row_grad<VEC>(a, t, q, base + (int)ru, drop, v, d, g, xh);
+                    f((int)ru, g, xh);
+                }
             }
         }
     }
@@ -621,7 +674,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_k(BnArgs a, CAT... s) {
         }
     }
     __syncthreads();
-    bn_dx_rows<VEC, XT, YT>(a, t, X, q, row0, row1, fn, sm, 0);
+    if constexpr (kBnXSeg<XT>) bn_seg_typed(X, [&](auto xt) { bn_dx_rows<VEC, decltype(xt), YT>(a, t, X, q, row0, row1, fn, sm, 0); });
+    else bn_dx_rows<VEC, XT, YT>(a, t, X, q, row0, row1, fn, sm, 0);
 }
 
 // ---- batch statistics across the ranks of a process group (mccnn_bn_sync_*) ----------------------------------------------
@@ -922,43 +976,68 @@ int mccnn_bn_act_bwd(const float* x, const float* dy, int n, int c, const float*
                                  ws, ws_bytes, stream);
 }
 
-// ---- over a column-wise concatenation of f32 segments (ABI 28): the plan, launches and arithmetic of the f32-x entries at
-// width C = sum c_s; wherever that plan is the one the contiguous op takes on the concatenated tensor, the same bytes ----
+// ---- over a column-wise concatenation (ABI 28; typed segments: ABI 30): the plan, launches and arithmetic of the f32-x
+// entries at width C = sum c_s, whatever the segments' types; wherever that plan is the one the contiguous op takes on the
+// concatenated (widened) tensor, the same bytes ----
 }  // extern "C"
 
 namespace mccnn {
 
-// the family over (columns per thread, y's / dy's type): go(v, yt) as in bn_launch
+// the family over (columns per thread, x's type -- float, or BnXSeg: the segment's, when one of them is bf16 -- and y's / dy's
+// type): go(v, xt, yt) as in bn_launch
 template <typename F>
-inline int bn_cat_launch(int vec, int y_bf16, F&& go) {
-    if (!y_bf16) { if (vec == 4) go(BnVec<4>(), float()); else go(BnVec<1>(), float()); }
-    else { if (vec == 4) go(BnVec<4>(), bn_bf16()); else go(BnVec<1>(), bn_bf16()); }
+inline int bn_cat_launch(int vec, bool typed, int y_bf16, F&& go) {
+    if (!typed) {
+        if (!y_bf16) { if (vec == 4) go(BnVec<4>(), float(), float()); else go(BnVec<1>(), float(), float()); }
+        else { if (vec == 4) go(BnVec<4>(), float(), bn_bf16()); else go(BnVec<1>(), float(), bn_bf16()); }
+    } else {
+        if (!y_bf16) { if (vec == 4) go(BnVec<4>(), BnXSeg(), float()); else go(BnVec<1>(), BnXSeg(), float()); }
+        else { if (vec == 4) go(BnVec<4>(), BnXSeg(), bn_bf16()); else go(BnVec<1>(), BnXSeg(), bn_bf16()); }
+    }
     MCCNN_LAUNCHED();
     return 0;
 }
 
-// The segments of a call, checked, as the table the kernels take: 0 or the error. dxs: NULL, or per segment where its
-// gradient goes (NULL: not wanted). c: C; wide: every width and every segment pointer allows 4 columns per thread;
-// any_dx: some gradient is wanted.
-inline int bn_cat_table(BnCat& s, int& c, bool& wide, bool& any_dx, const float* const* xs, const int* cs, int nseg, int n,
-                        float* const* dxs) {
+// what the table of a call says beside the table itself
+struct BnCatCall {
+    int c;         // C
+    bool wide;     // every width and every segment pointer allows 4 columns per thread (bn_cat_rows_wide)
+    bool any_dx;   // some gradient is wanted
+    bool typed;    // some segment is bf16: the BnXSeg instantiations
+    bool odd;      // a bf16 x_s or wanted dx_s off a 2-byte boundary
+};
+
+// The segments of a call, checked, as the table the kernels take: 0 or the error. xs_bf16: NULL (all f32), or per segment
+// whether its rows are bf16; dxs: NULL, or per segment where its gradient goes (NULL: not wanted).
+inline int bn_cat_table(BnCat& s, BnCatCall& k, const void* const* xs, const int* xs_bf16, const int* cs, int nseg, int n,
+                        void* const* dxs) {
+    k = BnCatCall();
     if (nseg < 1 || nseg > kBnCatMax || n < 1 || !xs || !cs) return MCCNN_E_BADARG;
-    for (int k = 0; k < nseg; ++k)
-        if (cs[k] < 1 || !xs[k]) return MCCNN_E_BADARG;
+    for (int i = 0; i < nseg; ++i)
+        if (cs[i] < 1 || !xs[i] || (xs_bf16 && (xs_bf16[i] & ~1))) return MCCNN_E_BADARG;
     if (bn_cat_fill(s, cs, nseg) > 0x7fffffffll) return MCCNN_E_TOOLARGE;
-    c = s.col0[kBnCatMax];
-    wide = bn_cat_widths_by4(cs, nseg);
-    any_dx = false;
-    for (int k = 0; k < kBnCatMax; ++k) {
-        const int from = k < nseg ? k : 0;
-        s.x[k] = xs[from];
-        s.dx[k] = dxs ? dxs[from] : nullptr;
-        if (k < nseg) {
-            wide = wide && bn_aligned16(s.x[k]) && bn_aligned16(s.dx[k]);
-            any_dx = any_dx || s.dx[k];
+    k.c = s.col0[kBnCatMax];
+    k.wide = bn_cat_rows_wide(xs, xs_bf16, cs, nseg, dxs);
+    k.typed = bn_cat_set_types(s, xs_bf16, nseg);
+    for (int i = 0; i < kBnCatMax; ++i) {
+        const int from = i < nseg ? i : 0;
+        s.x[i] = xs[from];
+        s.dx[i] = dxs ? dxs[from] : nullptr;
+        if (i < nseg) {
+            k.any_dx = k.any_dx || s.dx[i];
+            if ((s.bf16 >> i) & 1u) k.odd = k.odd || (((uintptr_t)s.x[i] | (uintptr_t)s.dx[i]) & 1u);
         }
     }
     return 0;
+}
+
+// the rest of what the two entries share: the plan at (n, C) from y's / dy's rows and the workspace, always the f32-x one
+inline int bn_cat_setup(BnArgs& a, BnPlan& p, const BnCatCall& k, int n, const void* y, int y_bf16, size_t need, void* ws,
+                        size_t ws_bytes) {
+    const int e = bn_setup(a, p, n, k.c, {{nullptr, 0}, {y, y_bf16}}, need, ws, ws_bytes, k.wide);
+    if (e == MCCNN_E_BADARG) return e;
+    if (k.odd) return MCCNN_E_SHAPE;
+    return e;
 }
 
 }  // namespace mccnn
@@ -967,14 +1046,13 @@ extern "C" {
 
 int mccnn_bn_act_cat_max_segments(void) { return kBnCatMax; }
 
-int mccnn_bn_act_cat_fwd(const float* const* xs, const int* cs, int nseg, int n, const float* gamma, const float* beta,
-                         float* moving_mean, float* moving_var, float momentum, float eps, int training, int relu,
-                         unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16, float* saved,
-                         void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+int mccnn_bn_act_cat_fwd_rows(const void* const* xs, const int* xs_bf16, const int* cs, int nseg, int n, const float* gamma,
+                              const float* beta, float* moving_mean, float* moving_var, float momentum, float eps, int training,
+                              int relu, unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16,
+                              float* saved, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
     BnCat s = {};
-    int c = 0;
-    bool wide = false, any_dx = false;
-    const int table = bn_cat_table(s, c, wide, any_dx, xs, cs, nseg, n, nullptr);
+    BnCatCall k;
+    const int table = bn_cat_table(s, k, xs, xs_bf16, cs, nseg, n, nullptr);
     if (table == MCCNN_E_BADARG) return table;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!gamma || !beta || !moving_mean || !moving_var || !y) return MCCNN_E_BADARG;
@@ -982,61 +1060,77 @@ int mccnn_bn_act_cat_fwd(const float* const* xs, const int* cs, int nseg, int n,
     if (table) return table;   // (C past 2^31 - 1: behind the other argument errors)
     BnArgs a = {};
     BnPlan p;
-    if (const int e = bn_setup(a, p, n, c, {{s.x[0], 0}, {y, y_bf16}}, training ? mccnn_bn_act_workspace_bytes(n, c) : 0, ws, ws_bytes, wide))
-        return e;
+    if (const int e = bn_cat_setup(a, p, k, n, y, y_bf16, training ? mccnn_bn_act_workspace_bytes(n, k.c) : 0, ws, ws_bytes)) return e;
     a.out = y; a.gamma = gamma; a.beta = beta; a.mov_mean = moving_mean; a.mov_var = moving_var; a.saved = saved;
     a.relu = relu ? 1 : 0; a.momentum = momentum; a.eps = eps; a.keep_scale = keep_scale; a.seed = seed;
     a.T = training ? keep_threshold : kBnDropAll;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
     if (!training)
-        return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
-            bn_apply_k<v(), float, decltype(yt), 2><<<grid, kBnThreads, 0, st>>>(a, s);
+        return bn_cat_launch(p.vec, k.typed, y_bf16, [&](auto v, auto xt, auto yt) {
+            bn_apply_k<v(), decltype(xt), decltype(yt), 2><<<grid, kBnThreads, 0, st>>>(a, s);
         });
     if (n <= kBnSmallRows)
-        return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
-            bn_apply_k<v(), float, decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
+        return bn_cat_launch(p.vec, k.typed, y_bf16, [&](auto v, auto xt, auto yt) {
+            bn_apply_k<v(), decltype(xt), decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
         });
-    if (const int e = bn_cat_launch(p.vec, 0, [&](auto v, auto) { bn_stats_k<v(), float><<<grid, kBnThreads, 0, st>>>(a, s); }))
+    if (const int e = bn_cat_launch(p.vec, k.typed, 0, [&](auto v, auto xt, auto) {
+            bn_stats_k<v(), decltype(xt)><<<grid, kBnThreads, 0, st>>>(a, s);
+        }))
         return e;
-    return bn_cat_launch(p.vec, y_bf16, [&](auto v, auto yt) {
-        bn_apply_k<v(), float, decltype(yt), 0><<<grid, kBnThreads, 0, st>>>(a, s);
+    return bn_cat_launch(p.vec, k.typed, y_bf16, [&](auto v, auto xt, auto yt) {
+        bn_apply_k<v(), decltype(xt), decltype(yt), 0><<<grid, kBnThreads, 0, st>>>(a, s);
     });
 }
 
-int mccnn_bn_act_cat_bwd(const float* const* xs, const int* cs, int nseg, const void* dy, int dy_bf16, int n, const float* gamma,
-                         const float* beta, const float* saved, int relu, unsigned long long keep_threshold, float keep_scale,
-                         unsigned seed, float* const* dxs, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
-                         mccnn_stream_t stream) {
+int mccnn_bn_act_cat_bwd_rows(const void* const* xs, const int* xs_bf16, const int* cs, int nseg, const void* dy, int dy_bf16, int n,
+                              const float* gamma, const float* beta, const float* saved, int relu,
+                              unsigned long long keep_threshold, float keep_scale, unsigned seed, void* const* dxs, float* dgamma,
+                              float* dbeta, void* ws, size_t ws_bytes, mccnn_stream_t stream) {
     BnCat s = {};
-    int c = 0;
-    bool wide = false, any_dx = false;
-    const int table = bn_cat_table(s, c, wide, any_dx, xs, cs, nseg, n, dxs);
+    BnCatCall k;
+    const int table = bn_cat_table(s, k, xs, xs_bf16, cs, nseg, n, dxs);
     if (table == MCCNN_E_BADARG) return table;
     if (keep_threshold == 0 || keep_threshold > kBnDropAll) return MCCNN_E_BADARG;
     if (!dy || !gamma || !beta || !saved || !dgamma || !dbeta) return MCCNN_E_BADARG;
     if (table) return table;
     BnArgs a = {};
     BnPlan p;
-    if (const int e = bn_setup(a, p, n, c, {{s.x[0], 0}, {dy, dy_bf16}}, mccnn_bn_act_workspace_bytes(n, c), ws, ws_bytes, wide))
-        return e;
+    if (const int e = bn_cat_setup(a, p, k, n, dy, dy_bf16, mccnn_bn_act_workspace_bytes(n, k.c), ws, ws_bytes)) return e;
     a.dy = dy; a.gamma = gamma; a.beta = beta; a.saved = const_cast<float*>(saved);
-    a.dgamma = dgamma; a.dbeta = dbeta; a.relu = relu ? 1 : 0; a.want_dx = any_dx ? 1 : 0;
+    a.dgamma = dgamma; a.dbeta = dbeta; a.relu = relu ? 1 : 0; a.want_dx = k.any_dx ? 1 : 0;
     a.keep_scale = keep_scale; a.seed = seed; a.T = keep_threshold;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p.tiles, (unsigned)p.slabs);
     if (n <= kBnSmallRows)
-        return bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
-            bn_bwd_dx_k<v(), float, decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
+        return bn_cat_launch(p.vec, k.typed, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_bwd_dx_k<v(), decltype(xt), decltype(yt), 1><<<grid, kBnThreads, 0, st>>>(a, s);
         });
-    if (const int e = bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
-            bn_bwd_sums_k<v(), float, decltype(yt)><<<grid, kBnThreads, 0, st>>>(a, s);
+    if (const int e = bn_cat_launch(p.vec, k.typed, dy_bf16, [&](auto v, auto xt, auto yt) {
+            bn_bwd_sums_k<v(), decltype(xt), decltype(yt)><<<grid, kBnThreads, 0, st>>>(a, s);
         }))
         return e;
-    const dim3 grid2((unsigned)p.tiles, any_dx ? (unsigned)p.slabs : 1u);
-    return bn_cat_launch(p.vec, dy_bf16, [&](auto v, auto yt) {
-        bn_bwd_dx_k<v(), float, decltype(yt), 0><<<grid2, kBnThreads, 0, st>>>(a, s);
+    const dim3 grid2((unsigned)p.tiles, k.any_dx ? (unsigned)p.slabs : 1u);
+    return bn_cat_launch(p.vec, k.typed, dy_bf16, [&](auto v, auto xt, auto yt) {
+        bn_bwd_dx_k<v(), decltype(xt), decltype(yt), 0><<<grid2, kBnThreads, 0, st>>>(a, s);
     });
+}
+
+// the float32-segment entries (ABI 28): the typed ones without flags -- the same plan, kernels, launches and bytes
+int mccnn_bn_act_cat_fwd(const float* const* xs, const int* cs, int nseg, int n, const float* gamma, const float* beta,
+                         float* moving_mean, float* moving_var, float momentum, float eps, int training, int relu,
+                         unsigned long long keep_threshold, float keep_scale, unsigned seed, void* y, int y_bf16, float* saved,
+                         void* ws, size_t ws_bytes, mccnn_stream_t stream) {
+    return mccnn_bn_act_cat_fwd_rows((const void* const*)xs, nullptr, cs, nseg, n, gamma, beta, moving_mean, moving_var, momentum, eps,
+                                     training, relu, keep_threshold, keep_scale, seed, y, y_bf16, saved, ws, ws_bytes, stream);
+}
+
+int mccnn_bn_act_cat_bwd(const float* const* xs, const int* cs, int nseg, const void* dy, int dy_bf16, int n, const float* gamma,
+                         const float* beta, const float* saved, int relu, unsigned long long keep_threshold, float keep_scale,
+                         unsigned seed, float* const* dxs, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                         mccnn_stream_t stream) {
+    return mccnn_bn_act_cat_bwd_rows((const void* const*)xs, nullptr, cs, nseg, dy, dy_bf16, n, gamma, beta, saved, relu,
+                                     keep_threshold, keep_scale, seed, (void* const*)dxs, dgamma, dbeta, ws, ws_bytes, stream);
 }
 
 // ---- statistics across ranks (ABI 22): the four stages around the caller's two collectives ----

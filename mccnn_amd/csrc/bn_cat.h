@@ -8,6 +8,11 @@
 // inside one segment, because every segment starts at a multiple of 4. A thread walks the at most 8 column prefixes once
 // (an unrolled compare and select over kernel arguments, uniform loads) and from then on addresses
 // x_s + r * c_s + (col - col0_s) where the contiguous op addresses x + r * C + col.
+//
+// A segment is f32 or bf16 storage (mccnn_bn_act_cat_fwd_rows / _bwd_rows; tools/bn_cat_rows_check.cpp): the table carries a
+// bit per segment, the lookup hands the thread its segment's, and the plan stays the f32 one at (n, C) whatever the types.
+// 4 columns per thread then ask a bf16 segment's rows for 8-byte alignment where they ask an f32 one's for 16
+// (bn_cat_rows_wide).
 #pragma once
 #include <cstdint>
 
@@ -51,12 +56,14 @@ inline BnPlan bn_plan(int n, int c, bool aligned, int x_bf16 = 0) {
 constexpr int kBnCatMax = 8;   // segments of a call
 
 // The segment table of a call, by value in the kernel arguments. col0[s]: the first global column of segment s; from
-// s = nseg on col0 is C (no column reaches it) and x, dx, c repeat segment 0's.
+// s = nseg on col0 is C (no column reaches it) and x, dx, c repeat segment 0's. bf16: bit s is set where x_s (and dx_s) is
+// bfloat16 storage; only the typed-segment instantiations look at it.
 struct BnCat {
-    const float* x[kBnCatMax];
-    float* dx[kBnCatMax];   // backward: NULL where no gradient is wanted
+    const void* x[kBnCatMax];
+    void* dx[kBnCatMax];    // backward: NULL where no gradient is wanted; x_s's type
     int c[kBnCatMax];
     int col0[kBnCatMax + 1];
+    unsigned bf16;
 };
 
 // the widths of a call: every segment a multiple of 4 columns wide (with aligned pointers: 4 columns per thread)
@@ -64,6 +71,29 @@ inline bool bn_cat_widths_by4(const int* cs, int nseg) {
     for (int s = 0; s < nseg; ++s)
         if (cs[s] % 4 != 0) return false;
     return true;
+}
+
+// Columns per thread of a call over typed segments (xs_bf16: NULL, or per segment 1 for bf16 rows; dxs: NULL, or per segment
+// where its gradient goes, NULL: not wanted): 4 iff every width is a multiple of 4, every f32 x_s and wanted f32 dx_s is on
+// 16 bytes and every bf16 x_s and wanted bf16 dx_s on 8 -- what a thread's 4 elements of a row take in either type. (y, dy
+// and the workspace come on top: the rule of the _rows entries, bn_setup in bn_act.hip.) Otherwise 1; a bf16 element then
+// moves as one 16-bit access.
+inline bool bn_cat_rows_wide(const void* const* xs, const int* xs_bf16, const int* cs, int nseg, const void* const* dxs) {
+    if (!bn_cat_widths_by4(cs, nseg)) return false;
+    for (int s = 0; s < nseg; ++s) {
+        const uintptr_t mask = (xs_bf16 && xs_bf16[s]) ? 7u : 15u;
+        if ((uintptr_t)xs[s] & mask) return false;
+        if (dxs && ((uintptr_t)dxs[s] & mask)) return false;   // (NULL: not wanted, and on every boundary)
+    }
+    return true;
+}
+
+// the types of the nseg segments into the table (xs_bf16: NULL -- all f32 -- or per segment 0 / 1); -> some segment is bf16
+inline bool bn_cat_set_types(BnCat& t, const int* xs_bf16, int nseg) {
+    t.bf16 = 0;
+    for (int s = 0; xs_bf16 && s < nseg; ++s)
+        if (xs_bf16[s]) t.bf16 |= 1u << s;
+    return t.bf16 != 0;
 }
 
 // fills c and col0 from the nseg widths (1 <= nseg <= kBnCatMax, every width >= 1); -> C, as 64 bits
@@ -81,8 +111,9 @@ inline long long bn_cat_fill(BnCat& t, const int* cs, int nseg) {
 // where global column col (0 <= col < C) is: its segment, that segment's rows and the column inside them
 struct BnCatAt {
     int seg, ld, col;
-    const float* x;
-    float* dx;
+    const void* x;
+    void* dx;
+    bool bf16;   // the segment's rows are bf16 storage
 };
 MCCNN_CAT_FN BnCatAt bn_cat_at(const BnCat& t, int col) {
     BnCatAt at;
@@ -93,12 +124,13 @@ MCCNN_CAT_FN BnCatAt bn_cat_at(const BnCat& t, int col) {
 #endif
     for (int s = 1; s < kBnCatMax; ++s) {   // (every entry is read, then selected: values, never an address into the table)
         const int c0 = t.col0[s], ld = t.c[s];
-        const float* const x = t.x[s];
-        float* const dx = t.dx[s];
+        const void* const x = t.x[s];
+        void* const dx = t.dx[s];
         const bool in = col >= c0;
         at.seg = in ? s : at.seg; at.ld = in ? ld : at.ld; at.x = in ? x : at.x; at.dx = in ? dx : at.dx; first = in ? c0 : first;
     }
     at.col = col - first;
+    at.bf16 = (t.bf16 >> at.seg) & 1u;
     return at;
 }
 

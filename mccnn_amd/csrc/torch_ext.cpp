@@ -1478,9 +1478,10 @@ Tensor bn_relu_drop(const Tensor& x_in, const Tensor& gamma, const Tensor& beta,
     return y;
 }
 
-// ---- ... over a column-wise concatenation that is never materialised (mccnn_bn_act_cat_fwd / _bwd): the C++ form of
-// dense_glue.bn_relu_dropout_cat -- the same library calls with the same arguments, so the same bytes. f32 segments; a segment
-// that does not require a gradient gets none (a NULL pointer in the call, an undefined tensor out of the node).
+// ---- ... over a column-wise concatenation that is never materialised (mccnn_bn_act_cat_fwd_rows / _bwd_rows): the C++ form
+// of dense_glue.bn_relu_dropout_cat -- the same library calls with the same arguments, so the same bytes. Every segment f32 or
+// bf16 on its own, dx_s of x_s's type; a segment that does not require a gradient gets none (a NULL pointer in the call, an
+// undefined tensor out of the node).
 struct BnCatBackward : public torch::autograd::Node {
     std::vector<Tensor> xs;
     std::vector<uint32_t> x_versions;
@@ -1505,26 +1506,27 @@ struct BnCatBackward : public torch::autograd::Node {
                         "segment ", k, ")");
         const DevGuard device_guard((int)gamma_.device().index());
         std::vector<Tensor> dxs(nseg);
-        const float* px[8];
-        float* pdx[8];
-        int cs[8];
+        const void* px[8];
+        void* pdx[8];
+        int cs[8], bf[8];
         bool any = false;
         for (int k = 0; k < nseg; ++k) {
-            px[k] = xs[k].data_ptr<float>();
+            px[k] = xs[k].data_ptr();
+            bf[k] = is_bf16(xs[k]) ? 1 : 0;
             cs[k] = (int)xs[k].size(1);
             pdx[k] = nullptr;
             if (task_should_compute_output(k)) {
                 dxs[k] = at::empty_like(xs[k]);
-                pdx[k] = dxs[k].data_ptr<float>();
+                pdx[k] = dxs[k].data_ptr();
                 any = true;
             }
         }
         Tensor dgb = at::empty({2, (int64_t)c}, gamma_.options());
         void* st = cur_stream(gamma_);
         Tensor& ws = scratch(mccnn_bn_act_workspace_bytes(n, c), gamma_, st);
-        check(mccnn_bn_act_cat_bwd(px, cs, nseg, gy.data_ptr(), y_bf16 ? 1 : 0, n, gamma_.data_ptr<float>(), beta_.data_ptr<float>(),
-                                   saved.data_ptr<float>(), relu, thr, scale, seed, any ? pdx : nullptr, dgb.data_ptr<float>(),
-                                   dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
+        check(mccnn_bn_act_cat_bwd_rows(px, bf, cs, nseg, gy.data_ptr(), y_bf16 ? 1 : 0, n, gamma_.data_ptr<float>(),
+                                        beta_.data_ptr<float>(), saved.data_ptr<float>(), relu, thr, scale, seed, any ? pdx : nullptr,
+                                        dgb.data_ptr<float>(), dgb.data_ptr<float>() + c, ws.data_ptr(), (size_t)ws.numel(), st),
               "bn_relu_dropout_cat_grad");
         torch::autograd::variable_list out(nseg + 2);
         for (int k = 0; k < nseg; ++k) out[k] = dxs[k];
@@ -1535,24 +1537,26 @@ struct BnCatBackward : public torch::autograd::Node {
     void release_variables() override { xs.clear(); gamma_.reset(); beta_.reset(); saved.reset(); }
 };
 
-// out_type: -1 / 0 float32, 1 bfloat16. The caller (dense_glue._bn_cat_args) has checked the arguments; what is looked at
+// out_type: 0 float32, 1 bfloat16, -1 what torch.cat of the segments has (bfloat16 iff every segment is). The caller (dense_glue._bn_cat_args) has checked the arguments; what is looked at
 // here again is what this function itself relies on.
 Tensor bn_relu_drop_cat(const std::vector<Tensor>& xs, const Tensor& gamma, const Tensor& beta, const Tensor& mov_mean,
                         const Tensor& mov_var, bool training, bool relu, unsigned long long thr, double scale, unsigned seed,
                         double momentum, double eps, int out_type) {
     TORCH_CHECK(!xs.empty() && (int)xs.size() <= mccnn_bn_act_cat_max_segments(), "bn_relu_drop_cat expects 1 to 8 segments");
-    TORCH_CHECK(out_type >= -1 && out_type <= 1, "bn_relu_drop_cat: out_type must be -1 / 0 (float32) or 1 (bfloat16)");
-    const bool y_bf16 = out_type == 1;
+    TORCH_CHECK(out_type >= -1 && out_type <= 1, "bn_relu_drop_cat: out_type must be -1 (the segments'), 0 (float32) or 1 (bfloat16)");
+    bool all_bf16 = true;
     int64_t c64 = 0;
     bool need_grad = at::GradMode::is_enabled() && (gamma.requires_grad() || beta.requires_grad());
     for (const Tensor& x : xs) {
-        check_dev(x, at::kFloat, "segment");
+        check_dev(x, is_bf16(x) ? at::kBFloat16 : at::kFloat, "segment");
+        all_bf16 = all_bf16 && is_bf16(x);
         TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) == xs[0].size(0) && x.device() == xs[0].device(),
                     "bn_relu_drop_cat expects segments with dimensions (n, c_s) on one device, n, c_s >= 1");
         c64 += x.size(1);
         need_grad = need_grad || (at::GradMode::is_enabled() && x.requires_grad());
     }
     TORCH_CHECK(xs[0].size(0) < (1ll << 31) && c64 < (1ll << 31), "bn_relu_drop_cat: x too large");
+    const bool y_bf16 = out_type == 1 || (out_type == -1 && all_bf16);
     TORCH_CHECK(!y_bf16 || c64 % 2 == 0, "bn_relu_drop_cat: bfloat16 rows need an even number of columns");
     for (const Tensor* t : {&gamma, &beta, &mov_mean, &mov_var}) {
         check_dev(*t, at::kFloat, "per-column tensor");
@@ -1566,15 +1570,15 @@ Tensor bn_relu_drop_cat(const std::vector<Tensor>& xs, const Tensor& gamma, cons
         at::AutoDispatchBelowADInplaceOrView guard;
         y = at::empty({(int64_t)n, c64}, gamma.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
         if (training) saved = at::empty({2, c64}, gamma.options());
-        const float* px[8];
-        int cs[8];
-        for (int k = 0; k < nseg; ++k) { px[k] = xs[k].data_ptr<float>(); cs[k] = (int)xs[k].size(1); }
+        const void* px[8];
+        int cs[8], bf[8];
+        for (int k = 0; k < nseg; ++k) { px[k] = xs[k].data_ptr(); bf[k] = is_bf16(xs[k]) ? 1 : 0; cs[k] = (int)xs[k].size(1); }
         void* st = cur_stream(gamma);
         Tensor& ws = scratch(training ? mccnn_bn_act_workspace_bytes(n, c) : 0, gamma, st);
-        check(mccnn_bn_act_cat_fwd(px, cs, nseg, n, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
-                                   mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
-                                   training ? thr : mccnn::kBnDropAll, training ? (float)scale : 1.f, seed, y.data_ptr(), y_bf16 ? 1 : 0,
-                                   training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
+        check(mccnn_bn_act_cat_fwd_rows(px, bf, cs, nseg, n, gamma.data_ptr<float>(), beta.data_ptr<float>(), mov_mean.data_ptr<float>(),
+                                        mov_var.data_ptr<float>(), (float)momentum, (float)eps, training ? 1 : 0, relu ? 1 : 0,
+                                        training ? thr : mccnn::kBnDropAll, training ? (float)scale : 1.f, seed, y.data_ptr(),
+                                        y_bf16 ? 1 : 0, training ? saved.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), st),
               "bn_relu_dropout_cat");
     }
     if (need_grad) {

@@ -198,26 +198,37 @@ def _bn_act_run(x, gamma, beta, movingMean, movingVar, training, relu, seed, mom
 
 # ---------------------------------------------------------------------------------------------
 # ... over a column-wise concatenation that is never materialised (include/mccnn.h "... OVER A CONCATENATION"): up to 8
-# float32 segments [n, c_s]; y, and everything per column, at width C = sum c_s.
+# segments [n, c_s], each float32 or bfloat16; y, and everything per column, at width C = sum c_s.
 BN_CAT_MAX = 8
+
+
+def _bn_cat_out_dtype(dtypes, outDtype=None):
+    """y's type over segments of the types `dtypes`: outDtype where it is given, else what torch.cat of them would return --
+    bfloat16 iff every segment is bfloat16, float32 otherwise."""
+    if outDtype is not None:
+        return outDtype
+    return torch.bfloat16 if all(d == torch.bfloat16 for d in dtypes) else torch.float32
 
 
 def _bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype=None, *, training=True):
     """Checks of bn_relu_dropout_cat (nothing is launched before they pass) -> (keep threshold, keep scale). xs: a list or
-    tuple of 1 .. 8 float32 contiguous (n, c_s) tensors on one device; outDtype: None / torch.float32, or torch.bfloat16;
-    everything per column is float32 (C,). training=False adds the eval form's check, behind all the others."""
+    tuple of 1 .. 8 contiguous (n, c_s) tensors on one device, each float32 or bfloat16; outDtype: None (_bn_cat_out_dtype:
+    bfloat16 iff every segment is), torch.float32 or torch.bfloat16; everything per column is float32 (C,). training=False
+    adds the eval form's check, behind all the others."""
     op = "bn_relu_dropout_cat"
     thr, scale = _drop_args(op, keepProb, seed, outDtype)
     _req(isinstance(xs, (list, tuple)) and 1 <= len(xs) <= BN_CAT_MAX, "%s expects a list of 1 to %d segments" % (op, BN_CAT_MAX))
     for x in xs:
-        _req(isinstance(x, torch.Tensor) and x.dtype == torch.float32, "%s: every segment must be a float32 tensor" % op)
+        _req(isinstance(x, torch.Tensor) and x.dtype in (torch.float32, torch.bfloat16),
+             "%s: every segment must be a float32 (or bfloat16 storage) tensor" % op)
         _req(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1, "%s expects segments with dimensions (n, c_s), n, c_s >= 1" % op)
         _req(x.shape[0] == xs[0].shape[0], "%s: the segments must have the same number of rows" % op)
         _req(x.is_contiguous(), "%s: every segment must be contiguous" % op)
         _req(x.device == xs[0].device, "%s: the segments must be on one device" % op)
     n, c = xs[0].shape[0], sum(x.shape[1] for x in xs)
     _req(n < (1 << 31) and c < (1 << 31), "%s: x too large" % op)
-    _req(c % 2 == 0 or outDtype in (None, torch.float32), "%s: bfloat16 rows need an even number of columns" % op)
+    _req(c % 2 == 0 or _bn_cat_out_dtype([x.dtype for x in xs], outDtype) == torch.float32,
+         "%s: bfloat16 rows need an even number of columns" % op)
     for t, name in ((gamma, "gamma"), (beta, "beta"), (movingMean, "moving_mean"), (movingVar, "moving_variance")):
         _req(isinstance(t, torch.Tensor) and t.dtype == torch.float32, "%s: %s must be a float32 tensor" % (op, name))
         _req(t.is_contiguous(), "%s: %s must be contiguous" % (op, name))
@@ -232,16 +243,18 @@ def _bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtyp
 
 
 def _cat_table(ts):
-    """The host arrays of a call: (pointers, widths) of the tensors ts (None: a NULL pointer, width 0)."""
+    """The host arrays of a call: (pointers, bf16 flags, widths) of the tensors ts (None: a NULL pointer, flag and width 0)."""
     import ctypes as C
-    return ((C.c_void_p * len(ts))(*[ptr(t) for t in ts]), (C.c_int * len(ts))(*[0 if t is None else t.shape[1] for t in ts]))
+    return ((C.c_void_p * len(ts))(*[ptr(t) for t in ts]),
+            (C.c_int * len(ts))(*[int(t is not None and t.dtype == torch.bfloat16) for t in ts]),
+            (C.c_int * len(ts))(*[0 if t is None else t.shape[1] for t in ts]))
 
 
 def _bn_cat_fwd(lib, xs, gamma, beta, movingMean, movingVar, momentum, epsilon, training, relu, thr, scale, seed, y, saved, ws):
-    px, cs = _cat_table(xs)
-    check(lib.mccnn_bn_act_cat_fwd(px, cs, len(xs), xs[0].shape[0], ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar), momentum,
-                                   epsilon, training, relu, thr, scale, seed, ptr(y), int(y.dtype == torch.bfloat16), ptr(saved),
-                                   ptr(ws), 0 if ws is None else ws.numel(), stream_handle()), "bn_relu_dropout_cat")
+    px, bf, cs = _cat_table(xs)
+    check(lib.mccnn_bn_act_cat_fwd_rows(px, bf, cs, len(xs), xs[0].shape[0], ptr(gamma), ptr(beta), ptr(movingMean), ptr(movingVar),
+                                        momentum, epsilon, training, relu, thr, scale, seed, ptr(y), int(y.dtype == torch.bfloat16),
+                                        ptr(saved), ptr(ws), 0 if ws is None else ws.numel(), stream_handle()), "bn_relu_dropout_cat")
 
 
 class _BnReluDropoutCat(torch.autograd.Function):
@@ -250,7 +263,7 @@ class _BnReluDropoutCat(torch.autograd.Function):
         lib = _lib.load()
         n, c = xs[0].shape[0], gamma.shape[0]
         xd, gd, bd = tuple(x.detach() for x in xs), gamma.detach(), beta.detach()
-        y = torch.empty((n, c), dtype=outDtype or torch.float32, device=gamma.device)
+        y = torch.empty((n, c), dtype=_bn_cat_out_dtype([x.dtype for x in xs], outDtype), device=gamma.device)
         saved = torch.empty((2, c), dtype=torch.float32, device=gamma.device)
         ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), gamma.device)
         _bn_cat_fwd(lib, xd, gd, bd, movingMean, movingVar, momentum, epsilon, 1, int(relu), thr, scale, seed, y, saved, ws)
@@ -271,23 +284,26 @@ class _BnReluDropoutCat(torch.autograd.Function):
         dxs = tuple(torch.empty_like(x) if need[11 + k] else None for k, x in enumerate(xs))
         dgb = torch.empty((2, c), dtype=torch.float32, device=gamma.device)
         ws = _ws(lib.mccnn_bn_act_workspace_bytes(n, c), gamma.device)
-        px, cs = _cat_table(xs)
-        pdx = _cat_table(dxs)[0] if any(d is not None for d in dxs) else None
-        check(lib.mccnn_bn_act_cat_bwd(px, cs, len(xs), ptr(gy), int(ydt == torch.bfloat16), n, ptr(gamma), ptr(beta), ptr(saved), relu,
-                                       thr, scale, seed, pdx, ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(), stream_handle()),
-              "bn_relu_dropout_cat_grad")
+        px, bf, cs = _cat_table(xs)
+        pdx = _cat_table(dxs)[0] if any(d is not None for d in dxs) else None   # (dx_s is empty_like(x_s): x_s's type)
+        check(lib.mccnn_bn_act_cat_bwd_rows(px, bf, cs, len(xs), ptr(gy), int(ydt == torch.bfloat16), n, ptr(gamma), ptr(beta),
+                                            ptr(saved), relu, thr, scale, seed, pdx, ptr(dgb[0]), ptr(dgb[1]), ptr(ws), ws.numel(),
+                                            stream_handle()), "bn_relu_dropout_cat_grad")
         return (dgb[0] if need[0] else None, dgb[1] if need[1] else None) + (None,) * 9 + dxs
 
 
 def bn_relu_dropout_cat(xs, gamma, beta, movingMean, movingVar, training, relu=True, keepProb=None, seed=0, momentum=0.99,
                         epsilon=1e-3, outDtype=None):
     """bn_relu_dropout over torch.cat(xs, 1) in one library op, without the concatenation: xs a list or tuple of 1 .. 8
-    float32 contiguous (n, c_s) tensors, gamma, beta and the moving statistics (C,), C = sum c_s; y is (n, C), float32 or
-    (outDtype=torch.bfloat16, an even C) bfloat16. The definition, the moving statistics, the mask -- element (row, column
+    contiguous (n, c_s) tensors, each float32 or bfloat16 on its own, gamma, beta and the moving statistics (C,), C = sum c_s;
+    y is (n, C) of type outDtype -- None: what torch.cat(xs, 1) has, bfloat16 iff every segment is bfloat16 and float32
+    otherwise; a bfloat16 y needs an even C. A bfloat16 segment is widened exactly on load, the statistics and all
+    arithmetic are float32, and its gradient is bfloat16, rounded to nearest even at the store. The definition, the moving statistics, the mask -- element (row, column
     of the concatenation) -- and the eval form are bn_relu_dropout's; differentiable (once) with respect to every segment,
     gamma and beta: each segment that requires a gradient gets a contiguous one of its own, the others None. The launches
-    are those of bn_relu_dropout on the concatenated tensor, and wherever the library takes the same plan for both (C % 4 != 0,
-    or every c_s % 4 == 0 and every tensor on a 16-byte boundary) so are the bytes."""
+    are those of bn_relu_dropout on the concatenated float32 tensor, and wherever the library takes the same plan for both
+    (C % 4 != 0, or every c_s % 4 == 0 and every tensor on a 16-byte boundary -- 8 bytes do for a bfloat16 segment) so are the
+    bytes, a bfloat16 segment's gradient being that op's slice rounded to bfloat16."""
     return _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, momentum, epsilon, outDtype,
                        *_bn_cat_args(xs, gamma, beta, movingMean, movingVar, keepProb, seed, outDtype, training=training))
 
@@ -298,7 +314,7 @@ def _bn_cat_run(xs, gamma, beta, movingMean, movingVar, training, relu, seed, mo
         return _BnReluDropoutCat.apply(gamma, beta, movingMean, movingVar, bool(relu), thr, scale, seed, float(momentum),
                                        float(epsilon), outDtype, *xs)
     lib = _lib.load()
-    y = torch.empty((xs[0].shape[0], gamma.shape[0]), dtype=outDtype or torch.float32, device=gamma.device)
+    y = torch.empty((xs[0].shape[0], gamma.shape[0]), dtype=_bn_cat_out_dtype([x.dtype for x in xs], outDtype), device=gamma.device)
     _bn_cat_fwd(lib, tuple(x.detach() for x in xs), gamma.detach(), beta.detach(), movingMean, movingVar, float(momentum),
                 float(epsilon), 0, int(bool(relu)), BN_DROP_ALL, 1.0, seed, y, None, None)
     return y

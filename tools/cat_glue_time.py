@@ -1,7 +1,7 @@
 """The dense glue over a concatenation (VariableStore(fused=True, fusedCat=True), dense_glue.bn_relu_dropout_cat) against
 the path it replaces -- torch.cat, the contiguous op, column slices of its gradient made contiguous -- measured in ONE
 process with the two settings alternating block by block; the off path is the yardstick:
-    python tools/cat_glue_time.py [--part a|b|both] [--batch 16] [--points 8192] [--k 32] [--steps 200]   (on the GPU box)
+    python tools/cat_glue_time.py [--part a|b|both] [--batch 16] [--points 8192] [--k 32] [--steps 200] [--bf16-rows]   (on the GPU box)
 
 (a) Per glue shape: MCSeg's six blocks over a concatenation at the given size (rows per level from the built hierarchy),
     forward + backward through batch_norm_RELU_drop_out with fused_ on, fusedCat_ off against on. The segments' gradients
@@ -9,6 +9,10 @@ process with the two settings alternating block by block; the off path is the ya
     best of five blocks of 50 calls, worst in brackets; library launches per call (mccnn_debug_launch_count).
 (b) The whole training step of examples/mcseg.py with every fused switch on, fusedCat off against on: five alternating
     blocks of --steps steps; a gain only if EVERY on block is below EVERY off block.
+--bf16-rows: MCSeg(rows=torch.bfloat16), the cfg3 form. The depth-wise layers then return bf16 rows, so (a) times the six
+    blocks with the segment types they have in that network -- bf16 throughout but for the f32 block of Conv_1 in
+    DeConv_1_Reduce_In_BN -- and the off path is torch.cat of the typed segments (which widens a mixed list), the contiguous op
+    and autograd's slices cast back; (b) is the step of examples/mcseg.py --bf16-rows.
 """
 import argparse
 import os
@@ -27,22 +31,27 @@ from mcseg import MCSeg  # noqa: E402
 dev = torch.device("cuda", 0)
 
 
-def cat_shapes(levels, k):
-    """(block name, rows, segment widths) of MCSeg's six blocks over a concatenation."""
-    return [("Reduce_Pool_2_In_BN", levels[1], (2 * k, 2 * k)), ("Reduce_Pool_3_In_BN", levels[2], (4 * k, 4 * k)),
-            ("Up_3_4_BN", levels[3], (8 * k, 8 * k)), ("DeConv_3_Reduce_In_BN", levels[2], (16 * k, 4 * k, 4 * k)),
-            ("DeConv_2_Reduce_In_BN", levels[1], (8 * k, 2 * k, 2 * k)), ("DeConv_1_Reduce_In_BN", levels[0], (4 * k, 8 * k, k))]
+def cat_shapes(levels, k, bf16_rows=False):
+    """(block name, rows, segment widths, segment types, y's type) of MCSeg's six blocks over a concatenation; bf16_rows: the
+    types of MCSeg(rows=torch.bfloat16) -- every segment a depth-wise layer's output but the last of DeConv_1_Reduce_In_BN
+    (Conv_1), y float32 into a matmul and bf16 into the depth-wise Up_3_4."""
+    f, b = torch.float32, torch.bfloat16 if bf16_rows else torch.float32
+    return [("Reduce_Pool_2_In_BN", levels[1], (2 * k, 2 * k), (b, b), f), ("Reduce_Pool_3_In_BN", levels[2], (4 * k, 4 * k), (b, b), f),
+            ("Up_3_4_BN", levels[3], (8 * k, 8 * k), (b, b), b), ("DeConv_3_Reduce_In_BN", levels[2], (16 * k, 4 * k, 4 * k), (b, b, b), f),
+            ("DeConv_2_Reduce_In_BN", levels[1], (8 * k, 2 * k, 2 * k), (b, b, b), f),
+            ("DeConv_1_Reduce_In_BN", levels[0], (4 * k, 8 * k, k), (b, b, f), f)]
 
 
-def time_block(n, widths, calls=50, blocks=5):
+def time_block(n, widths, types=None, out=None, calls=50, blocks=5):
     """-> {fusedCat: (best us, worst us, library launches per call)} of forward + backward of one block, alternating."""
     lib = _lib.load()
-    xs = [(torch.randn(n, w, device=dev) * 2 + 3).requires_grad_(True) for w in widths]
-    dy = torch.randn(n, sum(widths), device=dev)
+    types = types or (torch.float32,) * len(widths)
+    xs = [(torch.randn(n, w, device=dev) * 2 + 3).to(t).requires_grad_(True) for w, t in zip(widths, types)]
+    dy = torch.randn(n, sum(widths), device=dev).to(out or torch.float32)
     stores = {c: U.VariableStore(dev, fused=True, fusedCat=c) for c in (False, True)}
 
     def call(st):
-        y = U.batch_norm_RELU_drop_out("T", xs, True, False, None, st)
+        y = U.batch_norm_RELU_drop_out("T", xs, True, False, None, st, outDtype=out)
         for x in xs:
             x.grad = None
         y.backward(dy)
@@ -67,14 +76,14 @@ def time_block(n, widths, calls=50, blocks=5):
     return {c: (min(times[c]), max(times[c]), launches[c]) for c in (False, True)}
 
 
-def part_a(levels, k):
+def part_a(levels, k, bf16_rows=False):
     print("(a) one block over a concatenation, forward + backward, us per call: best of 5 alternating blocks of 50 calls [worst]")
     print("| block | n | segments | fusedCat off us | on us | off / on | launches off | on | every on block below every off block |")
     print("|---|---|---|---|---|---|---|---|---|")
-    for name, n, widths in cat_shapes(levels, k):
-        r = time_block(n, widths)
+    for name, n, widths, types, out in cat_shapes(levels, k, bf16_rows):
+        r = time_block(n, widths, types, out if bf16_rows else None)
         print("| %s | %d | %s | %.1f [%.1f] | %.1f [%.1f] | %.2f | %.1f | %.1f | %s |" % (
-            name, n, "+".join(str(w) for w in widths), r[False][0], r[False][1], r[True][0], r[True][1], r[False][0] / r[True][0],
+            name, n, "+".join("%d%s" % (w, " bf16" if t == torch.bfloat16 else "") for w, t in zip(widths, types)), r[False][0], r[False][1], r[True][0], r[True][1], r[False][0] / r[True][0],
             r[False][2], r[True][2], "yes" if r[True][1] < r[False][0] else "no"))
 
 
@@ -122,19 +131,21 @@ def main():
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--bf16-rows", action="store_true", help="MCSeg(rows=torch.bfloat16): bf16 and mixed-type segments")
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
     numCats = 4
-    net = MCSeg(1, args.batch, args.k, numCats, NUM_PARTS, dev, fused=True, fusedCat=False, fusedLinear=True, fusedLoss=True)
+    net = MCSeg(1, args.batch, args.k, numCats, NUM_PARTS, dev, fused=True, fusedCat=False, fusedLinear=True, fusedLoss=True,
+                rows=torch.bfloat16 if args.bf16_rows else None)
     P, Bi, F, N = synthetic_normals_batch(args.batch, args.points, rng, dev)
     batch = (P, Bi, F, (Bi % numCats).reshape(-1), part_labels(N))
     with torch.no_grad():
         net(*batch[:4], True)   # creates the variables
     levels = [int(p.shape[0]) for p in net.lastHierarchy.points_]
-    print("MCSeg %d x %d points, k = %d: levels %s" % (args.batch, args.points, args.k, levels))
+    print("MCSeg %d x %d points, k = %d%s: levels %s" % (args.batch, args.points, args.k, ", bf16 rows" if args.bf16_rows else "", levels))
     if args.part in ("a", "both"):
-        part_a(levels, args.k)
+        part_a(levels, args.k, args.bf16_rows)
     if args.part in ("b", "both"):
         part_b(net, batch, steps=args.steps)
 
