@@ -725,12 +725,22 @@ const int* mccnn_geometry_cap(const mccnn_geometry_t* g);
  * mccnn_geometry_records: the `avg` the geometry's records hold (0 / 1) and their device address (e_capacity records, E
  *   valid), or -1 and NULL when it has none. Records a row plan's build evaluated into an attached buffer are reported too.
  * mccnn_conv_uses_records: 1 when a layer of this shape and `avg` can read the geometry's records -- a combin layer with one
- *   input feature on the factored kernels, records of that `avg` present. Such a layer passes flags bit 2 to
- *   mccnn_conv_prepare / _forward / _backward. */
+ *   input feature on the factored kernels, records of that `avg` present. Such a layer passes MCCNN_CONV_READS_RECORDS to
+ *   mccnn_conv_prepare / _forward / _backward.
+ * mccnn_conv_rows_shape (ABI 31): THE rule that sends a layer to the row-per-lane depth-wise kernels (1) or the edge-streaming
+ *   ones (0), for a list of e edges over `rows` rows (the centres; backward != 0: the n_points points) whose feature rows
+ *   start at `feats`. mccnn_conv_* decide with it, and a caller that runs the layers op by op asks it instead of restating
+ *   it (MCConvModule._rows_shape). A pure host function: only the VALUE of `feats` is looked at (16-byte alignment), nothing
+ *   is launched, no GPU is needed. It honours MCCNN_ROW_KERNELS and MCCNN_DEBUG=rows_min_degree / rows_force (read once per
+ *   process) and bits 0-1 of mccnn_debug_conv_impl. The thresholds: rows_shape() in csrc/exec.hip; their measurements: DESIGN 5b.
+ * mccnn_conv_unsorted_max_points (ABI 31): levels of up to this many points whose layer takes the row kernels in both
+ *   directions have their feature rows read where they lie, unsorted (MCCNN_DEBUG=unsorted_max_points, default 32768). */
 size_t mccnn_geometry_records_bytes(int e_capacity);
 int mccnn_geometry_want_records(mccnn_geometry_t* g, int avg);
 int mccnn_geometry_records(const mccnn_geometry_t* g, const void** records);
 int mccnn_conv_uses_records(const mccnn_geometry_t* g, int num_in_feats, int num_out_feats, int combin, int avg);
+int mccnn_conv_rows_shape(int combin, int num_in_feats, const void* feats, int rows, int n_points, int e, int backward);
+int mccnn_conv_unsorted_max_points(void);
 /* E, or -1 while the count pass has not retired (wait_us: 0 = look once, < 0 = wait, > 0 = wait at most that long). */
 int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
 /* out[0..7]: device addresses of sortPts [n,3], sortBatchs [n], cellIndexs [B,nc,nc,nc,2], index_new_pos [n], its
@@ -738,8 +748,12 @@ int mccnn_geometry_edges(mccnn_geometry_t* g, int wait_us);
  * e_capacity, E (-1 = not read yet), batch_size; out[14]: device word holding E; out[15]: 1 = owns its grid. */
 int mccnn_geometry_info(const mccnn_geometry_t* g, long long out[16]);
 /* Further pieces a geometry keeps for the layers over it, each in a caller-provided buffer (256-byte aligned) that lives
- * as long as the geometry: what = 1 forward row plan, 2 transposed row plan, 4 transposed neighbour list, 8 per-edge
- * records. mccnn_conv_prepare says which are missing and how large they are. */
+ * as long as the geometry: what = MCCNN_PIECE_PLAN_FWD (1) forward row plan, _PLAN_TR (2) transposed row plan, _TLIST (4)
+ * transposed neighbour list, _RECORDS (8) per-edge records. mccnn_conv_prepare says which are missing and how large they are. */
+#define MCCNN_PIECE_PLAN_FWD 1
+#define MCCNN_PIECE_PLAN_TR 2
+#define MCCNN_PIECE_TLIST 4
+#define MCCNN_PIECE_RECORDS 8
 int mccnn_geometry_attach(mccnn_geometry_t* g, int what, void* buffer, size_t bytes);
 /* Pieces built ahead of the layers that need them (the transposed list and the transposed row plan of a depth-wise
  * layer's backward pass on a side stream, under the forward passes): piece_bytes waits for E and gives the size of the
@@ -764,16 +778,20 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
 /* One layer over a geometry: SpatialConv / SpatialConvGrad INCLUDING sort_features / its gradient
  * (MCConvModuleSrc:35-45,70-81). feats [n, num_in_feats] and feat_grad are rows of the UNSORTED points (f32, or bf16
  * with bf16 != 0: depth-wise layers, num_in_feats % 8 == 0); out [m, combin ? num_out_feats : num_in_feats].
- * flags: bit 0 = keep the forward state for the backward pass, bit 1 = deterministic feature gradient of combin layers
- * with 2..4 input features (gathered through the transposed list instead of float atomics), bit 2 = the layer reads the
- * geometry's per-edge records (only where mccnn_conv_uses_records says 1, and in all three calls of the layer alike): the
+ * flags: MCCNN_CONV_KEEP_STATE (bit 0) = keep the forward state for the backward pass, MCCNN_CONV_DETERMINISTIC (bit 1) =
+ * deterministic feature gradient of combin layers with 2..4 input features (gathered through the transposed list instead of
+ * float atomics), MCCNN_CONV_READS_RECORDS (bit 2) = the layer reads the geometry's per-edge records (only where
+ * mccnn_conv_uses_records says 1, and in all three calls of the layer alike): the
  * forward pass neither evaluates nor stores records, `saved` holds the sorted rows and the per-centre sums alone (16 bytes per
  * edge less), and the backward pass reads the same records (or evaluates them afresh, should a row plan of the other `avg`
  * have replaced them in between).
  * prepare (forward or backward): waits for E, then reports need_mask / need_bytes[k] (pieces to attach first, bit k),
  * the scratch bytes of the call and -- forward -- the bytes of `saved`, which the caller keeps from forward to
- * backward (sorted feature rows + forward state). The kernel family is chosen as the Python op surface chooses it
- * (row-per-lane depth-wise kernels, factored one-feature kernels, edge streaming). */
+ * backward (sorted feature rows + forward state). The kernel family (row-per-lane depth-wise kernels, factored one-feature
+ * kernels, edge streaming) is decided once per call, by the rule mccnn_conv_rows_shape answers. */
+#define MCCNN_CONV_KEEP_STATE 1
+#define MCCNN_CONV_DETERMINISTIC 2
+#define MCCNN_CONV_READS_RECORDS 4
 int mccnn_conv_prepare(mccnn_geometry_t* g, const void* feats, int num_in_feats, int num_out_feats, int combin, int bf16,
                        int backward, int flags, int* need_mask, long long need_bytes[4], long long* ws_bytes,
                        long long* saved_bytes, int* edges);

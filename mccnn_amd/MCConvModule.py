@@ -10,6 +10,7 @@ Shape / attribute validation mirrors the OP_REQUIRES blocks of the reference wra
 raises InvalidArgumentError (the analogue of tf.errors.InvalidArgumentError).
 """
 import ctypes as C
+import functools
 import os
 import threading
 import time
@@ -331,11 +332,21 @@ def _transposed_neighbors(packed, n):
 
 
 #: depth-wise layers (numFeatures % 8 == 0) run the row-per-lane kernels over SELL layouts of the neighbour list
-#: (conv_rows.hip); False = the edge-streaming kernels of conv.hip for every layer
+#: (conv_rows.hip); False = the edge-streaming kernels of conv.hip for every layer (the tools flip it at run time)
 ROW_KERNELS = _env.flag("ROW_KERNELS")
-ROWS_MIN_DEGREE = _env.debug("rows_min_degree", 16.0)
-#: levels of up to this many points: the row kernels read the feature rows of the UNSORTED points in place (featIndex)
-UNSORTED_MAX_POINTS = _env.debug("unsorted_max_points", 32768)
+
+
+def _unsorted_max_points():
+    """UNSORTED_MAX_POINTS: levels of up to this many points have the row kernels read the feature rows of the UNSORTED points
+    in place (featIndex). The library's value (mccnn_conv_unsorted_max_points), asked once, then a plain module attribute."""
+    v = globals().get("UNSORTED_MAX_POINTS")
+    return v if v is not None else globals().setdefault("UNSORTED_MAX_POINTS", _lib.load().mccnn_conv_unsorted_max_points())
+
+
+def __getattr__(name):
+    if name == "UNSORTED_MAX_POINTS":
+        return _unsorted_max_points()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 class RowPlan:
@@ -459,29 +470,16 @@ def prefetch_rowplan(packed, transposed, stream, *args):
                 rec_e[1].record_stream(main)
 
 
+@functools.lru_cache(maxsize=4096)
+def _rows_query(*args):  # (a step asks the same few again and again, and the call is ~1 us of a host-bound op-by-op step)
+    return bool(_lib.load().mccnn_conv_rows_shape(*args))
+
+
 def _rows_shape(combin, fin, feats, rows, e, backward=False):
-    """Row-per-lane kernels for this (layer, list)? Depth-wise rows of 8-feature blocks. Every list of <= 500 k edges: yes
-    (long rows are cut into pieces, lists of short rows put several slices into a workgroup). Forward on larger lists: see
-    below. Backward: the edge-streaming kernels keep
-    LARGE lists (> 500 k edges) unless the layer is wide and its rows long: their waves own equal edge ranges, while the
-    176-sum sweep of the row kernel, two waves per SIMD, has too few (slice, block) items on such a list to hide its
-    quantisation and its per-item reduction when the layer has <= 16 blocks, and pays set-up and window padding too often
-    below ~16 edges per point. Measured (rows against streaming, ms): BASELINE cfg3 Up_1_2 (128 features, 41 k points x
-    18.9 edges) 0.49 / 0.36, Conv_2 (64, 41 k x 25.4) 0.27 / 0.24, DeConv_1 (128, 131 k x 8.7) 0.54 / 0.42; the 100k room
-    (45 edges per point) 64 features 1.07 / 0.87, 128: 1.67 / 1.53, 256: 2.43 / 2.73; cfg3 Up_1_3 (256, 3 495 points x 386)
-    0.77 / 1.18; every list below 500 k edges: rows, by up to 6x on the coarse levels."""
-    if not (ROW_KERNELS and _DEBUG_IMPL == 0 and (not combin) and fin % 8 == 0 and e > 0 and rows > 0
-            and (feats.data_ptr() & 15) == 0):
-        return False
-    if e <= 500000:
-        return True
-    if not backward:
-        # the row kernel walks windows of 1 024 centres sorted by row length, the streaming kernel the centres in their
-        # cell-coherent order: on a large list whose gathered rows do not fit the L2s (>= 64 k points) and whose layer is
-        # narrow (<= 16 blocks: little arithmetic per gathered byte) the better locality wins -- room, 64 features 0.38 /
-        # 0.32 ms; cfg3 Pool_1 0.16 / 0.12, DeConv_1 0.24 / 0.21; the other way round on 41 k points (Conv_2 0.13 / 0.15)
-        return not (fin <= 128 and feats.shape[0] >= 65536)
-    return fin >= 256 and e / float(rows) >= ROWS_MIN_DEGREE
+    """Row-per-lane kernels for this (layer, list)? The library's rule (mccnn_conv_rows_shape: rows_shape() in csrc/exec.hip,
+    measurements in DESIGN.md 5b), kept by its integer arguments, behind the two switches that live here: ROW_KERNELS and bit 2
+    of debug_conv_impl's mask (which drops the kept answers: bits 0-1 of that mask move the library's rule)."""
+    return bool(ROW_KERNELS) and not _DEBUG_IMPL & 4 and _rows_query(int(bool(combin)), fin, feats.data_ptr(), rows, feats.shape[0], e, int(backward))
 
 
 def clear_caches():
@@ -519,6 +517,7 @@ def debug_conv_impl(mask):
     global _DEBUG_IMPL
     prev = _DEBUG_IMPL
     _DEBUG_IMPL = int(mask)
+    _rows_query.cache_clear()
     _lib.load().mccnn_debug_conv_impl((int(mask) & 3) | 16)  # bit 4: bits 0-1 only
     return prev
 
@@ -1460,7 +1459,7 @@ class _SpatialConv(torch.autograd.Function):
             # back in the same order -- two launches and two allocations less per convolution. Large levels keep the
             # sorted copy: its gathers follow the grid's spatial order.
             e_ = inPDFs.shape[0]
-            unsorted = (featIndex is not None and feats.shape[0] <= UNSORTED_MAX_POINTS and e_ > 0 and inSamplePts.shape[0] > 0
+            unsorted = (featIndex is not None and feats.shape[0] <= _unsorted_max_points() and e_ > 0 and inSamplePts.shape[0] > 0
                         and _rows_shape(combin, feats.shape[1], feats, inSamplePts.shape[0], e_)
                         and _rows_shape(combin, feats.shape[1], feats, feats.shape[0], e_, backward=True))
             if not unsorted:

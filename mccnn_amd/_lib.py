@@ -122,6 +122,8 @@ SIGNATURES = {
     "mccnn_geometry_want_records": (_i, [_vp, _i]),
     "mccnn_geometry_records": (_i, [_vp, _vp]),
     "mccnn_conv_uses_records": (_i, [_vp, _i, _i, _i, _i]),
+    "mccnn_conv_rows_shape": (_i, [_i, _i, _vp, _i, _i, _i, _i]),
+    "mccnn_conv_unsorted_max_points": (_i, []),
     "mccnn_geometry_edges": (_i, [_vp, _i]),
     "mccnn_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "mccnn_geometry_attach": (_i, [_vp, _i, _vp, _sz]),

@@ -129,7 +129,7 @@ struct mccnn_geometry {
 
 namespace {
 
-enum { NEED_PLAN_FWD = 1, NEED_PLAN_TR = 2, NEED_TLIST = 4, NEED_RECORDS = 8 };
+enum { NEED_PLAN_FWD = MCCNN_PIECE_PLAN_FWD, NEED_PLAN_TR = MCCNN_PIECE_PLAN_TR, NEED_TLIST = MCCNN_PIECE_TLIST, NEED_RECORDS = MCCNN_PIECE_RECORDS };
 
 struct GeoLayout {
     size_t s_pts, s_bids, cells, new_idx, inv_idx, start, packed, pdfs, total, order, ws, ws_bytes, total_bytes;
@@ -204,9 +204,10 @@ bool row_kernels_on() { static const bool on = env_flag("MCCNN_ROW_KERNELS", tru
 float rows_min_degree() { static const float d = (float)debug_float("rows_min_degree", 16.0); return d; }
 int unsorted_max_points() { static const int v = debug_int("unsorted_max_points", 32768); return v; }
 
-// Row-per-lane kernels for this (layer, list, direction)? The measured rule of the Python op surface
-// (MCConvModule._rows_shape): every list of <= 500 k edges; forward of larger lists unless the layer is narrow and the
-// gathered rows miss the L2s; backward of larger lists only for wide layers with long rows.
+// Row-per-lane kernels for this (layer, list, direction)? THE rule: the executor below and, through mccnn_conv_rows_shape,
+// the Python op surface (MCConvModule._rows_shape) both ask it. Every list of <= 500 k edges; forward of larger lists unless
+// the layer is narrow and the gathered rows miss the L2s; backward of larger lists only for wide layers with long rows
+// (the measurements behind each threshold: DESIGN.md 5b).
 bool rows_shape(bool combin, int fin, const void* feats, int rows, int n_points, int e, bool backward) {
     if (!row_kernels_on() || read_mask() != 0 || combin || fin % 8 != 0 || e <= 0 || rows <= 0 || (((uintptr_t)feats) & 15)) return false;
     static const int force = debug_int("rows_force", 0);  // A/B: 1 = rows wherever they apply
@@ -262,20 +263,47 @@ bool make_shape(Shape& s, int fin, int fout, int combin, int bf16) {
     return true;
 }
 
-// what the forward pass of a layer does with the feature rows
-struct FwdMode {
-    bool rows_fwd, rows_bwd, unsorted;
+// The route of one layer over one list: decided ONCE, by conv_route() from plain values, and read by requirements(),
+// mccnn_conv_forward() and mccnn_conv_backward() -- none of them looks at the shape, the flags or the feature pointer again
+// to pick a branch. A new route is a new value here.
+enum { FAM_STREAM, FAM_BF16, FAM_RECORDS };      // the kernels of a pass that does not take the row-per-lane ones:
+                                                 // edge streaming (factored for Fin = 1), its bf16 form, Fin = 1 reading records
+enum { TL_NONE, TL_IF_BUILT, TL_REQUIRED };      // the transposed list in a streaming backward pass
+struct ConvRoute {
+    bool rows_fwd, rows_bwd;  // row-per-lane kernels (rows_bwd: if the out-gradient allows it, rows_bwd_takes)
+    bool unsorted;            // both, on a small level: the rows are read where they lie (feat_index), none kept sorted
+    int family;               // FAM_*
+    bool f1;                  // the factored Fin = 1 kernels take the shape (the only ones that read records)
+    size_t rows_bytes;        // the feature rows in grid order: the head of `saved` unless `unsorted`
+    size_t state_bytes;       // the forward state behind them (0: none kept): (A, S) alone for FAM_RECORDS, else the full state
+    int tlist;                // TL_*
 };
-FwdMode fwd_mode(const mccnn_geometry* g, const Shape& s, const void* feats, int e) {
-    FwdMode f;
+ConvRoute conv_route(int n, int m, int e, const Shape& s, int flags, bool feats_aligned) {
+    ConvRoute r;
     // (the sorted copy of the rows lives in a 256-byte aligned buffer of this layer's own: only the unsorted mode reads
     // the caller's rows in place and depends on their alignment)
-    f.rows_fwd = rows_shape(s.combin, s.fin, nullptr, g->m, g->n, e, false);
-    f.rows_bwd = rows_shape(s.combin, s.fin, nullptr, g->n, g->n, e, true);
-    // small levels whose layer takes the row kernels in both directions: the rows are read where they lie (feat_index)
-    f.unsorted = g->n <= unsorted_max_points() && e > 0 && g->m > 0 && f.rows_fwd && f.rows_bwd && ((((uintptr_t)feats) & 15) == 0);
-    return f;
+    r.rows_fwd = rows_shape(s.combin, s.fin, nullptr, m, n, e, false);
+    r.rows_bwd = rows_shape(s.combin, s.fin, nullptr, n, n, e, true) && m > 0;
+    r.unsorted = n <= unsorted_max_points() && e > 0 && r.rows_fwd && r.rows_bwd && feats_aligned;
+    r.family = s.bf16 ? FAM_BF16 : (flags & MCCNN_CONV_READS_RECORDS) ? FAM_RECORDS : FAM_STREAM;
+    r.f1 = conv_f1_shape(s.fin, s.fout, s.combin);
+    r.rows_bytes = al((size_t)n * s.fin * s.elem);
+    r.state_bytes = 0;
+    if ((flags & MCCNN_CONV_KEEP_STATE) && !r.rows_fwd && r.family != FAM_BF16)
+        r.state_bytes = r.family == FAM_RECORDS && r.f1 ? (m > 0 && e > 0 ? conv_f1_state_bytes(m, s.fout) : 0)
+                                                         : mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin);
+    // depth-wise layers need the transposed list; combin layers with 2..4 input features gather their feature gradient
+    // through it when the caller asks for the deterministic form, or when the list exists already
+    const bool few = s.combin && s.fin >= 2 && s.fin <= 4;
+    r.tlist = e <= 0 ? TL_NONE : (!s.combin || (few && (flags & MCCNN_CONV_DETERMINISTIC))) ? TL_REQUIRED : few ? TL_IF_BUILT : TL_NONE;
+    return r;
 }
+ConvRoute conv_route(const mccnn_geometry* g, const Shape& s, const void* feats, int flags, int e) {
+    return conv_route(g->n, g->m, e, s, flags, (((uintptr_t)feats) & 15) == 0);
+}
+// The one input that arrives late: the out-gradient's alignment is not known when the call is prepared (requirements()
+// budgets for both answers).
+bool rows_bwd_takes(const ConvRoute& rt, const void* out_grad) { return rt.rows_bwd && (((uintptr_t)out_grad) & 15) == 0; }
 
 int plan_prepare(mccnn_geometry* g, int tr, int e) {
     Plan& p = g->plan[tr];
@@ -648,6 +676,11 @@ int mccnn_conv_uses_records(const mccnn_geometry_t* g, int num_in_feats, int num
     return (g->rec_avg == (avg ? 1 : 0) && conv_f1_shape(num_in_feats, num_out_feats, combin)) ? 1 : 0;
 }
 
+int mccnn_conv_rows_shape(int combin, int num_in_feats, const void* feats, int rows, int n_points, int e, int backward) {
+    return rows_shape(combin != 0, num_in_feats, feats, rows, n_points, e, backward != 0) ? 1 : 0;
+}
+int mccnn_conv_unsorted_max_points(void) { return unsorted_max_points(); }
+
 // (the uncapped entries are the capped ones with no cap, the capped ones the point ones with no point record, the point
 // ones the budget ones with no budget)
 int mccnn_geometry_build_budget(mccnn_geometry_t* g, const float* pts, const int* batch_ids, int n, const float* centres,
@@ -894,10 +927,10 @@ size_t mccnn_geometry_prebuild_batch_ws_bytes(mccnn_geometry_t* const* geoms, co
             long long b = 0, w = 0;
             if (mccnn_geometry_piece_bytes(g, bit, &b, &w) == 0 && (size_t)w > single) single = (size_t)w;
         }
-        if ((what[k] & 6) && !g->tl_built)
+        if ((what[k] & (NEED_PLAN_TR | NEED_TLIST)) && !g->tl_built)
             trs += transpose_small(e, g->n) ? al(plan_batch_tr_ws_bytes(g->n, e)) : al(mccnn_transpose_neighbors_workspace_bytes(g->n, e));
         for (int tr = 0; tr < 2; ++tr)
-            if ((what[k] & (tr ? 2 : 1)) && plan_large_batchable(tr ? g->n : g->m, e, g->n, tr, 0))
+            if ((what[k] & (tr ? NEED_PLAN_TR : NEED_PLAN_FWD)) && plan_large_batchable(tr ? g->n : g->m, e, g->n, tr, 0))
                 trs += al(plan_large_ws_bytes(tr ? g->n : g->m, e, g->n, tr, 0));
     }
     return al(single) + trs + 512;
@@ -999,22 +1032,22 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
         const int e = g->e;
         if (e <= 0 || e > g->e_cap) continue;   // (an overflowing list is rebuilt by its first layer: nothing to build ahead)
         const mccnn_geometry* go = grid_owner(g);
-        int rest = what[k] & 7;
+        int rest = what[k] & (NEED_PLAN_FWD | NEED_PLAN_TR | NEED_TLIST);
         if (nLay + 2 > MCCNN_PLAN_BATCH_MAX || nTr + 1 > MCCNN_PLAN_BATCH_MAX || nCh + 1 > MCCNN_PLAN_BATCH_MAX) {
             int rc = flush();
             if (rc) return rc;
         }
         const bool tl_room = g->tl_buf && g->tl_bytes >= tlist_bytes(g->n, e) && (long long)g->n <= 2048LL * 1024;
         // the transposed list: on its own (a combin layer's deterministic feature gradient) or under a small transposed plan
-        const bool tr_plan_small = (rest & 2) && plan_batchable(g->n, e, 1) && !(g->plan[1].built && g->plan[1].avg == avg);
-        if (((rest & 4) || tr_plan_small) && !g->tl_built && tl_room && (!(rest & 2) || tr_plan_small)) {
+        const bool tr_plan_small = (rest & NEED_PLAN_TR) && plan_batchable(g->n, e, 1) && !(g->plan[1].built && g->plan[1].avg == avg);
+        if (((rest & NEED_TLIST) || tr_plan_small) && !g->tl_built && tl_room && (!(rest & NEED_PLAN_TR) || tr_plan_small)) {
             int rc = batch_tlist(g, e);
             if (rc) return rc;
             g->tl_built = true;
         }
-        if (g->tl_built) rest &= ~4;
+        if (g->tl_built) rest &= ~NEED_TLIST;
         for (int tr = 0; tr < 2; ++tr) {
-            const int bit = tr ? 2 : 1;
+            const int bit = tr ? NEED_PLAN_TR : NEED_PLAN_FWD;
             if (!(rest & bit)) continue;
             Plan& p = g->plan[tr];
             if (p.built && p.avg == avg) { rest &= ~bit; continue; }
@@ -1038,12 +1071,12 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
             p.built = true;
             p.avg = avg;
             rest &= ~bit;
-            if (tr) rest &= ~4;
+            if (tr) rest &= ~NEED_TLIST;
         }
         // the large plans of the batch (records in the geometry's own array: evaluated by the forward plan's fill, or by a
         // pass of the batch when the transposed plan comes alone)
         for (int tr = 0; tr < 2; ++tr) {
-            const int bit = tr ? 2 : 1;
+            const int bit = tr ? NEED_PLAN_TR : NEED_PLAN_FWD;
             if (!(rest & bit)) continue;
             Plan& p = g->plan[tr];
             const int rows = tr ? g->n : g->m;
@@ -1074,7 +1107,7 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
             p.built = true;
             p.avg = avg;
             rest &= ~bit;
-            if (tr) rest &= ~4;
+            if (tr) rest &= ~NEED_TLIST;
         }
         if (rest && nLater < 256) later[nLater++] = Later{g, rest};
     }
@@ -1091,7 +1124,10 @@ int mccnn_geometry_prebuild_batch(mccnn_geometry_t* const* geoms, const int* wha
     return 0;
 }
 
-// What one mccnn_conv_forward / _backward call of this layer shape needs from the caller: which pieces the geometry does
+// records of this `avg` for all e edges are with the geometry
+static bool has_records(const mccnn_geometry* g, int avg, int e) { return g->rec_buf && g->rec_avg == avg && g->rec_bytes >= (size_t)e * 16; }
+
+// What one mccnn_conv_forward / _backward call on this route needs from the caller: which pieces the geometry does
 // not hold yet (mask, need_bytes[k] for bit k), the scratch of the call, and (forward) what has to be kept for the
 // backward pass.
 struct Req {
@@ -1099,9 +1135,8 @@ struct Req {
     long long need_bytes[4];
     size_t ws, saved;
 };
-static int requirements(mccnn_geometry* g, const Shape& s, const void* feats, int backward, int flags, int e, Req& r) {
+static int requirements(mccnn_geometry* g, const Shape& s, const ConvRoute& rt, int backward, int e, Req& r) {
     const int n = g->n, m = g->m;
-    const FwdMode f = fwd_mode(g, s, feats, e);
     int mask = 0;
     for (int k = 0; k < 4; ++k) r.need_bytes[k] = 0;
     size_t ws = 256, saved = 0;
@@ -1121,54 +1156,38 @@ static int requirements(mccnn_geometry* g, const Shape& s, const void* feats, in
         if (b > ws) ws = b;
         return 0;
     };
-    auto want_tlist = [&]() {
-        if (!g->tl_buf || g->tl_bytes < tlist_bytes(n, e)) { mask |= NEED_TLIST; r.need_bytes[2] = (long long)tlist_bytes(n, e); }
-        if (!g->tl_built) {
-            const size_t b = mccnn_transpose_neighbors_workspace_bytes(n, e);
-            if (b > ws) ws = b;
-        }
-    };
     if (!backward) {
-        if (!f.unsorted) saved += al((size_t)n * s.fin * s.elem);  // the sorted feature rows
-        if (f.rows_fwd) {
+        if (!rt.unsorted) saved += rt.rows_bytes;
+        if (rt.rows_fwd) {
             int rc = want_plan(0);
             if (rc) return rc;
             const size_t scratch = al((size_t)g->plan[0].scratch_rows * s.outF * 4);
             // (the plan is built and its workspace released before the layer's own scratch is used: they share `ws`)
             ws = max3(ws, scratch, 256);
-        } else if (!s.bf16) {
+        } else if (rt.family != FAM_BF16) {
             const size_t w = mccnn_spatial_conv_fwd_workspace_bytes(m, e, s.fin, s.fout, s.combin);
             if (w > ws) ws = w;
-            // (flags bit 2: a Fin = 1 layer that reads the geometry's records keeps (A, S) alone)
-            if ((flags & 1) && (flags & 4) && conv_f1_shape(s.fin, s.fout, s.combin)) saved += al(m > 0 && e > 0 ? conv_f1_state_bytes(m, s.fout) : 0);
-            else if (flags & 1) saved += al(mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin));
+            saved += al(rt.state_bytes);
         }
     } else {
-        const bool rows_bwd = f.rows_bwd && m > 0;
-        size_t fg_sorted = f.unsorted && rows_bwd ? 0 : al((size_t)n * s.fin * s.elem);  // the gradient rows in grid order
-        size_t sort_again = 0;
-        if (rows_bwd) {
+        size_t tb = 0;
+        if (rt.tlist == TL_REQUIRED) {
+            if (!g->tl_buf || g->tl_bytes < tlist_bytes(n, e)) { mask |= NEED_TLIST; r.need_bytes[2] = (long long)tlist_bytes(n, e); }
+            const size_t t = mccnn_transpose_neighbors_workspace_bytes(n, e);
+            tb = al(t);
+            if (!g->tl_built && t > ws) ws = t;
+        }
+        if (rt.rows_bwd) {
             int rc = want_plan(1);
             if (rc) return rc;
-            want_tlist();
             const size_t w = al(mccnn_spatial_conv_bwd_rows_workspace_bytes(n, e, s.fin)) + al((size_t)g->plan[1].scratch_rows * s.fin * 4);
-            ws = max3(ws, w + fg_sorted, 256);
-            // mccnn_conv_backward leaves the row kernels when the out-gradient it is handed is not 16-byte aligned (the
-            // pointer is not known here): the scratch covers the streaming path of the same layer as well
-            const size_t w2 = al(mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, s.fin, s.fout, s.combin));
-            const size_t tb = e > 0 ? al(mccnn_transpose_neighbors_workspace_bytes(n, e)) : 0;
-            const size_t full = al((size_t)n * s.fin * s.elem);
-            ws = max3(ws, (w2 > tb ? w2 : tb) + full + (f.unsorted ? full : 0), 256);
-        } else {
-            if (f.unsorted) sort_again = al((size_t)n * s.fin * s.elem);  // (an out-gradient the row kernel cannot take)
-            size_t tb = 0;
-            if (e > 0 && (!s.combin || ((flags & 2) && s.fin >= 2 && s.fin <= 4))) {
-                want_tlist();
-                tb = al(mccnn_transpose_neighbors_workspace_bytes(n, e));
-            }
-            const size_t w = al(mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, s.fin, s.fout, s.combin));
-            ws = max3(ws, (w > tb ? w : tb) + fg_sorted + sort_again, 256);
+            ws = max3(ws, w + (rt.unsorted ? 0 : rt.rows_bytes), 256);  // (+ the gradient rows in grid order)
         }
+        // the streaming pass: this layer's own or, on a row route, what mccnn_conv_backward falls back to when the
+        // out-gradient it is handed is not 16-byte aligned (rows_bwd_takes) -- gradient rows in grid order and, for an
+        // unsorted layer, the feature rows sorted after all
+        const size_t w = al(mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, s.fin, s.fout, s.combin));
+        ws = max3(ws, (w > tb ? w : tb) + rt.rows_bytes + (rt.unsorted ? rt.rows_bytes : 0), 256);
     }
     r.mask = mask;
     r.ws = ws + 512;
@@ -1188,7 +1207,7 @@ int mccnn_conv_prepare(mccnn_geometry_t* g, const void* feats, int num_in_feats,
     *edges = e;
     if (e > g->e_cap) return MCCNN_E_CAPACITY;
     Req r;
-    int rc = requirements(g, s, feats, backward, flags, e, r);
+    int rc = requirements(g, s, conv_route(g, s, feats, flags, e), backward, e, r);
     if (rc) return rc;
     *need_mask = r.mask;
     for (int k = 0; k < 4; ++k) need_bytes[k] = r.need_bytes[k];
@@ -1209,12 +1228,12 @@ int mccnn_conv_forward(mccnn_geometry_t* g, const void* feats, int num_in_feats,
     if (e > g->e_cap) return MCCNN_E_CAPACITY;
     const int n = g->n, m = g->m;
     const mccnn_geometry* go = grid_owner(g);
-    const FwdMode f = fwd_mode(g, s, feats, e);
+    const ConvRoute rt = conv_route(g, s, feats, flags, e);
     avg = avg ? 1 : 0;
     {   // nothing is launched unless everything this call needs is there (the caller may call optimistically, with the
         // sizes of the last batch, and only ask mccnn_conv_prepare when this says no)
         Req r;
-        int rc = requirements(g, s, feats, 0, flags, e, r);
+        int rc = requirements(g, s, rt, 0, e, r);
         if (rc) return rc;
         if (r.mask || ws_bytes < r.ws || (r.saved && (!saved || saved_bytes < r.saved))) return MCCNN_E_WORKSPACE;
     }
@@ -1222,15 +1241,14 @@ int mccnn_conv_forward(mccnn_geometry_t* g, const void* feats, int num_in_feats,
     const void* rows_in = feats;
     char* sv = (char*)saved;
     size_t sv_off = 0;
-    if (!f.unsorted) {
-        const size_t b = al((size_t)n * s.fin * s.elem);
-        if (!saved || saved_bytes < b) return MCCNN_E_WORKSPACE;
+    if (!rt.unsorted) {
+        if (!saved || saved_bytes < rt.rows_bytes) return MCCNN_E_WORKSPACE;
         int rc = mccnn_permute_scatter((const float*)feats, go->new_idx, n, s.words, (float*)sv, n, 0, stream);
         if (rc) return rc;
         rows_in = sv;
-        sv_off = b;
+        sv_off = rt.rows_bytes;
     }
-    if (f.rows_fwd) {
+    if (rt.rows_fwd) {
         int rc = ensure_plan(g, 0, e, avg, ws, ws_bytes, stream);
         if (rc) return rc;
         const Plan& p = g->plan[0];
@@ -1240,31 +1258,23 @@ int mccnn_conv_forward(mccnn_geometry_t* g, const void* feats, int num_in_feats,
                                            w1, b1, w2, b2, w3, b3, n, m, e, s.fin, g->B, g->radius, g->scale_inv, avg, s.bf16,
                                            (const int*)(pb + p.off[0]), (const int*)(pb + p.off[1]), (const int*)(pb + p.off[2]),
                                            (const int*)(pb + p.off[3]), pb + p.off[5], (const int*)(pb + p.off[4]), out,
-                                           (float*)ws, f.unsorted ? go->inv_idx : nullptr, stream);
+                                           (float*)ws, rt.unsorted ? go->inv_idx : nullptr, stream);
     }
-    if (s.bf16)
+    if (rt.family == FAM_BF16)
         return mccnn_spatial_conv_fwd_bf16(go->s_pts, rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1,
                                            b1, w2, b2, w3, b3, n, m, e, s.fin, g->B, g->radius, g->scale_inv, avg, out, ws, ws_bytes,
                                            stream);
+    // the records of this list exist (the geometry's KDE left them): read, not evaluated, and not kept a second time
+    if (rt.family == FAM_RECORDS && !(rt.f1 && has_records(g, avg, e))) return MCCNN_E_BADARG;
     void* state = nullptr;
-    if (flags & 4) {
-        // the records of this list exist (the geometry's KDE left them): read, not evaluated, and not kept a second time
-        if (!mccnn_conv_uses_records(g, s.fin, s.fout, s.combin, avg) || g->rec_bytes < (size_t)e * 16) return MCCNN_E_BADARG;
-        if ((flags & 1) && m > 0 && e > 0) {
-            if (!saved || saved_bytes < sv_off + conv_f1_state_bytes(m, s.fout)) return MCCNN_E_WORKSPACE;
-            state = sv + sv_off;
-        }
+    if (rt.state_bytes) {
+        if (!saved || saved_bytes < sv_off + rt.state_bytes) return MCCNN_E_WORKSPACE;
+        state = sv + sv_off;
+    }
+    if (rt.family == FAM_RECORDS)
         return conv_fwd_rec(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1, b1,
                             w2, b2, w3, b3, n, m, e, s.fin, s.fout, s.combin, g->B, g->radius, g->scale_inv, avg, (float*)out, state, ws,
                             ws_bytes, stream, g->rec_buf);
-    }
-    if (flags & 1) {
-        const size_t sb = mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin);
-        if (sb) {
-            if (!saved || saved_bytes < sv_off + sb) return MCCNN_E_WORKSPACE;
-            state = sv + sv_off;
-        }
-    }
     return mccnn_spatial_conv_fwd(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn,
                                   g->mx, w1, b1, w2, b2, w3, b3, n, m, e, s.fin, s.fout, s.combin, g->B, g->radius, g->scale_inv,
                                   avg, (float*)out, state, ws, ws_bytes, stream);
@@ -1283,33 +1293,32 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
     if (e > g->e_cap) return MCCNN_E_CAPACITY;
     const int n = g->n, m = g->m;
     const mccnn_geometry* go = grid_owner(g);
-    const FwdMode f = fwd_mode(g, s, feats, e);
+    const ConvRoute rt = conv_route(g, s, feats, flags, e);
     avg = avg ? 1 : 0;
     {
         Req r;
-        int rc = requirements(g, s, feats, 1, flags, e, r);
+        int rc = requirements(g, s, rt, 1, e, r);
         if (rc) return rc;
         if (r.mask || ws_bytes < r.ws) return MCCNN_E_WORKSPACE;
     }
-    const size_t rows_b = al((size_t)n * s.fin * s.elem);
+    const size_t rows_b = rt.rows_bytes;
     const char* sv = (const char*)saved;
     size_t sv_off = 0;
     const void* rows_in = feats;  // unsorted mode: the rows of the unsorted points
-    if (!f.unsorted) {
+    if (!rt.unsorted) {
         if (!saved || saved_bytes < rows_b) return MCCNN_E_WORKSPACE;
         rows_in = sv;
         sv_off = rows_b;
     }
     Arena a(ws, ws_bytes);
-    const bool rows_bwd = f.rows_bwd && m > 0 && ((((uintptr_t)out_grad) & 15) == 0);
     int rc;
-    if (rows_bwd) {
+    if (rows_bwd_takes(rt, out_grad)) {
         // ONE sweep over the transposed row plan: feature gradient and the six parameter gradients
         rc = ensure_plan(g, 1, e, avg, ws, ws_bytes, stream);  // (its workspace is free again when the sweep starts)
         if (rc) return rc;
         const Plan& p = g->plan[1];
         void* fg = feat_grad;
-        if (!f.unsorted) {
+        if (!rt.unsorted) {
             fg = a.take<char>(rows_b);
             if (!fg) return MCCNN_E_WORKSPACE;
         }
@@ -1323,13 +1332,13 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
                                          tl_start(g), (const int*)(pb + p.off[0]), (const int*)(pb + p.off[1]),
                                          (const int*)(pb + p.off[2]), (const int*)(pb + p.off[3]), pb + p.off[5],
                                          (const int*)(pb + p.off[4]), fg, scratch, dw1, db1, dw2, db2, dw3, db3,
-                                         f.unsorted ? go->inv_idx : nullptr, w, wb, stream);
+                                         rt.unsorted ? go->inv_idx : nullptr, w, wb, stream);
         if (rc) return rc;
-        if (!f.unsorted)  // back into the order the features arrived in: fg_in[i] = fg_sorted[new_idx[i]]
+        if (!rt.unsorted)  // back into the order the features arrived in: fg_in[i] = fg_sorted[new_idx[i]]
             return mccnn_permute_gather((const float*)fg, go->new_idx, n, s.words, (float*)feat_grad, stream);
         return 0;
     }
-    if (f.unsorted) {  // the streaming kernels want the rows in grid order after all
+    if (rt.unsorted) {  // the streaming kernels want the rows in grid order after all
         char* sorted = a.take<char>(rows_b);
         if (!sorted) return MCCNN_E_WORKSPACE;
         rc = mccnn_permute_scatter((const float*)feats, go->new_idx, n, s.words, (float*)sorted, n, 0, stream);
@@ -1339,9 +1348,7 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
     char* fg = a.take<char>(rows_b);
     if (!fg) return MCCNN_E_WORKSPACE;
     const int *st = nullptr, *pt = nullptr;
-    if (e > 0 && (!s.combin || ((flags & 2) && s.fin >= 2 && s.fin <= 4) || (s.combin && s.fin >= 2 && s.fin <= 4 && g->tl_built))) {
-        // depth-wise layers need the transposed list; combin layers with 2..4 input features gather their feature
-        // gradient through it when the caller asks for the deterministic form or the list exists already
+    if (rt.tlist == TL_REQUIRED || (rt.tlist == TL_IF_BUILT && g->tl_built)) {
         const size_t tb = mccnn_transpose_neighbors_workspace_bytes(n, e);
         if (!g->tl_built) {
             char* tw = a.base + a.off;  // free until the convolution's own scratch is carved out below
@@ -1355,27 +1362,20 @@ int mccnn_conv_backward(mccnn_geometry_t* g, const void* feats, const void* save
     const size_t wb = mccnn_spatial_conv_bwd_workspace_bytes(n, m, e, s.fin, s.fout, s.combin);
     char* w = a.take<char>(wb);
     if (!w) return MCCNN_E_WORKSPACE;
-    if (s.bf16) {
+    // the state the forward call kept: written only when IT ran the streaming / factored kernels (state_bytes is 0 otherwise)
+    const void* state = rt.state_bytes && saved && saved_bytes >= sv_off + rt.state_bytes ? sv + sv_off : nullptr;
+    if (rt.family == FAM_BF16) {
         rc = mccnn_spatial_conv_bwd_bf16(go->s_pts, rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1,
                                          b1, w2, b2, w3, b3, out_grad, n, m, e, s.fin, g->B, g->radius, g->scale_inv, avg, st, pt,
                                          fg, dw1, db1, dw2, db2, dw3, db3, w, wb, stream);
-    } else if (flags & 4) {
+    } else if (rt.family == FAM_RECORDS) {
         // the forward call read the geometry's records and kept (A, S) alone; the records are read again where they still
         // are the ones of this `avg` (a layer with the other flag may have rebuilt them for a row plan: evaluated afresh then)
-        if (!conv_f1_shape(s.fin, s.fout, s.combin) || f.unsorted || f.rows_fwd) return MCCNN_E_BADARG;
-        const void* state = nullptr;
-        if ((flags & 1) && m > 0 && e > 0 && saved && saved_bytes >= sv_off + conv_f1_state_bytes(m, s.fout)) state = sv + sv_off;
-        const bool have = mccnn_conv_uses_records(g, s.fin, s.fout, s.combin, avg) && g->rec_bytes >= (size_t)e * 16;
+        if (!rt.f1 || rt.rows_fwd) return MCCNN_E_BADARG;
         rc = conv_bwd_rec(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn, g->mx, w1, b1,
                           w2, b2, w3, b3, (const float*)out_grad, n, m, e, s.fin, s.fout, s.combin, g->B, g->radius, g->scale_inv, avg,
-                          state, st, pt, (float*)fg, dw1, db1, dw2, db2, dw3, db3, w, wb, stream, have ? g->rec_buf : nullptr);
+                          state, st, pt, (float*)fg, dw1, db1, dw2, db2, dw3, db3, w, wb, stream, has_records(g, avg, e) ? g->rec_buf : nullptr);
     } else {
-        const void* state = nullptr;
-        if (flags & 1) {
-            const size_t sb = mccnn_spatial_conv_state_bytes(m, e, s.fin, s.fout, s.combin);
-            // (written by the forward call only when IT ran the edge-streaming / factored kernels)
-            if (sb && saved && saved_bytes >= sv_off + sb && !f.unsorted && !f.rows_fwd) state = sv + sv_off;
-        }
         rc = mccnn_spatial_conv_bwd(go->s_pts, (const float*)rows_in, go->s_bids, g->pdfs, g->centres, g->start, g->packed, g->mn,
                                     g->mx, w1, b1, w2, b2, w3, b3, (const float*)out_grad, n, m, e, s.fin, s.fout, s.combin, g->B,
                                     g->radius, g->scale_inv, avg, state, st, pt, (float*)fg, dw1, db1, dw2, db2, dw3, db3, w, wb,

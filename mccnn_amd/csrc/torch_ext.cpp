@@ -1114,7 +1114,7 @@ struct ConvBackward : public torch::autograd::Node {
         // several layers share this neighbour list: its transposed form is built once and the feature gradient of combin
         // layers with 2..4 input features is gathered through it in a fixed order (bit-reproducible) instead of added
         // with float atomics; a bare single call keeps the atomics (the list would cost more than they do)
-        if (geo->uses > 1) flags |= 2;
+        if (geo->uses > 1) flags |= MCCNN_CONV_DETERMINISTIC;
         { const Tick tj(T_BWD_JOIN); geo->join(cur_stream(feats), true); }
         long long wsb = 0, svb = 0;
         prepare(*geo, feats, L, 1, flags, wsb, svb);
@@ -1180,9 +1180,9 @@ Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats_in, const Tensor& w1, 
     const bool need_grad = at::GradMode::is_enabled() &&
                            (feats_in.requires_grad() || w1.requires_grad() || b1.requires_grad() || w2.requires_grad() ||
                             b2.requires_grad() || w3.requires_grad() || b3.requires_grad());
-    // bit 1: the caller asks for bit-reproducible feature gradients (combin layers with 2..4 input features gather them
+    // MCCNN_CONV_DETERMINISTIC: the caller asks for bit-reproducible feature gradients (combin layers with 2..4 input features gather them
     // through the transposed list instead of adding them with float atomics)
-    L.flags = (need_grad ? 1 : 0) | (deterministic ? 2 : 0);
+    L.flags = (need_grad ? MCCNN_CONV_KEEP_STATE : 0) | (deterministic ? MCCNN_CONV_DETERMINISTIC : 0);
     Tensor out, saved;
     // bf16 rows that do not start on a 16-byte boundary (a view into a larger buffer): the bf16 kernels move 16-byte pieces
     // and the permutes see the rows as 32-bit words, so such rows are copied into an allocation of their own, which both
@@ -1195,8 +1195,8 @@ Tensor conv(std::shared_ptr<Geo> geo, const Tensor& feats_in, const Tensor& w1, 
         const Tensor& feats = rows_copy.defined() ? rows_copy : feats_in;
         geo->join(cur_stream(feats), geo->pre_avg != L.avg);
         if (geo->grid_owner) geo->grid_owner->join(cur_stream(feats));
-        // bit 2: the geometry holds the per-edge records of this layer (its KDE wrote them): read in both passes, kept by neither
-        if (L.fin == 1 && L.combin && mccnn_conv_uses_records(geo->h, L.fin, L.fout, L.combin, L.avg)) L.flags |= 4;
+        // MCCNN_CONV_READS_RECORDS: the geometry holds the per-edge records of this layer (its KDE wrote them): read in both passes, kept by neither
+        if (L.fin == 1 && L.combin && mccnn_conv_uses_records(geo->h, L.fin, L.fout, L.combin, L.avg)) L.flags |= MCCNN_CONV_READS_RECORDS;
         long long wsb = 0, svb = 0;
         prepare(*geo, feats, L, 0, L.flags, wsb, svb);
         {

@@ -52,7 +52,8 @@ if _EXT is not None:
     atexit.register(_EXT.shutdown_helpers)
 
 E_CAPACITY = -6
-NEED_PLAN_FWD, NEED_PLAN_TR, NEED_TLIST, NEED_RECORDS = 1, 2, 4, 8
+NEED_PLAN_FWD, NEED_PLAN_TR, NEED_TLIST, NEED_RECORDS = 1, 2, 4, 8      # mccnn.h: MCCNN_PIECE_*
+CONV_KEEP_STATE, CONV_DETERMINISTIC, CONV_READS_RECORDS = 1, 2, 4        # mccnn.h: MCCNN_CONV_*, the flags of mccnn_conv_*
 
 _TLS = threading.local()
 _EDGE_GUESS = {}   # (device, n, m, radius, B, scaleInv[, maxNeighbors]) -> capacity to try first
@@ -516,14 +517,14 @@ class _Conv(torch.autograd.Function):
         need_grad = feats.requires_grad or w1.requires_grad or w3.requires_grad or w2.requires_grad or b1.requires_grad \
             or b2.requires_grad or b3.requires_grad
         feats = _bf16_rows_aligned(feats)   # (no-op for f32 rows and aligned bf16 rows; both passes read the same tensor)
-        flags = (1 if need_grad else 0) | (2 if deterministic else 0)
+        flags = (CONV_KEEP_STATE if need_grad else 0) | (CONV_DETERMINISTIC if deterministic else 0)
         combin = 1 if combin else 0
         avg = 1 if avg else 0
         if fin == 1 and combin and lib.mccnn_conv_uses_records(geo.handle, fin, fout, combin, avg):
-            flags |= 4   # the geometry holds this layer's per-edge records: read in both passes, kept by neither
+            flags |= CONV_READS_RECORDS   # the geometry holds this layer's per-edge records: read in both passes, kept by neither
         dev = feats.device
         out = torch.empty((geo.m, fout if combin else fin), dtype=feats.dtype, device=dev)
-        skey = (flags & 5, fin, fout, combin, bf16, geo.n, geo.m)
+        skey = (flags & (CONV_KEEP_STATE | CONV_READS_RECORDS), fin, fout, combin, bf16, geo.n, geo.m)
         wsb, svb = _SIZES.get(skey, (0, -1))
         if svb < 0:
             wsb, svb = _prepare(geo, feats, fin, fout, combin, bf16, 0, flags)
@@ -566,7 +567,7 @@ class _Conv(torch.autograd.Function):
             # several layers share this neighbour list: its transposed form is built once and the feature gradient of
             # combin layers with 2..4 input features is gathered through it in a fixed order (bit-reproducible) instead
             # of added with float atomics; a bare single call keeps the atomics (the list would cost more than they do)
-            flags |= 2
+            flags |= CONV_DETERMINISTIC
         lib = _lib.load()
         og = outGrad if outGrad.is_contiguous() else outGrad.contiguous()
         if og.dtype != feats.dtype:
@@ -580,7 +581,7 @@ class _Conv(torch.autograd.Function):
         gflat = torch.empty(n1 + n2 + n3 + n4 + n5 + n6, dtype=torch.float32, device=dev)
         dw1, db1, dw2, db2, dw3, db3 = gflat.split((n1, n2, n3, n4, n5, n6))
         base = gflat.data_ptr()
-        skey = (2, flags & 2, fin, fout, combin, bf16, geo.n, geo.m)   # (deterministic and atomic backward passes differ in scratch)
+        skey = (2, flags & CONV_DETERMINISTIC, fin, fout, combin, bf16, geo.n, geo.m)   # (deterministic and atomic backward passes differ in scratch)
         wsb = _SIZES.get(skey, (-1, 0))[0]
         if wsb < 0:
             wsb, _ = _prepare(geo, feats, fin, fout, combin, bf16, 1, flags)
